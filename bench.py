@@ -9,16 +9,21 @@ Workload (BASELINE.json configs[3] on ONE GPU; it fits: L 0.8 GB + V^T 8.2 GB fp
   N = 10 000 train points (100 x 100 mixture-of-Gaussians field, utils.py:90-108), D = 2, fp64,
   M = 100 000 candidates IN TOTAL (--scaling strong, the headline: BASELINE config 4 -- the 100 000 are split over
   the ranks, agent.py:317-347 being independent per candidate), or PER GPU with --scaling weak; --scaling both (the
-  default) reports the strong run as the headline and, for N > 1, the weak one under "weak_scaling";
+  default) reports the strong run as the headline and, with --full and N > 1, the weak one under "weak_scaling";
   information-gain criterion = entropy (the reference's effective default, agent.py:125; the MI criterion needs
   diag(C_rest^-1) over the whole pool: 2 x 110 000^2 x 8 B = 194 GB of scratch would fit the 288 GB, the two
   pool-wide O(n^3) factorisations behind it -- 9e14 flop -- are what rules it out at this size; it does not shard
   and is timed at single-GPU sizes in `extra.mi_criterion`), sigma_s = 0.1, sigma_m = 1.
 Inputs (coordinates, targets, noise) are resident in HBM before the timed region.
 
-Launch: python bench.py [--gpus N --steps K --warmup W].  For N > 1 either under torch.distributed.run, or plainly:
-without WORLD_SIZE in the environment the script starts the N ranks itself as a child `python -m torch.distributed.run`
-(before importing torch or touching HIP) and relays rank 0's line.  Prints ONE JSON line.
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR].  For N > 1 either under
+torch.distributed.run, or plainly: without WORLD_SIZE in the environment the script starts the N ranks itself as a child
+`python -m torch.distributed.run` (before importing torch or touching HIP) and relays rank 0's line.  Prints ONE JSON line.
+A plain run sets up, warms up, times the K steps (with the library's HIP-event stage timers, which the roofline and
+stage figures read) and prints the line.  --full adds every other leg: the K steps again without the stage timers, the
+host-inclusive steps, the one-stream solve, the strong-scaling emulation, the C3 / C5 / MI / fit extras, the CPU
+baseline and, for N > 1, the weak-scaling case and config 5's loop (--no-extras / --no-cpu-baseline / --no-emulation
+leave parts of it out).  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -233,6 +238,23 @@ def _c5_field(rng, R=250, C=200, M=100000):
 
 def _pct(v, q):
     return float(np.percentile(np.asarray(v, dtype=np.float64), q))
+
+
+DUMP_MAX_ELEMS = 1 << 21          # per array: a dump's three long arrays stay under 64 MB together in fp64
+
+
+def dump_outputs(out_dir, ctx, picks):
+    """What a caller of the timed step receives from its last run: the picks (pool indices), the candidates' posterior
+    mean and variance as the step leaves them (algp_get_posterior; this rank's candidates), the fit's alpha and the
+    log-determinant of S.  Arrays longer than DUMP_MAX_ELEMS are replaced by a fixed, seeded sample of their entries."""
+    os.makedirs(out_dir, exist_ok=True)
+    mu, pv = ctx.posterior()
+    arrays = {'picks': np.asarray(picks, dtype=np.float64), 'posterior_mean': mu, 'posterior_var': pv,
+              'alpha': ctx.alpha(), 'logdet': np.array([ctx.logdet()], dtype=np.float64)}
+    for name, a in arrays.items():
+        if a.size > DUMP_MAX_ELEMS:
+            a = a[np.sort(np.random.RandomState(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
 
 
 def _tail_traffic(alg_bytes):
@@ -894,13 +916,19 @@ def main():
     ap.add_argument('--cand', type=int, default=100000, help='candidates in total (strong) / per GPU (weak)')
     ap.add_argument('--scaling', default='both', choices=['weak', 'strong', 'both'],
                     help='strong (BASELINE config 4: the 100 000 candidates are split over the ranks), weak (100 000 per rank), both '
-                         '(default: the headline is the strong run; for N > 1 the weak one follows and is reported under "weak_scaling")')
+                         '(default: the headline is the strong run; with --full and N > 1 the weak one follows and is reported under '
+                         '"weak_scaling")')
     ap.add_argument('--dtype', default='f64', choices=['f64', 'f32'])
     ap.add_argument('--picks', type=int, default=4)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='skip the C3 / C5 / MI legs (they run after the timed region)')
-    ap.add_argument('--no-emulation', action='store_true', help='skip the one-stream leg and the strong-scaling emulation (profiling runs: '
-                    'only the workload\'s own launches in the trace)')
+    ap.add_argument('--full', action='store_true', help='also run every leg beyond the headline (see the module docstring); '
+                    'a plain run only sets up, warms up, times the --steps steps and prints the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (picks, the candidates\' posterior mean and variance, alpha, '
+                         'log-determinant) as DIR/<name>.npy, float32 / float64')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the C3 / C5 / MI legs (they run after the timed region)')
+    ap.add_argument('--no-emulation', action='store_true', help='with --full: skip the host-inclusive steps, the one-stream leg and the '
+                    'strong-scaling emulation (profiling runs: only the workload\'s own launches in the trace)')
     ap.add_argument('--force-dist', action='store_true', help='use the torch.distributed/RCCL path even with one rank')
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'],
                     help='gloo only for rehearsing several ranks on ONE card (RCCL refuses duplicate devices)')
@@ -912,11 +940,15 @@ def main():
                     'instead of the config-4 step (candidates sharded, factor replicated; see loop_mode)')
     ap.add_argument('--loop-field', type=lambda v: tuple(int(x) for x in v.split('x')), default=(250, 200), help='RxC of the loop\'s field (default 250x200 = 50 000 sites)')
     ap.add_argument('--extra-loop-timeout', type=int, default=300, help='seconds after which the N > 1 extra leg is abandoned (the line is printed without it)')
-    ap.add_argument('--extra-loop-steps', type=int, default=200, help='with --gpus N > 1 the line also carries extra.c5_loop: config 5\'s loop '
+    ap.add_argument('--extra-loop-steps', type=int, default=200, help='with --full and --gpus N > 1 the line also carries extra.c5_loop: config 5\'s loop '
                     'for this many incremental steps on the N ranks (0 or --no-extras: skipped)')
     ap.add_argument('--cpu-train', type=int, default=6000)
     ap.add_argument('--traffic-json', default=os.path.join(REPO, 'profiles', 'r06_traffic_pmc.json'))
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    if args.loop > 0 and args.dump_outputs:
+        ap.error('--dump-outputs writes the config-4 step\'s outputs; it does not apply to --loop')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         raise SystemExit(self_spawn(args))
@@ -1002,8 +1034,9 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
-    def run_case(scaling):
-        """W warm-up steps, K timed steps with the stage timers, K more without, on the workload of `scaling`."""
+    def run_case(scaling, dump=False):
+        """W warm-up steps, K timed steps with the stage timers (with --full: K more without), on the workload of `scaling`;
+        dump: write the last timed step's outputs to --dump-outputs (rank 0)."""
         args.scaling = scaling
         w = build_workload(args, world)
         ctx.set_pool(w['pool'])
@@ -1050,7 +1083,7 @@ def main():
         for _ in range(args.warmup):
             step()
         # the timed region: K steps with the library's HIP-event profiling on (the roofline figures below come from these
-        # very launches); the same K steps are then repeated without the ~600 event pairs per step
+        # very launches); with --full the same K steps are then repeated without the ~600 event pairs per step
         ctx.prof_enable(True)
         ctx.prof_reset()
         s0 = ctx.sync_count()
@@ -1059,12 +1092,14 @@ def main():
         prof = {k: ctx.prof_get(k) for k in _hip.PROF}
         chol_stats = ctx.cholesky_task_stats()
         ctx.prof_enable(False)
-        elapsed_unprof = timed(args.steps)
+        if dump and args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, ctx, picks_log[-1])
+        elapsed_unprof = timed(args.steps) if args.full else None
         # SURVEY 8(d)'s second clock: host wall time around the ABI with the inputs handed over as host NumPy buffers every
         # step -- pool coordinates, train set and candidate list up (H2D inside the calls), the picks back on the host -- where
         # the headline's steps start from resident inputs (reference utils.py:293-319 is host-in / host-out)
         host_ms = []
-        if world == 1 and not args.no_emulation:                  # (profiling runs, --no-emulation, hold only the workload's own 7 solves)
+        if args.full and world == 1 and not args.no_emulation:    # (profiling runs, --no-emulation, hold only the workload's own 7 solves)
             picks_resident = picks_log[-1]
             for _ in range(max(3, min(args.steps, 10))):
                 barrier()
@@ -1080,16 +1115,16 @@ def main():
                     syncs_per_step=syncs / float(args.steps), step_ms=step_ms, host_ms=host_ms)
 
     want = args.scaling
-    res = run_case('weak' if want == 'weak' else 'strong')
+    res = run_case('weak' if want == 'weak' else 'strong', dump=True)
     weak = None
-    if want == 'both' and world > 1:
+    if want == 'both' and world > 1 and args.full:
         weak = run_case('weak')
         args.scaling = 'strong'
     elif want == 'both':
         args.scaling = 'strong'
 
     serial = None
-    if rank == 0 and world == 1 and not args.no_emulation:
+    if args.full and rank == 0 and world == 1 and not args.no_emulation:
         # the same solve with ONE row-chunk stream: the launches run back to back, so the sum of their own durations is
         # the GEMM kernel's rate without help from overlapping another stream's tail (what a --pmc pass also measures)
         try:
@@ -1111,7 +1146,7 @@ def main():
             ctx.set_trsm_chunks(0)
 
     emu = None
-    if rank == 0 and world == 1 and want != 'weak' and not args.no_emulation:
+    if args.full and rank == 0 and world == 1 and want != 'weak' and not args.no_emulation:
         emu = strong_emulation(ctx, _hip, res, args)
 
     if rank == 0:
@@ -1197,8 +1232,8 @@ def main():
                                     'NumPy buffers inside the clock (algp_set_pool / algp_set_train / algp_set_candidates: H2D in the calls) and '
                                     'return the picks to the host; ms_per_step / _median / _p95: inputs resident, rank 0\'s own clock per step'
                                     % (len(res['host_ms']), N + total_c)) if res['host_ms'] else None,
-            'ms_per_step_unprofiled': 1e3 * elapsed_unprof / K,
-            'value_unprofiled': total_c / (elapsed_unprof / K),
+            'ms_per_step_unprofiled': 1e3 * elapsed_unprof / K if elapsed_unprof is not None else None,
+            'value_unprofiled': total_c / (elapsed_unprof / K) if elapsed_unprof is not None else None,
             'higher_is_better': True, 'scaling': 'weak' if want == 'weak' else 'strong', 'vs_baseline': None,
             'dtype': args.dtype, 'data': 'synthetic',
             'config': {'workload': '%d-point MoG field (train) x %d candidates %s, %d greedy picks, entropy criterion, D=2'
@@ -1255,12 +1290,12 @@ def main():
                                    'candidates_per_gpu': weak['M0'], 'candidates_total': weak['total_c'],
                                    'picks_last_step': weak['picks']}
 
-    # N > 1: BASELINE config 5 in its stated form as well -- the active-learning loop on the N ranks (every rank takes part).
+    # --full, N > 1: BASELINE config 5 in its stated form as well -- the active-learning loop on the N ranks (every rank takes part).
     # The headline line is complete at this point and must not be lost to this leg: every rank runs it under a watchdog that,
     # when no result has come after --extra-loop-timeout seconds (a rank stuck in a collective), lets rank 0 print the line
     # with the failure noted and ends the process (each rank its own: all of them leave).
     c5_multi = None
-    if world > 1 and not args.no_extras and args.extra_loop_steps > 0:
+    if args.full and world > 1 and not args.no_extras and args.extra_loop_steps > 0:
         import threading
         if ctx is not None:
             ctx.close()
@@ -1306,7 +1341,7 @@ def main():
 
     if rank == 0:
         extras = {}
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             ctx.close()
             ctx = None
             for name, fn in (('fit_iteration', lambda: extra_fit(_hip, local_rank)),
@@ -1322,7 +1357,7 @@ def main():
         if c5_multi is not None:
             extras['c5_loop'] = c5_multi
         out['extra'] = extras
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(w, hyp_vals, args)
         else:
             out['cpu_baseline'] = None

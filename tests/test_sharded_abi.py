@@ -296,8 +296,8 @@ def _bench(args, env_extra=None):
 def test_bench_plain_launch_with_two_ranks_on_one_card():
     """`python bench.py --gpus 2` with no WORLD_SIZE: the script starts its ranks itself (child torch.distributed.run),
     prints ONE JSON line with n_gpus 2, config 4's strong reading as the headline (the candidates are split, so the picks
-    equal the one-rank run's) and the weak figure beside it."""
-    common = ['--steps', '1', '--warmup', '1', '--train', '2500', '--cand', '20000', '--no-extras', '--no-cpu-baseline']
+    equal the one-rank run's) and, with --full, the weak figure beside it."""
+    common = ['--steps', '1', '--warmup', '1', '--train', '2500', '--cand', '20000', '--full', '--no-extras', '--no-cpu-baseline']
     one = _bench(['--gpus', '1'] + common)
     two = _bench(['--gpus', '2', '--backend', 'gloo'] + common, {'ALGP_BENCH_DEVICE': '0'})
     assert one['n_gpus'] == 1 and two['n_gpus'] == 2

@@ -257,10 +257,10 @@ def test_bench_loop_mode_two_ranks_on_one_card_equals_one_rank():
 
 
 def test_bench_multi_rank_line_carries_the_loop_as_an_extra():
-    """With --gpus N > 1 the default bench line also times config 5's loop on the N ranks (extra.c5_loop): two ranks on one card
+    """With --full and --gpus N > 1 the bench line also times config 5's loop on the N ranks (extra.c5_loop): two ranks on one card
     over gloo at a reduced size; the headline stays config 4's."""
     two = _bench(['--gpus', '2', '--backend', 'gloo', '--steps', '1', '--warmup', '1', '--train', '2500', '--cand', '9000',
-                  '--loop-field', '60x50', '--extra-loop-steps', '4', '--no-cpu-baseline'], {'ALGP_BENCH_DEVICE': '0'})
+                  '--loop-field', '60x50', '--extra-loop-steps', '4', '--full', '--no-cpu-baseline'], {'ALGP_BENCH_DEVICE': '0'})
     assert two['n_gpus'] == 2 and two['config']['candidates_total'] == 9000
     lp = two['extra']['c5_loop']
     assert 'error' not in lp, lp
@@ -269,12 +269,12 @@ def test_bench_multi_rank_line_carries_the_loop_as_an_extra():
 
 
 def test_bench_multi_rank_line_survives_a_stuck_extra_leg():
-    """The N > 1 extra leg runs under a watchdog on every rank: with a limit the leg cannot meet (0 s) the headline line is
-    still printed -- exactly once, by rank 0, with the failure and the place the loop had reached noted under extra.c5_loop --
+    """The N > 1 extra leg (--full) runs under a watchdog on every rank: with a limit the leg cannot meet (0 s) the headline
+    line is still printed -- exactly once, by rank 0, with the failure and the place the loop had reached noted under extra.c5_loop --
     and every rank ends with a NON-ZERO status (a process abandoned in a collective did not succeed), which `bench.py --gpus N`
     relays together with the line."""
     two = _bench(['--gpus', '2', '--backend', 'gloo', '--steps', '1', '--warmup', '1', '--train', '2500', '--cand', '9000',
-                  '--loop-field', '60x50', '--extra-loop-steps', '50', '--extra-loop-timeout', '0', '--no-cpu-baseline'],
+                  '--loop-field', '60x50', '--extra-loop-steps', '50', '--extra-loop-timeout', '0', '--full', '--no-cpu-baseline'],
                  {'ALGP_BENCH_DEVICE': '0'}, want_rc=3)
     assert two['n_gpus'] == 2 and two['config']['candidates_total'] == 9000 and two['value'] > 0
     assert 'abandoned' in two['extra']['c5_loop']['error'] and 'rank 0 was at' in two['extra']['c5_loop']['error']

@@ -9,7 +9,7 @@ set -e -o pipefail
 DT=${1:-f64}
 OUT=${2:-gpurun_out/prof_r06_$DT}
 TRAFFIC=${3:-$OUT/traffic_pmc.json}
-ARGS="bench.py --dtype $DT --steps 3 --warmup 1 --no-cpu-baseline --no-extras --no-emulation --traffic-json $TRAFFIC"
+ARGS="bench.py --dtype $DT --steps 3 --warmup 1 --full --no-cpu-baseline --no-extras --no-emulation --traffic-json $TRAFFIC"
 mkdir -p $OUT $(dirname $TRAFFIC)
 cd /tmp 2>/dev/null && export TMPDIR=/tmp && cd - >/dev/null
 python3 $ARGS > $OUT/bench_plain.json 2> $OUT/bench_plain.err

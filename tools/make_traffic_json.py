@@ -17,7 +17,7 @@ spec.loader.exec_module(bench)
 
 out = {'sources_sha16': bench.sources_sha16(),
        'commit': subprocess.run(['git', 'rev-parse', 'HEAD'], cwd=REPO, capture_output=True, text=True).stdout.strip() or None,
-       'command': 'bench.py --dtype <dt> --steps 3 --warmup 1 --no-cpu-baseline --no-extras --no-emulation (7 candidate solves per run: 1 warm-up + 3 timed with the stage timers + 3 without)',
+       'command': 'bench.py --dtype <dt> --steps 3 --warmup 1 --full --no-cpu-baseline --no-extras --no-emulation (7 candidate solves per run: 1 warm-up + 3 timed with the stage timers + 3 without)',
        'fetch_factor': 2.0,
        'fetch_factor_source': 'profiles/r06_fetch_calibration.txt (tools/fetch_calibrate.sh): FETCH_SIZE x 2 = the true byte count to 0.1 % for '
                               '64 / 128 / 256 / 1024-byte row pieces, plain loads and LDS-DMA, all three lane orders of the GEMM\'s 64-byte pieces',
