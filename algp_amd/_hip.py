@@ -85,6 +85,7 @@ SIGNATURES = {
     'algp_prof_get': (C.c_int, [_c_ctx, C.c_int, _dblp, _dblp, _dblp, _i64p]),
     'algp_cholesky_task_stats': (C.c_int, [_c_ctx, _dblp]),
     'algp_score_paths': (C.c_int, [_c_ctx, _i64p, C.c_int, C.c_int, C.c_double, _dblp]),
+    'algp_score_paths_mi': (C.c_int, [_c_ctx, _i64p, C.c_int, C.c_int, C.c_double, C.c_double, _dblp, _dblp]),
     'algp_comm_unique_id': (C.c_int, [C.c_void_p]),
     'algp_comm_init': (C.c_int, [_c_ctx, C.c_int, C.c_int, C.c_void_p]),
     'algp_comm_init_host': (C.c_int, [_c_ctx, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
@@ -404,6 +405,21 @@ class Context(object):
             self._check(self.lib.algp_score_paths(self.h, _i64(sites.ravel()), sites.shape[0], sites.shape[1], float(mobile_std),
                                                   out.ctypes.data_as(_dblp)))
         return out
+
+    def score_paths_mi(self, sites, static_std, mobile_std, want_terms=False):
+        """Mutual-information utility of every row of `sites` relative to the base state, dMI[p] = dH_A + dH_Abar - dH_all
+        (npaths x maxlen pool indices, -1 padded: the sites the path changes -- new ones and re-measured train rows; see
+        algp_score_paths_mi).  want_terms: also the (npaths, 3) array of the three terms."""
+        sites = np.ascontiguousarray(sites, dtype=np.int64)
+        if sites.ndim != 2:
+            raise ValueError('sites must be (npaths, maxlen)')
+        out = np.empty(sites.shape[0], dtype=np.float64)
+        terms = np.empty((sites.shape[0], 3), dtype=np.float64) if want_terms else None
+        if sites.shape[0]:
+            self._check(self.lib.algp_score_paths_mi(self.h, _i64(sites.ravel()), sites.shape[0], sites.shape[1], float(static_std),
+                                                     float(mobile_std), out.ctypes.data_as(_dblp),
+                                                     None if terms is None else terms.ctypes.data_as(_dblp)))
+        return (out, terms) if want_terms else out
 
     # -- multi-GPU: the collective behind the ABI (RCCL) ---------------------------------------
     @staticmethod

@@ -5,7 +5,7 @@ Hot-path methods (device):
   _post_update  agent.py:89-90     pool coordinates go to the GPU; `cov_matrix` is built lazily
   greedy        agent.py:295-356   one factorisation + one blocked solve + k rank-1 row appends
                                     instead of k*M fresh slogdets
-  best_path     agent.py:358-403   one set entropy per path
+  best_path     agent.py:358-403   all paths from one resident factor + candidate solve (MI: + two pool-wide inverses)
   predict       agent.py:289-293   -> utils.predictive_distribution
   update_model  agent.py:84-87     -> GPR.fit (analytic MLL gradient on the device)
 Host bookkeeping (sample logs, sensor fusion, the IPP loop) follows the reference's behaviour and
@@ -421,11 +421,28 @@ class Agent(object):
             # row form: every path only APPENDS rows (a mobile row for each of its sites that has none yet) behind
             # the common base, even where it re-measures a static site; H is brought back to the fused form
             return int(np.argmax(self._path_utilities_rows(c, paths_mobile_indices, static, mobile0)))
+        return int(np.argmax(self._path_utilities_fused(c, paths_mobile_indices, static, mobile0)))
+
+    def _path_utilities_fused(self, c, paths, static, mobile0, batched=True):
+        """Utility of every path, one fused train row per site (agent.py:374-400).  Batched, MI criterion, one GPU: the
+        base is factored and solved once and every path is scored at once from the two resident pool-wide inverses
+        (algp_score_paths_mi; utilities relative to the base).  The per-path loop (absolute utilities; one factor update
+        and, under MI, two pool-sized set entropies per path) remains for paths of more than 256 changing sites, a pool
+        whose inverses do not fit, sharded agents, the entropy criterion in this form and as the cross-check of the tests."""
+        n = self.env.num_samples
         base = self._train_order(static | mobile0)          # sites sampled whichever path is taken
+        if batched and self.criterion == 'mutual_information' and self.comm is None:
+            # the sites a path changes: distinct, on the field, not mobile-sampled already (a new site, or a re-measured one)
+            clean = [[j for j in dict.fromkeys(int(v) for v in path) if j != -1 and not mobile0[j]] for path in paths]
+            if max((len(p) for p in clean), default=0) <= 256:
+                try:
+                    return self._path_utilities_mi(c, base, clean, static, mobile0)
+                except MemoryError:
+                    pass                                        # the two pool-wide inverses do not fit: one path at a time
         in_base = np.zeros(n, bool)
         in_base[base] = True
         utilities = []
-        for path in paths_mobile_indices:
+        for path in paths:
             mobile = mobile0.copy()
             mobile[path] = True
             sampled = static | mobile
@@ -445,7 +462,22 @@ class Agent(object):
                 var_all[A] = var
                 ut -= c.set_entropy(np.arange(n), var_all)
             utilities.append(ut)
-        return int(np.argmax(utilities))
+        return np.array(utilities)
+
+    def _path_utilities_mi(self, c, base, clean, static, mobile0):
+        """MI utility of every path relative to the base: ONE factor update and candidate solve of the base (candidates:
+        every site some path changes), then algp_score_paths_mi (its pool-wide inverses are built once per solve)."""
+        c.set_train(base, np.zeros(len(base)), self._fused_var(static[base], mobile0[base]))
+        c.factorize(incremental=True)
+        cand = sorted(set(j for pth in clean for j in pth))
+        if not cand:
+            return np.zeros(len(clean))                       # no path changes anything
+        c.set_candidates(np.array(cand, dtype=np.int64), prior_includes_noise=True)
+        c.solve_candidates()
+        sites = np.full((len(clean), max(1, max(len(p) for p in clean))), -1, dtype=np.int64)
+        for k, pth in enumerate(clean):
+            sites[k, :len(pth)] = pth
+        return c.score_paths_mi(sites, self.static_std, self.mobile_std)
 
     def _path_utilities_rows(self, c, paths, static, mobile0, batched=True):
         """Entropy utility of every path relative to the common base (row form).  Batched: ONE factor update + ONE

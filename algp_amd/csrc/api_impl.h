@@ -134,6 +134,8 @@ struct Impl {
     static int score_paths_big(algp_ctx* c, const std::vector<int64_t>& cpos, const std::vector<int64_t>& lpos, int npaths, int maxlen,
                                int maxused, double mobile_std, double* dH);
     static int score_paths(algp_ctx* c, const int64_t* sites, int npaths, int maxlen, double mobile_std, double* dH);
+    static int score_paths_mi(algp_ctx* c, const int64_t* sites, int npaths, int maxlen, double static_std, double mobile_std,
+                              double* dMI, double* terms);
     static int mll_grad(algp_ctx* c, double* grad_out, bool have_X = false, bool inv_enqueued = false);
     static int fit_step(algp_ctx* c, double* mll_out, double* grad_out);
     static int get_alpha(algp_ctx* c, void* out);

@@ -125,6 +125,177 @@ int Impl<T>::score_paths(algp_ctx* c, const int64_t* sites, int npaths, int maxl
     return sync(c);
 }
 
+// Factor a batch of ppad x ppad blocks (ppad = 128 or 256, lower tiles) as 2 x 2 tiles of 128, the way score_paths_big does:
+// L11 and L22 in place, L21 = G21 inv(L11)^T into L21 (NB x NB per block), log det added to logdet[b], first bad pivot to info[b]
+template <typename T>
+static int factor_blocks_batched(algp_ctx* c, T* G, int ppad, T* inv, T* L21, double* logdet, int* info, int B) {
+    ALGP_TRY(potrf_diag_batched_launch<T>(c, G, (int64_t)ppad * ppad, ppad, inv, 2 * NB * NB, logdet, info, B));
+    if (ppad > NB) {
+        T* G21 = G + (int64_t)NB * ppad;
+        T* G22 = G21 + NB;
+        ALGP_TRY(gemm_nt_launch_batched<T>(c, ALGP_PROF_GEMM_OTHER, NB, NB, NB, (T)1, G21, ppad, (int64_t)ppad * ppad, inv, NB, 2 * NB * NB,
+                                           (T)0, nullptr, 0, 0, L21, NB, NB * NB, 0, B));
+        ALGP_TRY(gemm_nt_launch_batched<T>(c, ALGP_PROF_GEMM_OTHER, NB, NB, NB, (T)-1, L21, NB, NB * NB, L21, NB, NB * NB, (T)1, G22, ppad,
+                                           (int64_t)ppad * ppad, G22, ppad, (int64_t)ppad * ppad, 0, B));
+        ALGP_TRY(potrf_diag_batched_launch<T>(c, G22, (int64_t)ppad * ppad, ppad, inv + NB * NB, 2 * NB * NB, logdet, info, B));
+    }
+    return ALGP_OK;
+}
+
+// best_path under the MI criterion (agent.py:374-400: ent_a + ent_abar - ent_all per path, two of them pool-sized).  Relative
+// to the base state (train set A0, complement Abar0, noise D0), path p changes S = S_new u S_rm: new sites join A with noise
+// sm and leave Abar; re-measured train sites keep their place and their fused noise goes v_a -> v_a sm / (v_a + sm).
+//   dH_A    = H(A0 u S_new, fused) - H(A0): score_paths' dH (a re-measured site as a second row) minus
+//             sum over S_rm of CONST + 1/2 log(v_a + sm) (row form -> fused form)
+//   dH_Abar = 1/2 log det P[S_new, S_new] - |S_new| CONST            (Jacobi: det C_{Abar0 \ S} = det C_Abar0 det (C^-1)_SS)
+//   dH_all  = 1/2 log det (I + G^T D G), Q[S, S] = G G^T            (determinant lemma; D = diag(delta) < 0 on S_rm, so the
+//             symmetric form sqrt(D) Q sqrt(D) does not exist -- I + G^T D G is congruent to the Schur complement of C + D_p)
+// P and Q are the resident inverses of mi_build, built only when the MI state is not valid; per batch of paths their rows are
+// gathered (masked left of the diagonal tile), the blocks are batched Gram products on MFMA, then 2 x 2 tiled factorisations.
+template <typename T>
+int Impl<T>::score_paths_mi(algp_ctx* c, const int64_t* sites, int npaths, int maxlen, double static_std, double mobile_std,
+                            double* dMI, double* terms) {
+    if (!c->solved) return fail(c, ALGP_ERR_STATE, "score_paths_mi: call algp_solve_candidates first");
+    if (!c->prior_noise) return fail(c, ALGP_ERR_STATE, "score_paths_mi: candidates were set with predictive semantics");
+    if (!c->picks.empty()) return fail(c, ALGP_ERR_STATE, "score_paths_mi: picks were committed since the candidate solve; solve again");
+    const double ss = static_std * static_std, sm = mobile_std * mobile_std;
+    // per path: its changing sites, new ones first (pool indices), and how many of them are new
+    const size_t tot = (size_t)npaths * maxlen;
+    std::vector<int64_t> packed(tot, -1);
+    std::vector<int> knew(npaths, 0), kall(npaths, 0);
+    int maxk = 0;
+    for (int pth = 0; pth < npaths; ++pth) {
+        std::vector<int64_t> nw, rm;
+        for (int a = 0; a < maxlen; ++a) {
+            const int64_t j = sites[(size_t)pth * maxlen + a];
+            if (j < 0) continue;
+            if (j >= c->n_pool) return fail(c, ALGP_ERR_BAD_ARG, "score_paths_mi: index outside the pool");
+            if (c->cand_pos[j] < 0)
+                return fail(c, ALGP_ERR_STATE, "score_paths_mi: site " + std::to_string(j) + " is not a resident candidate");
+            auto& lst = c->pos_in_train[j] >= 0 ? rm : nw;
+            if (std::find(lst.begin(), lst.end(), j) == lst.end()) lst.push_back(j);   // a site crossed twice counts once
+        }
+        const int k = (int)(nw.size() + rm.size());
+        if (k > 256) return fail(c, ALGP_ERR_BAD_ARG, "score_paths_mi: more than 256 changing sites in a path");
+        knew[pth] = (int)nw.size();
+        kall[pth] = k;
+        for (int a = 0; a < k; ++a) packed[(size_t)pth * maxlen + a] = a < knew[pth] ? nw[a] : rm[a - knew[pth]];
+        maxk = std::max(maxk, k);
+    }
+    // the pool-wide inverses (their O(n^3) build, or ALGP_ERR_OOM up front): only when the MI state is not valid -- a solve
+    // invalidates it, and no pick has been committed since, so a valid state was built for this train set with no picks
+    if (!c->mi_valid) ALGP_TRY(mi_build(c, ss, sm));
+    // dH_A: the entropy block scorer on the same sites (both of its regimes)
+    std::vector<double> dHA(npaths);
+    ALGP_TRY(score_paths(c, packed.data(), npaths, maxlen, mobile_std, dHA.data()));
+
+    const int64_t npad = c->mi_npad, mb = c->mi_mb, mbpad = c->mi_mbpad;
+    const int ppad = maxk <= NB ? NB : 2 * NB;
+    const size_t mat = (size_t)ppad * ppad;
+    // per path: its gathered rows (ppad x npad, P's narrower rows reuse them), four blocks, two inverse tiles, one L21 tile
+    const double per_path = (double)sizeof(T) * ((double)ppad * npad + 4.0 * mat + 3.0 * NB * NB);
+    const int bmax = (int)std::max<double>(1.0, std::min<double>({(double)npaths, 4e9 / per_path, 65535.0}));
+    ALGP_TRY(ensure(c, c->auxW, sizeof(T) * (size_t)bmax * ppad * npad));
+    ALGP_TRY(ensure(c, c->auxA, sizeof(T) * (4 * (size_t)bmax + 1) * mat));
+    ALGP_TRY(ensure(c, c->auxInv, sizeof(T) * (size_t)bmax * 2 * NB * NB));
+    ALGP_TRY(ensure(c, c->auxD, sizeof(T) * (size_t)bmax * NB * NB));
+    ALGP_TRY(ensure(c, c->auxIdx, sizeof(int64_t) * 2 * (size_t)bmax * ppad));
+    ALGP_TRY(ensure(c, c->auxVar, sizeof(T) * (size_t)bmax * ppad + sizeof(int) * 2 * (size_t)bmax + 256));
+    ALGP_TRY(ensure(c, c->hostStage, sizeof(double) * 3 * (size_t)bmax + sizeof(int) * 3 * (size_t)bmax + 64));
+    T* rows = p(c->auxW);
+    T* GP = p(c->auxA);                                      // P_SS, then I + G^T D G
+    T* GQ = GP + (size_t)bmax * mat;                         // Q_SS -> its factor G
+    T* Lt = GQ + (size_t)bmax * mat;
+    T* LtD = Lt + (size_t)bmax * mat;
+    T* ident = LtD + (size_t)bmax * mat;
+    T* inv = p(c->auxInv);
+    T* L21 = p(c->auxD);
+    int64_t* d_srcP = (int64_t*)c->auxIdx.p;
+    int64_t* d_srcQ = d_srcP + (size_t)bmax * ppad;
+    T* d_delta = p(c->auxVar);
+    int* d_cntP = (int*)((char*)c->auxVar.p + sizeof(T) * (size_t)bmax * ppad);
+    int* d_cntQ = d_cntP + bmax;
+    double* d_ld = (double*)c->hostStage.p;                  // [log det P_SS | log det Q_SS | log det (I + G^T D G)]
+    int* d_info = (int*)(d_ld + 3 * (size_t)bmax);
+    ALGP_TRY(set_identity_launch<T>(c, ident, ppad, ppad));
+    std::vector<int64_t> srcP((size_t)bmax * ppad), srcQ((size_t)bmax * ppad);
+    std::vector<T> delta((size_t)bmax * ppad);
+    std::vector<int> cnt(2 * (size_t)bmax);
+    std::vector<double> ld(3 * (size_t)bmax), ldP(npaths), ldM(npaths);
+    std::vector<int> info(3 * (size_t)bmax), bad(npaths);
+    for (int p0 = 0; p0 < npaths; p0 += bmax) {
+        const int B = std::min(bmax, npaths - p0);
+        for (int b = 0; b < B; ++b) {
+            const int pth = p0 + b;
+            for (int a = 0; a < ppad; ++a) {
+                const size_t e = (size_t)b * ppad + a;
+                const int64_t j = a < kall[pth] ? packed[(size_t)pth * maxlen + a] : -1;
+                srcP[e] = a < knew[pth] ? c->mi_posbar[j] : -1;
+                srcQ[e] = j;
+                double dl = 0.0;
+                if (a < knew[pth]) dl = sm;
+                else if (j >= 0) {
+                    const double va = c->train_var_host[(size_t)c->pos_in_train[j]];
+                    dl = va * sm / (va + sm) - va;
+                }
+                delta[e] = (T)dl;
+            }
+            cnt[b] = knew[pth];
+            cnt[bmax + b] = kall[pth];
+        }
+        const size_t nrow = (size_t)B * ppad;
+        ALGP_HIP(hipMemcpyAsync(d_srcP, srcP.data(), sizeof(int64_t) * nrow, hipMemcpyHostToDevice, c->stream));
+        ALGP_HIP(hipMemcpyAsync(d_srcQ, srcQ.data(), sizeof(int64_t) * nrow, hipMemcpyHostToDevice, c->stream));
+        ALGP_HIP(hipMemcpyAsync(d_delta, delta.data(), sizeof(T) * nrow, hipMemcpyHostToDevice, c->stream));
+        ALGP_HIP(hipMemcpyAsync(d_cntP, cnt.data(), sizeof(int) * 2 * (size_t)bmax, hipMemcpyHostToDevice, c->stream));
+        ALGP_HIP(hipMemsetAsync(d_ld, 0, sizeof(double) * 3 * (size_t)bmax, c->stream));
+        ALGP_HIP(hipMemsetAsync(d_info, 0, sizeof(int) * 3 * (size_t)bmax, c->stream));
+        // P_SS over the new sites (nothing to do when every site is sampled: no path then has a new site)
+        if (mb > 0) {
+            ALGP_TRY(mi_tri_gather_launch<T>(c, p(c->miXbar), mbpad, d_srcP, rows, mbpad, (int64_t)nrow, mbpad));
+            ALGP_TRY(gemm_nt_launch_batched<T>(c, ALGP_PROF_GEMM_OTHER, ppad, ppad, mbpad, (T)1, rows, mbpad, (int64_t)ppad * mbpad, rows,
+                                               mbpad, (int64_t)ppad * mbpad, (T)0, nullptr, 0, 0, GP, ppad, (int64_t)mat, 1, B));
+            ALGP_TRY(mi_pad_diag_launch<T>(c, GP, ppad, d_cntP, B));
+            ALGP_TRY(factor_blocks_batched<T>(c, GP, ppad, inv, L21, d_ld, d_info, B));
+        }
+        // Q_SS over all changing sites -> G, then I + G^T D G = I + Lt LtD^T
+        ALGP_TRY(mi_tri_gather_launch<T>(c, p(c->miXall), npad, d_srcQ, rows, npad, (int64_t)nrow, npad));
+        ALGP_TRY(gemm_nt_launch_batched<T>(c, ALGP_PROF_GEMM_OTHER, ppad, ppad, npad, (T)1, rows, npad, (int64_t)ppad * npad, rows, npad,
+                                           (int64_t)ppad * npad, (T)0, nullptr, 0, 0, GQ, ppad, (int64_t)mat, 1, B));
+        ALGP_TRY(mi_pad_diag_launch<T>(c, GQ, ppad, d_cntQ, B));
+        ALGP_TRY(factor_blocks_batched<T>(c, GQ, ppad, inv, L21, d_ld + bmax, d_info + bmax, B));
+        ALGP_TRY(mi_transpose_launch<T>(c, GQ, L21, d_delta, ppad, Lt, LtD, B));
+        ALGP_TRY(gemm_nt_launch_batched<T>(c, ALGP_PROF_GEMM_OTHER, ppad, ppad, ppad, (T)1, Lt, ppad, (int64_t)mat, LtD, ppad, (int64_t)mat,
+                                           (T)1, ident, ppad, 0, GP, ppad, (int64_t)mat, 1, B));
+        ALGP_TRY(factor_blocks_batched<T>(c, GP, ppad, inv, L21, d_ld + 2 * bmax, d_info + 2 * bmax, B));
+        ALGP_HIP(hipMemcpyAsync(ld.data(), d_ld, sizeof(double) * 3 * (size_t)bmax, hipMemcpyDeviceToHost, c->stream));
+        ALGP_HIP(hipMemcpyAsync(info.data(), d_info, sizeof(int) * 3 * (size_t)bmax, hipMemcpyDeviceToHost, c->stream));
+        ALGP_TRY(sync(c));                                   // the index vectors are reused by the next batch
+        for (int b = 0; b < B; ++b) {
+            ldP[p0 + b] = ld[b];
+            ldM[p0 + b] = ld[2 * (size_t)bmax + b];
+            bad[p0 + b] = info[b] != 0 || info[bmax + b] != 0 || info[2 * (size_t)bmax + b] != 0;
+        }
+    }
+    for (int pth = 0; pth < npaths; ++pth) {
+        double fuse = 0.0;                                   // row form -> fused form, per re-measured site
+        for (int a = knew[pth]; a < kall[pth]; ++a) {
+            const int64_t j = packed[(size_t)pth * maxlen + a];
+            fuse += ENT_CONST + 0.5 * log(c->train_var_host[(size_t)c->pos_in_train[j]] + sm);
+        }
+        const double hA = dHA[pth] - fuse;
+        const double hBar = bad[pth] ? NAN : 0.5 * ldP[pth] - (double)knew[pth] * ENT_CONST;
+        const double hAll = bad[pth] ? NAN : 0.5 * ldM[pth];
+        dMI[pth] = hA + hBar - hAll;
+        if (terms) {
+            terms[3 * (size_t)pth + 0] = hA;
+            terms[3 * (size_t)pth + 1] = hBar;
+            terms[3 * (size_t)pth + 2] = hAll;
+        }
+    }
+    return ALGP_OK;
+}
+
 template struct Impl<float>;
 template struct Impl<double>;
 
@@ -137,6 +308,15 @@ int algp_score_paths(algp_ctx* c, const int64_t* sites, int npaths, int maxlen, 
     if (npaths < 0 || maxlen < 1 || (npaths > 0 && (!sites || !dH_out))) return fail(c, ALGP_ERR_BAD_ARG, "score_paths: bad arguments");
     if (npaths == 0) return ALGP_OK;
     FINISH(c, DISPATCH(c, score_paths(c, sites, npaths, maxlen, mobile_std, dH_out)));
+}
+
+int algp_score_paths_mi(algp_ctx* c, const int64_t* sites, int npaths, int maxlen, double static_std, double mobile_std, double* dMI_out,
+                        double* terms_out) {
+    CHECK_CTX(c);
+    if (npaths < 0 || maxlen < 1 || (npaths > 0 && (!sites || !dMI_out)) || !(static_std > 0) || !(mobile_std > 0))
+        return fail(c, ALGP_ERR_BAD_ARG, "score_paths_mi: bad arguments");
+    if (npaths == 0) return ALGP_OK;
+    FINISH(c, DISPATCH(c, score_paths_mi(c, sites, npaths, maxlen, static_std, mobile_std, dMI_out, terms_out)));
 }
 
 }  // extern "C"

@@ -49,6 +49,16 @@ template <typename T>
 int path_assemble_launch(algp_ctx* c, const int64_t* cpos, int batch, int ppad, const int64_t* cidx, const T* Xs, const T* Cp,
                          int64_t n_pool, int DP, int kernel, double os, double noise, double sm, T* G);
 int path_finish_launch(algp_ctx* c, const int64_t* cpos, int ppad, int batch, const double* logdet, const int* info, double* out);
+// best_path under the MI criterion (paths_mi.hip): rows of a resident triangular inverse X = L^-T, zero left of each row's
+// diagonal tile (-1: a zero row); ones on the diagonal behind each path's cnt[b] sites; the operands Lt = G^T, LtD = G^T diag(delta)
+// of I + G^T diag(delta) G from the 2 x 2 tiled factor G of a batch of ppad x ppad blocks (L21 in its own NB x NB buffer per block)
+template <typename T>
+int mi_tri_gather_launch(algp_ctx* c, const T* X, int64_t ldx, const int64_t* src_row, T* dst, int64_t ldd, int64_t nrows,
+                         int64_t ncols);
+template <typename T>
+int mi_pad_diag_launch(algp_ctx* c, T* G, int ppad, const int* cnt, int batch);
+template <typename T>
+int mi_transpose_launch(algp_ctx* c, const T* G, const T* L21, const T* delta, int ppad, T* Lt, T* LtD, int batch);
 // greedy commit bookkeeping on the device: scale of the appended row, pick record, winner retired, (d_c, scale) out
 template <typename T>
 int commit_finalize_launch(algp_ctx* c, const T* dsrc, int in_train, double ss, double delta, LazyPick* lp_out,

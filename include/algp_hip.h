@@ -212,8 +212,25 @@ int algp_greedy(algp_ctx* ctx, int criterion, double static_std, double mobile_s
  * 2 x 2 tiles of 128 (batches of paths sized to ~4 GB of scratch).  More than 256 distinct sites: ALGP_ERR_BAD_ARG.  A site that already is a train row
  * (a statically sampled site crossed by the path) receives a second row, which is the same GP as the reference's fused
  * noise (agent.py:100-109) up to the constant log(sigma_s^2 + sigma_m^2)/2 + CONST per such site (the caller's to
- * subtract, see algp_amd/agent.py); the caller leaves out sites that already have a mobile row (no new reading).  The MI criterion's path utility stays with algp_set_entropy. */
+ * subtract, see algp_amd/agent.py); the caller leaves out sites that already have a mobile row (no new reading).  The MI
+ * criterion's path utility is algp_score_paths_mi below. */
 int algp_score_paths(algp_ctx* ctx, const int64_t* sites, int npaths, int maxlen, double mobile_std, double* dH_out);
+/* algp_score_paths_mi: Agent.best_path under the mutual-information criterion (agent.py:374-400: ent_a + ent_abar - ent_all
+ * per path, the last two pool-sized).  The train set is the fused base A0 (one row per site, its noise v_a); sites[] as for
+ * algp_score_paths, holding the sites path p CHANGES: a site outside A0 joins it with noise mobile_std^2 and leaves the
+ * complement; a train site is re-measured, its noise v_a -> v_a sm / (v_a + sm) (sm = mobile_std^2).  The caller leaves out
+ * sites whose reading changes nothing (already mobile-sampled); -1 entries are skipped, a site listed twice counts once.
+ * dMI_out[p] = dH_A + dH_Abar - dH_all, the path's utility minus the base's; terms_out (npaths x 3: the three terms, may be
+ * NULL).  dH_A = the fused-form entropy gain (algp_score_paths' rows form minus CONST + log(v_a + sm)/2 per re-measured site);
+ * dH_Abar = 1/2 log det P[S_new, S_new] - |S_new| CONST with P = C_AbarAbar^-1 (Jacobi's identity); dH_all = 1/2 log det
+ * (I + G^T D G), Q[S, S] = G G^T, Q = (C + D0)^-1, D = diag of the noise changes (matrix determinant lemma).  P and Q are
+ * the two pool-wide inverses the MI greedy keeps resident: built once per candidate solve (ALGP_ERR_OOM with the byte count,
+ * before any allocation, when they do not fit), reused by every later call on the same state.  Per batch of paths their
+ * rows are gathered, the blocks are batched MFMA Gram products, factored as 2 x 2 tiles of 128.  Preconditions as for
+ * algp_score_paths (a candidate solve with prior_includes_noise, every site a resident candidate, no pick committed since):
+ * ALGP_ERR_STATE; a train set that lists a site twice: ALGP_ERR_STATE; more than 256 changing sites: ALGP_ERR_BAD_ARG. */
+int algp_score_paths_mi(algp_ctx* ctx, const int64_t* sites, int npaths, int maxlen, double static_std, double mobile_std,
+                        double* dMI_out, double* terms_out);
 
 /* ---- (e) multi-GPU: the loop over candidates (agent.py:317-347) cut into shards, one process and one ctx per GPU ----
  * Every rank factorises the same train set (algp_factorize / algp_fit_and_solve) and holds a share of the candidate list
