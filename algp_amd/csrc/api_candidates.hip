@@ -31,11 +31,15 @@ int Impl<T>::set_candidates(algp_ctx* c, const int64_t* idx, int64_t M, int prio
     return ALGP_OK;
 }
 
+// The candidate solve's route (SolvePlan), decided once per call.  The only reader of the solve's switches, per plan (tests
+// flip them): $ALGP_TAIL_COLS=0 (the 128-column blocks, the full last tile), $ALGP_SOLVE_DAG=0 (the sweep for mid-sized
+// solves), $ALGP_ROW_STATS=0 (the sweep without its row statistics), $ALGP_FOLD=0 (fit_and_solve as its two phases).
 template <typename T>
-int Impl<T>::solve_prepare(algp_ctx* c, int incremental, typename Impl<T>::SolvePlan& pl) {
+void Impl<T>::plan_route(algp_ctx* c, int incremental, bool allow_fold, typename Impl<T>::SolvePlan& pl) {
+    const bool tail_on = env_switch("ALGP_TAIL_COLS", true), solve_dag_on = env_switch("ALGP_SOLVE_DAG", true),
+               stats_on = env_switch("ALGP_ROW_STATS", true), fold_on = allow_fold && env_switch("ALGP_FOLD", true);
     const int64_t N = c->N, Npad = c->Npad, M = c->M, Mpad = c->Mpad;
     pl.carried_sums = incremental && c->uw_rows == N && c->uvec.p && c->wvec.p;
-    const int64_t ldv = Npad + MAX_APPEND;
     int64_t keep = 0;
     if (incremental && c->Vt.p && c->vt_hyp_stamp == c->hyp_stamp && c->vt_prior_noise == c->prior_noise &&
         !c->vt_has_extra && !c->cextra.p && c->vt_cand_idx == c->cand_idx) {
@@ -47,8 +51,7 @@ int Impl<T>::solve_prepare(algp_ctx* c, int incremental, typename Impl<T>::Solve
         // so only [p0, N) has to be solved -- at 16-column granularity, as one or two ranges of at most 64 columns inside
         // a 128-column block of the factor (tail.hip): HBM-bound, where re-solving the whole open 128-block walks all of
         // V^T on the matrix cores at full tile width (28 -> 13 ms per step at N = 50 000 x 100 000 candidates).
-        // $ALGP_TAIL_COLS=0: the 128-column blocks as before.  Small problems keep them too (nothing to gain).
-        const bool tail_on = env_switch("ALGP_TAIL_COLS", true);                                 // read per call: tests flip it
+        // Small problems keep the 128-column blocks (nothing to gain).
         if (tail_on && p0 >= 2048 && Mpad >= 2048 && c->cur == c->stream) {
             // exactly the appended rows [p0, N) when there are at most 64 of them (tail.hip handles any first column; the
             // epilogue's inverse is that of a window of L around the range, solve_run); more than 64: from the 16-column
@@ -106,6 +109,32 @@ int Impl<T>::solve_prepare(algp_ctx* c, int incremental, typename Impl<T>::Solve
     }
     if (keep == 0) { pl.nseg = 0; pl.seg_window = false; }
     pl.keep = keep;
+    if (pl.nseg > 0) { pl.route = SolveRoute::Segments; return; }
+    // Up to 400 x 128 rows, from scratch: fit_and_solve folds the solve into the factorisation's launch; solve_candidates
+    // runs 33 .. 400 tile rows (a rank's share of the candidates on 4-8 GPUs, a held-out set) as ONE task-list launch
+    // (chol_dag.hip without the factorisation's own tasks).  Everything else is the sweep.
+    if (fold_on && M > 0 && panel_fits(Npad, Mpad)) pl.route = SolveRoute::Folded;
+    else if (solve_dag_on && keep == 0 && Mpad / NB > 32 && panel_fits(Npad, Mpad) && c->cur == c->stream) pl.route = SolveRoute::TaskList;
+    else pl.route = SolveRoute::Sweep;
+    // A train set that ends a few columns into its last 128-column tile (N = 10 000: 16 of 128) pays a full tile's price for
+    // them: 79 K-steps of the task list per tile row, 2 M 128 N flop of the sweep (2.1 % of config 4's solve).  Up to 64 such
+    // columns are instead what an append would add to a factor of N - r rows: the route solves the full tiles, the tail
+    // kernel (tail.hip, HBM-bound: one pass over V^T) the rest.  On the task-list and folded routes the tile row that
+    // carries y - ybar (a last tile with padding rows, fit_and_solve) keeps every column, so both do the same arithmetic.
+    const int64_t r = N % NB, N1 = Npad - NB;
+    const bool narrow = r > 0 && r <= 64 && N1 >= 2048 && Mpad >= 2048 && tail_on &&
+                        (pl.route != SolveRoute::Sweep || (keep == 0 && c->cur == c->stream && Mpad / NB > SWEEP_PUSH_TILES));
+    if (narrow) {
+        pl.narrow_r = (int)r;
+        pl.short_rows = pl.route == SolveRoute::Sweep ? Mpad : M < Mpad ? Mpad - NB : Mpad;
+    }
+    pl.row_stats = pl.route == SolveRoute::Sweep && stats_on && keep == 0 && !pl.carried_sums;
+}
+
+template <typename T>
+int Impl<T>::solve_prepare(algp_ctx* c, int incremental, typename Impl<T>::SolvePlan& pl) {
+    const int64_t N = c->N, Npad = c->Npad, M = c->M, Mpad = c->Mpad, keep = pl.keep;
+    const int64_t ldv = Npad + MAX_APPEND;
     c->solved = false;
     if (!c->Vt.p || c->ldv_cap < ldv || (keep == 0 && !incremental && c->ldv_cap != ldv) ||
         c->Vt.cap < sizeof(T) * Mpad * c->ldv_cap) {
@@ -138,11 +167,12 @@ int Impl<T>::solve_prepare(algp_ctx* c, int incremental, typename Impl<T>::Solve
         // greedy semantics: a candidate that is a train site is the unit vector e_pos (its
         // noise changes); predictive semantics: it is an ordinary point at the same location
         ALGP_TRY(ensure(c, c->ckind, sizeof(int) * Mpad));
-        ALGP_HIP(hipMemcpyAsync(c->ckind.p, kind.data(), sizeof(int) * Mpad, hipMemcpyHostToDevice, c->stream));
-        if (!became_unit.empty() && keep > 0) {                      // one launch for all of them
-            ALGP_TRY(ensure(c, c->auxIdx, sizeof(int64_t) * became_unit.size()));
-            ALGP_HIP(hipMemcpyAsync(c->auxIdx.p, became_unit.data(), sizeof(int64_t) * became_unit.size(), hipMemcpyHostToDevice, c->stream));
-            ALGP_TRY(zero_listed_rows_launch<T>(c, p(c->Vt), ldc, (const int64_t*)c->auxIdx.p, (int64_t)became_unit.size(), keep));
+        ALGP_HIP(hipMemcpyAsync(c->ckind.p, pl.kind.data(), sizeof(int) * Mpad, hipMemcpyHostToDevice, c->stream));
+        if (!pl.became_unit.empty() && keep > 0) {                      // one launch for all of them
+            const size_t nb = pl.became_unit.size();
+            ALGP_TRY(ensure(c, c->auxIdx, sizeof(int64_t) * nb));
+            ALGP_HIP(hipMemcpyAsync(c->auxIdx.p, pl.became_unit.data(), sizeof(int64_t) * nb, hipMemcpyHostToDevice, c->stream));
+            ALGP_TRY(zero_listed_rows_launch<T>(c, p(c->Vt), ldc, (const int64_t*)c->auxIdx.p, (int64_t)nb, keep));
         }
         ALGP_TRY(sync(c));
     }
@@ -155,17 +185,14 @@ int Impl<T>::solve_prepare(algp_ctx* c, int incremental, typename Impl<T>::Solve
 }
 
 
-// the solve proper, against the resident factor.  A from-scratch solve of 33 .. 400 tile rows (a rank's share of the
-// candidates on 4-8 GPUs, a held-out set) runs as ONE task-list launch (chol_dag.hip without the factorisation's
-// own tasks; $ALGP_SOLVE_DAG=0: the launch sequences of potrf.hip); everything else is trsm_blocked.
+// the solve proper, against the resident factor: the plan's route, then its narrow last tile
 template <typename T>
 int Impl<T>::solve_run(algp_ctx* c, typename Impl<T>::SolvePlan& pl) {
-    const bool solve_dag_on = env_switch("ALGP_SOLVE_DAG", true);                                // read per call: tests flip it
     const int64_t Npad = c->Npad, Mpad = c->Mpad, ldc = c->ldv, keep = pl.keep;
     prof_span_begin(c, ALGP_PROF_TRSM, (double)(Npad - keep) * (double)(Npad + keep) * (double)Mpad,
                     sizeof(T) * (double)Mpad * (double)Npad);
     int trc = ALGP_OK;
-    if (pl.nseg > 0 && pl.seg_window) {
+    if (pl.route == SolveRoute::Segments && pl.seg_window) {
         // the inverse of a 128 x 128 window of L that contains the range (inv(D)[S, S] = inv(D[S, S]) for any diagonal range S of
         // a lower-triangular D): from the range's first column, or -- near the end of the factor -- the last 128 rows
         const int64_t w0 = std::min<int64_t>(pl.seg_c0[0], Npad - NB), o = pl.seg_c0[0] - w0;
@@ -174,47 +201,42 @@ int Impl<T>::solve_run(algp_ctx* c, typename Impl<T>::SolvePlan& pl) {
         if (trc == ALGP_OK)
             trc = tail_cols_launch<T>(c, ALGP_PROF_TAIL_COLS, p(c->Vt), Mpad, ldc, p(c->L), c->Lld, Npad, (const T*)nullptr,
                                       pl.seg_c0[0], pl.seg_w[0], p(c->tailE) + o * NB + o);
-    } else if (pl.nseg > 0) {
+    } else if (pl.route == SolveRoute::Segments) {
         for (int q = 0; q < pl.nseg && trc == ALGP_OK; ++q)
             trc = tail_cols_launch<T>(c, ALGP_PROF_TAIL_COLS, p(c->Vt), Mpad, ldc, p(c->L), c->Lld, Npad,
                                       p(c->invD) + (pl.seg_c0[q] / NB) * NB * NB, pl.seg_c0[q], pl.seg_w[q]);
-    } else if (solve_dag_on && keep == 0 && Mpad / NB > 32 && panel_fits(Npad, Mpad) && c->cur == c->stream) {
-        // (a narrow last tile: every tile row leaves it out of the list, the tail kernel solves its columns -- as in
-        // fit_and_solve, so that the two forms stay the same arithmetic)
-        const int64_t r = c->N % NB, N1 = Npad - NB;
-        const bool narrow = r > 0 && r <= 64 && N1 >= 2048 && Mpad >= 2048 && env_switch("ALGP_TAIL_COLS", true);
-        // the tile row in which fit_and_solve carries y - ybar (a last tile with padding rows) keeps every column here too
-        const int64_t short_rows = !narrow ? 0 : (c->M < Mpad ? Mpad - NB : Mpad);
+    } else if (pl.route == SolveRoute::TaskList) {
         trc = solve_dag_panel<T>(c, p(c->L), Npad, c->Lld, p(c->invD), (int*)((double*)c->scal.p + SC_STALL), p(c->Vt), ldc, Mpad, 1,
-                                 (int)(short_rows / NB));
-        if (short_rows > 0 && trc == ALGP_OK)
-            trc = tail_cols_launch<T>(c, ALGP_PROF_TAIL_COLS, p(c->Vt), short_rows, ldc, p(c->L), c->Lld, Npad, p(c->invD) + (N1 / NB) * NB * NB,
-                                      N1, (int)round_up(r, 16));
-    } else {
-        // a from-scratch solve of more than 320 tile rows: its launches leave the rows' sums of v^2 and v z per column tile
-        // (utils.py:301-304 needs nothing else of V^T), the 8 GB pass over V^T at config 4 falls away
+                                 (int)(pl.short_rows / NB));
+    } else if (pl.route == SolveRoute::Sweep) {
+        // a from-scratch solve of more than SWEEP_PUSH_TILES tile rows: its launches leave the rows' sums of v^2 and v z per
+        // column tile (utils.py:301-304 needs nothing else of V^T), the 8 GB pass over V^T at config 4 falls away
         T* stat = nullptr;
-        const bool stats_on = env_switch("ALGP_ROW_STATS", true);                                  // read per call: tests flip it
-        if (stats_on && keep == 0 && !pl.carried_sums && ensure(c, c->rowstat, sizeof(T) * 2 * (size_t)(Npad / NB) * (size_t)Mpad) == ALGP_OK)
+        if (pl.row_stats && ensure(c, c->rowstat, sizeof(T) * 2 * (size_t)(Npad / NB) * (size_t)Mpad) == ALGP_OK)
             stat = p(c->rowstat);
-        // A train set that ends a few columns into its last 128-column tile (N = 10 000: 16 of 128) pays the sweep's full price
-        // for that tile -- 2 M 128 N flop, 2.1 % of config 4's solve, for 16 columns.  Up to 64 such columns are instead what an
-        // APPEND would add to a factor of N - r rows: the sweep solves the full tiles, the tail kernel (tail.hip, HBM-bound:
-        // one pass over V^T) the rest, and one 128-column reduction leaves the last tile's row statistics where the sweep's
-        // launches would have (round 6; $ALGP_TAIL_COLS=0: the sweep alone).
-        const int64_t r = c->N % NB, N1 = Npad - NB;
-        const bool narrow = keep == 0 && r > 0 && r <= 64 && N1 >= 2048 && Mpad >= 2048 && c->cur == c->stream &&
-                            Mpad / NB > 320 && env_switch("ALGP_TAIL_COLS", true);      // (320 tile rows: where the chunked sweep begins, potrf.hip)
-        trc = trsm_blocked<T>(c, ALGP_PROF_GEMM_TRSM, p(c->Vt), Mpad, ldc, p(c->L), narrow ? N1 : Npad, c->Lld, p(c->invD), keep, p(c->z),
-                              stat, Mpad, &pl.rowstat_done);
-        if (narrow && trc == ALGP_OK)
-            trc = tail_cols_launch<T>(c, ALGP_PROF_TAIL_COLS, p(c->Vt), Mpad, ldc, p(c->L), c->Lld, Npad, p(c->invD) + (N1 / NB) * NB * NB, N1,
-                                      (int)round_up(r, 16));
-        if (narrow && trc == ALGP_OK && pl.rowstat_done)
-            trc = rows_reduce_launch<T>(c, p(c->Vt) + N1, Mpad, ldc, NB, p(c->z) + N1, stat + 2 * (N1 / NB) * Mpad, stat + (2 * (N1 / NB) + 1) * Mpad);
+        trc = trsm_blocked<T>(c, ALGP_PROF_GEMM_TRSM, p(c->Vt), Mpad, ldc, p(c->L), pl.narrow_r ? Npad - NB : Npad, c->Lld, p(c->invD),
+                              keep, p(c->z), stat, Mpad, &pl.rowstat_done);
+    } else {
+        trc = fail(c, ALGP_ERR_STATE, "internal: the folded route is solved by the factorisation's launch (fit_and_solve)");
     }
+    if (trc == ALGP_OK) trc = solve_narrow_tile(c, pl);
     prof_span_end(c);
     return trc;
+}
+
+
+// behind the route's launch: the tail kernel solves a narrow last tile's columns of the first short_rows rows (one pass over
+// V^T), and where the sweep's launches left the row statistics, one 128-column reduction adds the last tile's
+template <typename T>
+int Impl<T>::solve_narrow_tile(algp_ctx* c, const typename Impl<T>::SolvePlan& pl) {
+    if (pl.narrow_r == 0) return ALGP_OK;
+    const int64_t Mpad = c->Mpad, ldc = c->ldv, N1 = c->Npad - NB;
+    ALGP_TRY(tail_cols_launch<T>(c, ALGP_PROF_TAIL_COLS, p(c->Vt), pl.short_rows, ldc, p(c->L), c->Lld, c->Npad,
+                                 p(c->invD) + (N1 / NB) * NB * NB, N1, (int)round_up(pl.narrow_r, 16)));
+    if (!pl.rowstat_done) return ALGP_OK;
+    T* stat = p(c->rowstat);
+    return rows_reduce_launch<T>(c, p(c->Vt) + N1, Mpad, ldc, NB, p(c->z) + N1, stat + 2 * (N1 / NB) * Mpad,
+                                 stat + (2 * (N1 / NB) + 1) * Mpad);
 }
 
 
@@ -283,6 +305,7 @@ template <typename T>
 int Impl<T>::solve_candidates(algp_ctx* c, int incremental, const unsigned char* alive_host) {
     if (!c->factored || c->train_dirty) return fail(c, ALGP_ERR_STATE, "solve_candidates: call algp_factorize first");
     SolvePlan pl;
+    plan_route(c, incremental, false, pl);
     ALGP_TRY(solve_prepare(c, incremental, pl));
     ALGP_TRY(solve_run(c, pl));
     return solve_finish(c, incremental, alive_host, pl);
@@ -290,23 +313,25 @@ int Impl<T>::solve_candidates(algp_ctx* c, int incremental, const unsigned char*
 
 
 // GP-fit + candidate solve of one planning step (bench.py's step).  Up to 400 x 128 candidate rows (a rank's share on
-// 2-8 GPUs) the two are ONE launch: the rows of B^T are extra block rows of the factorisation's task list (TRSM / UPD
-// tasks without a diagonal), so V^T = B^T L^-T comes out of the launch that factors S -- the candidates' tile products
-// fill the machine while the diagonal chain alone would leave it idle, and the 140 short launches of a separate
-// mid-sized solve disappear ($ALGP_FOLD=0: the two phases back to back).  Larger candidate sets keep the two phases:
-// the factorisation, then the three-stream sweep of potrf.hip, which wins from ~55 000 rows on.  (Overlapping the two
-// as separate launch sequences on streams was measured in round 1 -- 207 vs 193 ms/step -- and removed.)
+// 2-8 GPUs) the two are ONE launch (the folded route): the rows of B^T are extra block rows of the factorisation's task
+// list (TRSM / UPD tasks without a diagonal), so V^T = B^T L^-T comes out of the launch that factors S -- the candidates'
+// tile products fill the machine while the diagonal chain alone would leave it idle, and the 140 short launches of a
+// separate mid-sized solve disappear.  Larger candidate sets keep the two phases: the factorisation, then the
+// three-stream sweep of potrf.hip, which wins from ~55 000 rows on.  (Overlapping the two as separate launch sequences on
+// streams was measured in round 1 -- 207 vs 193 ms/step -- and removed.)
 template <typename T>
 int Impl<T>::fit_and_solve(algp_ctx* c) {
-    const bool fold_on = env_switch("ALGP_FOLD", true);                                          // read per call: tests flip it
-    if (!fold_on || c->M == 0 || !panel_fits(c->Npad, c->Mpad)) {
+    SolvePlan pl;
+    plan_route(c, 0, true, pl);
+    if (pl.route != SolveRoute::Folded) {
         ALGP_TRY(factorize(c, 0));
-        return solve_candidates(c, 0, nullptr);
+        ALGP_TRY(solve_prepare(c, 0, pl));
+        ALGP_TRY(solve_run(c, pl));
+        return solve_finish(c, 0, nullptr, pl);
     }
     c->factored = false;
-    SolvePlan pl;
     ALGP_TRY(solve_prepare(c, 0, pl));                           // B^T is in place before the launch that consumes it
-    Panel pn{p(c->Vt), c->ldv, c->Mpad, 1, false};
+    Panel pn{p(c->Vt), c->ldv, c->Mpad, 1};
     // a spare (padding) row of the candidates' last tile carries y - ybar through the launch: z = L^-1 (y - ybar) comes out
     // as that row of P L^-T, and the forward substitution behind the launch (0.41 ms at N = 10 000, with the machine
     // idle) falls away (a candidate count that fills its last tile keeps the substitution)
@@ -314,20 +339,9 @@ int Impl<T>::fit_and_solve(algp_ctx* c) {
         pn.z_row = c->M;
         ALGP_HIP(hipMemcpyAsync(p(c->Vt) + c->M * c->ldv, c->y0.p, sizeof(T) * c->Npad, hipMemcpyDeviceToDevice, c->stream));
     }
-    // A narrow last tile (N = 10 000: 16 of 128 columns) costs every panel tile row 79 K-steps of the list for 16 columns --
-    // 2.5 % of the panel's work.  The tile rows that do not carry z leave that column tile out (DagShape::pshort) and the
-    // tail kernel solves the r columns behind the launch (one pass over the rank's V^T: 0.2 ms for 12 500 rows).
-    const int64_t r = c->N % NB, N1 = c->Npad - NB;
-    if (r > 0 && r <= 64 && N1 >= 2048 && c->Mpad >= 2048 && env_switch("ALGP_TAIL_COLS", true))
-        pn.short_rows = pn.z_row >= 0 ? c->Mpad - NB : c->Mpad;
+    pn.short_rows = pl.short_rows;
     ALGP_TRY(factorize(c, 0, &pn));
-    if (!pn.done) {
-        if (pn.z_row >= 0) ALGP_HIP(hipMemsetAsync(p(c->Vt) + pn.z_row * c->ldv, 0, sizeof(T) * c->Npad, c->stream));
-        ALGP_TRY(solve_run(c, pl));
-    } else if (pn.short_rows > 0) {
-        ALGP_TRY(tail_cols_launch<T>(c, ALGP_PROF_TAIL_COLS, p(c->Vt), pn.short_rows, c->ldv, p(c->L), c->Lld, c->Npad,
-                                     p(c->invD) + (N1 / NB) * NB * NB, N1, (int)round_up(r, 16)));
-    }
+    ALGP_TRY(solve_narrow_tile(c, pl));
     return solve_finish(c, 0, nullptr, pl);
 }
 

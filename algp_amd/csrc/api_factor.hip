@@ -17,13 +17,14 @@ bool Impl<T>::panel_fits(int64_t npad, int64_t mpad) {
 template <typename T>
 int Impl<T>::factor_resident(algp_ctx* c, T* A, int64_t n, int64_t npad, T* invD, int slot_logdet, int slot_info,
                                double* logdet, int64_t ld, int64_t pivot_offset, typename Impl<T>::Panel* panel) {
+    if (panel && !panel_fits(npad, panel->mpad))
+        return fail(c, ALGP_ERR_STATE, "internal: factor_resident was given a panel that does not fit the task list");
     if (ld == 0) ld = npad;
     double* sc = (double*)c->scal.p;
     ALGP_HIP(hipMemsetAsync(sc + slot_logdet, 0, 2 * sizeof(double), c->stream));
-    if (panel && panel_fits(npad, panel->mpad)) {
+    if (panel) {
         ALGP_TRY(cholesky_dag_panel<T>(c, A, npad, ld, invD, sc + slot_logdet, (int*)(sc + slot_info), panel->P, panel->ldp,
                                        panel->mpad, panel->mode, (int)(panel->short_rows / NB)));
-        panel->done = true;
         if (panel->mode == 2 && panel->inv_out && c->stream2 && c->cur == c->stream) {
             hipEvent_t ready = sync_event_api(c, 20), done = sync_event_api(c, 21);
             ALGP_HIP(hipEventRecord(ready, c->stream));
@@ -278,6 +279,7 @@ int Impl<T>::exchange_new_rows(algp_ctx* c, int64_t Nb, int64_t p0, int* placed,
 
 template <typename T>
 int Impl<T>::factorize(algp_ctx* c, int incremental, typename Impl<T>::Panel* panel) {
+    if (panel && incremental) return fail(c, ALGP_ERR_STATE, "internal: a panel rides along with a from-scratch factorisation only");
     const int64_t N = c->N, Npad = c->Npad;
     int64_t keep = 0, p0 = 0;                                // rows of the resident factor to keep; unchanged leading rows
     if (incremental && c->factored && c->fact_hyp_stamp == c->hyp_stamp && c->Lld > 0) {
@@ -383,7 +385,7 @@ int Impl<T>::factorize(algp_ctx* c, int incremental, typename Impl<T>::Panel* pa
     }
     prof_span_end(c);
     ALGP_TRY(frc);
-    T* z_src = (panel && panel->done && panel->z_row >= 0) ? panel->P + panel->z_row * panel->ldp : nullptr;
+    T* z_src = (panel && panel->z_row >= 0) ? panel->P + panel->z_row * panel->ldp : nullptr;
     return finish_factor(c, keep, p0, ld_total, z_src);
 }
 

@@ -57,18 +57,19 @@ template <typename T>
 int Impl<T>::fit_step(algp_ctx* c, double* mll_out, double* grad_out) {
     if (c->pool_is_cov) return fail(c, ALGP_ERR_BAD_ARG, "fit_step needs a coordinate pool");
     const int64_t Npad = c->Npad;
-    bool have_X = false, inv_enq = false;
+    bool inv_enq = false;
     // Round 5: z rides along too (a dense tile row behind the identity that carries y - ybar), and alpha = X z is one pass
     // over the X the launch leaves -- no substitution chain runs beside S^-1 = X X^T any more (the two took 5.5 ms there,
     // starved by the GEMM).  (X X^T as tasks of the same launch as well was built
     // and measured in round 5 -- the launch grew by what the separate 5.1-ms GEMM launch costs, 12.9 -> 18.9 ms at N = 10 000
     // fp64: the list leaves nothing idle to fill -- and removed again: EXPERIMENTS.md.)
     const int64_t prow = grad_out ? Npad + NB : Npad;
-    if (c->N > 0 && panel_fits(Npad, prow)) {
+    const bool have_X = c->N > 0 && panel_fits(Npad, prow);          // the identity rides along: X = L^-T in auxW
+    if (have_X) {
         ALGP_TRY(ensure(c, c->auxW, sizeof(T) * prow * Npad));
         ALGP_TRY(ensure(c, c->auxA, sizeof(T) * Npad * Npad));
         ALGP_TRY(set_identity_launch<T>(c, p(c->auxW), Npad, Npad));
-        Panel pn{p(c->auxW), Npad, prow, 2, false};
+        Panel pn{p(c->auxW), Npad, prow, 2};
         pn.inv_out = grad_out ? p(c->auxA) : nullptr;
         if (prow > Npad) {
             ALGP_HIP(hipMemsetAsync(p(c->auxW) + Npad * Npad, 0, sizeof(T) * NB * Npad, c->stream));
@@ -78,7 +79,6 @@ int Impl<T>::fit_step(algp_ctx* c, double* mll_out, double* grad_out) {
         const int frc = factorize(c, 0, &pn);
         if (pn.inv_enqueued && (frc != ALGP_OK || !grad_out)) hipStreamSynchronize(c->stream2);   // nothing outlives the call
         ALGP_TRY(frc);
-        have_X = pn.done;
         inv_enq = pn.inv_enqueued;
     } else {
         ALGP_TRY(factorize(c, 0));

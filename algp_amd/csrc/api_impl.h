@@ -22,6 +22,10 @@ KmatSrc make_src(algp_ctx* c);
 int sync(algp_ctx* c);
 int sync_checked(algp_ctx* c, const char* what);
 
+// how the candidate solve runs (Impl::SolvePlan): the new columns only (tail.hip), one task-list launch (chol_dag.hip),
+// the sweep (trsm_blocked, potrf.hip), or folded into the factorisation's own launch (fit_and_solve)
+enum class SolveRoute { Segments, TaskList, Sweep, Folded };
+
 template <typename T>
 struct Impl {
     static T* p(DevBuf& b) { return (T*)b.p; }
@@ -34,18 +38,17 @@ struct Impl {
     static int set_train(algp_ctx* c, const int64_t* idx, int64_t N, const void* y, const void* var);
 
     // Rows that ride along with a factorisation as extra block rows of its task list (chol_dag.hip): P <- P L^-T comes out
-    // of the same launch.  done: the launch took them (otherwise the caller solves them afterwards).
+    // of the same launch.  Only a from-scratch factorisation takes a panel, and only one that panel_fits (its caller checks).
     struct Panel {
         T* P;
         int64_t ldp, mpad;
         int mode;                  // 1: dense rows (the candidates' B^T), 2: the identity (-> L^-T)
-        bool done;
         T* inv_out = nullptr;      // mode 2: S^-1 = P P^T (lower tiles, ld = mpad) is enqueued on the helper stream right behind
         bool inv_enqueued = false; // the launch, beside the substitutions and read-backs that follow on the main stream
         int64_t z_row = -1;        // this row of P holds y - ybar (mode 1: a padding row; mode 2: a dense tile row behind the identity):
                                    // z^T = (y - ybar)^T L^-T comes out of the launch too
         int64_t short_rows = 0;    // mode 1: the first short_rows rows (a multiple of 128) leave their last column tile to the caller
-                                   // (the tail kernel solves a narrow last tile's columns afterwards: fit_and_solve)
+                                   // (SolvePlan::short_rows)
     };
     static bool panel_fits(int64_t npad, int64_t mpad);
     static int factor_resident(algp_ctx* c, T* A, int64_t n, int64_t npad, T* invD, int slot_logdet, int slot_info,
@@ -65,22 +68,31 @@ struct Impl {
     // were solved against rows of the factor that are unchanged (same leading train rows, same
     // hyper-parameters, same candidate list) are kept and only the trailing column blocks are solved.
     // `alive` (M bytes, may be null) disables candidates (sites that became static-sampled).
-    // Three parts, so that algp_fit_and_solve can put the factorisation between the first two and let the rows of B^T
-    // ride along in its launch: solve_prepare (buffers, candidate kinds, B^T), the solve itself, solve_finish (row
+    // plan_route decides the whole route once per call; then solve_prepare (buffers, candidate kinds' upload, B^T), the
+    // solve itself (solve_run, or the factorisation's launch on the folded route: fit_and_solve), solve_finish (row
     // statistics, bookkeeping).
     struct SolvePlan {
+        SolveRoute route = SolveRoute::Sweep;
         int64_t keep = 0;                    // leading columns of V^T that stay
         std::vector<int> kind;               // per candidate: its train row (a unit right-hand side) or -1
         std::vector<int64_t> became_unit;
         bool carried_sums = false;           // solve_finish will carry the rows' sums from step to step (u, w form of z)
-        bool rowstat_done = false;           // solve_run's launches left the rows' sums per column tile in c->rowstat
-        int nseg = 0;                        // > 0: only the new columns are solved (tail.hip), as 1-2 ranges [seg_c0, seg_c0 + seg_w)
+        int nseg = 0;                        // Segments: only the new columns are solved (tail.hip), as 1-2 ranges [seg_c0, seg_c0 + seg_w)
         int64_t seg_c0[2] = {0, 0};
         int seg_w[2] = {0, 0};
         bool seg_window = false;             // the one range straddles two 128-column blocks of the factor
+        int narrow_r = 0;                    // > 0: the last column tile holds only narrow_r columns: the route solves the first
+        int64_t short_rows = 0;              // short_rows rows without that tile, the tail kernel its columns (solve_narrow_tile)
+        bool row_stats = false;              // Sweep: ask its launches for the rows' sums per column tile
+        bool rowstat_done = false;           // solve_run's launches left the rows' sums per column tile in c->rowstat
     };
+    // a sweep of more than this many tile rows runs left-looking in row chunks; only there does a narrow last tile go to
+    // the tail kernel (and only there do the row statistics ride along).  Mirrors TRSM_PUSH_TILES in potrf.hip.
+    static constexpr int64_t SWEEP_PUSH_TILES = 320;
+    static void plan_route(algp_ctx* c, int incremental, bool allow_fold, SolvePlan& pl);
     static int solve_prepare(algp_ctx* c, int incremental, SolvePlan& pl);
     static int solve_run(algp_ctx* c, SolvePlan& pl);
+    static int solve_narrow_tile(algp_ctx* c, const SolvePlan& pl);
     static int solve_finish(algp_ctx* c, int incremental, const unsigned char* alive_host, const SolvePlan& pl);
     static int solve_candidates(algp_ctx* c, int incremental, const unsigned char* alive_host);
     static int fit_and_solve(algp_ctx* c);
