@@ -91,6 +91,7 @@ SIGNATURES = {
     'algp_comm_init_host': (C.c_int, [_c_ctx, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'algp_comm_destroy': (C.c_int, [_c_ctx]),
     'algp_comm_set_owners': (C.c_int, [_c_ctx, C.POINTER(C.c_int32), C.c_int64]),
+    'algp_comm_set_mi_groups': (C.c_int, [_c_ctx, C.c_int]),
     'algp_debug_first_max': (C.c_int, [_c_ctx, _dblp, C.c_int, _dblp]),
     'algp_debug_fail_next_pick': (C.c_int, [_c_ctx, C.c_int]),
     'algp_debug_set_trsm_chunks': (C.c_int, [_c_ctx, C.c_int]),
@@ -472,6 +473,12 @@ class Context(object):
         o = np.ascontiguousarray(owner, dtype=np.int32).reshape(-1)
         self._check(self.lib.algp_comm_set_owners(self.h, o.ctypes.data_as(C.POINTER(C.c_int32)), len(o)))
 
+    def comm_set_mi_groups(self, n_complement_ranks):
+        """The MI criterion's layout for greedy_sharded: ranks [0, n_complement_ranks) hold the complement's inverse, the
+        others the whole pool's (a world of one: 1, both on the one rank; 0 detaches).  Every rank, the same value, after
+        comm_init[_host] (algp_comm_set_mi_groups)."""
+        self._check(self.lib.algp_comm_set_mi_groups(self.h, int(n_complement_ranks)))
+
     def counter(self, which):
         """algp_debug_counter: 0 stream synchronisations so far | 1 rows of L the last factor update placed without a
         triangular solve | 2 how many of them arrived from other ranks | 3 row exchanges so far | 4 agreed fall-backs."""
@@ -493,7 +500,8 @@ class Context(object):
 
     def debug_fail_at(self, where, code):
         """Inject `code` into this rank's next greedy pick: where = 0 resolving its best, 1 committing the winner (after the
-        exchange), 2 packing its contribution, 3 the agreement word of its next sharded factor update (algp_debug_fail_at)."""
+        exchange), 2 packing its contribution, 3 the agreement word of its next sharded factor update, 4 the next step of the
+        sharded MI state -- its build after a solve, else the fold of a committed pick (algp_debug_fail_at)."""
         self._check(self.lib.algp_debug_fail_at(self.h, int(where), int(code)))
 
     def debug_trsv_stall(self, block):
@@ -524,7 +532,8 @@ class Context(object):
         return int(self.lib.algp_debug_counter(self.h, 0))
 
     def greedy_sharded(self, criterion, static_std, mobile_std, k, want_utilities=False):
-        """k picks over the candidate shards of all ranks (one RCCL all-gather per pick inside the library)."""
+        """k picks over the candidate shards of all ranks (one all-gather per pick inside the library; the MI criterion also
+        needs comm_set_mi_groups and adds two per pick)."""
         picks = np.empty(int(k), dtype=np.int64)
         ut = np.empty(int(k), dtype=np.float64) if want_utilities else None
         self._check(self.lib.algp_greedy_sharded(self.h, int(criterion), float(static_std), float(mobile_std), int(k),

@@ -395,8 +395,6 @@ class Agent(object):
             c.set_candidates(cand[~static[cand]], prior_includes_noise=True)
             c.fit_and_solve()                                   # one task-list launch up to 51 200 candidates
         if self.comm is not None:
-            if self.criterion != 'entropy':
-                raise ValueError('only the entropy criterion shards (the MI criterion needs the pool-wide complement on one GPU)')
             picks = c.greedy_sharded(_CRIT[self.criterion], self.static_std, self.mobile_std, int(num_samples))
         else:
             picks = c.greedy(_CRIT[self.criterion], self.static_std, self.mobile_std, int(num_samples))

@@ -100,6 +100,7 @@ int Impl<T>::mi_build(algp_ctx* c, double ss, double sm) {
     c->mi_nbar = 0;
     c->mi_ss = ss;
     c->mi_sm = sm;
+    c->mi_form = 0;
     c->mi_valid = true;
     return ALGP_OK;
 }
@@ -134,7 +135,12 @@ int Impl<T>::mi_apply_pick(algp_ctx* c, int64_t q, double ss, double sm) {
 
 template <typename T>
 int Impl<T>::mi_scores_enqueue(algp_ctx* c, double ss, double sm, double delta, double* dst) {
-    if (!c->mi_valid || c->mi_ss != ss || c->mi_sm != sm || (int64_t)c->picks.size() < c->mi_npicks) {
+    // a sharded state (api_mi_shard.hip) that is up to date scores as it is: its diagonals and entropies are whole on every
+    // rank; with picks still to fold (they need its collectives) this GPU builds the whole inverses instead
+    const bool sharded_current = c->mi_form == 1 && c->mi_valid && c->mi_ss == ss && c->mi_sm == sm &&
+                                 c->mi_npicks == (int64_t)c->picks.size();
+    if (!sharded_current && (!c->mi_valid || c->mi_form != 0 || c->mi_ss != ss || c->mi_sm != sm ||
+                             (int64_t)c->picks.size() < c->mi_npicks)) {
         c->mi_valid = false;
         ALGP_TRY(mi_build(c, ss, sm));
     }
@@ -424,7 +430,8 @@ int Impl<T>::best_candidate(algp_ctx* c, int criterion, double static_std, doubl
 // Nothing rank-local returns before the exchange: a failure becomes this rank's status word, every rank sees it in
 // the same gather and every rank returns it -- nobody is left waiting in a collective.
 template <typename T>
-int Impl<T>::greedy_picks(algp_ctx* c, double static_std, double mobile_std, int k, int64_t* picks_out, double* ut_out) {
+int Impl<T>::greedy_picks(algp_ctx* c, int criterion, double static_std, double mobile_std, int k, int64_t* picks_out,
+                           double* ut_out) {
     const double ss = static_std * static_std, sm = mobile_std * mobile_std;
     const double delta = 1.0 / (1.0 / ss + 1.0 / sm) - sm;
     double* sc = (double*)c->scal.p;
@@ -447,7 +454,13 @@ int Impl<T>::greedy_picks(algp_ctx* c, double static_std, double mobile_std, int
                 st = fail(c, c->pending_pick_error, c->pending_pick_msg);
                 c->pending_pick_error = 0;
             }
-            if (st == ALGP_OK && c->M > 0) st = ensure_bounds(c, ALGP_CRIT_ENTROPY, static_std, mobile_std, ss, delta);
+            if (criterion == ALGP_CRIT_MUTUAL_INFORMATION && round == 0 && c->comm_nranks > 1) {
+                // the sharded MI state catches up with the committed picks: collectives of every rank, which carry st and
+                // return the same code on every rank when any of them failed (api_mi_shard.hip).  A world of one keeps the
+                // one-GPU state (mi_build, in place: two pool-sized matrices), built and folded by ensure_bounds below.
+                ALGP_TRY(mi_shard_step(c, ss, sm, st, pck == 0));
+            }
+            if (st == ALGP_OK && c->M > 0) st = ensure_bounds(c, criterion, static_std, mobile_std, ss, delta);
             if (st == ALGP_OK && c->M > 0) st = enqueue_local_best(c, ss, delta);
             const bool have = st == ALGP_OK && c->M > 0;             // an empty shard offers nothing; that is not an error
             const std::string local_err = c->err;
@@ -495,7 +508,7 @@ template <typename T>
 int Impl<T>::greedy(algp_ctx* c, int criterion, double static_std, double mobile_std, int k, const int64_t* forced,
                       int64_t* picks_out, double* ut_out) {
     if (!ut_out && !forced && criterion == ALGP_CRIT_ENTROPY && !c->comm && !c->host_gather)
-        return greedy_picks(c, static_std, mobile_std, k, picks_out, nullptr);
+        return greedy_picks(c, criterion, static_std, mobile_std, k, picks_out, nullptr);
     for (int pck = 0; pck < k; ++pck) {
         int64_t pool_idx;
         if (ut_out || forced) {
@@ -622,7 +635,8 @@ int algp_debug_fail_at(algp_ctx* c, int where, int code) {
     else if (where == 1) c->debug_fail_next_commit = code;
     else if (where == 2) c->debug_fail_next_pack = code;
     else if (where == 3) c->debug_fail_next_rowx = code;
-    else return fail(c, ALGP_ERR_BAD_ARG, "debug_fail_at: where = 0 (pick), 1 (commit), 2 (pack), 3 (row exchange)");
+    else if (where == 4) c->debug_fail_next_mi = code;
+    else return fail(c, ALGP_ERR_BAD_ARG, "debug_fail_at: where = 0 (pick), 1 (commit), 2 (pack), 3 (row exchange), 4 (sharded MI step)");
     return ALGP_OK;
 }
 #endif
@@ -638,11 +652,13 @@ int algp_greedy_sharded(algp_ctx* c, int criterion, double static_std, double mo
                         double* utilities_out) {
     CHECK_CTX(c);
     if (k < 0 || k > MAX_APPEND) return fail(c, ALGP_ERR_BAD_ARG, "greedy_sharded: 0 <= k <= 128");
-    if (criterion != ALGP_CRIT_ENTROPY)
-        return fail(c, ALGP_ERR_BAD_ARG, "greedy_sharded: only the entropy criterion shards (the MI criterion needs the "
-                                         "pool-wide complement on one GPU: use algp_greedy)");
+    if (criterion != ALGP_CRIT_ENTROPY && criterion != ALGP_CRIT_MUTUAL_INFORMATION)
+        return fail(c, ALGP_ERR_BAD_ARG, "greedy_sharded: unknown criterion");
+    if (criterion == ALGP_CRIT_MUTUAL_INFORMATION && c->mi_ncomp <= 0)
+        return fail(c, ALGP_ERR_BAD_ARG, "greedy_sharded: the MI criterion shards its pool-wide inverses over the ranks only with "
+                                         "a layout attached: call algp_comm_set_mi_groups on every rank first (or use algp_greedy)");
     if (!c->comm && !c->host_gather) return fail(c, ALGP_ERR_STATE, "greedy_sharded: call algp_comm_init (or algp_comm_init_host) first");
-    FINISH(c, DISPATCH(c, greedy_picks(c, static_std, mobile_std, k, picks_out, utilities_out)));
+    FINISH(c, DISPATCH(c, greedy_picks(c, criterion, static_std, mobile_std, k, picks_out, utilities_out)));
 }
 
 }  // extern "C"

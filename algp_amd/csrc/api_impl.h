@@ -111,6 +111,12 @@ struct Impl {
     static int trsm_host(algp_ctx* c, const void* L, int64_t n, const void* B, int64_t m, void* X);
     static int mi_build(algp_ctx* c, double ss, double sm);
     static int mi_apply_pick(algp_ctx* c, int64_t q, double ss, double sm);
+    // the MI state dealt over the ranks (api_mi_shard.hip): collectives, every rank calls them with its status st
+    struct MiPlan;
+    static int mi_shard_plan(algp_ctx* c, double ss, double sm, MiPlan& pl);
+    static int mi_shard_build(algp_ctx* c, MiPlan& pl, double* H3);
+    static int mi_shard_fold(algp_ctx* c, int st);
+    static int mi_shard_step(algp_ctx* c, double ss, double sm, int st, bool first_of_call);
     static int mi_scores_enqueue(algp_ctx* c, double ss, double sm, double delta, double* dst);
     static int scores_enqueue(algp_ctx* c, int criterion, double static_std, double mobile_std, double* dst);
     static int scores(algp_ctx* c, int criterion, double static_std, double mobile_std, void* out, int out_is_device);
@@ -140,7 +146,7 @@ struct Impl {
     static int ensure_bounds(algp_ctx* c, int criterion, double static_std, double mobile_std, double ss, double delta);
     static int best_candidate(algp_ctx* c, int criterion, double static_std, double mobile_std, int64_t* local_pos,
                               int64_t* pool_idx, double* value);
-    static int greedy_picks(algp_ctx* c, double static_std, double mobile_std, int k, int64_t* picks_out, double* ut_out);
+    static int greedy_picks(algp_ctx* c, int criterion, double static_std, double mobile_std, int k, int64_t* picks_out, double* ut_out);
     static int greedy(algp_ctx* c, int criterion, double static_std, double mobile_std, int k, const int64_t* forced,
                       int64_t* picks_out, double* ut_out);
     static int score_paths_big(algp_ctx* c, const std::vector<int64_t>& cpos, const std::vector<int64_t>& lpos, int npaths, int maxlen,

@@ -184,7 +184,7 @@ int Impl<T>::score_paths_mi(algp_ctx* c, const int64_t* sites, int npaths, int m
     }
     // the pool-wide inverses (their O(n^3) build, or ALGP_ERR_OOM up front): only when the MI state is not valid -- a solve
     // invalidates it, and no pick has been committed since, so a valid state was built for this train set with no picks
-    if (!c->mi_valid) ALGP_TRY(mi_build(c, ss, sm));
+    if (!c->mi_valid || c->mi_form != 0) ALGP_TRY(mi_build(c, ss, sm));     // (a sharded state holds only this rank's rows)
     // dH_A: the entropy block scorer on the same sites (both of its regimes)
     std::vector<double> dHA(npaths);
     ALGP_TRY(score_paths(c, packed.data(), npaths, maxlen, mobile_std, dHA.data()));

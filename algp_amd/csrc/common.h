@@ -204,6 +204,13 @@ struct algp_ctx {
     int64_t mi_npicks = 0, mi_base = 0, mi_nbar = 0;   // picks folded in; picks.size() at the build; rank-1 terms of P so far
     int64_t mi_mb = 0, mi_mbpad = 0, mi_npad = 0;
     double mi_ss = 0, mi_sm = 0;
+    // the same state dealt over the ranks of a communicator (api_mi_shard.hip): algp_comm_set_mi_groups puts ranks
+    // [0, mi_ncomp) on C_AbarAbar and the others on C + D_all (0: no layout; one rank: both); miXbar / miXall then hold only
+    // this rank's row blocks of X, miDP / miDQ / miU / miW / miH stay whole on every rank
+    int mi_ncomp = 0;
+    int mi_form = 0;                     // what the mi* buffers hold: 0 the whole inverses (one GPU), 1 this rank's rows of them
+    algp::DevBuf miFull, miFold;         // the matrix being factored and inverted (released after the build); a gathered column
+    double mi_hdr[4] = {0, 0, 0, 0};     // this rank's header of the next gather (host memory that outlives the copy)
 
     // multi-GPU: transport of the sharded greedy loop's one all-gather (comm.hip): an RCCL communicator
     // (algp_comm_init), a caller-supplied host all-gather (algp_comm_init_host), or neither (one rank)
@@ -232,6 +239,7 @@ struct algp_ctx {
     int debug_fail_next_pick = 0;   // algp_debug_fail_next_pick: error code this rank reports in its next pick
     int debug_fail_next_commit = 0; // algp_debug_fail_at(1): the next commit of a greedy pick fails with this code (after the exchange)
     int debug_fail_next_pack = 0;   // algp_debug_fail_at(2): the next pick's pack launch counts as failed
+    int debug_fail_next_mi = 0;     // algp_debug_fail_at(4): the next step of the sharded MI state (its build or a pick's fold) fails
 
     // scratch for auxiliary factorizations (entropy_from_cov, set entropies, MI terms, posterior cov)
     algp::DevBuf auxA, auxInv, auxW, auxIdx, auxVar, auxD, hostStage;

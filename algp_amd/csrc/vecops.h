@@ -71,6 +71,16 @@ int mi_rank1_launch(algp_ctx* c, int64_t m, const T* col0, T* U, int64_t ldu, do
 template <typename T>
 int mi_score_launch(algp_ctx* c, int64_t M, const int* ckind, const int64_t* cidx, const unsigned char* alive, const T* dstat,
                     double ss, double delta, const int64_t* posbar, const T* dP, const T* dQ, const double* Hs, double* out);
+// MI criterion dealt over ranks (mi_shard.hip): a rank's row blocks t g + member of X = L^-T (nloc of them, X zeroed here),
+// its pieces of a pick's column with the earlier picks' terms removed, and a whole vector put together from gathered pieces
+template <typename T>
+int mi_trinv_rows(algp_ctx* c, int klass, T* X, int64_t ldx, int64_t nloc, int g, int member, const T* L, int64_t ldl,
+                  int64_t npad, const T* invD);
+template <typename T>
+int mi_cols_local_launch(algp_ctx* c, int64_t rows, int g, int member, int64_t m, const T* raw, const T* U, int64_t ldu,
+                         const double* sgn, int q, int64_t cpos, T* out);
+template <typename T>
+int mi_assemble_launch(algp_ctx* c, int64_t m, int g, int first, const char* gathered, int64_t stride, int64_t off, T* dst);
 template <typename T>
 int kgemv_launch(algp_ctx* c, int64_t M, const int64_t* qidx, const T* Xs, int DP, int64_t N, const int64_t* aidx,
                  const T* alpha, int kernel, T os, T ybar, T* mu);

@@ -39,7 +39,8 @@ class ShardLink(object):
     """How an Agent's pool context joins the other ranks of a sharded run (one process and one context per GPU): the
     rank's place in the job, the transport of the library's collectives, and which rank holds which pool site as a
     candidate.  `Agent(env, args, comm=ShardLink(...))` then scores only its share of the pool in `greedy`
-    (algp_greedy_sharded: one all-gather per pick) and its factor updates take the rows of the new train sites from
+    (algp_greedy_sharded: one all-gather per pick; under the MI criterion the pool-wide inverses are dealt over the ranks
+    too, algp_comm_set_mi_groups) and its factor updates take the rows of the new train sites from
     their owners (algp_comm_set_owners: one all-gather per planning step) -- agent.py:125-229 with the loop of
     agent.py:313-354 cut into shards; every rank ends each step with the same picks and the same factor.
 
@@ -49,15 +50,23 @@ class ShardLink(object):
     layout: 'strided' (site q on rank q mod n: a path's neighbouring sites spread over all owners, so a step's row
     exchange carries ~1/n of the new rows per rank, and retired static sites thin every shard alike) or 'contiguous'
     (rank r owns `partition(n_pool, n)[r]`).  Picks are the same either way: equal utilities go to
-    the smaller pool index, which is np.argmax's first maximum (agent.py:349)."""
+    the smaller pool index, which is np.argmax's first maximum (agent.py:349).
+    mi_complement_ranks: under the MI criterion, how many ranks (the first ones) hold the complement's pool-wide inverse;
+    the others hold the whole pool's (algp_comm_set_mi_groups).  Default: half of them, and both on the one rank of a
+    world of one."""
 
-    def __init__(self, rank, world_size, unique_id=None, all_gather=None, layout='strided'):
+    def __init__(self, rank, world_size, unique_id=None, all_gather=None, layout='strided', mi_complement_ranks=None):
         if (unique_id is None) == (all_gather is None):
             raise ValueError('give exactly one transport: unique_id (RCCL) or all_gather (host)')
         if layout not in ('strided', 'contiguous'):
             raise ValueError("layout must be 'strided' or 'contiguous'")
         self.rank, self.world_size = int(rank), int(world_size)
         self.unique_id, self.all_gather, self.layout = unique_id, all_gather, layout
+        if mi_complement_ranks is None:
+            mi_complement_ranks = max(1, self.world_size // 2)
+        if not (self.world_size == 1 and mi_complement_ranks == 1) and not 1 <= mi_complement_ranks < self.world_size:
+            raise ValueError('mi_complement_ranks: 1 <= n < world_size (a world of one: 1)')
+        self.mi_complement_ranks = int(mi_complement_ranks)
         self._id_used = False
 
     def owners(self, n_pool):
@@ -91,6 +100,7 @@ class ShardLink(object):
                 ctx.comm_init_host(self.world_size, self.rank, self.all_gather)
             ctx._shard_link = self
         ctx.comm_set_owners(self.owners(n_pool))
+        ctx.comm_set_mi_groups(self.mi_complement_ranks)
 
 
 class LocalComm(object):

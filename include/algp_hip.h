@@ -191,7 +191,8 @@ int algp_posterior_mean(algp_ctx* ctx, const int64_t* idx, int64_t M, void* mu_o
  * algp_greedy: k picks on one GPU.  utilities_out (k*M doubles, local candidate order) may be
  *   NULL; forced_picks (k pool indices) may be NULL.  With both NULL and the entropy criterion a pick
  *   is one host round trip (see algp_greedy_sharded: the same chain without the gather).
- * MI criterion (agent.py:330-339) is exact and single-GPU: it needs the pool-wide complement. */
+ * MI criterion (agent.py:330-339) is exact; here it holds the pool-wide inverses on one GPU (algp_comm_set_mi_groups deals
+ * them over the ranks of algp_greedy_sharded). */
 int algp_scores(algp_ctx* ctx, int criterion, double static_std, double mobile_std, void* out,
                 int out_is_device);
 int algp_argmax(algp_ctx* ctx, int64_t* local_pos, int64_t* pool_idx, double* value);
@@ -249,7 +250,7 @@ int algp_score_paths_mi(algp_ctx* ctx, const int64_t* sites, int npaths, int max
  *   (the winner is then chosen on the host and only its row goes back to the device).
  *   This is also how two ranks can share one card.
  * Both reserve the exchange's buffers for the current train set; algp_set_train re-reserves them when its size changes.
- * algp_greedy_sharded: k picks (entropy criterion; the MI criterion does not shard).  Per pick, stream-ordered and with
+ * algp_greedy_sharded: k picks (entropy criterion; the MI criterion with a layout of algp_comm_set_mi_groups, below).  Per pick, stream-ordered and with
  *   a single read-back (40 bytes): each rank's best candidate resolved on the device (argmax, refresh of the rows
  *   whose bound can still win, argmax), the all-gather, the first maximum in rank order (= np.argmax over the
  *   concatenated scores, agent.py:349, shards being contiguous in rank order), then the commit of the winner on every
@@ -289,6 +290,34 @@ int algp_comm_init_host(algp_ctx* ctx, int nranks, int rank, algp_allgather_fn f
 int algp_comm_destroy(algp_ctx* ctx);
 int algp_greedy_sharded(algp_ctx* ctx, int criterion, double static_std, double mobile_std, int k, int64_t* picks_out,
                         double* utilities_out);
+/* algp_comm_set_mi_groups: the layout under which algp_greedy_sharded scores the MUTUAL-INFORMATION criterion (agent.py:330-339)
+ * with its two pool-wide inverses dealt over the ranks instead of whole on one GPU (without a layout that criterion is refused
+ * there with ALGP_ERR_BAD_ARG).  Ranks [0, n_complement_ranks) hold P = C_AbarAbar^-1 (the unsampled sites, no noise), ranks
+ * [n_complement_ranks, world) hold Q = (C + D_all)^-1 (the whole pool with its noise); 1 <= n_complement_ranks < world.  A
+ * world of one takes 1 and keeps exactly the one-GPU state of algp_greedy (both inverses in place, two pool-sized matrices).
+ * 0 detaches the layout.  Call it on every rank with the same value, after algp_comm_init[_host] (which drops a layout
+ * attached before); a rank attached with another value makes every rank return ALGP_ERR_BAD_ARG from its next
+ * algp_greedy_sharded.  The split is the caller's choice between memory and time.
+ * What the sharded criterion costs (api_mi_shard.hip): at the first pick after a solve every member of a group of g ranks
+ * builds and factors its group's matrix (m^3 / 3 flop, replicated), computes only its 128-row blocks b = member + j g of
+ * X = L^-T (~ m^3 / (3 g) flop on the MFMA GEMM path) and releases the factor.  PEAK device memory of the MI state per rank:
+ * the matrix (m_pad^2 elements, m = its group's size) + its rows of X (~ m_pad^2 / g) + 256 whole vectors of n_pool; AFTER
+ * the build the rows and the vectors only.  Config 4's 110 000 sites in fp64, 8 ranks split 4 + 4: 121 GB peak and 24.5 GB
+ * of MI state after the build, against 194 GB on one GPU (the rest of a rank's device memory -- train factor, candidate
+ * solve, the train set's entropy scratch -- comes on top, as on one GPU).  Every rank checks its peak BEFORE anything is
+ * allocated and the check is agreed on: a rank that does not fit makes every rank return ALGP_ERR_OOM with the byte count.
+ * Collectives (all of them all-gathers through the attached transport, no other RCCL call): at the first pick of a call a
+ * 32-byte agreement word per rank (+ a stream synchronisation), and after a solve one gather of every rank's diagonal entries;
+ * per committed pick folded, two gathers of O(n_pool) bytes per rank (the owners' rows of X at the pick, then every rank's
+ * entries of the pick's columns); each gather carries every rank's status word, so that a rank which fails in its share of a
+ * step (memory, a matrix that is not positive definite, a HIP error) still joins every collective and every rank returns its
+ * code from the same call; the MI state is then rebuilt by the next call.  Not covered: a HIP failure AFTER a step's last
+ * gather (the copies behind the build's gather, the launches that fold a gathered column, a header copy inside a gather)
+ * returns from that rank alone while its peers go on to the pick's exchange -- as for algp_factorize_update, a caller that
+ * sees ALGP_ERR_HIP must tear the job down.  Picks and utilities equal algp_greedy's on one GPU (to rounding: the diagonals
+ * come from differently blocked products).  algp_scores with the MI criterion on such a context scores from the sharded
+ * state while it is current; with picks committed outside algp_greedy_sharded it builds the whole inverses on this GPU. */
+int algp_comm_set_mi_groups(algp_ctx* ctx, int n_complement_ranks);
 /* ---- test hooks -----------------------------------------------------------------------------------------------------
  * Compiled in when ALGP_TEST_HOOKS is 1 -- the default of algp_amd/csrc/Makefile, and what this repository's tests and
  * bench.py (its one-stream leg, the strong-scaling emulation) need; `make TEST_HOOKS=0` builds the library without them
@@ -319,7 +348,9 @@ int algp_greedy_sharded(algp_ctx* ctx, int criterion, double static_std, double 
  * that chose it (the code travels in this rank's status word of its next pick: every rank returns it from that call; after
  * the last pick of a call it is returned by this rank at once and reported again in its next call's first exchange),
  * 2 = the launch that packs its contribution counts as failed (ALGP_ERR_HIP in its status word, the gather still runs),
- * 3 = this rank's agreement word of its next sharded algp_factorize_update carries `code`: every rank returns it. */
+ * 3 = this rank's agreement word of its next sharded algp_factorize_update carries `code`: every rank returns it,
+ * 4 = the next step of the sharded MI criterion on this rank (its build after a solve, else the fold of a committed pick) fails
+ * with `code`; every rank returns it from that algp_greedy_sharded call (a world of one has no such step). */
 int algp_debug_fail_at(algp_ctx* ctx, int where, int code);
 int algp_debug_trsv_stall(algp_ctx* ctx, int block);
 int algp_debug_get_pick(algp_ctx* ctx, int q, void* row_out, int64_t row_capacity, int64_t* ncols_out, double* d_out);
