@@ -286,7 +286,7 @@ int Impl<T>::solve_finish(algp_ctx* c, int incremental, const unsigned char* ali
     ALGP_TRY(sync_checked(c, "solve_candidates"));
     c->ncols = Npad;
     c->picks.clear();
-    c->mi_valid = false;
+    c->mi.valid = false;
     ALGP_TRY(reset_lazy(c));
     c->solved = true;
     c->vt_fact_idx = c->fact_idx;

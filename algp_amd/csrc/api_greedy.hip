@@ -1,5 +1,5 @@
 // api_greedy.hip -- information-gain scoring and the greedy picks: utilities, lazy resolution of the argmax, commits, the
-// sharded pick exchange and its communicator entry points, the MI criterion's pool-wide inverses.
+// sharded pick exchange and its communicator entry points (the MI criterion's state: api_mi.hip).
 #include "api_impl.h"
 
 using namespace algp;
@@ -8,149 +8,6 @@ namespace algp {
 
 
 // ------------------------------------------------------------------ greedy
-// ---- MI criterion (agent.py:330-339): H(A u i) + H(Abar \ i) - H(all_i) per candidate --------------------------------
-// The last two terms need the diagonals of P = C_AbarAbar^-1 and Q = (C + D_all)^-1 over the WHOLE pool (see
-// mi_rank1_kernel in vecops.hip).  mi_build factors both matrices once per candidate solve and leaves the triangular
-// inverses X (P = X X^T) resident; mi_apply_pick folds a committed pick into both diagonals with one pass over each X
-// (O(n^2)) where the reference -- and round 2 of this library -- refactorised both matrices for every pick.
-template <typename T>
-int Impl<T>::mi_build(algp_ctx* c, double ss, double sm) {
-    const int64_t n = c->n_pool;
-    if (c->train_has_repeats)
-        return fail(c, ALGP_ERR_STATE, "mutual_information: the train set lists a site more than once; fuse its readings first");
-    const double vf = 1.0 / (1.0 / ss + 1.0 / sm);
-    // current state: train set (with its noise) + committed picks
-    std::vector<char> sampled(n, 0);
-    std::vector<double> noise(n, 0.0);
-    std::vector<T> trvar(c->Npad);
-    ALGP_HIP(hipMemcpyAsync(trvar.data(), c->varA.p, sizeof(T) * c->Npad, hipMemcpyDeviceToHost, c->stream));
-    ALGP_TRY(sync(c));
-    for (int64_t a = 0; a < c->N; ++a) { sampled[c->train_idx[a]] = 1; noise[c->train_idx[a]] = (double)trvar[a]; }
-    for (auto& pk : c->picks) {
-        noise[pk.pool_idx] = sampled[pk.pool_idx] ? vf : ss;
-        sampled[pk.pool_idx] = 1;
-    }
-    std::vector<int64_t> A, Abar, all(n);
-    std::vector<T> vA, vall(n);
-    c->mi_posbar.assign(n, -1);
-    for (int64_t i = 0; i < n; ++i) {
-        all[i] = i;
-        vall[i] = (T)noise[i];
-        if (sampled[i]) { A.push_back(i); vA.push_back((T)noise[i]); }
-        else { c->mi_posbar[i] = (int64_t)Abar.size(); Abar.push_back(i); }
-    }
-    const int64_t mb = (int64_t)Abar.size();
-    const int64_t npad = round_up(std::max<int64_t>(n, 1), NB), mbpad = round_up(std::max<int64_t>(mb, 1), NB);
-    {
-        // Two pool-wide matrices stay resident -- each is built, factored and inverted IN its buffer (L in the strictly
-        // lower tiles, X = L^-T on and above the diagonal: trinv_upper_inplace) -- say so with the byte count instead of
-        // failing half-way through the allocations.  At config 4's own pool (110 000 sites, fp64) that is 2 x 96.8 GB
-        // (round 5 held a third matrix, the factor being inverted: 290 GB) and 4 n^3 / 3 = 1.8e15 flop for the first pick.
-        const size_t need = sizeof(T) * ((size_t)npad * npad + (size_t)mbpad * mbpad + (size_t)npad * NB +
-                                         (size_t)MAX_APPEND * (npad + mbpad));
-        const size_t held = c->auxInv.cap + c->miXbar.cap + c->miXall.cap + c->miU.cap + c->miW.cap;
-        size_t free_b = 0, total_b = 0;
-        ALGP_HIP(hipMemGetInfo(&free_b, &total_b));
-        if (need > held + free_b)
-            return fail(c, ALGP_ERR_OOM,
-                        "mutual_information: the criterion keeps the triangular inverses of two pool-wide matrices resident: " +
-                            std::to_string(need) + " bytes for n_pool = " + std::to_string(n) + ", " +
-                            std::to_string(held + free_b) + " available; score this pool with the entropy criterion "
-                            "(it needs the candidates' rows only) or a smaller pool");
-    }
-    double H_A = 0, H_bar = 0, H_all = 0;
-    ALGP_TRY(set_entropy(c, A.data(), (int64_t)A.size(), vA.data(), &H_A));
-    ALGP_TRY(ensure(c, c->miXbar, sizeof(T) * mbpad * mbpad));
-    ALGP_TRY(ensure(c, c->miXall, sizeof(T) * npad * npad));
-    ALGP_TRY(ensure(c, c->miDP, sizeof(T) * mbpad));
-    ALGP_TRY(ensure(c, c->miDQ, sizeof(T) * npad));
-    ALGP_TRY(ensure(c, c->miU, sizeof(T) * (size_t)MAX_APPEND * mbpad));
-    ALGP_TRY(ensure(c, c->miW, sizeof(T) * (size_t)MAX_APPEND * npad));
-    ALGP_TRY(ensure(c, c->miCol, sizeof(T) * npad));
-    ALGP_TRY(ensure(c, c->miPos, sizeof(int64_t) * n));
-    ALGP_TRY(ensure(c, c->miH, sizeof(double) * (3 + 2 * MAX_APPEND)));
-    // C_AbarAbar carries no measurement noise (agent.py:331)
-    if (mb > 0) {
-        int64_t mp;
-        ALGP_TRY(build_set_matrix(c, Abar.data(), mb, nullptr, &mp, p(c->miXbar)));
-        double ld = 0;
-        ALGP_TRY(factor_resident(c, p(c->miXbar), mb, mbpad, p(c->auxInv), SC_AUXLOGDET, SC_AUXINFO, &ld));
-        H_bar = (double)mb * ENT_CONST + 0.5 * ld;
-        ALGP_TRY(trinv_upper_inplace<T>(c, ALGP_PROF_GEMM_OTHER, p(c->miXbar), mbpad, mbpad, p(c->auxInv)));
-        ALGP_TRY(rows_reduce_launch<T>(c, p(c->miXbar), mb, mbpad, mbpad, (const T*)nullptr, p(c->miDP), (T*)nullptr, 0));
-    }
-    {
-        int64_t np2;
-        ALGP_TRY(build_set_matrix(c, all.data(), n, vall.data(), &np2, p(c->miXall)));
-        double ld = 0;
-        ALGP_TRY(factor_resident(c, p(c->miXall), n, npad, p(c->auxInv), SC_AUXLOGDET, SC_AUXINFO, &ld));
-        H_all = (double)n * ENT_CONST + 0.5 * ld;
-        ALGP_TRY(trinv_upper_inplace<T>(c, ALGP_PROF_GEMM_OTHER, p(c->miXall), npad, npad, p(c->auxInv)));
-        ALGP_TRY(rows_reduce_launch<T>(c, p(c->miXall), n, npad, npad, (const T*)nullptr, p(c->miDQ), (T*)nullptr, 0));
-    }
-    const double Hs[3] = {H_A, H_bar, H_all};
-    ALGP_HIP(hipMemcpyAsync(c->miH.p, Hs, sizeof(Hs), hipMemcpyHostToDevice, c->stream));
-    ALGP_HIP(hipMemcpyAsync(c->miPos.p, c->mi_posbar.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice, c->stream));
-    ALGP_TRY(sync(c));                                       // Hs / mi_posbar (a member, but be plain about it) are host memory
-    c->mi_mb = mb;
-    c->mi_mbpad = mbpad;
-    c->mi_npad = npad;
-    c->mi_npicks = (int64_t)c->picks.size();
-    c->mi_base = c->mi_npicks;
-    c->mi_nbar = 0;
-    c->mi_ss = ss;
-    c->mi_sm = sm;
-    c->mi_form = 0;
-    c->mi_valid = true;
-    return ALGP_OK;
-}
-
-// fold pick number q (committed after mi_build) into P, Q and the three entropies: stream-ordered, O(n^2)
-template <typename T>
-int Impl<T>::mi_apply_pick(algp_ctx* c, int64_t q, double ss, double sm) {
-    const PickRec& pk = c->picks[(size_t)q];
-    const int r = (int)(q - c->mi_base);                      // its slot in the rank-1 lists
-    const double delta = 1.0 / (1.0 / ss + 1.0 / sm) - sm;
-    double* Hs = (double*)c->miH.p;
-    const LazyPick* lp = (const LazyPick*)c->lazypicks.p + q;
-    const int64_t n = c->n_pool, npad = c->mi_npad, mbpad = c->mi_mbpad;
-    if (!pk.in_train) {
-        // the site leaves the complement: column of P = X X^T at its row, then the rank-1 removal
-        const int64_t cb = c->mi_posbar[pk.pool_idx];
-        if (cb < 0) return fail(c, ALGP_ERR_STATE, "mutual_information: a picked site is missing from the complement set");
-        // column cb of P = X X^T: X's row cb is zero (the buffer holds L there) left of its own diagonal tile
-        ALGP_TRY(rows_reduce_launch<T>(c, p(c->miXbar), c->mi_mb, mbpad, mbpad, p(c->miXbar) + cb * mbpad, (T*)nullptr, p(c->miCol),
-                                       cb / NB * NB));
-        ALGP_TRY(mi_rank1_launch<T>(c, c->mi_mb, p(c->miCol), p(c->miU), mbpad, Hs + 3, c->mi_nbar, cb, 0, 0.0, p(c->miDP), Hs + 1,
-                                    (double*)nullptr, lp));
-        c->mi_nbar += 1;
-    }
-    // its noise in C + D_all changes by ss (new site: 0 -> ss) or by v_fused - sm (mobile-sampled site)
-    ALGP_TRY(rows_reduce_launch<T>(c, p(c->miXall), n, npad, npad, p(c->miXall) + pk.pool_idx * npad, (T*)nullptr, p(c->miCol),
-                                   pk.pool_idx / NB * NB));
-    ALGP_TRY(mi_rank1_launch<T>(c, n, p(c->miCol), p(c->miW), npad, Hs + 3 + MAX_APPEND, r, pk.pool_idx, 1, pk.in_train ? delta : ss,
-                                p(c->miDQ), Hs + 2, Hs + 0, lp));
-    return ALGP_OK;
-}
-
-template <typename T>
-int Impl<T>::mi_scores_enqueue(algp_ctx* c, double ss, double sm, double delta, double* dst) {
-    // a sharded state (api_mi_shard.hip) that is up to date scores as it is: its diagonals and entropies are whole on every
-    // rank; with picks still to fold (they need its collectives) this GPU builds the whole inverses instead
-    const bool sharded_current = c->mi_form == 1 && c->mi_valid && c->mi_ss == ss && c->mi_sm == sm &&
-                                 c->mi_npicks == (int64_t)c->picks.size();
-    if (!sharded_current && (!c->mi_valid || c->mi_form != 0 || c->mi_ss != ss || c->mi_sm != sm ||
-                             (int64_t)c->picks.size() < c->mi_npicks)) {
-        c->mi_valid = false;
-        ALGP_TRY(mi_build(c, ss, sm));
-    }
-    for (; c->mi_npicks < (int64_t)c->picks.size(); ++c->mi_npicks) ALGP_TRY(mi_apply_pick(c, c->mi_npicks, ss, sm));
-    return mi_score_launch<T>(c, c->M, (const int*)c->ckind.p, (const int64_t*)c->Cidx.p, (const unsigned char*)c->alive.p,
-                              (const T*)c->dstat.p, ss, delta, (const int64_t*)c->miPos.p, (const T*)c->miDP.p,
-                              (const T*)c->miDQ.p, (const double*)c->miH.p, dst);
-}
-
-
 // utilities of every row into `dst` (device; null = c->scores), stream-ordered; the entropy criterion never
 // synchronises here, the MI criterion only when it (re)builds its pool-wide inverses (first scoring after a solve)
 template <typename T>
@@ -456,7 +313,7 @@ int Impl<T>::greedy_picks(algp_ctx* c, int criterion, double static_std, double 
             }
             if (criterion == ALGP_CRIT_MUTUAL_INFORMATION && round == 0 && c->comm_nranks > 1) {
                 // the sharded MI state catches up with the committed picks: collectives of every rank, which carry st and
-                // return the same code on every rank when any of them failed (api_mi_shard.hip).  A world of one keeps the
+                // return the same code on every rank when any of them failed (api_mi.hip).  A world of one keeps the
                 // one-GPU state (mi_build, in place: two pool-sized matrices), built and folded by ensure_bounds below.
                 ALGP_TRY(mi_shard_step(c, ss, sm, st, pck == 0));
             }
@@ -654,7 +511,7 @@ int algp_greedy_sharded(algp_ctx* c, int criterion, double static_std, double mo
     if (k < 0 || k > MAX_APPEND) return fail(c, ALGP_ERR_BAD_ARG, "greedy_sharded: 0 <= k <= 128");
     if (criterion != ALGP_CRIT_ENTROPY && criterion != ALGP_CRIT_MUTUAL_INFORMATION)
         return fail(c, ALGP_ERR_BAD_ARG, "greedy_sharded: unknown criterion");
-    if (criterion == ALGP_CRIT_MUTUAL_INFORMATION && c->mi_ncomp <= 0)
+    if (criterion == ALGP_CRIT_MUTUAL_INFORMATION && c->mi.ncomp <= 0)
         return fail(c, ALGP_ERR_BAD_ARG, "greedy_sharded: the MI criterion shards its pool-wide inverses over the ranks only with "
                                          "a layout attached: call algp_comm_set_mi_groups on every rank first (or use algp_greedy)");
     if (!c->comm && !c->host_gather) return fail(c, ALGP_ERR_STATE, "greedy_sharded: call algp_comm_init (or algp_comm_init_host) first");

@@ -1,8 +1,8 @@
 // api_impl.h -- the typed host-side implementation behind the C ABI (include/algp_hip.h), declared once and defined by
 // concern: api.hip (context, hyper-parameters, pool, train set, the stand-alone matrix entry points), api_factor.hip (the
 // factor of the train set and its updates), api_candidates.hip (candidate solve and posterior), api_greedy.hip (scoring,
-// picks, the sharded exchange, the MI criterion), api_paths.hip (best_path block scoring), api_fit.hip (MLL gradient, one
-// fit iteration).  Every file defines its members of Impl<T> and instantiates Impl<float> / Impl<double> for them.
+// picks, the sharded exchange), api_mi.hip (the MI criterion's state, on one GPU and over the ranks), api_paths.hip
+// (best_path block scoring), api_fit.hip (MLL gradient, one fit iteration).  Every file defines its members of Impl<T> and instantiates Impl<float> / Impl<double> for them.
 #pragma once
 #include <limits.h>
 #include <math.h>
@@ -17,6 +17,7 @@
 namespace algp {
 
 void release(algp_ctx* c, DevBuf& b);
+void release(algp_ctx* c, MiState& mi);   // every MI buffer (api_mi.hip)
 hipEvent_t sync_event_api(algp_ctx* c, size_t i);
 KmatSrc make_src(algp_ctx* c);
 int sync(algp_ctx* c);
@@ -109,10 +110,19 @@ struct Impl {
     static int gemm_host(algp_ctx* c, int64_t m, int64_t n, int64_t k, double alpha, const void* A, const void* B,
                          double beta, const void* C, void* D);
     static int trsm_host(algp_ctx* c, const void* L, int64_t n, const void* B, int64_t m, void* X);
+    // the MI criterion's state (api_mi.hip).  A build: mi_sets (host), the form's own factorisations, mi_install.
+    struct MiPlan {
+        std::vector<int64_t> A, Abar, all, posbar;   // sampled sites, the others, every site; pool index -> row in Abar (-1)
+        std::vector<T> vA, vall;                     // the noise of A's sites, of every site (0 where unsampled)
+        int64_t mb = 0, mbpad = 0, npad = 0;
+        size_t rbytes = 0, cbytes = 0;               // form 1: bytes per rank of a pick's row gather and of a column gather
+    };
+    static int mi_sets(algp_ctx* c, double ss, double sm, MiPlan& pl);
+    static int mi_vectors(algp_ctx* c, const MiPlan& pl, int64_t col);
+    static int mi_install(algp_ctx* c, MiPlan& pl, const double* Hs, int form, double ss, double sm);
     static int mi_build(algp_ctx* c, double ss, double sm);
     static int mi_apply_pick(algp_ctx* c, int64_t q, double ss, double sm);
-    // the MI state dealt over the ranks (api_mi_shard.hip): collectives, every rank calls them with its status st
-    struct MiPlan;
+    // form 1, dealt over the ranks: collectives, every rank calls them with its status st
     static int mi_shard_plan(algp_ctx* c, double ss, double sm, MiPlan& pl);
     static int mi_shard_build(algp_ctx* c, MiPlan& pl, double* H3);
     static int mi_shard_fold(algp_ctx* c, int st);

@@ -182,14 +182,13 @@ int Impl<T>::score_paths_mi(algp_ctx* c, const int64_t* sites, int npaths, int m
         for (int a = 0; a < k; ++a) packed[(size_t)pth * maxlen + a] = a < knew[pth] ? nw[a] : rm[a - knew[pth]];
         maxk = std::max(maxk, k);
     }
-    // the pool-wide inverses (their O(n^3) build, or ALGP_ERR_OOM up front): only when the MI state is not valid -- a solve
-    // invalidates it, and no pick has been committed since, so a valid state was built for this train set with no picks
-    if (!c->mi_valid || c->mi_form != 0) ALGP_TRY(mi_build(c, ss, sm));     // (a sharded state holds only this rank's rows)
+    // the pool-wide inverses (their O(n^3) build, or ALGP_ERR_OOM up front) unless the one-GPU state is held (MiState::current)
+    if (!c->mi.holds(0)) ALGP_TRY(mi_build(c, ss, sm));
     // dH_A: the entropy block scorer on the same sites (both of its regimes)
     std::vector<double> dHA(npaths);
     ALGP_TRY(score_paths(c, packed.data(), npaths, maxlen, mobile_std, dHA.data()));
 
-    const int64_t npad = c->mi_npad, mb = c->mi_mb, mbpad = c->mi_mbpad;
+    const int64_t npad = c->mi.npad, mb = c->mi.mb, mbpad = c->mi.mbpad;
     const int ppad = maxk <= NB ? NB : 2 * NB;
     const size_t mat = (size_t)ppad * ppad;
     // per path: its gathered rows (ppad x npad, P's narrower rows reuse them), four blocks, two inverse tiles, one L21 tile
@@ -230,7 +229,7 @@ int Impl<T>::score_paths_mi(algp_ctx* c, const int64_t* sites, int npaths, int m
             for (int a = 0; a < ppad; ++a) {
                 const size_t e = (size_t)b * ppad + a;
                 const int64_t j = a < kall[pth] ? packed[(size_t)pth * maxlen + a] : -1;
-                srcP[e] = a < knew[pth] ? c->mi_posbar[j] : -1;
+                srcP[e] = a < knew[pth] ? c->mi.posbar[j] : -1;
                 srcQ[e] = j;
                 double dl = 0.0;
                 if (a < knew[pth]) dl = sm;
@@ -252,14 +251,14 @@ int Impl<T>::score_paths_mi(algp_ctx* c, const int64_t* sites, int npaths, int m
         ALGP_HIP(hipMemsetAsync(d_info, 0, sizeof(int) * 3 * (size_t)bmax, c->stream));
         // P_SS over the new sites (nothing to do when every site is sampled: no path then has a new site)
         if (mb > 0) {
-            ALGP_TRY(mi_tri_gather_launch<T>(c, p(c->miXbar), mbpad, d_srcP, rows, mbpad, (int64_t)nrow, mbpad));
+            ALGP_TRY(mi_tri_gather_launch<T>(c, p(c->mi.Xbar), mbpad, d_srcP, rows, mbpad, (int64_t)nrow, mbpad));
             ALGP_TRY(gemm_nt_launch_batched<T>(c, ALGP_PROF_GEMM_OTHER, ppad, ppad, mbpad, (T)1, rows, mbpad, (int64_t)ppad * mbpad, rows,
                                                mbpad, (int64_t)ppad * mbpad, (T)0, nullptr, 0, 0, GP, ppad, (int64_t)mat, 1, B));
             ALGP_TRY(mi_pad_diag_launch<T>(c, GP, ppad, d_cntP, B));
             ALGP_TRY(factor_blocks_batched<T>(c, GP, ppad, inv, L21, d_ld, d_info, B));
         }
         // Q_SS over all changing sites -> G, then I + G^T D G = I + Lt LtD^T
-        ALGP_TRY(mi_tri_gather_launch<T>(c, p(c->miXall), npad, d_srcQ, rows, npad, (int64_t)nrow, npad));
+        ALGP_TRY(mi_tri_gather_launch<T>(c, p(c->mi.Xall), npad, d_srcQ, rows, npad, (int64_t)nrow, npad));
         ALGP_TRY(gemm_nt_launch_batched<T>(c, ALGP_PROF_GEMM_OTHER, ppad, ppad, npad, (T)1, rows, npad, (int64_t)ppad * npad, rows, npad,
                                            (int64_t)ppad * npad, (T)0, nullptr, 0, 0, GQ, ppad, (int64_t)mat, 1, B));
         ALGP_TRY(mi_pad_diag_launch<T>(c, GQ, ppad, d_cntQ, B));

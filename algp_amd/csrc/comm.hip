@@ -180,8 +180,7 @@ int comm_init(algp_ctx* c, int nranks, int rank, const void* unique_id128) {
         return fail(c, ALGP_ERR_HIP, std::string("ncclCommInitRank: ") + (api->GetErrorString ? api->GetErrorString(r) : "failed"));
     c->comm = comm;
     c->host_gather = nullptr;
-    c->mi_ncomp = 0;
-    if (c->mi_form == 1) c->mi_valid = false;
+    c->mi.drop_layout();
     c->comm_nranks = nranks;
     c->comm_rank = rank;
     return comm_reserve(c);
@@ -246,8 +245,7 @@ void comm_destroy(algp_ctx* c) {
     c->rowx_host = nullptr;
     c->rowx_host_cap = 0;
     c->site_owner.clear();
-    c->mi_ncomp = 0;                                         // the MI layout belongs to the communicator
-    if (c->mi_form == 1) c->mi_valid = false;
+    c->mi.drop_layout();                                     // the MI layout belongs to the communicator
     c->comm = nullptr;
     c->host_gather = nullptr;
     c->host_gather_user = nullptr;

@@ -75,6 +75,41 @@ struct LazyPick {          // device copy of a committed pick for the lazy greed
     double d;              // the winner's statistic (pv or s) when it was committed: what `scale` was computed from
 };
 
+// The MI criterion's state (api_mi.hip): X = L^-T of P = C_AbarAbar^-1 (Xbar) and of Q = (C + D_all)^-1 (Xall), built once
+// per candidate solve, with the picks committed since folded into their diagonals.  form 0 (one GPU): both X whole, in place;
+// form 1 (dealt over the ranks of a communicator, ncomp: the layout of algp_comm_set_mi_groups): Xbar / Xall hold only this
+// rank's row blocks, everything else stays whole on every rank.
+struct MiState {
+    DevBuf Xbar, Xall;
+    DevBuf DP, DQ;                       // diag(P), diag(Q)
+    DevBuf Pos;                          // posbar on the device
+    DevBuf U, W;                         // the rank-1 lists of P and of Q (MAX_APPEND columns each)
+    DevBuf Col;                          // a pick's column of P or Q (form 1: of both, [mbpad | npad])
+    DevBuf H;                            // [H(A), H(Abar), H(all) | signs of the rank-1 terms of P | of Q]
+    DevBuf Full, Fold;                   // form 1: the matrix being factored and inverted (released after the build); a gathered column
+    std::vector<int64_t> posbar;         // host: pool index -> row of the complement matrix when it was built (-1: sampled)
+    bool valid = false;
+    int form = 0;
+    int64_t npicks = 0, base = 0, nbar = 0;   // picks folded in; picks.size() at the build; rank-1 terms of P so far
+    int64_t mb = 0, mbpad = 0, npad = 0;
+    double ss = 0, sm = 0;
+    int ncomp = 0;                       // ranks [0, ncomp) hold P, the others Q (0: no layout; a world of one: 1, both)
+    double hdr[4] = {0, 0, 0, 0};        // this rank's header of the next gather (host memory that outlives the copy)
+
+    bool holds(int f) const { return valid && form == f; }
+    // holds(f) for (ss, sm) with at most npicks_now picks folded in: catching up folds the later picks, nothing is rebuilt.
+    // score_paths_mi asks only holds(0): it refuses to run with picks committed, and a state built with none (a solve
+    // invalidates it and clears the picks) does not depend on ss or sm, which only set the noise of picked sites.
+    bool current(int f, double ss_now, double sm_now, int64_t npicks_now) const {
+        return holds(f) && ss == ss_now && sm == sm_now && npicks_now >= npicks;
+    }
+    // the communicator's layout goes, and with it a state dealt by that layout
+    void drop_layout() {
+        ncomp = 0;
+        if (form == 1) valid = false;
+    }
+};
+
 }  // namespace algp
 
 namespace algp {
@@ -196,21 +231,7 @@ struct algp_ctx {
     bool vt_has_extra = false;
     int64_t kept_cols_last = 0;
 
-    // MI criterion (agent.py:330-339): the triangular inverses of the two pool-wide matrices stay resident between picks
-    // (api.hip mi_build / mi_apply_pick); miH = [H(A), H(Abar), H(all) | signs of the rank-1 terms of P | of Q]
-    algp::DevBuf miXbar, miXall, miDP, miDQ, miPos, miU, miW, miCol, miH;
-    std::vector<int64_t> mi_posbar;      // host: pool index -> row of the complement matrix when it was built (-1: sampled)
-    bool mi_valid = false;
-    int64_t mi_npicks = 0, mi_base = 0, mi_nbar = 0;   // picks folded in; picks.size() at the build; rank-1 terms of P so far
-    int64_t mi_mb = 0, mi_mbpad = 0, mi_npad = 0;
-    double mi_ss = 0, mi_sm = 0;
-    // the same state dealt over the ranks of a communicator (api_mi_shard.hip): algp_comm_set_mi_groups puts ranks
-    // [0, mi_ncomp) on C_AbarAbar and the others on C + D_all (0: no layout; one rank: both); miXbar / miXall then hold only
-    // this rank's row blocks of X, miDP / miDQ / miU / miW / miH stay whole on every rank
-    int mi_ncomp = 0;
-    int mi_form = 0;                     // what the mi* buffers hold: 0 the whole inverses (one GPU), 1 this rank's rows of them
-    algp::DevBuf miFull, miFold;         // the matrix being factored and inverted (released after the build); a gathered column
-    double mi_hdr[4] = {0, 0, 0, 0};     // this rank's header of the next gather (host memory that outlives the copy)
+    algp::MiState mi;                    // the MI criterion's resident state (api_mi.hip)
 
     // multi-GPU: transport of the sharded greedy loop's one all-gather (comm.hip): an RCCL communicator
     // (algp_comm_init), a caller-supplied host all-gather (algp_comm_init_host), or neither (one rank)

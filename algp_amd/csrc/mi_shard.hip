@@ -1,4 +1,4 @@
-// mi_shard.hip -- the device side of the MI criterion dealt over ranks (api_mi_shard.hip): a rank holds the 128-row blocks
+// mi_shard.hip -- the device side of the MI criterion dealt over ranks (api_mi.hip): a rank holds the 128-row blocks
 // b = member, member + g, member + 2g, ... of X = L^-T for one pool-wide matrix (g ranks share it), computes them from the
 // factor on the MFMA GEMM path, and per committed pick turns its rows into its entries of the pick's column of P = X X^T.
 // Every rank then rebuilds the whole column from the gathered pieces and folds it with mi_rank1_kernel (vecops.hip).

@@ -1,7 +1,7 @@
 // paths_mi.hip -- best_path under the mutual-information criterion (agent.py:374-400): the device pieces that turn each
 // path's two pool-wide log-determinants into small blocks of the resident inverses P = C_AbarAbar^-1 and Q = (C + D)^-1
 // (api_paths.hip: score_paths_mi).  Both inverses are kept as X = L^-T on and above the diagonal tiles of their buffer
-// (api_greedy.hip: mi_build), so a block P_SS (Q_SS) is the Gram matrix of |S| rows of X:
+// (api_mi.hip: mi_build), so a block P_SS (Q_SS) is the Gram matrix of |S| rows of X:
 //   mi_tri_gather_kernel   the rows of X, zero left of each row's own diagonal tile (the buffer holds L there)
 //   mi_pad_diag_kernel     ones on the diagonal behind a path's sites (padding of the ppad x ppad block)
 //   mi_transpose_kernel    from the factor G of Q_SS (2 x 2 tiles of 128: L11, L22 in the block, L21 apart) the two

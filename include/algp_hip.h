@@ -298,7 +298,7 @@ int algp_greedy_sharded(algp_ctx* ctx, int criterion, double static_std, double 
  * 0 detaches the layout.  Call it on every rank with the same value, after algp_comm_init[_host] (which drops a layout
  * attached before); a rank attached with another value makes every rank return ALGP_ERR_BAD_ARG from its next
  * algp_greedy_sharded.  The split is the caller's choice between memory and time.
- * What the sharded criterion costs (api_mi_shard.hip): at the first pick after a solve every member of a group of g ranks
+ * What the sharded criterion costs (api_mi.hip): at the first pick after a solve every member of a group of g ranks
  * builds and factors its group's matrix (m^3 / 3 flop, replicated), computes only its 128-row blocks b = member + j g of
  * X = L^-T (~ m^3 / (3 g) flop on the MFMA GEMM path) and releases the factor.  PEAK device memory of the MI state per rank:
  * the matrix (m_pad^2 elements, m = its group's size) + its rows of X (~ m_pad^2 / g) + 256 whole vectors of n_pool; AFTER
