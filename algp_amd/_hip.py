@@ -297,13 +297,15 @@ class Context(object):
         self._check(self.lib.algp_get_mll_grad(self.h, g.ctypes.data_as(_dblp)))
         return g
 
-    def fit_step(self):
+    def fit_step(self, want_mll=True, want_grad=True):
         """(mll, grad): factorisation, marginal log likelihood and its gradient for the current hyper-parameters in one
-        call -- the device work of one iteration of GPR.fit (algp_fit_step)."""
-        g = np.empty(self.D + 2, dtype=np.float64)
+        call -- the device work of one iteration of GPR.fit (algp_fit_step).  want_mll=False / want_grad=False pass NULL
+        for that output (the ABI then skips its work) and return None in its place."""
+        g = np.empty(self.D + 2, dtype=np.float64) if want_grad else None
         v = C.c_double()
-        self._check(self.lib.algp_fit_step(self.h, C.byref(v), g.ctypes.data_as(_dblp)))
-        return v.value, g
+        self._check(self.lib.algp_fit_step(self.h, C.byref(v) if want_mll else None,
+                                           g.ctypes.data_as(_dblp) if want_grad else None))
+        return (v.value if want_mll else None), g
 
     def alpha(self):
         out = np.empty(self.N, dtype=self.dtype)

@@ -4,7 +4,8 @@
 //   MLL = -1/2 y0' S^-1 y0 - 1/2 log det S - N/2 log 2pi,   S = K + diag(var) + sigma_n^2 I
 //   dMLL/dtheta = 1/2 tr(W dS/dtheta),  W = alpha alpha' - S^-1
 //   dS/dlog os = K ; dS/dlog ls_d = K .* u_d^2 (RBF) | 3 os e^{-a} u_d^2 (Matern-1.5), u_d = (x_d-x'_d)/ls_d
-//   dS/dlog sigma_n^2 = sigma_n^2 I
+//   dS/dlog sigma_n^2 = sigma_n^2 E,  E_ij = 1 where rows i and j are the same pool site (I unless a site is listed more than
+//   once: the kernel matrix gives such rows' cross entries sigma_n^2 too, algp_hip.h at algp_set_train)
 // S^-1 = X X' with X = L^-T (trinv_upper + syrk_upper on the MFMA GEMM, both skipping X's zero half:
 // N^3/6 + N^3/6 multiply-adds);
 // the pairwise reduction below then streams the lower triangle of S^-1 once (HBM-bound, s*N^2/2
@@ -16,6 +17,7 @@ namespace algp {
 template <typename T, int DP>
 __global__ __launch_bounds__(256) void mll_grad_kernel(const T* Sinv, int64_t ld, int64_t N, const T* Xs,
                                                        const int64_t* aidx, const T* alpha, int kernel, T os,
+                                                       int repeats /* a pool site occurs in more than one row */,
                                                        double* partial /* per workgroup: [0]=os, [1]=noise trace, [2..2+DP) = ls */) {
     // one workgroup = a 64-row x 64-col tile of the lower triangle; the grid enumerates only those
     // (blockIdx.x -> (bi, bj <= bi)).  The 64 rows' coordinates and alpha are staged in LDS once.
@@ -26,6 +28,7 @@ __global__ __launch_bounds__(256) void mll_grad_kernel(const T* Sinv, int64_t ld
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;      // tx: column, ty: 4 row groups of 16
     __shared__ T s_x[64][DP];
     __shared__ T s_a[64];
+    __shared__ int64_t s_p[64];
     if (threadIdx.x < 64) {
         const int64_t i = (int64_t)bi * 64 + threadIdx.x;
         const bool ok = i < N;
@@ -33,16 +36,18 @@ __global__ __launch_bounds__(256) void mll_grad_kernel(const T* Sinv, int64_t ld
 #pragma unroll
         for (int d = 0; d < DP; ++d) s_x[threadIdx.x][d] = ok ? Xs[pi * DP + d] : (T)0;
         s_a[threadIdx.x] = ok ? alpha[i] : (T)0;
+        s_p[threadIdx.x] = ok ? pi : (int64_t)-1;
     }
     const int64_t j = (int64_t)bj * 64 + tx;
     double g_os = 0, g_tr = 0, g_ls[DP];
 #pragma unroll
     for (int d = 0; d < DP; ++d) g_ls[d] = 0;
     T xj[DP], aj = (T)0;
+    int64_t pj = -2;
 #pragma unroll
     for (int d = 0; d < DP; ++d) xj[d] = (T)0;
     if (j < N) {
-        const int64_t pj = aidx[j];
+        pj = aidx[j];
 #pragma unroll
         for (int d = 0; d < DP; ++d) xj[d] = Xs[pj * DP + d];
         aj = alpha[j];
@@ -81,6 +86,7 @@ __global__ __launch_bounds__(256) void mll_grad_kernel(const T* Sinv, int64_t ld
             }
             g_os += m * (double)(w * kv);
             if (i == j) g_tr += (double)w;
+            else if (repeats && s_p[li] == pj) g_tr += 2.0 * (double)w;   // a second row of the same site: S_ij holds sigma_n^2 too
 #pragma unroll
             for (int d = 0; d < DP; ++d) g_ls[d] += m * (double)(w * dk * u2[d]);
         }
@@ -126,12 +132,13 @@ template <typename T>
 int mll_grad_launch(algp_ctx* c, const T* Sinv, int64_t ld, int64_t N, const T* Xs, int DP, const int64_t* aidx,
                     const T* alpha, int kernel, T os, double* out_dev, double* partial) {
     if (N <= 0) return ALGP_OK;
+    const int rp = c->train_has_repeats ? 1 : 0;
     const unsigned nb = (unsigned)((N + 63) / 64);
     ProfScope ps(c, ALGP_PROF_KMAT, 0.5 * (double)N * N * (3.0 * DP + 8.0), sizeof(T) * 0.5 * (double)N * N);
     dim3 grid(nb * (nb + 1) / 2), blk(256);
-    if (DP == 2) hipLaunchKernelGGL((mll_grad_kernel<T, 2>), grid, blk, 0, c->cur, Sinv, ld, N, Xs, aidx, alpha, kernel, os, partial);
-    else if (DP == 4) hipLaunchKernelGGL((mll_grad_kernel<T, 4>), grid, blk, 0, c->cur, Sinv, ld, N, Xs, aidx, alpha, kernel, os, partial);
-    else hipLaunchKernelGGL((mll_grad_kernel<T, 8>), grid, blk, 0, c->cur, Sinv, ld, N, Xs, aidx, alpha, kernel, os, partial);
+    if (DP == 2) hipLaunchKernelGGL((mll_grad_kernel<T, 2>), grid, blk, 0, c->cur, Sinv, ld, N, Xs, aidx, alpha, kernel, os, rp, partial);
+    else if (DP == 4) hipLaunchKernelGGL((mll_grad_kernel<T, 4>), grid, blk, 0, c->cur, Sinv, ld, N, Xs, aidx, alpha, kernel, os, rp, partial);
+    else hipLaunchKernelGGL((mll_grad_kernel<T, 8>), grid, blk, 0, c->cur, Sinv, ld, N, Xs, aidx, alpha, kernel, os, rp, partial);
     ALGP_HIP(hipGetLastError());
     hipLaunchKernelGGL(mll_grad_reduce_kernel, dim3(1), dim3(256), 0, c->cur, partial, (int64_t)grid.x, 2 + DP, out_dev);
     ALGP_HIP(hipGetLastError());

@@ -140,7 +140,8 @@ int algp_get_factor(algp_ctx* ctx, void* L_out);             /* N x N lower, zer
 int algp_get_mll(algp_ctx* ctx, double* mll);                /* -1/2 y0'alpha - 1/2 logdet - N/2 log 2pi */
 /* ---- f2: gradient of the MLL for GPR.fit (models.py:137-159; the loss there is -MLL/N) ------
  * grad_out[D+2] = d MLL / d (log_lengthscale[0..D), log_outputscale, log_noise), NOT divided by N.
- * Needs a coordinate pool and a current factorisation.                                          */
+ * Needs a coordinate pool and a current factorisation.  With a site in more than one train row the
+ * cross entries of its rows hold sigma_n^2 (algp_set_train) and count in the log_noise entry.       */
 int algp_get_mll_grad(algp_ctx* ctx, double* grad_out);
 /* The device work of ONE iteration of GPR.fit (models.py:145-158: output = model(train_x); loss = -mll(output, train_y);
  * loss.backward()) in one call, for the current hyper-parameters and train set: = algp_factorize + algp_get_mll +

@@ -475,17 +475,33 @@ def generate_gaussian_data(num_rows, num_cols, k=5, min_var=10, max_var=100, alg
 # --------------------------------------------------------------------------
 # exact-GP marginal log likelihood and its gradient (models.py:137-159 loss)
 # --------------------------------------------------------------------------
-def mll_and_grad(hyp, x, y, var):
+def same_site(sites, N):
+    """E_ij = 1 where rows i and j carry the same site label; the identity for ``sites=None``."""
+    if sites is None:
+        return np.eye(N)
+    sites = np.asarray(sites).reshape(N)
+    return (sites[:, None] == sites[None, :]).astype(np.float64)
+
+
+def mll_and_grad(hyp, x, y, var, mean=None, sites=None):
     """loss = -MLL/N as gpytorch's ExactMarginalLogLikelihood divides by N
     (models.py:148).  Returns (mll_per_point, dict of d mll_per_point / d log-params).
-    RBF kernel only.  Parity unpinned (no reference fixture); used to check the
-    HIP fit path by finite differences."""
+    RBF and Matern-1.5; ``mean``: the constant mean to subtract in place of ``y.mean()``.
+    ``sites``: one label per row; rows with the same label are measurements of ONE pool site, whose
+    cross entries are C(i,i) = k(0) + sigma_n^2 (include/algp_hip.h at algp_set_train: the likelihood
+    noise belongs to the site, ``var`` to the measurement).  None: every row is a site of its own.
+    dMLL/dtheta = 1/2 tr(W dS/dtheta), W = alpha alpha' - S^-1, with
+      dS/dlog os = K ; dS/dlog sigma_n^2 = sigma_n^2 E, E_ij = [site_i == site_j] (I without ``sites``) ;
+      dS/dlog ls_d = K .* u_d^2 (RBF) | 3 os e^{-a} u_d^2 (Matern-1.5: a = sqrt(3) r,
+      u_d = (x_d - x'_d) / ls_d, r^2 = sum_d u_d^2).
+    Parity unpinned (no reference fixture); checked against central differences of
+    its own MLL in tests/test_oracle_golden.py, and what the HIP fit path is held to."""
     x = np.asarray(x, np.float64)
     y = np.asarray(y, np.float64)
     N = len(y)
-    y0 = y - y.mean()
+    y0 = y - (y.mean() if mean is None else float(mean))
     K = kernel_matrix(hyp, x)
-    S = K + hyp.noise * np.eye(N) + (np.diag(var) if var is not None else 0.0)
+    S = K + hyp.noise * same_site(sites, N) + (np.diag(var) if var is not None else 0.0)
     L = np.linalg.cholesky(S)
     from scipy.linalg import cho_solve
     alpha = cho_solve((L, True), y0)
@@ -494,11 +510,15 @@ def mll_and_grad(hyp, x, y, var):
     W = np.outer(alpha, alpha) - Sinv          # dMLL/dtheta = 1/2 tr(W dS/dtheta)
     g = {}
     g['log_outputscale'] = .5 * np.sum(W * K) / N
-    g['log_noise'] = .5 * np.trace(W) * hyp.noise / N
+    g['log_noise'] = .5 * np.sum(W * same_site(sites, N)) * hyp.noise / N
     inv_ls = np.exp(-hyp.log_lengthscale)
-    gl = np.zeros(hyp.D)
-    for d in range(hyp.D):
-        diff = (x[:, d][:, None] - x[:, d][None, :]) * inv_ls[d]
-        gl[d] = .5 * np.sum(W * K * diff * diff) / N
-    g['log_lengthscale'] = gl
+    u2 = [np.square((x[:, d][:, None] - x[:, d][None, :]) * inv_ls[d]) for d in range(hyp.D)]
+    if hyp.kernel == KERNEL_RBF:
+        dK = K                                  # dK/dlog ls_d = dK .* u_d^2
+    elif hyp.kernel == KERNEL_MATERN15:
+        dK = 3.0 * hyp.outputscale * np.exp(-np.sqrt(3.0 * sum(u2)))
+    else:
+        raise NotImplementedError(hyp.kernel)
+    WdK = W * dK
+    g['log_lengthscale'] = np.array([.5 * np.sum(WdK * u2[d]) / N for d in range(hyp.D)])
     return mll / N, g

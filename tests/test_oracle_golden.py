@@ -206,20 +206,45 @@ def test_kat_entropy_scaled_identity():
         assert O.entropy_from_cov_chol(s2 * np.eye(k)) == pytest.approx(want, rel=1e-13)
 
 
-def test_mll_grad_finite_difference():
-    rng = np.random.RandomState(3)
-    x = rng.uniform(0, 6, (30, 2))
-    y = np.sin(x[:, 0]) + 0.1 * rng.standard_normal(30)
-    var = np.full(30, 0.01)
-    hyp = O.Hypers(np.log([1.3, 2.1]), np.log(0.9), np.log(0.05))
-    f0, g = O.mll_and_grad(hyp, x, y, var)
+@pytest.mark.parametrize('kernel', [O.KERNEL_RBF, O.KERNEL_MATERN15], ids=['rbf', 'matern'])
+@pytest.mark.parametrize('D,mean,twice', [(1, None, False), (2, None, False), (3, None, False), (5, None, False),
+                                          (2, 0.3, False), (2, None, True)],
+                         ids=['D1', 'D2', 'D3', 'D5', 'D2_mean_given', 'D2_site_twice'])
+def test_mll_grad_finite_difference(kernel, D, mean, twice):
+    """The closed-form gradient against central differences of the oracle's own MLL (error O(eps^2) ~ 1e-12 plus the
+    rounding of the difference, ~1e-16 |MLL| / eps = 1e-10 ... 1e-9), for both kernels, D = 1 .. 5, and with the
+    constant mean given instead of y.mean(), and with one site measured twice (sites=: its two rows share the likelihood
+    noise, so the noise gradient has their cross entry too)."""
+    rng = np.random.RandomState(3 + D)
+    N = 30
+    x = rng.uniform(0, 6 if D <= 3 else 4, (N, D))
+    y = np.sin(x[:, 0]) + 0.1 * rng.standard_normal(N)
+    var = rng.uniform(0.005, 0.05, N)
+    ls = np.log(rng.uniform(0.8, 2.1, D))
+    hyp = O.Hypers(ls, np.log(0.9), np.log(0.05), kernel)
+    sites = None
+    if twice:
+        sites = np.arange(N)
+        sites[N - 1] = sites[3]
+        x[N - 1] = x[3]
+        assert O.mll_and_grad(hyp, x, y, var, sites=sites)[0] != O.mll_and_grad(hyp, x, y, var)[0]
+    f0, g = O.mll_and_grad(hyp, x, y, var, mean=mean, sites=sites)
+    if mean is None:                                         # the default is the mean of y
+        assert O.mll_and_grad(hyp, x, y, var, mean=y.mean(), sites=sites)[0] == f0
+    else:
+        assert O.mll_and_grad(hyp, x, y, var)[0] != f0
     eps = 1e-6
-    h = O.Hypers(hyp.log_lengthscale, hyp.log_outputscale + eps, hyp.log_noise)
-    assert (O.mll_and_grad(h, x, y, var)[0] - f0) / eps == pytest.approx(g['log_outputscale'], rel=1e-4)
-    h = O.Hypers(hyp.log_lengthscale, hyp.log_outputscale, hyp.log_noise + eps)
-    assert (O.mll_and_grad(h, x, y, var)[0] - f0) / eps == pytest.approx(g['log_noise'], rel=1e-4)
-    for d in range(2):
-        ls = hyp.log_lengthscale.copy()
-        ls[d] += eps
-        h = O.Hypers(ls, hyp.log_outputscale, hyp.log_noise)
-        assert (O.mll_and_grad(h, x, y, var)[0] - f0) / eps == pytest.approx(g['log_lengthscale'][d], rel=1e-4)
+
+    def central(dls, dos, dn):
+        hp = O.Hypers(ls + dls, hyp.log_outputscale + dos, hyp.log_noise + dn, kernel)
+        hm = O.Hypers(ls - dls, hyp.log_outputscale - dos, hyp.log_noise - dn, kernel)
+        return (O.mll_and_grad(hp, x, y, var, mean=mean, sites=sites)[0] -
+                O.mll_and_grad(hm, x, y, var, mean=mean, sites=sites)[0]) / (2 * eps)
+
+    zero = np.zeros(D)
+    assert central(zero, eps, 0.0) == pytest.approx(g['log_outputscale'], rel=1e-6, abs=1e-8)
+    assert central(zero, 0.0, eps) == pytest.approx(g['log_noise'], rel=1e-6, abs=1e-8)
+    for d in range(D):
+        e = zero.copy()
+        e[d] = eps
+        assert central(e, 0.0, 0.0) == pytest.approx(g['log_lengthscale'][d], rel=1e-6, abs=1e-8)
