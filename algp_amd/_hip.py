@@ -345,7 +345,11 @@ class Context(object):
         return (mu, var) if want_var else mu
 
     def posterior_cov(self, want_cov=True, want_mi=False):
-        cov = np.empty((self.M, self.M), dtype=self.dtype) if want_cov else None
+        """(cov, mi): the M x M posterior covariance K_** + diag(extra_var) - B^T S^-1 B and mi = H(cov_xx) - H(cov)
+        (algp_get_posterior_cov); None for the one not asked for.  Raises ValueError (ALGP_ERR_STATE) when a candidate is
+        a train site under prior_includes_noise=True, or when picks were committed since the candidate solve: the resident
+        V^T then does not describe that covariance (use prior_includes_noise=False; solve the candidates again)."""
+        cov =np.empty((self.M, self.M), dtype=self.dtype) if want_cov else None
         mi = C.c_double()
         self._check(self.lib.algp_get_posterior_cov(self.h, _ptr(cov), C.byref(mi) if want_mi else None))
         return cov, (mi.value if want_mi else None)

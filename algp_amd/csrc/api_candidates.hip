@@ -361,6 +361,28 @@ int Impl<T>::get_posterior_cov(algp_ctx* c, void* cov_out, double* mi_out) {
     if (!c->solved) return fail(c, ALGP_ERR_STATE, "get_posterior_cov: call algp_solve_candidates first");
     if (c->pool_is_cov) return fail(c, ALGP_ERR_BAD_ARG, "get_posterior_cov needs a coordinate pool");
     const int64_t M = c->M, Mpad = c->Mpad;
+    // cov = cov_xx - V^T V holds for ordinary rows of B^T solved against the train set alone.  Two resident states are
+    // something else and are refused instead of answered wrongly:
+    //  - a unit row e_pos (a candidate that is a train site under prior_includes_noise = 1) has V_j = L^T e_pos: its
+    //    products with the other rows are not K_jk - cov_ja S^-1 cov_ak;
+    //  - picks committed since the solve live in columns [Npad, ncols) of V^T, which this product does not read, while
+    //    algp_get_posterior's variances include them.
+    if (c->prior_noise)
+        for (int64_t j = 0; j < M; ++j)
+            if (c->vt_kind[j] >= 0)
+                return fail(c, ALGP_ERR_STATE,
+                            "get_posterior_cov: candidate " + std::to_string(j) + " (pool index " + std::to_string(c->cand_idx[j]) +
+                                ") is a train site and was solved as a unit row (prior_includes_noise = 1): set the "
+                                "candidates with prior_includes_noise = 0");
+    if (!c->picks.empty())
+        return fail(c, ALGP_ERR_STATE, "get_posterior_cov: " + std::to_string(c->picks.size()) +
+                                           " pick(s) were committed since the candidate solve, which the covariance would "
+                                           "not include: solve the candidates again");
+    c->last_jitter = 0.0;
+    if (M == 0) {                                             // an empty set: a 0 x 0 covariance, H(cov_xx) = H(cov) = 0
+        if (mi_out) *mi_out = 0.0;
+        return ALGP_OK;
+    }
     ALGP_TRY(ensure(c, c->auxA, sizeof(T) * Mpad * Mpad));
     ALGP_TRY(ensure(c, c->auxW, sizeof(T) * Mpad * Mpad));
     ALGP_TRY(ensure(c, c->auxInv, sizeof(T) * Mpad * NB));

@@ -169,7 +169,16 @@ int algp_solve_candidates_update(algp_ctx* ctx, const uint8_t* alive, int64_t* k
 int algp_set_candidate_alive(algp_ctx* ctx, const uint8_t* alive);
 int algp_get_posterior(algp_ctx* ctx, void* mu_out, void* var_out);      /* either may be NULL  */
 /* full M x M posterior covariance (utils.py:305) and mi = H(cov_xx) - H(cov) (utils.py:314);
- * cov_out / mi_out may be NULL.                                                                */
+ * cov_out / mi_out may be NULL.  cov_xx = K_xx + diag(extra_var) never carries sigma_n^2 (utils.py:297), also under
+ * prior_includes_noise = 1: diag(cov) is then algp_get_posterior's variance minus sigma_n^2.  extra_var is per row: two
+ * rows of one site share K(x, x) without it.  M = 0: nothing is written to cov_out, mi = 0.
+ * The product cov_xx - V^T V is the covariance only for ordinary rows solved against the train set alone, so two
+ * states are refused with ALGP_ERR_STATE instead of answered:
+ *  - a candidate that is a train site under prior_includes_noise = 1 (a unit row of B^T; the message names it):
+ *    set the candidates with prior_includes_noise = 0, where such a row is an ordinary point;
+ *  - picks committed since the candidate solve (algp_commit_pick / algp_greedy), which algp_get_posterior's variances
+ *    include and this product would not: solve the candidates again.
+ * An explicit-covariance pool: ALGP_ERR_BAD_ARG.                                               */
 int algp_get_posterior_cov(algp_ctx* ctx, void* cov_out, double* mi_out);
 /* mean only, mu = ybar + K_xa alpha with K never materialised (utils.py:301)                   */
 int algp_posterior_mean(algp_ctx* ctx, const int64_t* idx, int64_t M, void* mu_out);
