@@ -388,9 +388,18 @@ class Context(object):
         return pos.value, pool.value, val.value
 
     def commit_pick(self, pool_idx, static_std, mobile_std):
+        """Make pool site `pool_idx` static-sampled (algp_commit_pick).  It need not be a local candidate, and a candidate
+        masked with solve_candidates(alive=...) is accepted too (its row stays at -inf).  Raises ValueError for a site
+        committed before (ALGP_ERR_BAD_ARG) and for the 129th pick since the candidate solve (ALGP_ERR_STATE: solve the
+        candidates again; checked first, so with 128 picks committed a repeat is ALGP_ERR_STATE too); the state is
+        unchanged after either."""
         self._check(self.lib.algp_commit_pick(self.h, int(pool_idx), float(static_std), float(mobile_std)))
 
     def greedy(self, criterion, static_std, mobile_std, k, forced_picks=None, want_utilities=False):
+        """k picks (algp_greedy); with want_utilities also the (k, M) utilities every pick was chosen from.  k > 128, the
+        picks that fit behind one candidate solve, raises ValueError (ALGP_ERR_BAD_ARG) before anything is committed.
+        Only k is checked: a call whose picks, with those committed earlier, pass 128 commits the ones that fit and then
+        raises ValueError (ALGP_ERR_STATE)."""
         picks = np.empty(k, dtype=np.int64)
         ut = np.empty((k, self.M), dtype=np.float64) if want_utilities else None
         f = None if forced_picks is None else self._idx(forced_picks)

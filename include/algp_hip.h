@@ -197,7 +197,15 @@ int algp_posterior_mean(algp_ctx* ctx, const int64_t* idx, int64_t M, void* mu_o
  * algp_commit_pick: make pool index `pool_idx` static-sampled (agent.py:352-354): the rank-1 row
  *   append to V^T and to every candidate's pv / s.  The pick is recorded and the rows catch up on
  *   demand (all of them before algp_scores / algp_get_posterior read them).  The index need not be
- *   a local candidate (sharded scoring: every rank commits the global winner).
+ *   a local candidate (sharded scoring: every rank commits the global winner).  A candidate switched off with
+ *   algp_set_candidate_alive is accepted too: the mask takes a row out of the scoring and out of the library's own picks,
+ *   not out of the sites a caller may name; the row stays at -inf.  A site already committed since the candidate solve:
+ *   ALGP_ERR_BAD_ARG.  At most 128 picks fit behind one candidate solve (the appended columns of V^T): the 129th
+ *   algp_commit_pick is refused with ALGP_ERR_STATE and algp_greedy with k > 128 with ALGP_ERR_BAD_ARG before anything is
+ *   committed; either leaves the state, and what algp_scores returns, untouched.  Solve the candidates again to go on.
+ *   The capacity is checked before the repeat: once 128 picks are committed, naming one of them again is ALGP_ERR_STATE
+ *   too.  algp_greedy checks k alone, not k plus the picks already committed: a call that would pass 128 in total commits
+ *   the picks that fit and returns ALGP_ERR_STATE at the first that does not.
  * algp_greedy: k picks on one GPU.  utilities_out (k*M doubles, local candidate order) may be
  *   NULL; forced_picks (k pool indices) may be NULL.  With both NULL and the entropy criterion a pick
  *   is one host round trip (see algp_greedy_sharded: the same chain without the gather).
