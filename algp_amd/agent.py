@@ -23,7 +23,8 @@ from . import _hip
 from .models import GPR
 from .utils import CONST, compute_mae, find_equi_sample_path, find_shortest_path, predictive_distribution
 
-_CRIT = {'entropy': _hip.CRIT_ENTROPY, 'mutual_information': _hip.CRIT_MUTUAL_INFORMATION}
+_CRIT = {'entropy': _hip.CRIT_ENTROPY, 'mutual_information': _hip.CRIT_MUTUAL_INFORMATION,
+         'variance_reduction': _hip.CRIT_VARIANCE_REDUCTION}
 
 
 def get_heading(prev, cur):
@@ -371,6 +372,9 @@ class Agent(object):
 
     def greedy(self, num_samples):
         """k most informative static sampling sites, greedily (agent.py:295-356)."""
+        if self.criterion == 'variance_reduction' and self.comm is not None:
+            raise NotImplementedError("criterion 'variance_reduction' is not sharded: its targets are the whole candidate set, "
+                                      "which no rank of a sharded agent holds; run it on one GPU")
         c = self._load_pool()
         static, mobile = self._masks()
         sampled = static | mobile
@@ -410,6 +414,9 @@ class Agent(object):
         """Index of the most informative path (agent.py:358-403)."""
         if len(paths_mobile_indices) == 1:
             return 0
+        if self.criterion == 'variance_reduction':
+            raise NotImplementedError("criterion 'variance_reduction' scores single static sites (Agent.greedy, run_greedy_ipp); "
+                                      "a path utility would need a targets x path block of the posterior covariance per path")
         c = self._load_pool()
         n = self.env.num_samples
         static, mobile0 = self._masks()
@@ -549,6 +556,8 @@ class Agent(object):
     def run_ipp(self, render=False, num_runs=10, criterion='entropy', update=False, slack=0, strategy='MaxEnt',
                 disp=True):
         assert strategy in ['MaxEnt', 'Shortest', 'Equi-Sample'], 'Unknown strategy!!'
+        if criterion == 'variance_reduction':
+            raise NotImplementedError("criterion 'variance_reduction' has no path utility (Agent.best_path): use run_greedy_ipp")
         assert criterion in ['entropy', 'mutual_information'], 'Unknown criterion!!'
         self._setup_ipp(criterion, update)
         test_error, pred, var, error = [], None, None, None
@@ -580,6 +589,8 @@ class Agent(object):
         return {'mean': pred, 'error': test_error}
 
     def run_greedy_ipp(self, num_runs=10, criterion='entropy', strategy='MaxEnt', disp=True):
+        """criterion='variance_reduction' has no path utility: where the planner offers several paths to a waypoint, 'MaxEnt'
+        and 'Equi-Sample' raise NotImplementedError from best_path (one path is taken as it is); pass strategy='Shortest'."""
         self._setup_ipp(criterion)
         for i in range(num_runs):
             new_idx = self.greedy(self.num_samples_per_batch)

@@ -23,7 +23,7 @@ def get_parser():
     p.add_argument('--num_test', default=40, type=int)
     p.add_argument('--update', action='store_true')
     p.add_argument('--update_every', default=1, type=int)
-    p.add_argument('--criterion', default='entropy', choices=['entropy', 'mutual_information'])
+    p.add_argument('--criterion', default='entropy', choices=['entropy', 'mutual_information', 'variance_reduction'])
     p.add_argument('--static_std', default=.1, type=float)
     p.add_argument('--render', action='store_true')
     p.add_argument('--seed', default=1, type=int)

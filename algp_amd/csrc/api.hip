@@ -536,6 +536,7 @@ void algp_destroy(algp_ctx* c) {
                       &c->auxVar, &c->auxD, &c->hostStage, &c->rowx, &c->tailE, &c->tailPart, &c->ldpart};
     for (DevBuf* b : bufs) release(c, *b);
     release(c, c->mi);
+    release(c, c->vr);
     dag_release(c);
     comm_destroy(c);
     for (hipEvent_t e : c->event_pool) hipEventDestroy(e);

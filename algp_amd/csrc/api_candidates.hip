@@ -136,6 +136,7 @@ int Impl<T>::solve_prepare(algp_ctx* c, int incremental, typename Impl<T>::Solve
     const int64_t N = c->N, Npad = c->Npad, M = c->M, Mpad = c->Mpad, keep = pl.keep;
     const int64_t ldv = Npad + MAX_APPEND;
     c->solved = false;
+    c->vr.drop();
     if (!c->Vt.p || c->ldv_cap < ldv || (keep == 0 && !incremental && c->ldv_cap != ldv) ||
         c->Vt.cap < sizeof(T) * Mpad * c->ldv_cap) {
         // (re)allocate; keep the valid columns when growing.  A caller that asks for reuse gets 12.5 %
@@ -287,6 +288,7 @@ int Impl<T>::solve_finish(algp_ctx* c, int incremental, const unsigned char* ali
     c->ncols = Npad;
     c->picks.clear();
     c->mi.valid = false;
+    c->vr.drop();
     ALGP_TRY(reset_lazy(c));
     c->solved = true;
     c->vt_fact_idx = c->fact_idx;

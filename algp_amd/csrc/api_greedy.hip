@@ -20,6 +20,8 @@ int Impl<T>::scores_enqueue(algp_ctx* c, int criterion, double static_std, doubl
     if (!dst) dst = (double*)c->scores.p;
     if (criterion == ALGP_CRIT_MUTUAL_INFORMATION) {
         ALGP_TRY(mi_scores_enqueue(c, ss, sm, delta, dst));
+    } else if (criterion == ALGP_CRIT_VARIANCE_REDUCTION) {
+        ALGP_TRY(vr_scores_enqueue(c, ss, delta, dst));
     } else if (criterion == ALGP_CRIT_ENTROPY) {
         ALGP_TRY(score_launch<T>(c, c->M, (const int*)c->ckind.p, (const unsigned char*)c->alive.p, (const T*)c->dstat.p,
                                  ss, delta, (const double*)nullptr, dst));

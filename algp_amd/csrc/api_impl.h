@@ -1,8 +1,9 @@
 // api_impl.h -- the typed host-side implementation behind the C ABI (include/algp_hip.h), declared once and defined by
 // concern: api.hip (context, hyper-parameters, pool, train set, the stand-alone matrix entry points), api_factor.hip (the
 // factor of the train set and its updates), api_candidates.hip (candidate solve and posterior), api_greedy.hip (scoring,
-// picks, the sharded exchange), api_mi.hip (the MI criterion's state, on one GPU and over the ranks), api_paths.hip
-// (best_path block scoring), api_fit.hip (MLL gradient, one fit iteration).  Every file defines its members of Impl<T> and instantiates Impl<float> / Impl<double> for them.
+// picks, the sharded exchange), api_mi.hip (the MI criterion's state, on one GPU and over the ranks), api_vr.hip (the
+// variance-reduction criterion), api_paths.hip (best_path block scoring), api_fit.hip (MLL gradient, one fit iteration).
+// Every file defines its members of Impl<T> and instantiates Impl<float> / Impl<double> for them.
 #pragma once
 #include <limits.h>
 #include <math.h>
@@ -18,6 +19,7 @@ namespace algp {
 
 void release(algp_ctx* c, DevBuf& b);
 void release(algp_ctx* c, MiState& mi);   // every MI buffer (api_mi.hip)
+void release(algp_ctx* c, VrState& vr);   // every buffer of the variance-reduction criterion (api_vr.hip)
 hipEvent_t sync_event_api(algp_ctx* c, size_t i);
 KmatSrc make_src(algp_ctx* c);
 int sync(algp_ctx* c);
@@ -128,6 +130,10 @@ struct Impl {
     static int mi_shard_fold(algp_ctx* c, int st);
     static int mi_shard_step(algp_ctx* c, double ss, double sm, int st, bool first_of_call);
     static int mi_scores_enqueue(algp_ctx* c, double ss, double sm, double delta, double* dst);
+    // the variance-reduction criterion's column sums (api_vr.hip): the fused product, one pick's rank-1 fold, the utilities
+    static int vr_product(algp_ctx* c);
+    static int vr_fold(algp_ctx* c, int64_t q);
+    static int vr_scores_enqueue(algp_ctx* c, double ss, double delta, double* dst);
     static int scores_enqueue(algp_ctx* c, int criterion, double static_std, double mobile_std, double* dst);
     static int scores(algp_ctx* c, int criterion, double static_std, double mobile_std, void* out, int out_is_device);
     static int argmax(algp_ctx* c, int64_t* local_pos, int64_t* pool_idx, double* value);

@@ -110,6 +110,23 @@ struct MiState {
     }
 };
 
+// The variance-reduction criterion's state (api_vr.hip): w_c = sum over the targets j (the ordinary rows of the candidate
+// set, fixed by the solve) of E_jc^2, E the signed cross term of include/algp_hip.h, for the first npicks committed picks.
+// Built by one fused product per candidate solve (gemm.hip, gemm_nt_kernel_dma4_vr); later picks are folded in by the rank-1
+// identity, one pass over V^T each.  It does not depend on the noise levels (ss, sm): they enter when the utilities are formed.
+struct VrState {
+    DevBuf W;                            // w, one entry per candidate row
+    DevBuf Part;                         // the product's sums per column tile, for one chunk of column tiles
+    DevBuf R;                            // a pick's column of V^T: [all rows | targets only, zero elsewhere]
+    DevBuf Tp, Tv;                       // t = V_T^T r_T: its partial sums per row block, and t
+    DevBuf Y;                            // [sum_j C(c, j) r_j | V_c . t]
+    DevBuf Nrm;                          // |r_T|^2
+    bool valid = false;
+    int64_t npicks = 0;                  // picks folded in
+
+    void drop() { valid = false; npicks = 0; }
+};
+
 }  // namespace algp
 
 namespace algp {
@@ -232,6 +249,7 @@ struct algp_ctx {
     int64_t kept_cols_last = 0;
 
     algp::MiState mi;                    // the MI criterion's resident state (api_mi.hip)
+    algp::VrState vr;                    // the variance-reduction criterion's column sums (api_vr.hip)
 
     // multi-GPU: transport of the sharded greedy loop's one all-gather (comm.hip): an RCCL communicator
     // (algp_comm_init), a caller-supplied host all-gather (algp_comm_init_host), or neither (one rank)
@@ -297,7 +315,8 @@ void prof_span_end2(algp_ctx* c);
 //   ALGP_ROW_STATS=0 / ALGP_TRSM_INV512=0 (the chunked solve with a variance pass / with 128-column steps inside a block),
 //   ALGP_FACTOR_FROM_VT=0 (new rows of an updated factor solved, not gathered), ALGP_LAZY_GREEDY=0 (every row scored before
 //   every pick), ALGP_TRSM_CHUNKS=n (row-chunk streams of the big solve; bench.py's one-stream leg sets it by the ABI).
-// Cross-check routes: ALGP_CHOL_DAG=0 (launch-sequence factorisation), ALGP_GATHER_ROWS=0 (remote commits rebuild the row).
+// Cross-check routes: ALGP_CHOL_DAG=0 (launch-sequence factorisation), ALGP_GATHER_ROWS=0 (remote commits rebuild the row),
+//   ALGP_VR_RANK1=0 (variance-reduction criterion: the full product at every scoring instead of one rank-1 fold per pick).
 // Tooling: ALGP_LAUNCH_LOG=<file> (tools/trace_shapes.py), ALGP_RCCL_PATH=<file> (which librccl to dlopen).
 inline bool env_switch(const char* name, bool dflt) {
     const char* e = getenv(name);
@@ -377,6 +396,12 @@ int gemm_nt_launch_tri(algp_ctx* c, int klass, int64_t m, int64_t n, const T* A,
 template <typename T>
 int gemm_nt_launch_stats(algp_ctx* c, int klass, int64_t m, int64_t k, T alpha, const T* A, int64_t lda, const T* B, int64_t ldb,
                          T* D, int64_t ldd, const T* w, T* stat_out, int64_t stat_ld);
+// variance-reduction criterion: rows [0, mpad) of V^T against its rows [ncol0, ncol0 + n) over the first k columns; per row and
+// column tile bn of the launch the sum over the tile's target columns of (kappa_row C(row, j) - V_row . V_j)^2 goes to
+// part[bn * part_ld + row]; no matrix is written (gemm.hip)
+template <typename T>
+int gemm_nt_launch_vr(algp_ctx* c, int klass, int64_t mpad, int64_t n, int64_t k, const T* Vt, int64_t ldv, int64_t ncol0,
+                      const KmatSrc& s, const int64_t* cidx, const int* ckind, int64_t M, T* part, int64_t part_ld);
 // C (m x m, lower tiles) -= X X^T for a short, very wide X (m <= 512 rows, k columns): the k range is cut into
 // chunks that run as one batched launch, the partial products are summed in chunk order (deterministic)
 template <typename T>

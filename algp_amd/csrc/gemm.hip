@@ -31,6 +31,7 @@
 #include <hip/hip_ext.h>
 #include "mfma.h"
 #include <algorithm>
+#include <type_traits>
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -84,6 +85,101 @@ __device__ __forceinline__ T row16_sum(T x) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Variance-reduction criterion (api_vr.hip): A = B = V^T, rows c against columns j.  The tile's accumulators hold
+// G_cj = V_c . V_j; the epilogue forms E_cj = kappa_c C(c, j) - G_cj in registers (kappa_c = 1 for an ordinary row, 0 for a
+// unit row; C from the scaled coordinates of the tile's 128 rows and 128 columns staged in LDS, with the one kernel-value
+// definition kexp, or read from an explicit pool covariance), drops the columns that are not targets (unit rows, padding),
+// squares, and sums over the tile's 128 columns per row exactly as the STATS epilogue does: stat_out[bn * stat_ld + row].
+// Neither a D tile nor a kernel-matrix block is written.  Fixed order: the same bits in every run.
+// ---------------------------------------------------------------------------------------------
+template <typename T>
+struct VrGemmArgs : GemmArgs<T> {
+    const int64_t* cidx;           // pool index of every candidate row (M entries)
+    const int* ckind;              // >= 0: a unit row
+    int64_t M;                     // rows / columns beyond M are padding
+    int64_t ncol0;                 // candidate row that column 0 of this launch's B is
+    const T* Xs;                   // scaled coordinates, DP per site (coordinate pool)
+    const T* Cp;                   // or the explicit pool covariance (n_pool x n_pool)
+    int64_t n_pool;
+    int DP, kernel;
+    T os, noise;
+};
+
+template <typename T, typename ACC>
+__device__ __forceinline__ void vr_epilogue(const VrGemmArgs<T>& g, char* smem, const ACC (&acc)[4][4], int64_t m0, int64_t n0, int bn,
+                                            int wr, int wc, int lane, int tid) {
+    using F = MF<T>;
+    const int fr = lane & 15;
+    // LDS: [2 column halves][128 rows] sums | coordinates of the rows, of the columns ([128][MAXD], zero padded) | pool
+    // indices of the rows, of the columns | kappa of the rows | target mask of the columns
+    T* red = reinterpret_cast<T*>(smem);
+    T* xr = reinterpret_cast<T*>(smem + 2048);
+    T* xc = reinterpret_cast<T*>(smem + 2048 + 8192);
+    int64_t* pr = reinterpret_cast<int64_t*>(smem + 2048 + 16384);
+    int64_t* pc = pr + 128;
+    int* kr = reinterpret_cast<int*>(pc + 128);
+    int* mc = kr + 128;
+    __syncthreads();                                               // every wave is done with the last stage
+    {
+        const int t = tid & 127;
+        const bool is_col = tid >= 128;
+        const int64_t gi = is_col ? g.ncol0 + n0 + t : m0 + t;
+        const bool valid = gi < g.M;
+        const int64_t p = valid ? g.cidx[gi] : 0;
+        const int ordinary = (valid && g.ckind[gi] < 0) ? 1 : 0;
+        (is_col ? pc : pr)[t] = p;
+        (is_col ? mc : kr)[t] = ordinary;
+        if (!g.Cp) {
+            T* x = (is_col ? xc : xr) + t * MAXD;
+#pragma unroll
+            for (int d = 0; d < MAXD; ++d) x[d] = d < g.DP ? g.Xs[p * g.DP + d] : (T)0;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = wr * 64 + i * 16 + F::row_of(lane, r);
+            const int64_t prow = pr[row];
+            const T kap = kr[row] ? (T)1 : (T)0;
+            T xrow[MAXD];
+#pragma unroll
+            for (int d = 0; d < MAXD; ++d) xrow[d] = xr[row * MAXD + d];
+            T s2 = (T)0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int col = wc * 64 + j * 16 + fr;
+                const int64_t pcol = pc[col];
+                T cv;
+                if (g.Cp) {
+                    cv = g.Cp[prow * g.n_pool + pcol];
+                } else {
+                    T r2 = (T)0;
+#pragma unroll
+                    for (int d = 0; d < MAXD; ++d) {
+                        const T df = xrow[d] - xc[col * MAXD + d];
+                        r2 += df * df;
+                    }
+                    if (g.kernel == ALGP_KERNEL_RBF) cv = g.os * kexp((T)-0.5 * r2);
+                    else {
+                        const T rr = sqrt(r2) * (T)1.7320508075688772;
+                        cv = g.os * ((T)1 + rr) * kexp(-rr);
+                    }
+                    if (prow == pcol) cv += g.noise;
+                }
+                T e = kap * cv - acc[i][j][r];
+                e = mc[col] ? e : (T)0;
+                s2 += e * e;
+            }
+            s2 = row16_sum<T>(s2);
+            if (fr == 0) red[wc * 128 + row] = s2;
+        }
+    __syncthreads();
+    if (tid < 128) g.stat_out[(int64_t)bn * g.stat_ld + m0 + tid] = red[tid] + red[128 + tid];
+}
+
+// ---------------------------------------------------------------------------------------------
 // LDS-DMA staging with FOUR stages of 64-byte rows (4 x 16 KB, two workgroups per CU) and hand-placed waits, so
 // that the loads of THREE k-tiles (8 f64 / 16 f32 wide each) are in flight while one is multiplied.  Per k-tile and wave: s_waitcnt vmcnt(8) (own DMA of this tile landed, two
 // younger tiles may still fly), s_barrier (everybody's DMA landed, everybody is done reading the stage
@@ -102,8 +198,11 @@ __device__ __forceinline__ T row16_sum(T x) {
 #ifndef ALGP_GEMM_XOR_MASK
 #define ALGP_GEMM_XOR_MASK 2
 #endif
-template <typename T, bool STATS = false>
-__global__ __launch_bounds__(256, 2) void gemm_nt_kernel_dma4(GemmArgs<T> g) {
+// Args = VrGemmArgs<T>: the variance-reduction epilogue above instead of a D tile (STATS is then false).
+template <typename T, bool STATS = false, typename Args = GemmArgs<T>>
+__global__ __launch_bounds__(256, 2) void gemm_nt_kernel_dma4(Args g) {
+    constexpr bool VR = !std::is_same<Args, GemmArgs<T>>::value;
+    static_assert(!(VR && STATS), "one epilogue per kernel");
     constexpr int NST = 4;
     using F = MF<T>;
     using acc_t = typename F::acc_t;
@@ -223,6 +322,10 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel_dma4(GemmArgs<T> g) {
         st = (st + 1 == NST) ? 0 : st + 1;
     }
 
+    if constexpr (VR) {
+        vr_epilogue<T>(g, smem, acc, m0, n0, bn, wr, wc, lane, tid);
+        return;
+    }
     const T alpha = g.alpha, beta = g.beta;
     const T* Cb = g.C + bz * g.sC;
     T* Db = g.D + bz * g.sD;
@@ -291,6 +394,16 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel_dma4(GemmArgs<T> g) {
     }
 }
 
+// $ALGP_LAUNCH_LOG=<file>: one line per launch of gemm_nt_kernel_dma4 (any instantiation), in enqueue order (class m n k
+// lower_only batch ktri element-size kcut): joined with a rocprofv3 kernel trace by dispatch order, it gives the trace the K
+// its grid sizes do not show (tools/trace_shapes.py)
+static void launch_log_line(int klass, int64_t m, int64_t n, int64_t k, int lower_only, int batch, int ktri, int es, int kcut) {
+    static FILE* launch_log = getenv("ALGP_LAUNCH_LOG") ? fopen(getenv("ALGP_LAUNCH_LOG"), "w") : nullptr;
+    if (!launch_log) return;
+    fprintf(launch_log, "%d %lld %lld %lld %d %d %d %d %d\n", klass, (long long)m, (long long)n, (long long)k, lower_only, batch, ktri, es, kcut);
+    fflush(launch_log);
+}
+
 template <typename T>
 int gemm_nt_launch_batched(algp_ctx* c, int klass, int64_t m, int64_t n, int64_t k, T alpha, const T* A, int64_t lda,
                            int64_t sA, const T* B, int64_t ldb, int64_t sB, T beta, const T* C, int64_t ldc, int64_t sC,
@@ -328,15 +441,7 @@ int gemm_nt_launch_batched(algp_ctx* c, int klass, int64_t m, int64_t n, int64_t
                               : 2.0 * 128.0 * 128.0 * (double)k * (double)tiles * batch;
     const double bytes = sizeof(T) * batch * ((double)tiles * 128.0 * 128.0 * (beta != (T)0 ? 2.0 : 1.0) +
                                               (double)k * 128.0 * (double)(g.tiles_m + g.tiles_n));
-    {
-        // $ALGP_LAUNCH_LOG=<file>: one line per GEMM launch, in enqueue order (class m n k lower_only batch ktri element-size kcut): joined with a
-        // rocprofv3 kernel trace by dispatch order, it gives the trace the K its grid sizes do not show (tools/trace_shapes.py)
-        static FILE* launch_log = getenv("ALGP_LAUNCH_LOG") ? fopen(getenv("ALGP_LAUNCH_LOG"), "w") : nullptr;
-        if (launch_log) {
-            fprintf(launch_log, "%d %lld %lld %lld %d %d %d %d %d\n", klass, (long long)m, (long long)n, (long long)k, lower_only, batch, ktri, (int)sizeof(T), kcut);
-            fflush(launch_log);
-        }
-    }
+    launch_log_line(klass, m, n, k, lower_only, batch, ktri, (int)sizeof(T), kcut);
     int64_t gx = tiles;
     if (ktri) {                                                    // 8 x the largest per-XCD share (rows x, x + 8, ... of XCD x)
         int64_t most = 0;
@@ -360,6 +465,46 @@ int gemm_nt_launch_batched(algp_ctx* c, int klass, int64_t m, int64_t n, int64_t
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
+
+// The variance-reduction column sums of rows [0, mpad) of V^T against its rows [ncol0, ncol0 + n): per row and column
+// tile bn of the launch, part[bn * part_ld + row] = sum over the tile's target columns j of (kappa_row C(row, j) - V_row . V_j)^2,
+// the dot products over the first k columns.  Nothing else is written.
+template <typename T>
+int gemm_nt_launch_vr(algp_ctx* c, int klass, int64_t mpad, int64_t n, int64_t k, const T* Vt, int64_t ldv, int64_t ncol0,
+                      const KmatSrc& s, const int64_t* cidx, const int* ckind, int64_t M, T* part, int64_t part_ld) {
+    if (mpad <= 0 || n <= 0) return ALGP_OK;
+    if (mpad % 128 || n % 128 || k % 128 || k <= 0 || ldv % 4 || ncol0 % 128 || ncol0 + n > mpad || k > ldv || s.DP > MAXD)
+        return fail(c, ALGP_ERR_BAD_ARG, "gemm_nt_vr: operands must be padded to multiples of 128");
+    VrGemmArgs<T> g;
+    g.A = Vt; g.B = Vt + ncol0 * ldv; g.C = nullptr; g.D = nullptr;
+    g.lda = ldv; g.ldb = ldv; g.ldc = 0; g.ldd = 0;
+    g.sA = g.sB = g.sC = g.sD = 0;
+    g.tiles_m = (int)(mpad / 128);
+    g.tiles_n = (int)(n / 128);
+    g.ktiles = (int)(k / (8 * MF<T>::EPC));
+    g.alpha = (T)1; g.beta = (T)0;
+    g.lower_only = 0; g.ktri = 0; g.kcut = 0;
+    g.stat_w = nullptr; g.stat_out = part; g.stat_ld = part_ld;
+    g.cidx = cidx; g.ckind = ckind; g.M = M; g.ncol0 = ncol0;
+    g.Xs = (const T*)s.Xs; g.Cp = (const T*)s.Cp; g.n_pool = s.n_pool; g.DP = s.DP; g.kernel = s.kernel;
+    g.os = (T)s.outputscale; g.noise = (T)s.noise;
+    const int64_t tiles = (int64_t)g.tiles_m * g.tiles_n;
+    if (tiles > 0x7fffffff) return fail(c, ALGP_ERR_BAD_ARG, "gemm_nt_vr: grid too large");
+    const double flops = 2.0 * 128.0 * 128.0 * (double)k * (double)tiles;
+    const double bytes = sizeof(T) * ((double)k * 128.0 * (double)(g.tiles_m + g.tiles_n) + 128.0 * (double)tiles);
+    launch_log_line(klass, mpad, n, k, 0, 1, 0, (int)sizeof(T), 0);
+    hipEvent_t ev_a, ev_b;
+    const bool timed = prof_launch_events(c, klass, flops, bytes, &ev_a, &ev_b);
+    const dim3 grid((unsigned)tiles);
+    if (timed) hipExtLaunchKernelGGL((gemm_nt_kernel_dma4<T, false, VrGemmArgs<T>>), grid, dim3(256), 0, c->cur, ev_a, ev_b, 0, g);
+    else hipLaunchKernelGGL((gemm_nt_kernel_dma4<T, false, VrGemmArgs<T>>), grid, dim3(256), 0, c->cur, g);
+    ALGP_HIP(hipGetLastError());
+    return ALGP_OK;
+}
+template int gemm_nt_launch_vr<double>(algp_ctx*, int, int64_t, int64_t, int64_t, const double*, int64_t, int64_t, const KmatSrc&,
+                                       const int64_t*, const int*, int64_t, double*, int64_t);
+template int gemm_nt_launch_vr<float>(algp_ctx*, int, int64_t, int64_t, int64_t, const float*, int64_t, int64_t, const KmatSrc&,
+                                      const int64_t*, const int*, int64_t, float*, int64_t);
 
 template <typename T>
 int gemm_nt_launch(algp_ctx* c, int klass, int64_t m, int64_t n, int64_t k, T alpha, const T* A,

@@ -315,6 +315,183 @@ template int score_launch<double>(algp_ctx*, int64_t, const int*, const unsigned
 template int score_launch<float>(algp_ctx*, int64_t, const int*, const unsigned char*, const float*, double, double,
                                  const double*, double*);
 
+// ---------------------------------------------------------------------------------------------
+// Variance-reduction criterion (include/algp_hip.h; state and driver: api_vr.hip).  w_c = sum over the targets j of E_jc^2
+// comes from the fused product of gemm.hip as one partial sum per column tile; everything below is its HBM-bound rest.
+// Every reduction runs in a fixed order: the same bits in every run.
+// ---------------------------------------------------------------------------------------------
+// w[c] (+)= the partial sums of `ntiles` column tiles, in tile order (the sibling of rowstat_combine_kernel)
+template <typename T>
+__global__ __launch_bounds__(256) void vr_combine_kernel(const T* part, int64_t ld, int ntiles, int64_t rows, int accumulate, T* w) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= rows) return;
+    T s = accumulate ? w[j] : (T)0;
+    int t = 0;
+    for (; t + 8 <= ntiles; t += 8) {                          // eight loads in flight, added in tile order
+        T v[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = part[(int64_t)(t + e) * ld + j];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s += v[e];
+    }
+    for (; t < ntiles; ++t) s += part[(int64_t)t * ld + j];
+    w[j] = s;
+}
+template <typename T>
+int vr_combine_launch(algp_ctx* c, const T* part, int64_t ld, int ntiles, int64_t rows, int accumulate, T* w) {
+    if (rows <= 0) return ALGP_OK;
+    ProfScope ps(c, ALGP_PROF_ROWS, (double)rows * ntiles, sizeof(T) * (double)rows * ntiles);
+    hipLaunchKernelGGL(vr_combine_kernel<T>, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, c->cur, part, ld, ntiles, rows, accumulate, w);
+    ALGP_HIP(hipGetLastError());
+    return ALGP_OK;
+}
+template int vr_combine_launch<double>(algp_ctx*, const double*, int64_t, int, int64_t, int, double*);
+template int vr_combine_launch<float>(algp_ctx*, const float*, int64_t, int, int64_t, int, float*);
+
+// u_c = w_c / (pv_c + ss) (ordinary row) | -delta w_c / (1 + delta s_cc) (unit row); -inf where the row is not selectable
+template <typename T>
+__global__ void vr_score_kernel(int64_t M, const int* ckind, const unsigned char* alive, const T* dstat, const T* w, double ss,
+                                double delta, double* out) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= M) return;
+    double u = -INFINITY;
+    if (alive[j]) {
+        const double d = (double)dstat[j], wj = (double)w[j];
+        u = ckind[j] >= 0 ? -delta * wj / (1.0 + delta * d) : wj / (d + ss);
+    }
+    out[j] = u;
+}
+template <typename T>
+int vr_score_launch(algp_ctx* c, int64_t M, const int* ckind, const unsigned char* alive, const T* dstat, const T* w, double ss,
+                    double delta, double* out) {
+    if (M <= 0) return ALGP_OK;
+    ProfScope ps(c, ALGP_PROF_SCORE, 4.0 * M, (2.0 * sizeof(T) + 13.0) * M);
+    hipLaunchKernelGGL(vr_score_kernel<T>, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, c->cur, M, ckind, alive, dstat, w, ss,
+                       delta, out);
+    ALGP_HIP(hipGetLastError());
+    return ALGP_OK;
+}
+template int vr_score_launch<double>(algp_ctx*, int64_t, const int*, const unsigned char*, const double*, const double*, double, double,
+                                     double*);
+template int vr_score_launch<float>(algp_ctx*, int64_t, const int*, const unsigned char*, const float*, const float*, double, double,
+                                    double*);
+
+// a committed pick's column `col` of V^T: r[c] of every row, rt[c] = r[c] on the targets (ordinary rows) and 0 elsewhere, and
+// *nrm = |r_T|^2 (one workgroup: a thread adds its rows in ascending order, then the shuffle tree, then the waves left to right)
+template <typename T>
+__global__ __launch_bounds__(1024) void vr_pick_col_kernel(int64_t M, const int* ckind, const T* Vt, int64_t ldv, int64_t col, T* r, T* rt,
+                                                           T* nrm) {
+    __shared__ T red[16];
+    T s = (T)0;
+    for (int64_t j = threadIdx.x; j < M; j += 1024) {
+        const T v = Vt[j * ldv + col];
+        const T vt = ckind[j] < 0 ? v : (T)0;
+        r[j] = v;
+        rt[j] = vt;
+        s = __builtin_fma(vt, vt, s);
+    }
+    s = dot_tree<T>(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        T t = red[0];
+        for (int k = 1; k < 16; ++k) t += red[k];
+        *nrm = t;
+    }
+}
+// t = V_T^T r_T over the first ncols columns: row block b (rows_per rows) leaves its share at tp[b * ld + k] (a thread per
+// column, rows in ascending order, rows outside the targets skipped); vr_tsum_kernel adds the blocks in order
+template <typename T>
+__global__ __launch_bounds__(256) void vr_tpart_kernel(int64_t M, int64_t rows_per, const T* Vt, int64_t ldv, int64_t ncols, const T* rt,
+                                                       T* tp, int64_t ld) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= ncols) return;
+    const int64_t j0 = (int64_t)blockIdx.y * rows_per, j1 = j0 + rows_per < M ? j0 + rows_per : M;
+    T s = (T)0;
+    for (int64_t j = j0; j < j1; ++j) {
+        const T rj = rt[j];
+        if (rj != (T)0) s = __builtin_fma(Vt[j * ldv + k], rj, s);
+    }
+    tp[(int64_t)blockIdx.y * ld + k] = s;
+}
+template <typename T>
+__global__ __launch_bounds__(256) void vr_tsum_kernel(int nblocks, const T* tp, int64_t ld, int64_t ncols, T* t) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= ncols) return;
+    T s = (T)0;
+    for (int b = 0; b < nblocks; ++b) s += tp[(int64_t)b * ld + k];
+    t[k] = s;
+}
+// explicit pool covariance: y1[c] = sum_j Cp[pool(c)][pool(j)] rt[j] (a wave per row, as kgemv_kernel for a coordinate pool)
+template <typename T>
+__global__ __launch_bounds__(256) void vr_cov_gemv_kernel(int64_t M, const int64_t* cidx, const T* Cp, int64_t n_pool, const T* rt, T* y1) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int64_t nw = (int64_t)gridDim.x * 4;
+    for (int64_t c0 = wave; c0 < M; c0 += nw) {
+        const T* row = Cp + cidx[c0] * n_pool;
+        T s = (T)0;
+        for (int64_t j = lane; j < M; j += 64) s = __builtin_fma(row[cidx[j]], rt[j], s);
+        s = dot_tree<T>(s);
+        if (lane == 0) y1[c0] = s;
+    }
+}
+// the rank-1 fold of one pick: y_c = kappa_c (y1_c + noise rt_c) - y2_c, w_c <- w_c - 2 r_c y_c + r_c^2 |r_T|^2
+// (noise: sigma_n^2 of a coordinate pool, which the kernel-GEMV leaves out where the pool indices coincide; 0 for a covariance pool)
+template <typename T>
+__global__ void vr_fold_kernel(int64_t M, const int* ckind, const T* r, const T* rt, const T* y1, const T* y2, const T* nrm, T noise,
+                               T* w) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= M) return;
+    const T rj = r[j];
+    const T y = (ckind[j] < 0 ? y1[j] + noise * rt[j] : (T)0) - y2[j];
+    w[j] = w[j] - (T)2 * rj * y + rj * rj * *nrm;
+}
+
+template <typename T>
+int vr_fold_launch(algp_ctx* c, int64_t M, const int* ckind, const int64_t* cidx, const T* Vt, int64_t ldv, int64_t col, const T* Xs,
+                   const T* Cp, int64_t n_pool, int DP, int kernel, T os, T noise, T* r, T* rt, T* nrm, T* tp, T* t, T* y1, T* y2, T* w) {
+    if (M <= 0) return ALGP_OK;
+    {
+        ProfScope ps(c, ALGP_PROF_ROWS, 2.0 * M, sizeof(T) * 3.0 * M);
+        hipLaunchKernelGGL(vr_pick_col_kernel<T>, dim3(1), dim3(1024), 0, c->cur, M, ckind, Vt, ldv, col, r, rt, nrm);
+        ALGP_HIP(hipGetLastError());
+    }
+    const int nblocks = (int)std::min<int64_t>(VR_TBLOCKS, (M + 63) / 64);
+    const int64_t rows_per = (M + nblocks - 1) / nblocks;
+    {
+        ProfScope ps(c, ALGP_PROF_ROWS, 2.0 * M * col, sizeof(T) * (double)M * col);
+        hipLaunchKernelGGL(vr_tpart_kernel<T>, dim3((unsigned)((col + 255) / 256), (unsigned)nblocks), dim3(256), 0, c->cur, M, rows_per, Vt,
+                           ldv, col, (const T*)rt, tp, ldv);
+        ALGP_HIP(hipGetLastError());
+    }
+    {
+        ProfScope ps(c, ALGP_PROF_ROWS, (double)nblocks * col, sizeof(T) * (double)(nblocks + 1) * col);
+        hipLaunchKernelGGL(vr_tsum_kernel<T>, dim3((unsigned)((col + 255) / 256)), dim3(256), 0, c->cur, nblocks, (const T*)tp, ldv, col, t);
+        ALGP_HIP(hipGetLastError());
+    }
+    ALGP_TRY(rows_reduce_launch<T>(c, Vt, M, ldv, col, (const T*)t, (T*)nullptr, y2));
+    if (Cp) {
+        int64_t g = (M + 3) / 4;
+        if (g > 8192) g = 8192;
+        ProfScope ps(c, ALGP_PROF_KMAT, 2.0 * M * M, sizeof(T) * (double)M * M);
+        hipLaunchKernelGGL(vr_cov_gemv_kernel<T>, dim3((unsigned)g), dim3(256), 0, c->cur, M, cidx, Cp, n_pool, (const T*)rt, y1);
+        ALGP_HIP(hipGetLastError());
+    } else {
+        ALGP_TRY(kgemv_launch<T>(c, M, cidx, Xs, DP, M, cidx, (const T*)rt, kernel, os, (T)0, y1));
+    }
+    ProfScope ps(c, ALGP_PROF_SCORE, 6.0 * M, sizeof(T) * 6.0 * M);
+    hipLaunchKernelGGL(vr_fold_kernel<T>, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, c->cur, M, ckind, (const T*)r, (const T*)rt,
+                       (const T*)y1, (const T*)y2, (const T*)nrm, Cp ? (T)0 : noise, w);
+    ALGP_HIP(hipGetLastError());
+    return ALGP_OK;
+}
+template int vr_fold_launch<double>(algp_ctx*, int64_t, const int*, const int64_t*, const double*, int64_t, int64_t, const double*,
+                                    const double*, int64_t, int, int, double, double, double*, double*, double*, double*, double*, double*,
+                                    double*, double*);
+template int vr_fold_launch<float>(algp_ctx*, int64_t, const int*, const int64_t*, const float*, int64_t, int64_t, const float*, const float*,
+                                   int64_t, int, int, float, float, float*, float*, float*, float*, float*, float*, float*, float*);
+
 // first maximum (np.argmax semantics, agent.py:349): larger value wins, ties go to the smaller index
 __global__ __launch_bounds__(1024) void argmax_kernel(const double* s, int64_t M, double* out_val, int64_t* out_idx) {
     __shared__ double sv[16];

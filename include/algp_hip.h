@@ -35,7 +35,7 @@ typedef struct algp_ctx algp_ctx;
 
 enum { ALGP_F32 = 0, ALGP_F64 = 1 };
 enum { ALGP_KERNEL_RBF = 0, ALGP_KERNEL_MATERN15 = 1 };          /* models.py:217-220 */
-enum { ALGP_CRIT_ENTROPY = 0, ALGP_CRIT_MUTUAL_INFORMATION = 1 };  /* agent.py:128 */
+enum { ALGP_CRIT_ENTROPY = 0, ALGP_CRIT_MUTUAL_INFORMATION = 1, ALGP_CRIT_VARIANCE_REDUCTION = 2 };  /* agent.py:128; 2: below */
 enum {
     ALGP_OK = 0,
     ALGP_ERR_BAD_ARG = 1,
@@ -210,7 +210,25 @@ int algp_posterior_mean(algp_ctx* ctx, const int64_t* idx, int64_t M, void* mu_o
  *   NULL; forced_picks (k pool indices) may be NULL.  With both NULL and the entropy criterion a pick
  *   is one host round trip (see algp_greedy_sharded: the same chain without the gather).
  * MI criterion (agent.py:330-339) is exact; here it holds the pool-wide inverses on one GPU (algp_comm_set_mi_groups deals
- * them over the ranks of algp_greedy_sharded). */
+ * them over the ranks of algp_greedy_sharded).
+ * Variance-reduction criterion (ALGP_CRIT_VARIANCE_REDUCTION; Cohn's ALC / integrated-variance reduction): the utility of a
+ * candidate is how much its static reading lowers the summed predictive variance of the targets.  With ss = static_std^2,
+ * sm = mobile_std^2, delta = 1/(1/ss + 1/sm) - sm (the entropy score's delta), the rows of V^T ordinary (a site without a
+ * train row) or unit (a mobile-sampled site), G = V V^T over all current columns of V^T (the committed picks' included),
+ * and the targets T = the ordinary rows of the candidate set, fixed by the solve (a target stays one after it is picked or
+ * switched off with algp_set_candidate_alive):
+ *   signed cross term, j in T:   E_jc = [c ordinary] C(j, c) - G_jc     (ordinary c: the posterior covariance of j and c;
+ *                                unit c at train row u: -C_jA S^-1 e_u; C: the pool covariance, sigma_n^2 where the pool
+ *                                indices coincide)
+ *   ordinary c:  u_c = sum_{j in T} E_jc^2 / (pv_c + ss)         unit c:  u_c = -delta sum_{j in T} E_jc^2 / (1 + delta s_cc)
+ * with pv_c / s_cc the statistic the entropy criterion reads.  That is sum_{j in T} var(j | A) - sum_{j in T} var(j | A with
+ * c static-sampled), train noise fused as 1/(1/static_var + 1/mobile_var) (agent.py:302-308, 321-328).  Committed,
+ * static-sampled and switched-off rows get -inf, as for the entropy criterion.  The first scoring after a candidate solve is
+ * one fused M x M x (N + picks) product on the matrix cores (2 M^2 K flop; no M x M matrix is written); each pick committed
+ * after it is folded in with E' = E - r_T r_c^T (r: the pick's column of V^T): one fused kernel-GEMV and two passes over
+ * V^T.  algp_scores, algp_best_candidate (full scoring, as MI) and algp_greedy accept it; algp_greedy_sharded refuses it
+ * (ALGP_ERR_BAD_ARG); candidates set with an extra variance, or a candidate set that lists a pool site twice, are refused with
+ * ALGP_ERR_STATE. */
 int algp_scores(algp_ctx* ctx, int criterion, double static_std, double mobile_std, void* out,
                 int out_is_device);
 int algp_argmax(algp_ctx* ctx, int64_t* local_pos, int64_t* pool_idx, double* value);
