@@ -517,6 +517,8 @@ int algp_create(int device_id, int dtype, algp_ctx** out) {
     if (hipStreamCreateWithFlags(&c->stream3, hipStreamNonBlocking) != hipSuccess) c->stream3 = nullptr;
     if (hipStreamCreateWithFlags(&c->stream4, hipStreamNonBlocking) != hipSuccess) c->stream4 = nullptr;
     c->trsm_chunks = env_int("ALGP_TRSM_CHUNKS", c->trsm_chunks);
+    c->trsm_chunks_explicit = env_int("ALGP_TRSM_CHUNKS", 0) != 0;
+    if (hipDeviceGetAttribute(&c->cu_count, hipDeviceAttributeMultiprocessorCount, device_id) != hipSuccess) { (void)hipGetLastError(); c->cu_count = 0; }
     c->cur = c->stream;
     if (ensure(c, c->scal, sizeof(double) * SC_COUNT) != ALGP_OK) { hipStreamDestroy(c->stream); delete c; return ALGP_ERR_OOM; }
     hipMemsetAsync(c->scal.p, 0, sizeof(double) * SC_COUNT, c->stream);
@@ -532,7 +534,7 @@ void algp_destroy(algp_ctx* c) {
     prof_collect(c);
     DevBuf* bufs[] = {&c->Xs, &c->Xraw, &c->Cp, &c->Aidx, &c->yA, &c->varA, &c->y0, &c->L, &c->invD, &c->z, &c->alpha,
                       &c->scal, &c->Cidx, &c->ckind, &c->cextra, &c->Vt, &c->dstat, &c->mu, &c->alive, &c->scores,
-                      &c->lrow, &c->remote, &c->commbuf, &c->tvec, &c->amax, &c->prevrows, &c->fresh, &c->lazypicks, &c->yraw, &c->uvec, &c->wvec, &c->acc3, &c->rowstat, &c->inv512, &c->inv512_scr, &c->trsm_tmp, &c->splitk, &c->dag_state, &c->dag_stats, &c->trsv_ctrl, &c->auxA, &c->auxInv, &c->auxW, &c->auxIdx,
+                      &c->lrow, &c->remote, &c->commbuf, &c->tvec, &c->amax, &c->prevrows, &c->fresh, &c->lazypicks, &c->yraw, &c->uvec, &c->wvec, &c->acc3, &c->rowstat, &c->inv512, &c->inv512_scr, &c->trsm_tmp, &c->gemm_part, &c->splitk, &c->dag_state, &c->dag_stats, &c->trsv_ctrl, &c->auxA, &c->auxInv, &c->auxW, &c->auxIdx,
                       &c->auxVar, &c->auxD, &c->hostStage, &c->rowx, &c->tailE, &c->tailPart, &c->ldpart};
     for (DevBuf* b : bufs) release(c, *b);
     release(c, c->mi);
@@ -650,6 +652,7 @@ int algp_debug_set_trsm_chunks(algp_ctx* c, int chunks) {
     CHECK_CTX(c);
     if (chunks < 0 || chunks > 4) return fail(c, ALGP_ERR_BAD_ARG, "debug_set_trsm_chunks: 0 (default) .. 4");
     hipStreamSynchronize(c->stream);
+    c->trsm_chunks_explicit = chunks != 0 || env_int("ALGP_TRSM_CHUNKS", 0) != 0;
     if (chunks == 0) chunks = env_int("ALGP_TRSM_CHUNKS", 3);
     c->trsm_chunks = chunks;
     return ALGP_OK;

@@ -167,6 +167,9 @@ struct algp_ctx {
     hipStream_t stream2 = nullptr;   // helper streams: independent row chunks of the candidate solve overlap on them
     hipStream_t stream3 = nullptr, stream4 = nullptr;
     int trsm_chunks = 3;
+    bool trsm_chunks_explicit = false;   // set by $ALGP_TRSM_CHUNKS or algp_debug_set_trsm_chunks(k >= 1): the chunked sweep, not the scheduled one
+    int cu_count = 0;                // compute units of the device (the scheduled GEMM's grid is 2 x this)
+    bool gemm_sched = false;         // the GEMM launcher takes its scheduled form (gemm_sched.h) while this is set: the candidate sweep, bench_gemm
     hipStream_t cur = nullptr;       // stream the launch helpers currently target
     std::vector<hipEvent_t> sync_events;
     std::string err;
@@ -213,6 +216,7 @@ struct algp_ctx {
     algp::DevBuf ldpart;                 // logdiag_kernel's per-wave partial sums
     algp::DevBuf tailPart;               // tail.hip: partial accumulators of the k-split form
     algp::DevBuf tailE;                  // tail.hip: inverse of the 128 x 128 window of L at the first new column (a range that straddles two blocks)
+    algp::DevBuf gemm_part;              // scheduled GEMM: partial sums of the k slices of a launch's leftover tiles (2 x CUs tiles)
     algp::DevBuf inv512, inv512_scr, trsm_tmp;   // candidate solve: explicit inverses of the factor's 512-column blocks, their scratch, mpad x 512
     std::vector<algp::DagCache> dag_cache;   // task lists of the dependency-driven Cholesky, per matrix size
     algp::DevBuf dag_state;              // its per-launch tile versions / control words / per-block log-determinants
@@ -313,6 +317,7 @@ void prof_span_end2(algp_ctx* c);
 //   ALGP_TAIL_SPLIT=0 (the tail kernel without its k-split), ALGP_SOLVE_DAG=0 (mid-sized solves as the right-looking push
 //   instead of the task list), ALGP_FOLD=0 (fit and solve as two steps: what a candidate set beyond 51 200 rows takes),
 //   ALGP_ROW_STATS=0 / ALGP_TRSM_INV512=0 (the chunked solve with a variance pass / with 128-column steps inside a block),
+//   ALGP_TRSM_SCHED=0 (the big solve as row chunks on three streams instead of scheduled launches on one; read per call),
 //   ALGP_FACTOR_FROM_VT=0 (new rows of an updated factor solved, not gathered), ALGP_LAZY_GREEDY=0 (every row scored before
 //   every pick), ALGP_TRSM_CHUNKS=n (row-chunk streams of the big solve; bench.py's one-stream leg sets it by the ABI).
 // Cross-check routes: ALGP_CHOL_DAG=0 (launch-sequence factorisation), ALGP_GATHER_ROWS=0 (remote commits rebuild the row),

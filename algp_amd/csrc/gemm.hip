@@ -30,6 +30,7 @@
 #include "common.h"
 #include <hip/hip_ext.h>
 #include "mfma.h"
+#include "gemm_sched.h"
 #include <algorithm>
 #include <type_traits>
 #include <stdio.h>
@@ -57,6 +58,10 @@ struct GemmArgs {
     const T* stat_w;
     T* stat_out;
     int64_t stat_ld;
+    // SCHED kernels only: the launch's work list (gemm_sched.h) and where the k slices of its leftover tiles leave their partial
+    // sums (slice q: a row-major 128 x 128 tile at part + q * 128 * 128)
+    Sched sch;
+    T* part;
 };
 
 typedef __attribute__((address_space(3))) void* lds_vp;
@@ -199,10 +204,23 @@ __device__ __forceinline__ void vr_epilogue(const VrGemmArgs<T>& g, char* smem, 
 #define ALGP_GEMM_XOR_MASK 2
 #endif
 // Args = VrGemmArgs<T>: the variance-reduction epilogue above instead of a D tile (STATS is then false).
-template <typename T, bool STATS = false, typename Args = GemmArgs<T>>
+//
+// SCHED: the scheduled sibling for the candidate sweep's products.  A grid of G = min(tiles, 2 x CUs) workgroups, each
+// walking its fixed list of units (gemm_sched.h: whole tiles, or one k slice of a leftover tile whose alpha * acc goes to a
+// partials scratch for gemm_finish_kernel).  Same stages, k order, fragment layout and epilogues, so a whole tile has the
+// bits of the plain kernel's.  Between two units the first NST - 1 k-tiles of the NEXT unit are issued before the epilogue
+// of the current one (the LDS-DMA needs no registers): they go to the stages that follow the last one read, which no wave
+// can still be reading (every wave passed the last k-tile's barrier), so the stage rotation simply continues.  Wait
+// accounting: arrive()'s vmcnt(8/4/0) counts stage DMAs only, and in the epilogue the C loads and D stores fly with the
+// prefetched stages -- so the epilogue ends with an honest vmcnt(0), which covers the prefetched stages too, and the next
+// unit's loop starts from a clean counter exactly like a fresh workgroup whose prologue has landed.  The STATS epilogue's
+// `red` scratch has 4 KB of its own behind the stages (68 KB per workgroup, two per CU).  Workgroups never wait for,
+// signal or poll each other: partial sums meet only in the finish kernel, a later launch on the same stream.
+template <typename T, bool STATS = false, typename Args = GemmArgs<T>, bool SCHED = false>
 __global__ __launch_bounds__(256, 2) void gemm_nt_kernel_dma4(Args g) {
     constexpr bool VR = !std::is_same<Args, GemmArgs<T>>::value;
     static_assert(!(VR && STATS), "one epilogue per kernel");
+    static_assert(!(VR && SCHED), "the scheduled form serves the sweep's products only");
     constexpr int NST = 4;
     using F = MF<T>;
     using acc_t = typename F::acc_t;
@@ -210,10 +228,22 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel_dma4(Args g) {
     constexpr int EPC = F::EPC;
     constexpr int BK = 4 * EPC;                                    // elements per 64-byte row piece
 
-    __shared__ __attribute__((aligned(1024))) char smem[NST * 16384];
+    __shared__ __attribute__((aligned(1024))) char smem[NST * 16384 + (SCHED && STATS ? 4096 : 0)];
 
     const int nwg = gridDim.x;
     int bm, bn;
+    int kskip = 0;                                                 // 64-byte k-tiles this unit leaves out in front
+    int nkt;                                                       // ... and walks
+    int slice = -1, nunits = 1, ui = 0;
+    if constexpr (SCHED) {
+        nunits = sched_count(g.sch, blockIdx.x);
+        const SchedUnit u = sched_unit(g.sch, blockIdx.x, 0);
+        bm = u.tile / g.tiles_n;
+        bn = u.tile - bm * g.tiles_n;
+        kskip = u.kb0 * (128 / BK);
+        nkt = (u.kb1 - u.kb0) * (128 / BK);
+        slice = u.slice;
+    } else {
     if (g.ktri) {
         // Tile row bm costs (bm + 1) tiles x K = k - 128 bm: a contiguous share of the tile list per XCD (below) would give the
         // XCD with the first rows several times the work of the last.  Instead XCD x takes the tile rows bm = x, x + 8, ...
@@ -240,8 +270,10 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel_dma4(Args g) {
             bn = sid - bm * g.tiles_n;
         }
     }
-    const int64_t m0 = (int64_t)bm * 128, n0 = (int64_t)bn * 128;
-    const int kskip = g.ktri ? bm * (128 / (4 * MF<T>::EPC)) : 0;   // 64-byte k-tiles this output tile leaves out
+    kskip = g.ktri ? bm * (128 / BK) : 0;
+    nkt = g.ktiles * 2 - kskip;                                    // g.ktiles counts 128-byte tiles
+    if (g.kcut && (bn + 1) * (128 / BK) < nkt) nkt = (bn + 1) * (128 / BK);
+    }
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 1, wc = wave & 1;
@@ -251,8 +283,8 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel_dma4(Args g) {
     // the group, LDS slot l&3, which must hold chunk (l&3) ^ ((row>>2)&2) = (l&3) ^ ((l>>4)&2)
     const int srow = lane >> 2;
     const int schunk = (lane & 3) ^ ((lane >> 4) & ALGP_GEMM_XOR_MASK);
-    const T* Ag = g.A + bz * g.sA + (m0 + 32 * wave + srow) * g.lda + schunk * EPC + (int64_t)kskip * BK;
-    const T* Bg = g.B + bz * g.sB + (n0 + 32 * wave + srow) * g.ldb + schunk * EPC + (int64_t)kskip * BK;
+    const T* Ag = g.A + bz * g.sA + ((int64_t)bm * 128 + 32 * wave + srow) * g.lda + schunk * EPC + (int64_t)kskip * BK;
+    const T* Bg = g.B + bz * g.sB + ((int64_t)bn * 128 + 32 * wave + srow) * g.ldb + schunk * EPC + (int64_t)kskip * BK;
     auto stage = [&](int st, int kt) {
         char* As = smem + st * 16384 + wave * 2048;
         char* Bs = As + 8192;
@@ -272,15 +304,6 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel_dma4(Args g) {
     const int boff = (wc * 64 + fr) * 64 + coff;
 
     acc_t acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[i][j][r] = (T)0;
-
-    int nkt = g.ktiles * 2 - kskip;                                // g.ktiles counts 128-byte tiles
-    if (g.kcut && (bn + 1) * (128 / BK) < nkt) nkt = (bn + 1) * (128 / BK);
     // prologue: tiles 0 .. NST-2 in flight
 #pragma unroll
     for (int t = 0; t < NST - 1; ++t)
@@ -313,6 +336,13 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel_dma4(Args g) {
     };
 
     int st = 0;                                                    // stage of tile kt; tile kt+NST-1 goes to st-1 (mod NST)
+    for (;;) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[i][j][r] = (T)0;
     for (int kt = 0; kt < nkt; ++kt) {
         arrive(nkt - 1 - kt);
         chunk_t a[4], b[4];
@@ -321,15 +351,42 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel_dma4(Args g) {
         fmac(a, b);
         st = (st + 1 == NST) ? 0 : st + 1;
     }
+    const int64_t m0 = (int64_t)bm * 128, n0 = (int64_t)bn * 128;   // the unit whose accumulators are going out
+    const int cur_bn = bn, cur_slice = slice;
+    if constexpr (SCHED) {
+        // the next unit's first NST - 1 k-tiles, into the stages after the one read last (a unit has at least 128 / BK >= 8)
+        if (++ui < nunits) {
+            const SchedUnit u = sched_unit(g.sch, blockIdx.x, ui);
+            bm = u.tile / g.tiles_n;
+            bn = u.tile - bm * g.tiles_n;
+            nkt = (u.kb1 - u.kb0) * (128 / BK);
+            slice = u.slice;
+            Ag = g.A + ((int64_t)bm * 128 + 32 * wave + srow) * g.lda + schunk * EPC + (int64_t)u.kb0 * 128;
+            Bg = g.B + ((int64_t)bn * 128 + 32 * wave + srow) * g.ldb + schunk * EPC + (int64_t)u.kb0 * 128;
+#pragma unroll
+            for (int t = 0; t < NST - 1; ++t) stage((st + t) & (NST - 1), t);
+        }
+    }
 
     if constexpr (VR) {
-        vr_epilogue<T>(g, smem, acc, m0, n0, bn, wr, wc, lane, tid);
+        vr_epilogue<T>(g, smem, acc, m0, n0, cur_bn, wr, wc, lane, tid);
         return;
     }
     const T alpha = g.alpha, beta = g.beta;
     const T* Cb = g.C + bz * g.sC;
     T* Db = g.D + bz * g.sD;
-    if (beta != (T)0) {
+    if (SCHED && !STATS && cur_slice >= 0) {
+        // a k slice of a leftover tile: alpha * acc to the partials scratch, gemm_finish_kernel adds C and the other slices
+        T* P = g.part + (int64_t)cur_slice * (128 * 128);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = wr * 64 + i * 16 + F::row_of(lane, r);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) P[row * 128 + wc * 64 + j * 16 + fr] = alpha * acc[i][j][r];
+            }
+    } else if (beta != (T)0) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             T cv[4][4];
@@ -366,8 +423,10 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel_dma4(Args g) {
         T wv[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) wv[j] = g.stat_w[n0 + wc * 64 + j * 16 + fr];
-        T* red = reinterpret_cast<T*>(smem);                       // [column half][row][2]
-        __syncthreads();                                           // every wave is done with the last stage
+        // [column half][row][2]; SCHED: behind the stages, which the next unit's k-tiles are landing in -- the last reader
+        // of the previous unit's sums has since passed the barriers of a whole k loop
+        T* red = reinterpret_cast<T*>(smem + (SCHED ? NST * 16384 : 0));
+        if constexpr (!SCHED) __syncthreads();                     // every wave is done with the last stage
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -388,9 +447,36 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel_dma4(Args g) {
                     red[(wc * 128 + row) * 2 + 1] = sw;
                 }
             }
-        __syncthreads();
+        if constexpr (SCHED) {
+            // own LDS writes done, then meet: a __syncthreads() would also wait for the prefetched stages (vmcnt)
+            __builtin_amdgcn_s_waitcnt(0xC07F);                    // lgkmcnt(0)
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+        } else {
+            __syncthreads();
+        }
         const int row = tid >> 1, q = tid & 1;
-        g.stat_out[(int64_t)(2 * bn + q) * g.stat_ld + m0 + row] = red[row * 2 + q] + red[(128 + row) * 2 + q];
+        g.stat_out[(int64_t)(2 * cur_bn + q) * g.stat_ld + m0 + row] = red[row * 2 + q] + red[(128 + row) * 2 + q];
+    }
+    if constexpr (!SCHED) return;
+    if (ui >= nunits) return;
+    // every load and store of this epilogue and the next unit's prefetched k-tiles: the k loop's counted waits start clean
+    __builtin_amdgcn_s_waitcnt(0x0F70);                            // vmcnt(0)
+    }
+}
+
+// D = beta C + the partial sums of a scheduled launch's leftover tiles, slice by slice in ascending k: a fixed order, the
+// same bits in every run.  One workgroup per leftover tile (tile0 + blockIdx.x of the row-major list).
+template <typename T>
+__global__ __launch_bounds__(256) void gemm_finish_kernel(const T* part, int S, int tile0, int tiles_n, T beta, const T* C, int64_t ldc,
+                                                          T* D, int64_t ldd) {
+    const int tile = tile0 + blockIdx.x, bm = tile / tiles_n, bn = tile - bm * tiles_n;
+    const T* P = part + (int64_t)blockIdx.x * S * (128 * 128);
+    for (int e = threadIdx.x; e < 128 * 128; e += 256) {
+        const int64_t row = (int64_t)bm * 128 + (e >> 7), col = (int64_t)bn * 128 + (e & 127);
+        T v = beta * C[row * ldc + col];
+        for (int q = 0; q < S; ++q) v += P[(int64_t)q * (128 * 128) + e];
+        D[row * ldd + col] = v;
     }
 }
 
@@ -431,6 +517,8 @@ int gemm_nt_launch_batched(algp_ctx* c, int klass, int64_t m, int64_t n, int64_t
     g.stat_out = stat_out;
     g.stat_ld = stat_ld;
     g.kcut = kcut;
+    g.sch = Sched();
+    g.part = nullptr;
     if (ktri && (!lower_only || k != m)) return fail(c, ALGP_ERR_BAD_ARG, "gemm_nt: ktri needs a square lower-only product with k == m");
     const int64_t tiles = lower_only ? (int64_t)g.tiles_m * (g.tiles_m + 1) / 2 : (int64_t)g.tiles_m * g.tiles_n;
     if (tiles > 0x7fffffff) return fail(c, ALGP_ERR_BAD_ARG, "gemm_nt: grid too large");
@@ -452,8 +540,38 @@ int gemm_nt_launch_batched(algp_ctx* c, int klass, int64_t m, int64_t n, int64_t
         }
         gx = 8 * most;
     }
-    const dim3 grid((unsigned)gx, (unsigned)batch);
     hipEvent_t ev_a, ev_b;
+    if (c->gemm_sched && c->cu_count > 0 && !lower_only && !ktri && batch == 1) {
+        // the scheduled form (the candidate sweep's launches, potrf.hip): 2 x CUs resident workgroups walk the tile list; the
+        // leftover tiles of an update product are cut along k where the sweep has provided the partials scratch
+        const int slots = 2 * c->cu_count;
+        const bool split = beta != (T)0 && !stat_out && !kcut && c->gemm_part.p &&
+                           c->gemm_part.cap >= sizeof(T) * 128 * 128 * (size_t)slots;
+        g.sch = sched_make(slots, g.tiles_m, g.tiles_n, (int)(k / 128), kcut, split ? 1 : 0);
+        g.part = (T*)c->gemm_part.p;
+        const dim3 sgrid((unsigned)g.sch.G);
+        const bool timed = prof_launch_events(c, klass, flops, bytes, &ev_a, &ev_b);
+        if (stat_out) {
+            if (timed) hipExtLaunchKernelGGL((gemm_nt_kernel_dma4<T, true, GemmArgs<T>, true>), sgrid, dim3(256), 0, c->cur, ev_a, ev_b, 0, g);
+            else hipLaunchKernelGGL((gemm_nt_kernel_dma4<T, true, GemmArgs<T>, true>), sgrid, dim3(256), 0, c->cur, g);
+        } else {
+            if (timed) hipExtLaunchKernelGGL((gemm_nt_kernel_dma4<T, false, GemmArgs<T>, true>), sgrid, dim3(256), 0, c->cur, ev_a, ev_b, 0, g);
+            else hipLaunchKernelGGL((gemm_nt_kernel_dma4<T, false, GemmArgs<T>, true>), sgrid, dim3(256), 0, c->cur, g);
+        }
+        ALGP_HIP(hipGetLastError());
+        if (g.sch.S >= 2) {
+            const double fbytes = sizeof(T) * 128.0 * 128.0 * (double)g.sch.left * (g.sch.S + 2.0);
+            const bool ftimed = prof_launch_events(c, klass, 0.0, fbytes, &ev_a, &ev_b);
+            const dim3 fgrid((unsigned)g.sch.left);
+            if (ftimed) hipExtLaunchKernelGGL(gemm_finish_kernel<T>, fgrid, dim3(256), 0, c->cur, ev_a, ev_b, 0, (const T*)g.part, g.sch.S,
+                                              g.sch.full, g.tiles_n, beta, g.C, ldc, D, ldd);
+            else hipLaunchKernelGGL(gemm_finish_kernel<T>, fgrid, dim3(256), 0, c->cur, (const T*)g.part, g.sch.S, g.sch.full, g.tiles_n,
+                                    beta, g.C, ldc, D, ldd);
+            ALGP_HIP(hipGetLastError());
+        }
+        return ALGP_OK;
+    }
+    const dim3 grid((unsigned)gx, (unsigned)batch);
     const bool timed = prof_launch_events(c, klass, flops, bytes, &ev_a, &ev_b);
     if (stat_out) {
         if (timed) hipExtLaunchKernelGGL((gemm_nt_kernel_dma4<T, true>), grid, dim3(256), 0, c->cur, ev_a, ev_b, 0, g);
@@ -485,6 +603,7 @@ int gemm_nt_launch_vr(algp_ctx* c, int klass, int64_t mpad, int64_t n, int64_t k
     g.alpha = (T)1; g.beta = (T)0;
     g.lower_only = 0; g.ktri = 0; g.kcut = 0;
     g.stat_w = nullptr; g.stat_out = part; g.stat_ld = part_ld;
+    g.sch = Sched(); g.part = nullptr;
     g.cidx = cidx; g.ckind = ckind; g.M = M; g.ncol0 = ncol0;
     g.Xs = (const T*)s.Xs; g.Cp = (const T*)s.Cp; g.n_pool = s.n_pool; g.DP = s.DP; g.kernel = s.kernel;
     g.os = (T)s.outputscale; g.noise = (T)s.noise;
@@ -608,6 +727,10 @@ int bench_gemm(algp_ctx* c, int64_t m, int64_t n, int64_t k, int lower_only, int
     hipEventCreate(&e0);
     hipEventCreate(&e1);
     const T beta = beta_one ? (T)1 : (T)0;
+    // $ALGP_TRSM_SCHED (read per call, default on): the scheduled launcher the candidate sweep uses, with its partials scratch
+    const bool sched = !lower_only && c->cu_count > 0 && env_switch("ALGP_TRSM_SCHED", true) &&
+                       ensure(c, c->gemm_part, sizeof(T) * 128 * 128 * 2 * (size_t)c->cu_count) == ALGP_OK;
+    c->gemm_sched = sched;
     for (int w = 0; w < 2 && rc == ALGP_OK; ++w)
         rc = gemm_nt_launch<T>(c, ALGP_PROF_GEMM_OTHER, m, n, k, (T)-1, (const T*)a.p, k, (const T*)b.p, k, beta,
                                (const T*)cc.p, n, (T*)cc.p, n, lower_only);
@@ -616,6 +739,7 @@ int bench_gemm(algp_ctx* c, int64_t m, int64_t n, int64_t k, int lower_only, int
         rc = gemm_nt_launch<T>(c, ALGP_PROF_GEMM_OTHER, m, n, k, (T)-1, (const T*)a.p, k, (const T*)b.p, k, beta,
                                (const T*)cc.p, n, (T*)cc.p, n, lower_only);
     hipEventRecord(e1, c->cur);
+    c->gemm_sched = false;
     hipEventSynchronize(e1);
     float ms = 0;
     hipEventElapsedTime(&ms, e0, e1);

@@ -479,6 +479,18 @@ int trsm_blocked(algp_ctx* c, int klass, T* X, int64_t mpad, int64_t ldx, const 
             ALGP_HIP(hipMemcpy2DAsync(tmp512, sizeof(T) * WB, X, sizeof(T) * ldx, sizeof(T) * WB, (size_t)mpad, hipMemcpyDeviceToDevice, c->cur));
         }
     }
+    // The scheduled sweep (default): the same launches, one after the other on the caller's stream, each as a grid of 2 x CUs
+    // workgroups that walk a balanced work list (gemm.hip, SCHED; gemm_sched.h) -- no partial last round, the next tile's first
+    // k-tiles under the current tile's epilogue.  An explicit chunk count ($ALGP_TRSM_CHUNKS, algp_debug_set_trsm_chunks) or
+    // $ALGP_TRSM_SCHED=0 (read per call: tests flip it) keeps the row chunks below.  The partials scratch of the cut leftover
+    // tiles is provided here: nothing is allocated inside the sweep.
+    if (inv512 && !c->trsm_chunks_explicit && c->cu_count > 0 && env_switch("ALGP_TRSM_SCHED", true) &&
+        ensure(c, c->gemm_part, sizeof(T) * 128 * 128 * 2 * (size_t)c->cu_count) == ALGP_OK) {
+        c->gemm_sched = true;
+        const int rc = trsm_rows<T>(c, klass, X, mpad, ldx, L, npad, ldl, invD, col_start, true, stat_w, stat_out, stat_ld, inv512, tmp512);
+        c->gemm_sched = false;
+        return rc;
+    }
     hipStream_t streams[4] = {c->stream, c->stream2, c->stream3, c->stream4};
     int nch = c->trsm_chunks < 1 ? 1 : (c->trsm_chunks > 4 ? 4 : c->trsm_chunks);
     while (nch > 1 && (!streams[nch - 1] || tiles < 32 * nch)) --nch;

@@ -1,18 +1,33 @@
-"""This library's GEMM on the shapes tools/rocblas_yardstick.cpp gives the vendor's (the same card, the same minute)."""
+"""This library's GEMM on the shapes tools/rocblas_yardstick.cpp gives the vendor's (the same card, the same minute), in both
+forms of the launcher: one workgroup per tile (ALGP_TRSM_SCHED=0, "plain") and the candidate sweep's scheduled launches
+(the default, "sched"), alternated in one process -- ROUNDS times each, so the spread of the plain form is on the table."""
+import os
 import sys
 
 import numpy as np
 
 from algp_amd import _hip
 
+ROUNDS = 3
 for dt, peak in ((np.float64, 78.6), (np.float32, 157.3)):
     c = _hip.Context(dt)
-    shapes = [(33408, 512, 2048), (33408, 512, 5120), (33408, 512, 9728), (100096, 512, 5120), (100096, 512, 9728), (4096, 4096, 4096), (8192, 8192, 8192)]
+    shapes = [(33408, 512, 2048), (33408, 512, 5120), (33408, 512, 9728), (100096, 512, 2048), (100096, 512, 5120), (100096, 512, 9728),
+              (4096, 4096, 4096), (8192, 8192, 8192)]
     if dt == np.float32:
-        shapes = [(33408, 512, 5120), (8192, 8192, 8192)]
+        shapes = [(33408, 512, 5120), (100096, 512, 5120), (8192, 8192, 8192)]
+    name = 'dgemm' if dt == np.float64 else 'sgemm'
     for (m, n, k) in shapes:
-        ms = c.bench_gemm(m, n, k, beta_one=True, reps=5)
-        tf = 2.0 * m * n * k / ms / 1e9
-        print('algp %s  m %6d n %5d k %5d: %8.3f ms  %6.1f TFLOP/s = %5.1f %% of %.1f' % ('dgemm' if dt == np.float64 else 'sgemm', m, n, k, ms, tf, 100 * tf / peak, peak))
+        ms = {'plain': [], 'sched': []}
+        for _ in range(ROUNDS):
+            for form in ('plain', 'sched'):
+                os.environ['ALGP_TRSM_SCHED'] = '0' if form == 'plain' else '1'
+                ms[form].append(c.bench_gemm(m, n, k, beta_one=True, reps=5))
+        for form in ('plain', 'sched'):
+            best = min(ms[form])
+            tf = 2.0 * m * n * k / best / 1e9
+            print('algp %s %s m %6d n %5d k %5d: %s ms (spread %.3f)  best %6.1f TFLOP/s = %5.1f %% of %.1f' % (
+                name, form, m, n, k, ' '.join('%8.3f' % v for v in ms[form]), max(ms[form]) - min(ms[form]), tf, 100 * tf / peak, peak))
+        print('     sched / plain (medians): %.4f' % (float(np.median(ms['sched'])) / float(np.median(ms['plain']))))
         sys.stdout.flush()
     c.close()
+os.environ.pop('ALGP_TRSM_SCHED', None)
