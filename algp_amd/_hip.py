@@ -86,6 +86,7 @@ SIGNATURES = {
     'algp_cholesky_task_stats': (C.c_int, [_c_ctx, _dblp]),
     'algp_score_paths': (C.c_int, [_c_ctx, _i64p, C.c_int, C.c_int, C.c_double, _dblp]),
     'algp_score_paths_mi': (C.c_int, [_c_ctx, _i64p, C.c_int, C.c_int, C.c_double, C.c_double, _dblp, _dblp]),
+    'algp_score_paths_vr': (C.c_int, [_c_ctx, _i64p, C.c_int, C.c_int, C.c_double, C.c_int64, _dblp]),
     'algp_comm_unique_id': (C.c_int, [C.c_void_p]),
     'algp_comm_init': (C.c_int, [_c_ctx, C.c_int, C.c_int, C.c_void_p]),
     'algp_comm_init_host': (C.c_int, [_c_ctx, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
@@ -436,6 +437,19 @@ class Context(object):
                                                      float(mobile_std), out.ctypes.data_as(_dblp),
                                                      None if terms is None else terms.ctypes.data_as(_dblp)))
         return (out, terms) if want_terms else out
+
+    def score_paths_vr(self, sites, mobile_std, max_union=0):
+        """Variance-reduction utility of every row of `sites` (npaths x maxlen pool indices, -1 padded): how much the path's
+        mobile readings lower the summed posterior variance of the candidates without a train row (see algp_score_paths_vr).
+        max_union: the most union sites per group of paths (0: the library's default)."""
+        sites = np.ascontiguousarray(sites, dtype=np.int64)
+        if sites.ndim != 2:
+            raise ValueError('sites must be (npaths, maxlen)')
+        out = np.empty(sites.shape[0], dtype=np.float64)
+        if sites.shape[0]:
+            self._check(self.lib.algp_score_paths_vr(self.h, _i64(sites.ravel()), sites.shape[0], sites.shape[1], float(mobile_std),
+                                                     int(max_union), out.ctypes.data_as(_dblp)))
+        return out
 
     # -- multi-GPU: the collective behind the ABI (RCCL) ---------------------------------------
     @staticmethod

@@ -415,8 +415,8 @@ class Agent(object):
         if len(paths_mobile_indices) == 1:
             return 0
         if self.criterion == 'variance_reduction':
-            raise NotImplementedError("criterion 'variance_reduction' scores single static sites (Agent.greedy, run_greedy_ipp); "
-                                      "a path utility would need a targets x path block of the posterior covariance per path")
+            raise NotImplementedError("criterion 'variance_reduction' scores single static sites here (Agent.greedy, run_greedy_ipp); "
+                                      "its path utility is Agent.path_variance_reduction: choose paths with strategy='MaxVarRed'")
         c = self._load_pool()
         n = self.env.num_samples
         static, mobile0 = self._masks()
@@ -427,6 +427,36 @@ class Agent(object):
             # the common base, even where it re-measures a static site; H is brought back to the fused form
             return int(np.argmax(self._path_utilities_rows(c, paths_mobile_indices, static, mobile0)))
         return int(np.argmax(self._path_utilities_fused(c, paths_mobile_indices, static, mobile0)))
+
+    def path_variance_reduction(self, paths_mobile_indices, static_indices):
+        """Variance-reduction utility of every path: how much its mobile readings lower the summed posterior variance of every
+        site that stays unsampled (algp_score_paths_vr).  The sites a path changes are those best_path counts -- distinct, on
+        the field, not mobile-sampled already; the train set is in the agent's current form (a row per reading, else one fused
+        row per site).  One factor update, one candidate solve over every site, one scoring call for all paths."""
+        if self.comm is not None:
+            raise NotImplementedError("the variance-reduction path utility is not sharded: its targets are the whole candidate "
+                                      "set, which no rank of a sharded agent holds; run it on one GPU")
+        c = self._load_pool()
+        n = self.env.num_samples
+        static, mobile0 = self._masks()
+        static = static.copy()
+        static[static_indices] = True
+        clean = [[j for j in dict.fromkeys(int(v) for v in path) if j != -1 and not mobile0[j]] for path in paths_mobile_indices]
+        if max((len(p) for p in clean), default=0) > 256:
+            raise ValueError('path_variance_reduction: a path changes more than 256 sites, the limit of algp_score_paths_vr')
+        if self._use_rows():
+            A, is_static = self._train_rows(static, mobile0)
+            c.set_train(A, np.zeros(len(A)), self._rows_noise(is_static))
+        else:
+            A = self._train_order(static | mobile0)
+            c.set_train(A, np.zeros(len(A)), self._fused_var(static[A], mobile0[A]))
+        c.factorize(incremental=True)
+        c.set_candidates(np.arange(n), prior_includes_noise=True)     # the targets: every unsampled site
+        c.solve_candidates(incremental=True, alive=~static)
+        sites = np.full((len(clean), max(1, max((len(p) for p in clean), default=0))), -1, dtype=np.int64)
+        for k, pth in enumerate(clean):
+            sites[k, :len(pth)] = pth
+        return c.score_paths_vr(sites, self.mobile_std)
 
     def _path_utilities_fused(self, c, paths, static, mobile0, batched=True):
         """Utility of every path, one fused train row per site (agent.py:374-400).  Batched, MI criterion, one GPU: the
@@ -550,15 +580,20 @@ class Agent(object):
     def _choose(self, strategy, paths_indices, paths_cost, static_indices):
         if strategy == 'Shortest':
             return find_shortest_path(paths_cost)
+        if strategy == 'MaxVarRed':                               # route by variance reduction, whatever chose the waypoints
+            if len(paths_indices) == 1:
+                return 0
+            return int(np.argmax(self.path_variance_reduction(paths_indices, static_indices)))
         best = self.best_path(paths_indices, static_indices)
         return find_equi_sample_path(paths_indices, best) if strategy == 'Equi-Sample' else best
 
     def run_ipp(self, render=False, num_runs=10, criterion='entropy', update=False, slack=0, strategy='MaxEnt',
                 disp=True):
-        assert strategy in ['MaxEnt', 'Shortest', 'Equi-Sample'], 'Unknown strategy!!'
-        if criterion == 'variance_reduction':
-            raise NotImplementedError("criterion 'variance_reduction' has no path utility (Agent.best_path): use run_greedy_ipp")
-        assert criterion in ['entropy', 'mutual_information'], 'Unknown criterion!!'
+        assert strategy in ['MaxEnt', 'Shortest', 'Equi-Sample', 'MaxVarRed'], 'Unknown strategy!!'
+        if criterion == 'variance_reduction' and strategy != 'MaxVarRed':
+            raise NotImplementedError("criterion 'variance_reduction' has no path utility in Agent.best_path: pass "
+                                      "strategy='MaxVarRed' (Agent.path_variance_reduction), or use run_greedy_ipp")
+        assert criterion in ['entropy', 'mutual_information', 'variance_reduction'], 'Unknown criterion!!'
         self._setup_ipp(criterion, update)
         test_error, pred, var, error = [], None, None, None
         for i in range(num_runs):
@@ -589,8 +624,8 @@ class Agent(object):
         return {'mean': pred, 'error': test_error}
 
     def run_greedy_ipp(self, num_runs=10, criterion='entropy', strategy='MaxEnt', disp=True):
-        """criterion='variance_reduction' has no path utility: where the planner offers several paths to a waypoint, 'MaxEnt'
-        and 'Equi-Sample' raise NotImplementedError from best_path (one path is taken as it is); pass strategy='Shortest'."""
+        """criterion='variance_reduction': where the planner offers several paths to a waypoint, 'MaxEnt' and 'Equi-Sample' raise
+        NotImplementedError from best_path (one path is taken as it is); pass strategy='MaxVarRed' or 'Shortest'."""
         self._setup_ipp(criterion)
         for i in range(num_runs):
             new_idx = self.greedy(self.num_samples_per_batch)

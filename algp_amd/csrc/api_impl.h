@@ -2,7 +2,8 @@
 // concern: api.hip (context, hyper-parameters, pool, train set, the stand-alone matrix entry points), api_factor.hip (the
 // factor of the train set and its updates), api_candidates.hip (candidate solve and posterior), api_greedy.hip (scoring,
 // picks, the sharded exchange), api_mi.hip (the MI criterion's state, on one GPU and over the ranks), api_vr.hip (the
-// variance-reduction criterion), api_paths.hip (best_path block scoring), api_fit.hip (MLL gradient, one fit iteration).
+// variance-reduction criterion), api_paths.hip (best_path block scoring), api_paths_vr.hip (the variance-reduction utility of
+// whole paths), api_fit.hip (MLL gradient, one fit iteration).
 // Every file defines its members of Impl<T> and instantiates Impl<float> / Impl<double> for them.
 #pragma once
 #include <limits.h>
@@ -170,12 +171,30 @@ struct Impl {
     static int score_paths(algp_ctx* c, const int64_t* sites, int npaths, int maxlen, double mobile_std, double* dH);
     static int score_paths_mi(algp_ctx* c, const int64_t* sites, int npaths, int maxlen, double static_std, double mobile_std,
                               double* dMI, double* terms);
+    static int score_paths_vr(algp_ctx* c, const int64_t* sites, int npaths, int maxlen, double mobile_std, int64_t max_union, double* dV);
     static int mll_grad(algp_ctx* c, double* grad_out, bool have_X = false, bool inv_enqueued = false);
     static int fit_step(algp_ctx* c, double* mll_out, double* grad_out);
     static int get_alpha(algp_ctx* c, void* out);
     static int get_factor(algp_ctx* c, void* out);
     static int selftest(algp_ctx* c, int* mism);
 };
+
+// Factor a batch of ppad x ppad blocks (ppad = 128 or 256, lower tiles) as 2 x 2 tiles of 128, the way score_paths_big does:
+// L11 and L22 in place, L21 = G21 inv(L11)^T into L21 (NB x NB per block), log det added to logdet[b], first bad pivot to info[b]
+template <typename T>
+int factor_blocks_batched(algp_ctx* c, T* G, int ppad, T* inv, T* L21, double* logdet, int* info, int B) {
+    ALGP_TRY(potrf_diag_batched_launch<T>(c, G, (int64_t)ppad * ppad, ppad, inv, 2 * NB * NB, logdet, info, B));
+    if (ppad > NB) {
+        T* G21 = G + (int64_t)NB * ppad;
+        T* G22 = G21 + NB;
+        ALGP_TRY(gemm_nt_launch_batched<T>(c, ALGP_PROF_GEMM_OTHER, NB, NB, NB, (T)1, G21, ppad, (int64_t)ppad * ppad, inv, NB, 2 * NB * NB,
+                                           (T)0, nullptr, 0, 0, L21, NB, NB * NB, 0, B));
+        ALGP_TRY(gemm_nt_launch_batched<T>(c, ALGP_PROF_GEMM_OTHER, NB, NB, NB, (T)-1, L21, NB, NB * NB, L21, NB, NB * NB, (T)1, G22, ppad,
+                                           (int64_t)ppad * ppad, G22, ppad, (int64_t)ppad * ppad, 0, B));
+        ALGP_TRY(potrf_diag_batched_launch<T>(c, G22, (int64_t)ppad * ppad, ppad, inv + NB * NB, 2 * NB * NB, logdet, info, B));
+    }
+    return ALGP_OK;
+}
 
 }  // namespace algp
 

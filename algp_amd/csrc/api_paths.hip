@@ -125,23 +125,6 @@ int Impl<T>::score_paths(algp_ctx* c, const int64_t* sites, int npaths, int maxl
     return sync(c);
 }
 
-// Factor a batch of ppad x ppad blocks (ppad = 128 or 256, lower tiles) as 2 x 2 tiles of 128, the way score_paths_big does:
-// L11 and L22 in place, L21 = G21 inv(L11)^T into L21 (NB x NB per block), log det added to logdet[b], first bad pivot to info[b]
-template <typename T>
-static int factor_blocks_batched(algp_ctx* c, T* G, int ppad, T* inv, T* L21, double* logdet, int* info, int B) {
-    ALGP_TRY(potrf_diag_batched_launch<T>(c, G, (int64_t)ppad * ppad, ppad, inv, 2 * NB * NB, logdet, info, B));
-    if (ppad > NB) {
-        T* G21 = G + (int64_t)NB * ppad;
-        T* G22 = G21 + NB;
-        ALGP_TRY(gemm_nt_launch_batched<T>(c, ALGP_PROF_GEMM_OTHER, NB, NB, NB, (T)1, G21, ppad, (int64_t)ppad * ppad, inv, NB, 2 * NB * NB,
-                                           (T)0, nullptr, 0, 0, L21, NB, NB * NB, 0, B));
-        ALGP_TRY(gemm_nt_launch_batched<T>(c, ALGP_PROF_GEMM_OTHER, NB, NB, NB, (T)-1, L21, NB, NB * NB, L21, NB, NB * NB, (T)1, G22, ppad,
-                                           (int64_t)ppad * ppad, G22, ppad, (int64_t)ppad * ppad, 0, B));
-        ALGP_TRY(potrf_diag_batched_launch<T>(c, G22, (int64_t)ppad * ppad, ppad, inv + NB * NB, 2 * NB * NB, logdet, info, B));
-    }
-    return ALGP_OK;
-}
-
 // best_path under the MI criterion (agent.py:374-400: ent_a + ent_abar - ent_all per path, two of them pool-sized).  Relative
 // to the base state (train set A0, complement Abar0, noise D0), path p changes S = S_new u S_rm: new sites join A with noise
 // sm and leave Abar; re-measured train sites keep their place and their fused noise goes v_a -> v_a sm / (v_a + sm).

@@ -407,6 +407,12 @@ int gemm_nt_launch_stats(algp_ctx* c, int klass, int64_t m, int64_t k, T alpha, 
 template <typename T>
 int gemm_nt_launch_vr(algp_ctx* c, int klass, int64_t mpad, int64_t n, int64_t k, const T* Vt, int64_t ldv, int64_t ncol0,
                       const KmatSrc& s, const int64_t* cidx, const int* ckind, int64_t M, T* part, int64_t part_ld);
+// variance reduction of whole paths: E[u][j] = C(uidx[u], cidx[ncol0 + j]) - R_u . V_(ncol0 + j) on the target columns, 0 on the
+// others and on the rows behind U; the E tile is written (upad x n, leading dimension lde), nothing else (gemm.hip)
+template <typename T>
+int gemm_nt_launch_pvr(algp_ctx* c, int klass, int64_t upad, int64_t n, int64_t k, const T* R, int64_t ldr, const T* Vt, int64_t ldv,
+                       int64_t ncol0, const KmatSrc& s, const int64_t* uidx, int64_t U, const int64_t* cidx, const int* ckind, int64_t M,
+                       T* E, int64_t lde);
 // C (m x m, lower tiles) -= X X^T for a short, very wide X (m <= 512 rows, k columns): the k range is cut into
 // chunks that run as one batched launch, the partial products are summed in chunk order (deterministic)
 template <typename T>

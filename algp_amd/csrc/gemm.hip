@@ -110,6 +110,28 @@ struct VrGemmArgs : GemmArgs<T> {
     T os, noise;
 };
 
+// C(prow, pcol) for the two epilogues below: read from the explicit pool covariance, or formed from the scaled coordinates
+// of the row (in registers) and of the column (staged in LDS) with the one kernel-value definition kexp, sigma_n^2 added
+// where the pool indices coincide
+template <typename T>
+__device__ __forceinline__ T vr_pool_cov(const VrGemmArgs<T>& g, int64_t prow, int64_t pcol, const T (&xrow)[MAXD], const T* xcol) {
+    if (g.Cp) return g.Cp[prow * g.n_pool + pcol];
+    T r2 = (T)0;
+#pragma unroll
+    for (int d = 0; d < MAXD; ++d) {
+        const T df = xrow[d] - xcol[d];
+        r2 += df * df;
+    }
+    T cv;
+    if (g.kernel == ALGP_KERNEL_RBF) cv = g.os * kexp((T)-0.5 * r2);
+    else {
+        const T rr = sqrt(r2) * (T)1.7320508075688772;
+        cv = g.os * ((T)1 + rr) * kexp(-rr);
+    }
+    if (prow == pcol) cv += g.noise;
+    return cv;
+}
+
 template <typename T, typename ACC>
 __device__ __forceinline__ void vr_epilogue(const VrGemmArgs<T>& g, char* smem, const ACC (&acc)[4][4], int64_t m0, int64_t n0, int bn,
                                             int wr, int wc, int lane, int tid) {
@@ -156,23 +178,7 @@ __device__ __forceinline__ void vr_epilogue(const VrGemmArgs<T>& g, char* smem, 
             for (int j = 0; j < 4; ++j) {
                 const int col = wc * 64 + j * 16 + fr;
                 const int64_t pcol = pc[col];
-                T cv;
-                if (g.Cp) {
-                    cv = g.Cp[prow * g.n_pool + pcol];
-                } else {
-                    T r2 = (T)0;
-#pragma unroll
-                    for (int d = 0; d < MAXD; ++d) {
-                        const T df = xrow[d] - xc[col * MAXD + d];
-                        r2 += df * df;
-                    }
-                    if (g.kernel == ALGP_KERNEL_RBF) cv = g.os * kexp((T)-0.5 * r2);
-                    else {
-                        const T rr = sqrt(r2) * (T)1.7320508075688772;
-                        cv = g.os * ((T)1 + rr) * kexp(-rr);
-                    }
-                    if (prow == pcol) cv += g.noise;
-                }
+                const T cv = vr_pool_cov<T>(g, prow, pcol, xrow, xc + col * MAXD);
                 T e = kap * cv - acc[i][j][r];
                 e = mc[col] ? e : (T)0;
                 s2 += e * e;
@@ -182,6 +188,72 @@ __device__ __forceinline__ void vr_epilogue(const VrGemmArgs<T>& g, char* smem, 
         }
     __syncthreads();
     if (tid < 128) g.stat_out[(int64_t)bn * g.stat_ld + m0 + tid] = red[tid] + red[128 + tid];
+}
+
+// ---------------------------------------------------------------------------------------------
+// Variance reduction of whole paths (api_paths_vr.hip): A = R_U, the rows of V^T of the union U of the paths' sites (a site
+// with a train row already: its second-row form), B = rows [ncol0, ncol0 + n) of V^T.  The accumulators hold R_u . V_j; the
+// epilogue forms the cross covariance E_uj = C(u, j) - R_u . V_j in registers -- the kernel term as in vr_epilogue, but always
+// present on the row side and with the row's pool index from uidx -- zeroes the columns that are not targets (unit rows,
+// padding) and the padding rows behind U, and WRITES the tile: E[row][n0 + col], the launch's columns only (Phi = E E^T is
+// the caller's next product).  No kernel-matrix block is written.
+// ---------------------------------------------------------------------------------------------
+template <typename T>
+struct PvrGemmArgs : VrGemmArgs<T> {
+    const int64_t* uidx;           // pool index of every union row (U entries)
+    int64_t U;                     // rows beyond U are padding
+    T* E;                          // mpad x n
+    int64_t lde;
+};
+
+template <typename T, typename ACC>
+__device__ __forceinline__ void pvr_epilogue(const PvrGemmArgs<T>& g, char* smem, const ACC (&acc)[4][4], int64_t m0, int64_t n0, int wr,
+                                             int wc, int lane, int tid) {
+    using F = MF<T>;
+    const int fr = lane & 15;
+    // LDS: coordinates of the rows, of the columns ([128][MAXD], zero padded) | pool indices of the rows, of the columns |
+    // which rows are union sites | target mask of the columns
+    T* xr = reinterpret_cast<T*>(smem);
+    T* xc = reinterpret_cast<T*>(smem + 8192);
+    int64_t* pr = reinterpret_cast<int64_t*>(smem + 16384);
+    int64_t* pc = pr + 128;
+    int* kr = reinterpret_cast<int*>(pc + 128);
+    int* mc = kr + 128;
+    __syncthreads();                                               // every wave is done with the last stage
+    {
+        const int t = tid & 127;
+        const bool is_col = tid >= 128;
+        const int64_t gi = is_col ? g.ncol0 + n0 + t : m0 + t;
+        const bool valid = is_col ? gi < g.M : gi < g.U;
+        const int64_t p = valid ? (is_col ? g.cidx[gi] : g.uidx[gi]) : 0;
+        (is_col ? pc : pr)[t] = p;
+        (is_col ? mc : kr)[t] = is_col ? ((valid && g.ckind[gi] < 0) ? 1 : 0) : (valid ? 1 : 0);
+        if (!g.Cp) {
+            T* x = (is_col ? xc : xr) + t * MAXD;
+#pragma unroll
+            for (int d = 0; d < MAXD; ++d) x[d] = d < g.DP ? g.Xs[p * g.DP + d] : (T)0;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = wr * 64 + i * 16 + F::row_of(lane, r);
+            const int64_t prow = pr[row];
+            const bool rowon = kr[row] != 0;
+            T xrow[MAXD];
+#pragma unroll
+            for (int d = 0; d < MAXD; ++d) xrow[d] = xr[row * MAXD + d];
+            T* Er = g.E + (m0 + row) * g.lde + n0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int col = wc * 64 + j * 16 + fr;
+                const int64_t pcol = pc[col];
+                const T cv = vr_pool_cov<T>(g, prow, pcol, xrow, xc + col * MAXD);
+                Er[col] = (rowon && mc[col]) ? cv - acc[i][j][r] : (T)0;
+            }
+        }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -203,7 +275,8 @@ __device__ __forceinline__ void vr_epilogue(const VrGemmArgs<T>& g, char* smem, 
 #ifndef ALGP_GEMM_XOR_MASK
 #define ALGP_GEMM_XOR_MASK 2
 #endif
-// Args = VrGemmArgs<T>: the variance-reduction epilogue above instead of a D tile (STATS is then false).
+// Args = VrGemmArgs<T>: the variance-reduction epilogue above instead of a D tile (STATS is then false); Args =
+// PvrGemmArgs<T>: the path form's epilogue, which writes the E tile.
 //
 // SCHED: the scheduled sibling for the candidate sweep's products.  A grid of G = min(tiles, 2 x CUs) workgroups, each
 // walking its fixed list of units (gemm_sched.h: whole tiles, or one k slice of a leftover tile whose alpha * acc goes to a
@@ -368,7 +441,10 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel_dma4(Args g) {
         }
     }
 
-    if constexpr (VR) {
+    if constexpr (std::is_same<Args, PvrGemmArgs<T>>::value) {
+        pvr_epilogue<T>(g, smem, acc, m0, n0, wr, wc, lane, tid);
+        return;
+    } else if constexpr (VR) {
         vr_epilogue<T>(g, smem, acc, m0, n0, cur_bn, wr, wc, lane, tid);
         return;
     }
@@ -624,6 +700,50 @@ template int gemm_nt_launch_vr<double>(algp_ctx*, int, int64_t, int64_t, int64_t
                                        const int64_t*, const int*, int64_t, double*, int64_t);
 template int gemm_nt_launch_vr<float>(algp_ctx*, int, int64_t, int64_t, int64_t, const float*, int64_t, int64_t, const KmatSrc&,
                                       const int64_t*, const int*, int64_t, float*, int64_t);
+
+// The cross covariances of the union rows R (upad x k, the rows behind U zero) with rows [ncol0, ncol0 + n) of V^T:
+// E[u][j] = C(uidx[u], cidx[ncol0 + j]) - R_u . V_(ncol0 + j) where column ncol0 + j is a target, 0 elsewhere and on the
+// padding rows; E is upad x n with leading dimension lde.
+template <typename T>
+int gemm_nt_launch_pvr(algp_ctx* c, int klass, int64_t upad, int64_t n, int64_t k, const T* R, int64_t ldr, const T* Vt, int64_t ldv,
+                       int64_t ncol0, const KmatSrc& s, const int64_t* uidx, int64_t U, const int64_t* cidx, const int* ckind, int64_t M,
+                       T* E, int64_t lde) {
+    if (upad <= 0 || n <= 0) return ALGP_OK;
+    if (upad % 128 || n % 128 || k % 128 || k <= 0 || ldr % 4 || ldv % 4 || ncol0 % 128 || ncol0 + n > (M + 127) / 128 * 128 || k > ldv || k > ldr || U > upad || lde < n ||
+        s.DP > MAXD)
+        return fail(c, ALGP_ERR_BAD_ARG, "gemm_nt_pvr: operands must be padded to multiples of 128");
+    PvrGemmArgs<T> g;
+    g.A = R; g.B = Vt + ncol0 * ldv; g.C = nullptr; g.D = nullptr;
+    g.lda = ldr; g.ldb = ldv; g.ldc = 0; g.ldd = 0;
+    g.sA = g.sB = g.sC = g.sD = 0;
+    g.tiles_m = (int)(upad / 128);
+    g.tiles_n = (int)(n / 128);
+    g.ktiles = (int)(k / (8 * MF<T>::EPC));
+    g.alpha = (T)1; g.beta = (T)0;
+    g.lower_only = 0; g.ktri = 0; g.kcut = 0;
+    g.stat_w = nullptr; g.stat_out = nullptr; g.stat_ld = 0;
+    g.sch = Sched(); g.part = nullptr;
+    g.cidx = cidx; g.ckind = ckind; g.M = M; g.ncol0 = ncol0;
+    g.Xs = (const T*)s.Xs; g.Cp = (const T*)s.Cp; g.n_pool = s.n_pool; g.DP = s.DP; g.kernel = s.kernel;
+    g.os = (T)s.outputscale; g.noise = (T)s.noise;
+    g.uidx = uidx; g.U = U; g.E = E; g.lde = lde;
+    const int64_t tiles = (int64_t)g.tiles_m * g.tiles_n;
+    if (tiles > 0x7fffffff) return fail(c, ALGP_ERR_BAD_ARG, "gemm_nt_pvr: grid too large");
+    const double flops = 2.0 * 128.0 * 128.0 * (double)k * (double)tiles;
+    const double bytes = sizeof(T) * ((double)k * 128.0 * (double)(g.tiles_m + g.tiles_n) + 128.0 * 128.0 * (double)tiles);
+    launch_log_line(klass, upad, n, k, 0, 1, 0, (int)sizeof(T), 0);
+    hipEvent_t ev_a, ev_b;
+    const bool timed = prof_launch_events(c, klass, flops, bytes, &ev_a, &ev_b);
+    const dim3 grid((unsigned)tiles);
+    if (timed) hipExtLaunchKernelGGL((gemm_nt_kernel_dma4<T, false, PvrGemmArgs<T>>), grid, dim3(256), 0, c->cur, ev_a, ev_b, 0, g);
+    else hipLaunchKernelGGL((gemm_nt_kernel_dma4<T, false, PvrGemmArgs<T>>), grid, dim3(256), 0, c->cur, g);
+    ALGP_HIP(hipGetLastError());
+    return ALGP_OK;
+}
+template int gemm_nt_launch_pvr<double>(algp_ctx*, int, int64_t, int64_t, int64_t, const double*, int64_t, const double*, int64_t, int64_t,
+                                        const KmatSrc&, const int64_t*, int64_t, const int64_t*, const int*, int64_t, double*, int64_t);
+template int gemm_nt_launch_pvr<float>(algp_ctx*, int, int64_t, int64_t, int64_t, const float*, int64_t, const float*, int64_t, int64_t,
+                                       const KmatSrc&, const int64_t*, int64_t, const int64_t*, const int*, int64_t, float*, int64_t);
 
 template <typename T>
 int gemm_nt_launch(algp_ctx* c, int klass, int64_t m, int64_t n, int64_t k, T alpha, const T* A,

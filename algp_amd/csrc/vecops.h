@@ -61,6 +61,24 @@ template <typename T>
 int path_assemble_launch(algp_ctx* c, const int64_t* cpos, int batch, int ppad, const int64_t* cidx, const T* Xs, const T* Cp,
                          int64_t n_pool, int DP, int kernel, double os, double noise, double sm, T* G);
 int path_finish_launch(algp_ctx* c, const int64_t* cpos, int ppad, int batch, const double* logdet, const int* info, double* out);
+// variance reduction of whole paths (api_paths_vr.hip), over Gamma and Phi of a group's union sites (ld apart, lower tiles
+// valid): Gamma = C(U, U) - Gram in place; the paths of at most 64 sites, one workgroup each (upos: stride union positions per
+// path, packed to the front, -1 behind; pid: the slot of out each writes); for a batch of longer paths the gathered blocks
+// G = Gamma_SS + sm I (identity on the padding) and F = Phi_SS (both triangles), the block's L^-1 (Li) from the tiled factor's
+// inverse tiles and, at ppad = 256, tr = [L21^T | inv(L11)^T] per block for the products of its lower left tile; and
+// out[pid[b]] = sum over the lower triangle of W_ij Li_ij (NaN where info[b] != 0)
+template <typename T>
+int pvr_assemble_launch(algp_ctx* c, const int64_t* uidx, int64_t U, int64_t ld, const T* Xs, const T* Cp, int64_t n_pool, int DP,
+                        int kernel, double os, double noise, T* G);
+template <typename T>
+int pvr_small_launch(algp_ctx* c, const int* upos, int stride, const int* pid, int npaths, const T* Gam, const T* Phi, int64_t ld,
+                     double sm, double* out);
+template <typename T>
+int pvr_gather_launch(algp_ctx* c, const int* upos, int ppad, int batch, const T* Gam, const T* Phi, int64_t ld, double sm, T* G, T* F);
+template <typename T>
+int pvr_linv_launch(algp_ctx* c, const T* inv, const T* L21, int ppad, int batch, T* Li, T* tr);
+template <typename T>
+int pvr_trace_launch(algp_ctx* c, const T* W, const T* Li, int ppad, int batch, const int* info, const int* pid, double* out);
 // best_path under the MI criterion (paths_mi.hip): rows of a resident triangular inverse X = L^-T, zero left of each row's
 // diagonal tile (-1: a zero row); ones on the diagonal behind each path's cnt[b] sites; the operands Lt = G^T, LtD = G^T diag(delta)
 // of I + G^T diag(delta) G from the 2 x 2 tiled factor G of a batch of ppad x ppad blocks (L21 in its own NB x NB buffer per block)

@@ -1177,6 +1177,253 @@ int path_finish_launch(algp_ctx* c, const int64_t* cpos, int ppad, int batch, co
 }
 
 // ---------------------------------------------------------------------------------------------
+// Variance reduction of whole paths (api_paths_vr.hip): u_p = tr((Gamma_SS + sm I)^-1 Phi_SS) over the path's sites S, from
+// the two matrices the host has built over the union U of a group of paths: Gamma = C(U, U) - R_U R_U^T (the posterior
+// covariance of the union sites) and Phi = E E^T (E: their cross covariances with the targets).  A path is its sites'
+// positions in the union (upos: stride entries per path, packed to the front, -1 behind them) and the slot of the
+// caller's output it writes (pid).  Only the lower tiles of Gamma and Phi are valid: every read goes to [max][min].
+// ---------------------------------------------------------------------------------------------
+// Gamma = C(U, U) - Gram in place, on and below the diagonal (one workgroup per row; sm is added per path)
+template <typename T, int DP>
+__global__ __launch_bounds__(256) void pvr_assemble_kernel(const int64_t* uidx, int64_t U, int64_t ld, const T* Xs, const T* Cp, int64_t n_pool,
+                                                           int kernel, double os, double noise, T* G) {
+    const int64_t a = blockIdx.x;
+    const int64_t pa = uidx[a];
+    double xa[DP];
+#pragma unroll
+    for (int d = 0; d < DP; ++d) xa[d] = Cp ? 0.0 : (double)Xs[pa * DP + d];
+    for (int64_t b = threadIdx.x; b <= a; b += 256) {
+        const int64_t pb = uidx[b];
+        double cab;
+        if (Cp) {
+            cab = (double)Cp[pa * n_pool + pb];
+        } else {
+            double r2 = 0.0;
+#pragma unroll
+            for (int d = 0; d < DP; ++d) {
+                const double df = xa[d] - (double)Xs[pb * DP + d];
+                r2 += df * df;
+            }
+            if (kernel == ALGP_KERNEL_RBF) cab = os * kexp(-0.5 * r2);
+            else {
+                const double r = sqrt(r2) * 1.7320508075688772;
+                cab = os * (1.0 + r) * kexp(-r);
+            }
+            if (pa == pb) cab += noise;
+        }
+        G[a * ld + b] = (T)(cab - (double)G[a * ld + b]);
+    }
+}
+template <typename T>
+int pvr_assemble_launch(algp_ctx* c, const int64_t* uidx, int64_t U, int64_t ld, const T* Xs, const T* Cp, int64_t n_pool, int DP,
+                        int kernel, double os, double noise, T* G) {
+    if (U <= 0) return ALGP_OK;
+    dim3 grid((unsigned)U), blk(256);
+#define ALGP_PVA(DPV) \
+    hipLaunchKernelGGL((pvr_assemble_kernel<T, DPV>), grid, blk, 0, c->cur, uidx, U, ld, Xs, Cp, n_pool, kernel, os, noise, G)
+    if (DP == 2) ALGP_PVA(2);
+    else if (DP == 4) ALGP_PVA(4);
+    else ALGP_PVA(8);
+#undef ALGP_PVA
+    ALGP_HIP(hipGetLastError());
+    return ALGP_OK;
+}
+template int pvr_assemble_launch<double>(algp_ctx*, const int64_t*, int64_t, int64_t, const double*, const double*, int64_t, int, int, double,
+                                         double, double*);
+template int pvr_assemble_launch<float>(algp_ctx*, const int64_t*, int64_t, int64_t, const float*, const float*, int64_t, int, int, double,
+                                        double, float*);
+
+// Paths of at most 64 sites, one workgroup per path, fp64 in LDS for either dtype like path_score_kernel: both k x k blocks
+// gathered by union position, sm on Gamma's diagonal, the column Cholesky L L^T = Gamma_SS + sm I, W = L^-1 Phi_SS (a thread
+// per column), then from the other side Y = W L^-T (a thread per row, up to its diagonal entry: the trace needs no more)
+// and u = sum_r Y_rr in index order.  A pivot that is not positive: NaN.
+template <typename T>
+__global__ __launch_bounds__(256) void pvr_small_kernel(const int* upos, int stride, const int* pid, const T* Gam, const T* Phi, int64_t ld,
+                                                        double sm, double* out) {
+    __shared__ double G[PATH_SITES][PATH_SITES + 1];
+    __shared__ double W[PATH_SITES][PATH_SITES + 1];
+    __shared__ int s_u[PATH_SITES];
+    __shared__ int s_n;
+    const int tid = threadIdx.x;
+    const int* pu = upos + (int64_t)blockIdx.x * stride;
+    if (tid == 0) {
+        int n = 0;
+        while (n < stride && n < PATH_SITES && pu[n] >= 0) { s_u[n] = pu[n]; ++n; }
+        s_n = n;
+    }
+    __syncthreads();
+    const int P = s_n;
+    for (int e = tid; e < P * P; e += 256) {
+        const int a = e / P, b = e - a * P;
+        const int64_t ua = s_u[a], ub = s_u[b];
+        const int64_t at = ua >= ub ? ua * ld + ub : ub * ld + ua;
+        G[a][b] = (double)Gam[at] + (a == b ? sm : 0.0);
+        W[a][b] = (double)Phi[at];
+    }
+    __syncthreads();
+    bool bad = false;
+    for (int j = 0; j < P; ++j) {
+        const double d = G[j][j];
+        if (!(d > 0.0)) { bad = true; break; }                     // wave-uniform: every thread reads the same G[j][j]
+        const double rs = 1.0 / sqrt(d);
+        __syncthreads();
+        for (int i = j + tid; i < P; i += 256) G[i][j] *= rs;      // the diagonal entry becomes sqrt(d)
+        __syncthreads();
+        for (int e = tid; e < (P - j - 1) * (P - j - 1); e += 256) {
+            const int i = j + 1 + e / (P - j - 1), c2 = j + 1 + e % (P - j - 1);
+            if (c2 <= i) G[i][c2] -= G[i][j] * G[c2][j];
+        }
+        __syncthreads();
+    }
+    if (bad) {
+        if (tid == 0) out[pid[blockIdx.x]] = NAN;
+        return;
+    }
+    if (tid < P) {
+        for (int i = 0; i < P; ++i) {
+            double s = W[i][tid];
+            for (int m = 0; m < i; ++m) s -= G[i][m] * W[m][tid];
+            W[i][tid] = s / G[i][i];
+        }
+    }
+    __syncthreads();
+    if (tid < P) {
+        for (int j = 0; j <= tid; ++j) {
+            double s = W[tid][j];
+            for (int m = 0; m < j; ++m) s -= G[j][m] * W[tid][m];
+            W[tid][j] = s / G[j][j];
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double u = 0.0;
+        for (int r = 0; r < P; ++r) u += W[r][r];
+        out[pid[blockIdx.x]] = u;
+    }
+}
+template <typename T>
+int pvr_small_launch(algp_ctx* c, const int* upos, int stride, const int* pid, int npaths, const T* Gam, const T* Phi, int64_t ld,
+                     double sm, double* out) {
+    if (npaths <= 0) return ALGP_OK;
+    hipLaunchKernelGGL(pvr_small_kernel<T>, dim3((unsigned)npaths), dim3(256), 0, c->cur, upos, stride, pid, Gam, Phi, ld, sm, out);
+    ALGP_HIP(hipGetLastError());
+    return ALGP_OK;
+}
+template int pvr_small_launch<double>(algp_ctx*, const int*, int, const int*, int, const double*, const double*, int64_t, double, double*);
+template int pvr_small_launch<float>(algp_ctx*, const int*, int, const int*, int, const float*, const float*, int64_t, double, double*);
+
+// Paths of 65 .. 256 sites, a batch of ppad x ppad blocks (ppad = 128 or 256).  Gather: G = Gamma_SS + sm I on its lower
+// tiles, the identity behind the path's sites; F = Phi_SS in both triangles, zero behind them.
+template <typename T>
+__global__ __launch_bounds__(256) void pvr_gather_kernel(const int* upos, int ppad, const T* Gam, const T* Phi, int64_t ld, double sm, T* G,
+                                                         T* F) {
+    __shared__ int s_u[256];
+    const int tid = threadIdx.x;
+    if (tid < ppad) s_u[tid] = upos[(int64_t)blockIdx.x * ppad + tid];
+    __syncthreads();
+    T* Gp = G + (int64_t)blockIdx.x * ppad * ppad;
+    T* Fp = F + (int64_t)blockIdx.x * ppad * ppad;
+    for (int e = tid; e < ppad * ppad; e += 256) {
+        const int a = e / ppad, b = e - a * ppad;
+        const int64_t ua = s_u[a], ub = s_u[b];
+        T g = a == b ? (T)1 : (T)0, f = (T)0;
+        if (ua >= 0 && ub >= 0) {
+            const int64_t at = ua >= ub ? ua * ld + ub : ub * ld + ua;
+            g = (T)((double)Gam[at] + (a == b ? sm : 0.0));
+            f = Phi[at];
+        }
+        if ((a >> 7) >= (b >> 7)) Gp[e] = g;                       // tiles above the diagonal are never read
+        Fp[e] = f;
+    }
+}
+template <typename T>
+int pvr_gather_launch(algp_ctx* c, const int* upos, int ppad, int batch, const T* Gam, const T* Phi, int64_t ld, double sm, T* G, T* F) {
+    if (batch <= 0) return ALGP_OK;
+    if (ppad != NB && ppad != 2 * NB) return fail(c, ALGP_ERR_BAD_ARG, "pvr_gather: ppad must be 128 or 256");
+    hipLaunchKernelGGL(pvr_gather_kernel<T>, dim3((unsigned)batch), dim3(256), 0, c->cur, upos, ppad, Gam, Phi, ld, sm, G, F);
+    ALGP_HIP(hipGetLastError());
+    return ALGP_OK;
+}
+template int pvr_gather_launch<double>(algp_ctx*, const int*, int, int, const double*, const double*, int64_t, double, double*, double*);
+template int pvr_gather_launch<float>(algp_ctx*, const int*, int, int, const float*, const float*, int64_t, double, float*, float*);
+
+// The block's L^-1 from its 2 x 2 tiled factor: the two inverse tiles (inv: [inv(L11) | inv(L22)], zeros above their
+// diagonals) go to the diagonal tiles of Li, zeros above them; ppad = 256: tr = [L21^T | inv(L11)^T] are the transposed
+// operands of the two products that fill the tile below, -inv(L22) L21 inv(L11).  64 x 64 pieces through LDS.
+template <typename T>
+__global__ __launch_bounds__(256) void pvr_linv_kernel(const T* inv, const T* L21, int ppad, T* Li, T* tr) {
+    __shared__ T tile[64][65];
+    const int64_t b_ = blockIdx.z;
+    const int ta = blockIdx.x & 1, tb = blockIdx.x >> 1;           // a 64 x 64 piece of a 128 x 128 tile
+    const int which = blockIdx.y;                                  // 0, 1: the inverse tiles; 2: L21^T; 3: inv(L11)^T
+    const int tid = threadIdx.x;
+    const T* iv = inv + b_ * 2 * NB * NB;
+    T* Lo = Li + b_ * ppad * ppad;
+    if (which < 2) {
+        if (which == 1 && ppad == NB) return;
+        for (int e = tid; e < 64 * 64; e += 256) {
+            const int a = ta * 64 + (e >> 6), b = tb * 64 + (e & 63);
+            Lo[(int64_t)(which * NB + a) * ppad + which * NB + b] = iv[which * NB * NB + a * NB + b];
+            if (which == 0 && ppad > NB) Lo[(int64_t)a * ppad + NB + b] = (T)0;
+        }
+        return;
+    }
+    if (ppad == NB) return;
+    const T* src = which == 2 ? L21 + b_ * NB * NB : iv;
+    T* dst = tr + (b_ * 2 + (which - 2)) * NB * NB;
+    for (int e = tid; e < 64 * 64; e += 256) {
+        const int bb = e >> 6, aa = e & 63;
+        tile[bb][aa] = src[(tb * 64 + bb) * NB + ta * 64 + aa];
+    }
+    __syncthreads();
+    for (int e = tid; e < 64 * 64; e += 256) {
+        const int aa = e >> 6, bb = e & 63;
+        dst[(ta * 64 + aa) * NB + tb * 64 + bb] = tile[bb][aa];
+    }
+}
+template <typename T>
+int pvr_linv_launch(algp_ctx* c, const T* inv, const T* L21, int ppad, int batch, T* Li, T* tr) {
+    if (batch <= 0) return ALGP_OK;
+    if (ppad != NB && ppad != 2 * NB) return fail(c, ALGP_ERR_BAD_ARG, "pvr_linv: ppad must be 128 or 256");
+    hipLaunchKernelGGL(pvr_linv_kernel<T>, dim3(4, 4, (unsigned)batch), dim3(256), 0, c->cur, inv, L21, ppad, Li, tr);
+    ALGP_HIP(hipGetLastError());
+    return ALGP_OK;
+}
+template int pvr_linv_launch<double>(algp_ctx*, const double*, const double*, int, int, double*, double*);
+template int pvr_linv_launch<float>(algp_ctx*, const float*, const float*, int, int, float*, float*);
+
+// u = sum over the lower triangle of W_ij (L^-1)_ij = tr(L^-1 Phi_SS L^-T), W = L^-1 Phi_SS; fp64 sums in a fixed order (a
+// thread's strided share, then a tree over the 256 threads); NaN where the factorisation met a bad pivot
+template <typename T>
+__global__ __launch_bounds__(256) void pvr_trace_kernel(const T* W, const T* Li, int ppad, const int* info, const int* pid, double* out) {
+    __shared__ double red[256];
+    const int tid = threadIdx.x;
+    const T* Wp = W + (int64_t)blockIdx.x * ppad * ppad;
+    const T* Lp = Li + (int64_t)blockIdx.x * ppad * ppad;
+    double s = 0.0;
+    for (int e = tid; e < ppad * ppad; e += 256) {
+        const int a = e / ppad, b = e - a * ppad;
+        if (b <= a) s += (double)Wp[e] * (double)Lp[e];
+    }
+    red[tid] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) red[tid] += red[tid + w];
+        __syncthreads();
+    }
+    if (tid == 0) out[pid[blockIdx.x]] = info[blockIdx.x] != 0 ? NAN : red[0];
+}
+template <typename T>
+int pvr_trace_launch(algp_ctx* c, const T* W, const T* Li, int ppad, int batch, const int* info, const int* pid, double* out) {
+    if (batch <= 0) return ALGP_OK;
+    hipLaunchKernelGGL(pvr_trace_kernel<T>, dim3((unsigned)batch), dim3(256), 0, c->cur, W, Li, ppad, info, pid, out);
+    ALGP_HIP(hipGetLastError());
+    return ALGP_OK;
+}
+template int pvr_trace_launch<double>(algp_ctx*, const double*, const double*, int, int, const int*, const int*, double*);
+template int pvr_trace_launch<float>(algp_ctx*, const float*, const float*, int, int, const int*, const int*, double*);
+
+// ---------------------------------------------------------------------------------------------
 // fused kernel-GEMV: mu_j = ybar + sum_a k(x_j, x_a) alpha_a, K never materialised (utils.py:301).
 // One wave per output; lanes stride over the train set (coordinates and alpha are L2 resident).
 // ---------------------------------------------------------------------------------------------

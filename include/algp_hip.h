@@ -268,6 +268,25 @@ int algp_score_paths(algp_ctx* ctx, const int64_t* sites, int npaths, int maxlen
  * ALGP_ERR_STATE; a train set that lists a site twice: ALGP_ERR_STATE; more than 256 changing sites: ALGP_ERR_BAD_ARG. */
 int algp_score_paths_mi(algp_ctx* ctx, const int64_t* sites, int npaths, int maxlen, double static_std, double mobile_std,
                         double* dMI_out, double* terms_out);
+/* algp_score_paths_vr: the variance-reduction (ALC) utility of whole paths, the criterion's sentence applied to a set: with the
+ * targets T = the ordinary rows of the candidate set (fixed by the solve; a row switched off with algp_set_candidate_alive
+ * stays a target) and path p read once at each of its distinct sites with variance sm = mobile_std^2 -- a new site joins the
+ * train set with noise sm, a site that has a train row of noise v ends with v sm / (v + sm), i.e. receives a second row --
+ *   dV_out[p] = sum_{j in T} var(j | A) - sum_{j in T} var(j | A u path_p) = tr((Gamma_SS + sm I)^-1 Phi_SS),
+ * S the path's sites, Gamma = C - R R^T their posterior covariance (R_s: the site's row of V^T, second-row form for a train
+ * site; C: the pool covariance, sigma_n^2 where the pool indices coincide), E_sj = C(s, j) - R_s . V_j their cross covariance
+ * with the targets, Phi = E E^T.  Gamma and Phi are built once over the union U of a group of consecutive paths (max_union:
+ * the most union sites per group, at least 256; <= 0: the library's default, the largest union whose rows of V^T and whose two
+ * U x U matrices each stay within ~4 GB -- 15 744 sites in fp64, 22 272 in fp32, fewer beyond N of about 31 000 / 44 000; a site shared by
+ * paths of two groups is computed in both, so paths that share sites belong next to each other), then every path costs O(k^3) on its gathered k x k blocks: 2 U M N + 2 U^2 M flop per group (M candidate rows, N
+ * train rows), the first term one matrix-core product whose epilogue forms E, the second Phi += E E^T over chunks of the
+ * targets in a fixed order.  The grouping changes the result by rounding only.  sites[] as for algp_score_paths (-1 entries
+ * skipped, a site listed twice counts once); an empty path scores 0; a path whose block meets a pivot that is not positive
+ * scores NaN.  Preconditions as for algp_score_paths (a candidate solve with prior_includes_noise, no pick committed since:
+ * ALGP_ERR_STATE; every site a resident candidate, at most 256 distinct sites per path: ALGP_ERR_BAD_ARG), and the criterion's
+ * two refusals: candidates with an extra variance, or a candidate set that lists a pool site twice: ALGP_ERR_STATE. */
+int algp_score_paths_vr(algp_ctx* ctx, const int64_t* sites, int npaths, int maxlen, double mobile_std, int64_t max_union,
+                        double* dV_out);
 
 /* ---- (e) multi-GPU: the loop over candidates (agent.py:317-347) cut into shards, one process and one ctx per GPU ----
  * Every rank factorises the same train set (algp_factorize / algp_fit_and_solve) and holds a share of the candidate list
