@@ -78,6 +78,7 @@ SIGNATURES = {
     'algp_trsm_right_lt': (C.c_int, [_c_ctx, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     'algp_selftest_mfma': (C.c_int, [_c_ctx, C.POINTER(C.c_int)]),
     'algp_bench_gemm': (C.c_int, [_c_ctx, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, _dblp]),
+    'algp_bench_gemm_generated': (C.c_int, [_c_ctx, C.c_int64, C.c_int64, C.c_int64, C.c_int, _dblp]),
     'algp_sync': (C.c_int, [_c_ctx]),
     'algp_device_bytes': (C.c_int64, [_c_ctx]),
     'algp_prof_enable': (C.c_int, [_c_ctx, C.c_int]),
@@ -624,8 +625,13 @@ class Context(object):
         self._check(self.lib.algp_selftest_mfma(self.h, C.byref(v)))
         return v.value
 
-    def bench_gemm(self, m, n, k, lower_only=False, beta_one=True, reps=5):
+    def bench_gemm(self, m, n, k, lower_only=False, beta_one=True, reps=5, generated_c=False):
+        """generated_c: beta = 1 with the C tile formed in the epilogue from coordinates (the sweep's update product with fused
+        right-hand sides; scheduled form only) instead of loaded."""
         ms = C.c_double()
+        if generated_c:
+            self._check(self.lib.algp_bench_gemm_generated(self.h, m, n, k, int(reps), C.byref(ms)))
+            return ms.value
         self._check(self.lib.algp_bench_gemm(self.h, m, n, k, int(bool(lower_only)), int(bool(beta_one)),
                                              int(reps), C.byref(ms)))
         return ms.value

@@ -534,7 +534,7 @@ void algp_destroy(algp_ctx* c) {
     prof_collect(c);
     DevBuf* bufs[] = {&c->Xs, &c->Xraw, &c->Cp, &c->Aidx, &c->yA, &c->varA, &c->y0, &c->L, &c->invD, &c->z, &c->alpha,
                       &c->scal, &c->Cidx, &c->ckind, &c->cextra, &c->Vt, &c->dstat, &c->mu, &c->alive, &c->scores,
-                      &c->lrow, &c->remote, &c->commbuf, &c->tvec, &c->amax, &c->prevrows, &c->fresh, &c->lazypicks, &c->yraw, &c->uvec, &c->wvec, &c->acc3, &c->rowstat, &c->inv512, &c->inv512_scr, &c->trsm_tmp, &c->gemm_part, &c->splitk, &c->dag_state, &c->dag_stats, &c->trsv_ctrl, &c->auxA, &c->auxInv, &c->auxW, &c->auxIdx,
+                      &c->lrow, &c->remote, &c->commbuf, &c->tvec, &c->amax, &c->prevrows, &c->fresh, &c->lazypicks, &c->yraw, &c->uvec, &c->wvec, &c->acc3, &c->rowstat, &c->inv512, &c->inv512_scr, &c->trsm_tmp, &c->gemm_part, &c->rhs_rx, &c->rhs_cx, &c->rhs_rk, &c->splitk, &c->dag_state, &c->dag_stats, &c->trsv_ctrl, &c->auxA, &c->auxInv, &c->auxW, &c->auxIdx,
                       &c->auxVar, &c->auxD, &c->hostStage, &c->rowx, &c->tailE, &c->tailPart, &c->ldpart};
     for (DevBuf* b : bufs) release(c, *b);
     release(c, c->mi);
@@ -732,8 +732,18 @@ int algp_bench_gemm(algp_ctx* c, int64_t m, int64_t n, int64_t k, int lower_only
     if (!ms || m <= 0 || n <= 0 || k <= 0 || reps <= 0) return fail(c, ALGP_ERR_BAD_ARG, "bench_gemm: bad arguments");
     const bool was = c->prof_on;
     c->prof_on = false;
-    int rc = c->dtype == ALGP_F64 ? bench_gemm<double>(c, m, n, k, lower_only, beta_one, reps, ms)
-                                  : bench_gemm<float>(c, m, n, k, lower_only, beta_one, reps, ms);
+    int rc = c->dtype == ALGP_F64 ? bench_gemm<double>(c, m, n, k, lower_only, beta_one != 0, reps, ms)
+                                  : bench_gemm<float>(c, m, n, k, lower_only, beta_one != 0, reps, ms);
+    c->prof_on = was;
+    return rc;
+}
+
+int algp_bench_gemm_generated(algp_ctx* c, int64_t m, int64_t n, int64_t k, int reps, double* ms) {
+    CHECK_CTX(c);
+    if (!ms || m <= 0 || n <= 0 || k <= 0 || reps <= 0) return fail(c, ALGP_ERR_BAD_ARG, "bench_gemm_generated: bad arguments");
+    const bool was = c->prof_on;
+    c->prof_on = false;
+    int rc = c->dtype == ALGP_F64 ? bench_gemm<double>(c, m, n, k, 0, 1, reps, ms, true) : bench_gemm<float>(c, m, n, k, 0, 1, reps, ms, true);
     c->prof_on = was;
     return rc;
 }

@@ -33,7 +33,8 @@ int Impl<T>::set_candidates(algp_ctx* c, const int64_t* idx, int64_t M, int prio
 
 // The candidate solve's route (SolvePlan), decided once per call.  The only reader of the solve's switches, per plan (tests
 // flip them): $ALGP_TAIL_COLS=0 (the 128-column blocks, the full last tile), $ALGP_SOLVE_DAG=0 (the sweep for mid-sized
-// solves), $ALGP_ROW_STATS=0 (the sweep without its row statistics), $ALGP_FOLD=0 (fit_and_solve as its two phases).
+// solves), $ALGP_ROW_STATS=0 (the sweep without its row statistics), $ALGP_FOLD=0 (fit_and_solve as its two phases),
+// $ALGP_RHS_FUSED=0 (the scheduled sweep with B^T written to V^T first).
 template <typename T>
 void Impl<T>::plan_route(algp_ctx* c, int incremental, bool allow_fold, typename Impl<T>::SolvePlan& pl) {
     const bool tail_on = env_switch("ALGP_TAIL_COLS", true), solve_dag_on = env_switch("ALGP_SOLVE_DAG", true),
@@ -129,6 +130,21 @@ void Impl<T>::plan_route(algp_ctx* c, int incremental, bool allow_fold, typename
         pl.short_rows = pl.route == SolveRoute::Sweep ? Mpad : M < Mpad ? Mpad - NB : Mpad;
     }
     pl.row_stats = pl.route == SolveRoute::Sweep && stats_on && keep == 0 && !pl.carried_sums;
+    // Fused right-hand sides: where the sweep will run as scheduled launches with 512-block inverses (trsm_sched_wanted:
+    // trsm_blocked's own predicate; a buffer it then cannot get sends it back to the materialised form), B^T is not written and
+    // read back -- the update products generate their C tiles.  Two scaled coordinates per site only (rhs_gen_supported): wider
+    // coordinates and an explicit pool covariance keep the kernel-matrix launch.
+    pl.sweep_end = pl.narrow_r ? Npad - NB : Npad;
+    pl.rhs_fused = pl.route == SolveRoute::Sweep && keep == 0 && M > 0 && env_switch("ALGP_RHS_FUSED", true) &&
+                   trsm_sched_wanted(c, Mpad, pl.sweep_end, keep) && rhs_gen_supported(c->hyp.DP, c->pool_is_cov);
+}
+
+template <typename T>
+int Impl<T>::rhs_window(algp_ctx* c, int64_t c0, int64_t w, void* out, int64_t ldo) {
+    const int64_t live = std::max<int64_t>(0, std::min<int64_t>(c->N - c0, w));
+    KmatSrc s = make_src(c);
+    return kmat_launch<T>(c, s, (const int64_t*)c->Cidx.p, c->M, c->Mpad, (const int64_t*)c->Aidx.p + c0, live, w, nullptr, 0,
+                          c->prior_noise ? (const int*)c->ckind.p : nullptr, 0, (T*)out, ldo, 0, c0);
 }
 
 template <typename T>
@@ -178,6 +194,26 @@ int Impl<T>::solve_prepare(algp_ctx* c, int incremental, typename Impl<T>::Solve
         ALGP_TRY(sync(c));
     }
     KmatSrc s = make_src(c);
+    if (pl.rhs_fused) {
+        // B^T stays a generator: the coordinates of its rows and columns gathered once, and only the columns that no launch of
+        // the sweep writes -- a narrow last tile's (the tail kernel's) and the padding up to ldv -- go to V^T now
+        const int DP = c->hyp.DP;
+        ALGP_TRY(ensure(c, c->rhs_rx, sizeof(T) * (size_t)Mpad * DP));
+        ALGP_TRY(ensure(c, c->rhs_cx, sizeof(T) * (size_t)Npad * DP));
+        ALGP_TRY(ensure(c, c->rhs_rk, sizeof(int) * (size_t)Mpad));
+        ALGP_TRY(rhs_gather_launch<T>(c, (const T*)c->Xs.p, DP, (const int64_t*)c->Cidx.p, M, Mpad,
+                                      c->prior_noise ? (const int*)c->ckind.p : nullptr, (const int64_t*)c->Aidx.p, N, Npad,
+                                      p(c->rhs_rx), p(c->rhs_cx), (int*)c->rhs_rk.p));
+        pl.gen.rx = c->rhs_rx.p;
+        pl.gen.cx = c->rhs_cx.p;
+        pl.gen.rk = (const int*)c->rhs_rk.p;
+        pl.gen.ncols = N;
+        pl.gen.DP = DP;
+        pl.gen.kernel = s.kernel;
+        pl.gen.outputscale = s.outputscale;
+        pl.gen.window = &Impl<T>::rhs_window;
+        return rhs_window(c, pl.sweep_end, ldv - pl.sweep_end, p(c->Vt) + pl.sweep_end, ldc);
+    }
     // B^T: row j = C[cand_j, A] (ordinary) or e_pos (train-site candidate); zero padding.
     // Only columns >= keep are (re)generated and solved.
     return kmat_launch<T>(c, s, (const int64_t*)c->Cidx.p, M, Mpad, (const int64_t*)c->Aidx.p + keep, N - keep,
@@ -215,8 +251,8 @@ int Impl<T>::solve_run(algp_ctx* c, typename Impl<T>::SolvePlan& pl) {
         T* stat = nullptr;
         if (pl.row_stats && ensure(c, c->rowstat, sizeof(T) * 2 * (size_t)(Npad / NB) * (size_t)Mpad) == ALGP_OK)
             stat = p(c->rowstat);
-        trc = trsm_blocked<T>(c, ALGP_PROF_GEMM_TRSM, p(c->Vt), Mpad, ldc, p(c->L), pl.narrow_r ? Npad - NB : Npad, c->Lld, p(c->invD),
-                              keep, p(c->z), stat, Mpad, &pl.rowstat_done);
+        trc = trsm_blocked<T>(c, ALGP_PROF_GEMM_TRSM, p(c->Vt), Mpad, ldc, p(c->L), pl.sweep_end, c->Lld, p(c->invD),
+                              keep, p(c->z), stat, Mpad, &pl.rowstat_done, pl.rhs_fused ? &pl.gen : nullptr);
     } else {
         trc = fail(c, ALGP_ERR_STATE, "internal: the folded route is solved by the factorisation's launch (fit_and_solve)");
     }

@@ -89,7 +89,12 @@ struct Impl {
         int64_t short_rows = 0;              // short_rows rows without that tile, the tail kernel its columns (solve_narrow_tile)
         bool row_stats = false;              // Sweep: ask its launches for the rows' sums per column tile
         bool rowstat_done = false;           // solve_run's launches left the rows' sums per column tile in c->rowstat
+        bool rhs_fused = false;              // Sweep: B^T is not written to V^T; the scheduled sweep's update products generate it (gen)
+        int64_t sweep_end = 0;               // Sweep: the columns [0, sweep_end) are the sweep's, the rest the narrow tile's and padding
+        RhsGen gen;
     };
+    // columns [c0, c0 + w) of the candidates' B^T by the kernel-matrix build, to out (leading dimension ldo): RhsGen::window
+    static int rhs_window(algp_ctx* c, int64_t c0, int64_t w, void* out, int64_t ldo);
     // a sweep of more than this many tile rows runs left-looking in row chunks; only there does a narrow last tile go to
     // the tail kernel (and only there do the row statistics ride along).  Mirrors TRSM_PUSH_TILES in potrf.hip.
     static constexpr int64_t SWEEP_PUSH_TILES = 320;

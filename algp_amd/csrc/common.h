@@ -157,6 +157,48 @@ __device__ __forceinline__ double kexp(double x) {
     p = __builtin_fma(p, r, 1.0);
     return __builtin_ldexp(p, (int)k);
 }
+
+__device__ __forceinline__ float kfma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__device__ __forceinline__ double kfma(double a, double b, double c) { return __builtin_fma(a, b, c); }
+// ScaleKernel(RBF) / ScaleKernel(Matern-1.5) of a squared scaled distance
+template <typename T>
+__device__ __forceinline__ T kval(int kernel, T os, T r2) {
+    if (kernel == ALGP_KERNEL_RBF) return os * kexp((T)-0.5 * r2);
+    const T r = sqrt(r2) * (T)1.7320508075688772;
+    return os * ((T)1 + r) * kexp(-r);
+}
+// k(x, x') from the scaled, zero-padded coordinates of the two sites: ONE definition for the kernel-matrix build (kmat.hip)
+// and for the product epilogue that forms the candidates' right-hand sides in registers (gemm.hip, GEN), which must leave the
+// same bits.  Two coordinates (the form with two call sites): r^2 = fma(d0, d0, d1 * d1), the second square rounded on its own --
+// what the compiler has always made of `r2 = 0; r2 += d0 * d0; r2 += d1 * d1` in the matrix build, written out so that no call
+// site can be contracted differently.  Wider coordinates keep the plain sum (the matrix build is their only caller).
+template <typename T, int DP>
+__device__ __forceinline__ T kmat_value(int kernel, T os, const T (&xr)[DP], const T (&xc)[DP]) {
+    T r2;
+    if constexpr (DP == 2) {
+        const T d0 = xr[0] - xc[0], d1 = xr[1] - xc[1];
+        const T q1 = d1 * d1;
+        r2 = kfma(d0, d0, q1);
+    } else {
+        r2 = (T)0;
+#pragma unroll
+        for (int d = 0; d < DP; ++d) {
+            const T df = xr[d] - xc[d];
+            r2 += df * df;
+        }
+    }
+    return kval<T>(kernel, os, r2);
+}
+// Entry (row, global column gcol) of the candidates' right-hand side B^T = K(candidates, train) as the matrix build writes it:
+// kind -1: an ordinary row, k(x_row, x_col) in the columns of the train set (gcol < ncols), 0 in the padding behind them;
+// kind >= 0: the unit row e_kind (a candidate that is a train site under prior_includes_noise); kind -2: a padding row, 0.
+template <typename T, int DP>
+__device__ __forceinline__ T bt_entry(int kernel, T os, const T (&xr)[DP], const T (&xc)[DP], int kind, int64_t gcol, int64_t ncols) {
+    const T v = kmat_value<T, DP>(kernel, os, xr, xc);
+    const T ordinary = (kind == -1 && gcol < ncols) ? v : (T)0;
+    const T unit = gcol == (int64_t)kind ? (T)1 : (T)0;
+    return kind >= 0 ? unit : ordinary;
+}
 }  // namespace algp
 
 struct algp_ctx {
@@ -218,6 +260,7 @@ struct algp_ctx {
     algp::DevBuf tailE;                  // tail.hip: inverse of the 128 x 128 window of L at the first new column (a range that straddles two blocks)
     algp::DevBuf gemm_part;              // scheduled GEMM: partial sums of the k slices of a launch's leftover tiles (2 x CUs tiles)
     algp::DevBuf inv512, inv512_scr, trsm_tmp;   // candidate solve: explicit inverses of the factor's 512-column blocks, their scratch, mpad x 512
+    algp::DevBuf rhs_rx, rhs_cx, rhs_rk;         // fused right-hand sides (RhsGen): gathered coordinates of the candidate rows, of the train columns; row kinds
     std::vector<algp::DagCache> dag_cache;   // task lists of the dependency-driven Cholesky, per matrix size
     algp::DevBuf dag_state;              // its per-launch tile versions / control words / per-block log-determinants
     algp::DevBuf trsv_ctrl;              // ticket + per-block flags of the one-launch forward substitution (potrf.hip)
@@ -318,6 +361,8 @@ void prof_span_end2(algp_ctx* c);
 //   instead of the task list), ALGP_FOLD=0 (fit and solve as two steps: what a candidate set beyond 51 200 rows takes),
 //   ALGP_ROW_STATS=0 / ALGP_TRSM_INV512=0 (the chunked solve with a variance pass / with 128-column steps inside a block),
 //   ALGP_TRSM_SCHED=0 (the big solve as row chunks on three streams instead of scheduled launches on one; read per call),
+//   ALGP_RHS_FUSED=0 (the scheduled sweep reads the candidates' right-hand sides B^T from V^T, where a kernel-matrix launch has
+//   put them, instead of forming them in its update products' epilogues; read per call),
 //   ALGP_FACTOR_FROM_VT=0 (new rows of an updated factor solved, not gathered), ALGP_LAZY_GREEDY=0 (every row scored before
 //   every pick), ALGP_TRSM_CHUNKS=n (row-chunk streams of the big solve; bench.py's one-stream leg sets it by the ABI).
 // Cross-check routes: ALGP_CHOL_DAG=0 (launch-sequence factorisation), ALGP_GATHER_ROWS=0 (remote commits rebuild the row),
@@ -361,6 +406,32 @@ struct KmatSrc {
     double outputscale;
     double noise;        // sigma_n^2 added when pool indices coincide (coords mode only)
 };
+
+// The candidates' right-hand sides as a generator instead of a matrix (the scheduled sweep, potrf.hip: trsm_blocked): the update
+// product of a column block forms its C tile in registers from these (gemm.hip, GEN), so B^T is never written to V^T and read
+// back.  rx / cx: the scaled coordinates of the candidate rows and of the train columns, gathered once per solve (DP per entry,
+// zero behind the last row / column); rk: per row -1 (ordinary), the train row of a unit row, -2 (padding).  window(): what the
+// sweep cannot generate -- block 0's right-hand sides into its scratch, or all of them into V^T where the scheduled launches
+// are not taken after all: columns [c0, c0 + w) of B^T to out (leading dimension ldo), by the kernel-matrix build.
+struct RhsGen {
+    const void* rx = nullptr;
+    const void* cx = nullptr;
+    const int* rk = nullptr;
+    int64_t ncols = 0;   // N: the columns behind are zero
+    int DP = 0, kernel = 0;
+    double outputscale = 0;
+    int (*window)(algp_ctx* c, int64_t c0, int64_t w, void* out, int64_t ldo) = nullptr;
+};
+// rx[i] = Xs[ridx[i]] (i < rows), cx[j] = Xs[cidx[j]] (j < cols), zero up to rows_pad / cols_pad; rk from unit (or null) as above
+template <typename T>
+int rhs_gather_launch(algp_ctx* c, const T* Xs, int DP, const int64_t* ridx, int64_t rows, int64_t rows_pad, const int* unit,
+                      const int64_t* cidx, int64_t cols, int64_t cols_pad, T* rx, T* cx, int* rk);
+// the scheduled update product D = alpha A B^T + beta C with C generated: C[i][j] = B^T entry (i, col0 + j) of `gen` (gemm.hip)
+template <typename T>
+int gemm_nt_launch_gen(algp_ctx* c, int klass, int64_t m, int64_t n, int64_t k, T alpha, const T* A, int64_t lda, const T* B,
+                       int64_t ldb, T beta, const RhsGen& gen, int64_t col0, T* D, int64_t ldd);
+// whether gemm_nt_launch_gen has a kernel for this generator (DP = 2; wider coordinates take the materialised route)
+bool rhs_gen_supported(int DP, bool pool_is_cov);
 
 // out[r][c] for r<rows_pad, c<cols_pad (ld = ldo):
 //   r<rows && c<cols : value(ridx[r], cidx[c])  [+ diag terms when the pool indices coincide]
@@ -465,7 +536,11 @@ template <typename T>
 // stat_out[(2 tile + 0 / 1) * stat_ld + row]; *stats_done says whether that happened (else: take them in a pass over X)
 int trsm_blocked(algp_ctx* c, int klass, T* X, int64_t mpad, int64_t ldx, const T* L, int64_t npad,
                  int64_t ldl, const T* invD, int64_t col_start = 0, const T* stat_w = nullptr, T* stat_out = nullptr,
-                 int64_t stat_ld = 0, bool* stats_done = nullptr);
+                 int64_t stat_ld = 0, bool* stats_done = nullptr, const RhsGen* gen = nullptr);
+// whether trsm_blocked would run this solve as scheduled launches with 512-block inverses, buffers permitting (potrf.hip)
+bool trsm_sched_wanted(const algp_ctx* c, int64_t mpad, int64_t npad, int64_t col_start);
+// (gen: X does not hold the right-hand sides of columns [0, npad) yet.  The scheduled sweep generates them; where it is not
+// taken after all, gen->window writes them into X first)
 // columns [c0, c0 + w) of X <- the solution's new columns after rows c0.. were appended to L (tail.hip): c0 a multiple of 16,
 // w <= 64, inside one 128-column block whose explicit inverse is invD_blk; lrows = rows of L that exist
 template <typename T>
@@ -500,6 +575,6 @@ template <typename T>
 int test_mfma_launch(algp_ctx* c, int* mismatches_dev);
 template <typename T>
 int bench_gemm(algp_ctx* c, int64_t m, int64_t n, int64_t k, int lower_only, int beta_one, int reps,
-               double* ms_out);
+               double* ms_out, bool gen_c = false);
 
 }  // namespace algp

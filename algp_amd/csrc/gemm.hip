@@ -64,6 +64,25 @@ struct GemmArgs {
     T* part;
 };
 
+// GEN kernels only (the scheduled update products of the candidate sweep with fused right-hand sides, RhsGen in common.h): C is
+// not read -- entry (row, column) of the C tile is the B^T entry (row, col0 + column), formed in the epilogue by bt_entry from
+// the gathered coordinates rx / cx (DP per row / column) and the rows' kinds rk
+template <typename T, int DP_>
+struct GenGemmArgs : GemmArgs<T> {
+    static constexpr int DP = DP_;
+    const T* rx;
+    const T* cx;
+    const int* rk;
+    int64_t col0;                  // global column of V^T that column 0 of this launch's output is
+    int64_t ncols;                 // columns of the train set: the padding behind them is zero
+    int kernel;
+    T os;
+};
+template <typename A>
+struct gen_dp { static constexpr int value = 0; };
+template <typename T, int DP>
+struct gen_dp<GenGemmArgs<T, DP>> { static constexpr int value = DP; };
+
 typedef __attribute__((address_space(3))) void* lds_vp;
 typedef const __attribute__((address_space(1))) void* glb_vp;
 
@@ -289,11 +308,23 @@ __device__ __forceinline__ void pvr_epilogue(const PvrGemmArgs<T>& g, char* smem
 // unit's loop starts from a clean counter exactly like a fresh workgroup whose prologue has landed.  The STATS epilogue's
 // `red` scratch has 4 KB of its own behind the stages (68 KB per workgroup, two per CU).  Workgroups never wait for,
 // signal or poll each other: partial sums meet only in the finish kernel, a later launch on the same stream.
+//
+// Args = GenGemmArgs<T, DP> (SCHED only): the update product whose C tile is generated instead of loaded.  Per unit, thread t
+// holds one entry of the unit's 128 rows (t < 128: coordinates and kind) or 128 columns (coordinates) in registers, loaded
+// BEFORE the unit's first stage DMAs are issued (older than all of them: arrive()'s counts stay exact, and the k loop hides the
+// latency).  After the k loop they go to an LDS region of their own behind the stages (4.5 KB at DP = 2, fp64) -- before the next
+// unit's entries are loaded and its stages prefetched --, then lgkmcnt(0) + s_barrier (not __syncthreads(): no wait for the
+// prefetched stages), and the store loop forms alpha * acc + beta * bt_entry(...) with no C loads queued behind the prefetch.
+// The region's last readers (the previous unit's epilogue) have since passed the barriers of a whole k loop.  k-slice units
+// write alpha * acc to the partials scratch as before; gemm_finish_gen_kernel generates their C term.
 template <typename T, bool STATS = false, typename Args = GemmArgs<T>, bool SCHED = false>
 __global__ __launch_bounds__(256, 2) void gemm_nt_kernel_dma4(Args g) {
-    constexpr bool VR = !std::is_same<Args, GemmArgs<T>>::value;
+    constexpr int GDP = gen_dp<Args>::value;
+    constexpr bool GEN = GDP > 0;
+    constexpr bool VR = std::is_base_of<VrGemmArgs<T>, Args>::value;
     static_assert(!(VR && STATS), "one epilogue per kernel");
     static_assert(!(VR && SCHED), "the scheduled form serves the sweep's products only");
+    static_assert(!GEN || (SCHED && !STATS), "generated C tiles: the scheduled update product only");
     constexpr int NST = 4;
     using F = MF<T>;
     using acc_t = typename F::acc_t;
@@ -301,7 +332,8 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel_dma4(Args g) {
     constexpr int EPC = F::EPC;
     constexpr int BK = 4 * EPC;                                    // elements per 64-byte row piece
 
-    __shared__ __attribute__((aligned(1024))) char smem[NST * 16384 + (SCHED && STATS ? 4096 : 0)];
+    constexpr int GEN_LDS = GEN ? 2 * 128 * GDP * (int)sizeof(T) + 128 * (int)sizeof(int) : 0;
+    __shared__ __attribute__((aligned(1024))) char smem[NST * 16384 + (SCHED && STATS ? 4096 : 0) + GEN_LDS];
 
     const int nwg = gridDim.x;
     int bm, bn;
@@ -377,6 +409,24 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel_dma4(Args g) {
     const int boff = (wc * 64 + fr) * 64 + coff;
 
     acc_t acc[4][4];
+    // GEN: this thread's entry of the unit's rows (waves 0, 1) or columns (waves 2, 3), ahead of the unit's first stage DMAs
+    typedef T gen_vec_t __attribute__((ext_vector_type(GEN ? GDP : 1)));
+    gen_vec_t gx;
+    int gk = -1;
+    auto gen_load = [&](int ubm, int ubn) {
+        if constexpr (GEN) {
+            // (no branches: a k-slice unit loads its entries too, and the column waves a row kind, both unused -- loads under
+            // a condition made the compiler wait for them on the spot, in front of the stage prefetch)
+            int t = tid & 127;
+            asm volatile("" : "+v"(t));                            // (not hoisted out of the unit loop: see the epilogue)
+            const int64_t row = (int64_t)ubm * 128 + t;
+            const T* src = wave >= 2 ? g.cx + (g.col0 + (int64_t)ubn * 128 + t) * GDP : g.rx + row * GDP;
+            gx = *reinterpret_cast<const gen_vec_t*>(src);
+            gk = g.rk[row];
+            asm volatile("" ::: "memory");
+        }
+    };
+    gen_load(bm, bn);
     // prologue: tiles 0 .. NST-2 in flight
 #pragma unroll
     for (int t = 0; t < NST - 1; ++t)
@@ -426,6 +476,20 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel_dma4(Args g) {
     }
     const int64_t m0 = (int64_t)bm * 128, n0 = (int64_t)bn * 128;   // the unit whose accumulators are going out
     const int cur_bn = bn, cur_slice = slice;
+    if constexpr (GEN) {
+        // this unit's row and column entries into their LDS region (its last readers are a whole k loop behind), before the
+        // registers take the next unit's
+        if (cur_slice < 0) {
+            T* xr = reinterpret_cast<T*>(smem + NST * 16384);
+            T* xc = xr + 128 * GDP;
+            int* kr = reinterpret_cast<int*>(xc + 128 * GDP);
+            int t = tid & 127;
+            asm volatile("" : "+v"(t));
+            *reinterpret_cast<gen_vec_t*>((wave >= 2 ? xc : xr) + t * GDP) = gx;
+            if (wave < 2) kr[t] = gk;
+        }
+        asm volatile("" ::: "memory");
+    }
     if constexpr (SCHED) {
         // the next unit's first NST - 1 k-tiles, into the stages after the one read last (a unit has at least 128 / BK >= 8)
         if (++ui < nunits) {
@@ -434,6 +498,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel_dma4(Args g) {
             bn = u.tile - bm * g.tiles_n;
             nkt = (u.kb1 - u.kb0) * (128 / BK);
             slice = u.slice;
+            gen_load(bm, bn);
             Ag = g.A + ((int64_t)bm * 128 + 32 * wave + srow) * g.lda + schunk * EPC + (int64_t)u.kb0 * 128;
             Bg = g.B + ((int64_t)bn * 128 + 32 * wave + srow) * g.ldb + schunk * EPC + (int64_t)u.kb0 * 128;
 #pragma unroll
@@ -462,6 +527,51 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel_dma4(Args g) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) P[row * 128 + wc * 64 + j * 16 + fr] = alpha * acc[i][j][r];
             }
+    } else if constexpr (GEN) {
+        // the C tile from the staged coordinates: own LDS writes done, then meet (no wait for the prefetched stages)
+        const T* xr = reinterpret_cast<const T*>(smem + NST * 16384);
+        const T* xc = xr + 128 * GDP;
+        const int* kr = reinterpret_cast<const int*>(xc + 128 * GDP);
+        __builtin_amdgcn_s_waitcnt(0xC07F);                        // lgkmcnt(0)
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        // (the lane index through an opaque move: the per-lane row and column offsets below are the same in every unit, and
+        // hoisted out of the unit loop they would live across the k loop -- 268 bytes of scratch per lane)
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
+        const int gfr = ln & 15;
+        T xcol[4][GDP];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int d = 0; d < GDP; ++d) xcol[j][d] = xc[(wc * 64 + j * 16 + gfr) * GDP + d];
+        const int64_t gc = g.col0 + n0 + wc * 64 + gfr;            // global column of this lane's column j = 0; + 16 j
+        const T os = g.os;
+        const int64_t ncols = g.ncols;
+        // one copy of the loop per kernel form: the form is uniform, and as a run-time argument of kval both forms' arithmetic
+        // (a square root per value) would be done and selected
+        auto tile_out = [&](auto kform) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = wr * 64 + i * 16 + F::row_of(ln, r);
+                    T xrow[GDP];
+#pragma unroll
+                    for (int d = 0; d < GDP; ++d) xrow[d] = xr[row * GDP + d];
+                    const int kind = kr[row];
+                    T* Dr = Db + (m0 + row) * g.ldd + n0 + wc * 64 + gfr;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const T cv = bt_entry<T, GDP>(decltype(kform)::value, os, xrow, xcol[j], kind, gc + 16 * j, ncols);
+                        Dr[j * 16] = alpha * acc[i][j][r] + beta * cv;
+                        // two kernel values at a time: interleaved further, their exp polynomials cost registers the k loop needs
+                        if (j & 1) __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
+        };
+        if (g.kernel == ALGP_KERNEL_RBF) tile_out(std::integral_constant<int, ALGP_KERNEL_RBF>{});
+        else tile_out(std::integral_constant<int, ALGP_KERNEL_MATERN15>{});
     } else if (beta != (T)0) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -551,6 +661,27 @@ __global__ __launch_bounds__(256) void gemm_finish_kernel(const T* part, int S, 
     for (int e = threadIdx.x; e < 128 * 128; e += 256) {
         const int64_t row = (int64_t)bm * 128 + (e >> 7), col = (int64_t)bn * 128 + (e & 127);
         T v = beta * C[row * ldc + col];
+        for (int q = 0; q < S; ++q) v += P[(int64_t)q * (128 * 128) + e];
+        D[row * ldd + col] = v;
+    }
+}
+
+// The same with the C term generated (GenGemmArgs): the leftover tiles of a scheduled update product with fused right-hand sides
+template <typename T, int DP>
+__global__ __launch_bounds__(256) void gemm_finish_gen_kernel(const T* part, int S, int tile0, int tiles_n, T beta, const T* rx, const T* cx,
+                                                              const int* rk, int64_t col0, int64_t ncols, int kernel, T os, T* D, int64_t ldd) {
+    const int tile = tile0 + blockIdx.x, bm = tile / tiles_n, bn = tile - bm * tiles_n;
+    const T* P = part + (int64_t)blockIdx.x * S * (128 * 128);
+    const int64_t col = (int64_t)bn * 128 + (threadIdx.x & 127);   // e & 127 is the same in every round of the loop below
+    T xcol[DP];
+#pragma unroll
+    for (int d = 0; d < DP; ++d) xcol[d] = cx[(col0 + col) * DP + d];
+    for (int e = threadIdx.x; e < 128 * 128; e += 256) {
+        const int64_t row = (int64_t)bm * 128 + (e >> 7);
+        T xrow[DP];
+#pragma unroll
+        for (int d = 0; d < DP; ++d) xrow[d] = rx[row * DP + d];
+        T v = beta * bt_entry<T, DP>(kernel, os, xrow, xcol, rk[row], col0 + col, ncols);
         for (int q = 0; q < S; ++q) v += P[(int64_t)q * (128 * 128) + e];
         D[row * ldd + col] = v;
     }
@@ -659,6 +790,62 @@ int gemm_nt_launch_batched(algp_ctx* c, int klass, int64_t m, int64_t n, int64_t
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
+
+bool rhs_gen_supported(int DP, bool pool_is_cov) { return DP == 2 && !pool_is_cov; }
+
+// The scheduled update product with its C tile generated (GEN above): booked like the loading form -- the same flop; the C
+// tile's bytes are not read.
+template <typename T>
+int gemm_nt_launch_gen(algp_ctx* c, int klass, int64_t m, int64_t n, int64_t k, T alpha, const T* A, int64_t lda, const T* B,
+                       int64_t ldb, T beta, const RhsGen& gen, int64_t col0, T* D, int64_t ldd) {
+    if (m <= 0 || n <= 0) return ALGP_OK;
+    if (!c->gemm_sched || c->cu_count <= 0 || !rhs_gen_supported(gen.DP, false) || !gen.rx || !gen.cx || !gen.rk)
+        return fail(c, ALGP_ERR_BAD_ARG, "gemm_nt_gen: the scheduled form with two gathered coordinates only");
+    if (m % 128 || n % 128 || k % 128 || k <= 0 || lda % 4 || ldb % 4 || col0 < 0)
+        return fail(c, ALGP_ERR_BAD_ARG, "gemm_nt_gen: operands must be padded to multiples of 128");
+    GenGemmArgs<T, 2> g;
+    g.A = A; g.B = B; g.C = nullptr; g.D = D;
+    g.lda = lda; g.ldb = ldb; g.ldc = 0; g.ldd = ldd;
+    g.sA = g.sB = g.sC = g.sD = 0;
+    g.tiles_m = (int)(m / 128);
+    g.tiles_n = (int)(n / 128);
+    g.ktiles = (int)(k / (8 * MF<T>::EPC));
+    g.alpha = alpha; g.beta = beta;
+    g.lower_only = 0; g.ktri = 0; g.kcut = 0;
+    g.stat_w = nullptr; g.stat_out = nullptr; g.stat_ld = 0;
+    g.rx = (const T*)gen.rx; g.cx = (const T*)gen.cx; g.rk = gen.rk;
+    g.col0 = col0; g.ncols = gen.ncols; g.kernel = gen.kernel; g.os = (T)gen.outputscale;
+    const int64_t tiles = (int64_t)g.tiles_m * g.tiles_n;
+    if (tiles > 0x7fffffff) return fail(c, ALGP_ERR_BAD_ARG, "gemm_nt_gen: grid too large");
+    const double flops = 2.0 * 128.0 * 128.0 * (double)k * (double)tiles;
+    const double bytes = sizeof(T) * ((double)tiles * 128.0 * 128.0 + (double)k * 128.0 * (double)(g.tiles_m + g.tiles_n));
+    launch_log_line(klass, m, n, k, 0, 1, 0, (int)sizeof(T), 0);
+    const int slots = 2 * c->cu_count;
+    const bool split = beta != (T)0 && c->gemm_part.p && c->gemm_part.cap >= sizeof(T) * 128 * 128 * (size_t)slots;   // as the loading form
+    g.sch = sched_make(slots, g.tiles_m, g.tiles_n, (int)(k / 128), 0, split ? 1 : 0);
+    g.part = (T*)c->gemm_part.p;
+    hipEvent_t ev_a, ev_b;
+    const dim3 sgrid((unsigned)g.sch.G);
+    const bool timed = prof_launch_events(c, klass, flops, bytes, &ev_a, &ev_b);
+    if (timed) hipExtLaunchKernelGGL((gemm_nt_kernel_dma4<T, false, GenGemmArgs<T, 2>, true>), sgrid, dim3(256), 0, c->cur, ev_a, ev_b, 0, g);
+    else hipLaunchKernelGGL((gemm_nt_kernel_dma4<T, false, GenGemmArgs<T, 2>, true>), sgrid, dim3(256), 0, c->cur, g);
+    ALGP_HIP(hipGetLastError());
+    if (g.sch.S >= 2) {
+        const double fbytes = sizeof(T) * 128.0 * 128.0 * (double)g.sch.left * (g.sch.S + 1.0);
+        const bool ftimed = prof_launch_events(c, klass, 0.0, fbytes, &ev_a, &ev_b);
+        const dim3 fgrid((unsigned)g.sch.left);
+        if (ftimed) hipExtLaunchKernelGGL((gemm_finish_gen_kernel<T, 2>), fgrid, dim3(256), 0, c->cur, ev_a, ev_b, 0, (const T*)g.part, g.sch.S,
+                                          g.sch.full, g.tiles_n, beta, g.rx, g.cx, g.rk, col0, g.ncols, g.kernel, g.os, D, ldd);
+        else hipLaunchKernelGGL((gemm_finish_gen_kernel<T, 2>), fgrid, dim3(256), 0, c->cur, (const T*)g.part, g.sch.S, g.sch.full, g.tiles_n,
+                                beta, g.rx, g.cx, g.rk, col0, g.ncols, g.kernel, g.os, D, ldd);
+        ALGP_HIP(hipGetLastError());
+    }
+    return ALGP_OK;
+}
+template int gemm_nt_launch_gen<double>(algp_ctx*, int, int64_t, int64_t, int64_t, double, const double*, int64_t, const double*, int64_t,
+                                        double, const RhsGen&, int64_t, double*, int64_t);
+template int gemm_nt_launch_gen<float>(algp_ctx*, int, int64_t, int64_t, int64_t, float, const float*, int64_t, const float*, int64_t, float,
+                                       const RhsGen&, int64_t, float*, int64_t);
 
 // The variance-reduction column sums of rows [0, mpad) of V^T against its rows [ncol0, ncol0 + n): per row and column
 // tile bn of the launch, part[bn * part_ld + row] = sum over the tile's target columns j of (kappa_row C(row, j) - V_row . V_j)^2,
@@ -834,7 +1021,7 @@ __global__ void fill_random_kernel(T* p, int64_t n, unsigned seed) {
 
 template <typename T>
 int bench_gemm(algp_ctx* c, int64_t m, int64_t n, int64_t k, int lower_only, int beta_one, int reps,
-               double* ms_out) {
+               double* ms_out, bool gen_c) {
     DevBuf a, b, cc;
     int rc = ensure(c, a, sizeof(T) * m * k);
     if (rc == ALGP_OK) rc = ensure(c, b, sizeof(T) * n * k);
@@ -847,17 +1034,34 @@ int bench_gemm(algp_ctx* c, int64_t m, int64_t n, int64_t k, int lower_only, int
     hipEventCreate(&e0);
     hipEventCreate(&e1);
     const T beta = beta_one ? (T)1 : (T)0;
+    // gen_c: beta = 1 with the C tile GENERATED from (synthetic) coordinates, as the sweep's update products with fused
+    // right-hand sides form it (gemm_nt_launch_gen; the scheduled form only) -- timed against beta_one, the C tile loaded
+    DevBuf grx, gcx, grk;
+    RhsGen gen;
+    if (gen_c) {
+        rc = ensure(c, grx, sizeof(T) * m * 2);
+        if (rc == ALGP_OK) rc = ensure(c, gcx, sizeof(T) * n * 2);
+        if (rc == ALGP_OK) rc = ensure(c, grk, sizeof(int) * m);
+        if (rc == ALGP_OK) {
+            hipLaunchKernelGGL(fill_random_kernel<T>, dim3((unsigned)((m * 2 + 255) / 256)), dim3(256), 0, c->cur, (T*)grx.p, m * 2, 4u);
+            hipLaunchKernelGGL(fill_random_kernel<T>, dim3((unsigned)((n * 2 + 255) / 256)), dim3(256), 0, c->cur, (T*)gcx.p, n * 2, 5u);
+            hipMemsetAsync(grk.p, 0xff, sizeof(int) * m, c->cur);         // every row ordinary (-1)
+            gen.rx = grx.p; gen.cx = gcx.p; gen.rk = (const int*)grk.p;
+            gen.ncols = n; gen.DP = 2; gen.kernel = ALGP_KERNEL_RBF; gen.outputscale = 1.0;
+        }
+    }
+    auto one = [&]() {
+        if (gen_c) return gemm_nt_launch_gen<T>(c, ALGP_PROF_GEMM_OTHER, m, n, k, (T)-1, (const T*)a.p, k, (const T*)b.p, k, beta, gen, 0, (T*)cc.p, n);
+        return gemm_nt_launch<T>(c, ALGP_PROF_GEMM_OTHER, m, n, k, (T)-1, (const T*)a.p, k, (const T*)b.p, k, beta, (const T*)cc.p, n,
+                                 (T*)cc.p, n, lower_only);
+    };
     // $ALGP_TRSM_SCHED (read per call, default on): the scheduled launcher the candidate sweep uses, with its partials scratch
     const bool sched = !lower_only && c->cu_count > 0 && env_switch("ALGP_TRSM_SCHED", true) &&
                        ensure(c, c->gemm_part, sizeof(T) * 128 * 128 * 2 * (size_t)c->cu_count) == ALGP_OK;
     c->gemm_sched = sched;
-    for (int w = 0; w < 2 && rc == ALGP_OK; ++w)
-        rc = gemm_nt_launch<T>(c, ALGP_PROF_GEMM_OTHER, m, n, k, (T)-1, (const T*)a.p, k, (const T*)b.p, k, beta,
-                               (const T*)cc.p, n, (T*)cc.p, n, lower_only);
+    for (int w = 0; w < 2 && rc == ALGP_OK; ++w) rc = one();
     hipEventRecord(e0, c->cur);
-    for (int r = 0; r < reps && rc == ALGP_OK; ++r)
-        rc = gemm_nt_launch<T>(c, ALGP_PROF_GEMM_OTHER, m, n, k, (T)-1, (const T*)a.p, k, (const T*)b.p, k, beta,
-                               (const T*)cc.p, n, (T*)cc.p, n, lower_only);
+    for (int r = 0; r < reps && rc == ALGP_OK; ++r) rc = one();
     hipEventRecord(e1, c->cur);
     c->gemm_sched = false;
     hipEventSynchronize(e1);
@@ -866,11 +1070,11 @@ int bench_gemm(algp_ctx* c, int64_t m, int64_t n, int64_t k, int lower_only, int
     *ms_out = ms / (reps > 0 ? reps : 1);
     hipEventDestroy(e0);
     hipEventDestroy(e1);
-    hipFree(a.p); hipFree(b.p); hipFree(cc.p);
-    c->dev_bytes -= (int64_t)(a.cap + b.cap + cc.cap);
+    hipFree(a.p); hipFree(b.p); hipFree(cc.p); hipFree(grx.p); hipFree(gcx.p); hipFree(grk.p);
+    c->dev_bytes -= (int64_t)(a.cap + b.cap + cc.cap + grx.cap + gcx.cap + grk.cap);
     return rc;
 }
-template int bench_gemm<double>(algp_ctx*, int64_t, int64_t, int64_t, int, int, int, double*);
-template int bench_gemm<float>(algp_ctx*, int64_t, int64_t, int64_t, int, int, int, double*);
+template int bench_gemm<double>(algp_ctx*, int64_t, int64_t, int64_t, int, int, int, double*, bool);
+template int bench_gemm<float>(algp_ctx*, int64_t, int64_t, int64_t, int, int, int, double*, bool);
 
 }  // namespace algp

@@ -53,12 +53,7 @@ struct KmatArgs {
     int64_t ldo;
 };
 
-template <typename T>
-__device__ __forceinline__ T kval(int kernel, T os, T r2) {
-    if (kernel == ALGP_KERNEL_RBF) return os * kexp((T)-0.5 * r2);
-    const T r = sqrt(r2) * (T)1.7320508075688772;
-    return os * ((T)1 + r) * kexp(-r);
-}
+// (the kernel value itself: kval / kmat_value in common.h, shared with the product epilogue that generates B^T, gemm.hip)
 
 // EQ: entries whose row and column address the same pool site receive a diagonal term (the symmetric builds); without it
 // (the candidates' B^T, cross matrices) the index comparisons are not even compiled in -- they and the other per-element
@@ -133,13 +128,7 @@ __global__ __launch_bounds__(256) void kmat_kernel(KmatArgs<T> a) {
                 for (int d = 0; d < DP; ++d) xr[d] = s_x[rr][d];
 #pragma unroll
                 for (int v = 0; v < VEC; ++v) {
-                    T r2 = (T)0;
-#pragma unroll
-                    for (int d = 0; d < DP; ++d) {
-                        const T df = xr[d] - xc[v][d];
-                        r2 += df * df;
-                    }
-                    const T val = kval<T>(a.kernel, a.outputscale, r2);
+                    const T val = kmat_value<T, DP>(a.kernel, a.outputscale, xr, xc[v]);
                     o[v] = live[v] ? val : (T)0;
                 }
             }
@@ -260,6 +249,41 @@ template int kmat_xy_launch<double>(algp_ctx*, const double*, int64_t, const dou
                                     double, double*, int64_t);
 template int kmat_xy_launch<float>(algp_ctx*, const float*, int64_t, const float*, int64_t, int, const float*, double,
                                    float*, int64_t);
+
+// The candidates' right-hand sides as a generator (RhsGen, common.h): the coordinates of the candidate rows and of the train
+// columns gathered into two contiguous arrays, once per solve, so that the product epilogue that forms B^T entries has no
+// index -> coordinate dependent loads; and the rows' kinds (-1 ordinary, >= 0 a unit row's column, -2 padding).
+template <typename T>
+__global__ void rhs_gather_kernel(const T* Xs, int DP, const int64_t* ridx, int64_t rows, int64_t rows_pad, const int* unit,
+                                  const int64_t* cidx, int64_t cols, int64_t cols_pad, T* rx, T* cx, int* rk) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < rows_pad) {
+        const bool live = i < rows;
+        const int u = live ? (unit ? unit[i] : -1) : -2;
+        rk[i] = u < -1 ? -2 : u;
+        const int64_t p = live ? ridx[i] : 0;
+        for (int d = 0; d < DP; ++d) rx[i * DP + d] = (live && u < 0) ? Xs[p * DP + d] : (T)0;
+    } else if (i - rows_pad < cols_pad) {
+        const int64_t j = i - rows_pad;
+        const bool live = j < cols;
+        const int64_t p = live ? cidx[j] : 0;
+        for (int d = 0; d < DP; ++d) cx[j * DP + d] = live ? Xs[p * DP + d] : (T)0;
+    }
+}
+template <typename T>
+int rhs_gather_launch(algp_ctx* c, const T* Xs, int DP, const int64_t* ridx, int64_t rows, int64_t rows_pad, const int* unit,
+                      const int64_t* cidx, int64_t cols, int64_t cols_pad, T* rx, T* cx, int* rk) {
+    const int64_t tot = rows_pad + cols_pad;
+    if (tot <= 0) return ALGP_OK;
+    hipLaunchKernelGGL(rhs_gather_kernel<T>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->cur, Xs, DP, ridx, rows, rows_pad, unit,
+                       cidx, cols, cols_pad, rx, cx, rk);
+    ALGP_HIP(hipGetLastError());
+    return ALGP_OK;
+}
+template int rhs_gather_launch<double>(algp_ctx*, const double*, int, const int64_t*, int64_t, int64_t, const int*, const int64_t*,
+                                       int64_t, int64_t, double*, double*, int*);
+template int rhs_gather_launch<float>(algp_ctx*, const float*, int, const int64_t*, int64_t, int64_t, const int*, const int64_t*, int64_t,
+                                      int64_t, float*, float*, int*);
 
 // xs[i][d] = x[i][d] / lengthscale_d for d < D, 0 for D <= d < DP
 struct InvLs {

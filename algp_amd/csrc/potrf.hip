@@ -227,7 +227,11 @@ static size_t inv512_scratch_elems(int64_t npad) {
 template <typename T>
 static int trsm_rows_blocked(algp_ctx* c, int klass, T* X, int64_t mpad, int64_t ldx, const T* L, int64_t npad,
                      int64_t ldl, const T* invD, int64_t col_start, bool whole_solve, const T* stat_w = nullptr,
-                     T* stat_out = nullptr, int64_t stat_ld = 0, const T* inv512 = nullptr, T* tmp512 = nullptr) {
+                     T* stat_out = nullptr, int64_t stat_ld = 0, const T* inv512 = nullptr, T* tmp512 = nullptr,
+                     const RhsGen* gen = nullptr) {
+    // gen (the scheduled sweep only: left-looking order, col_start == 0, inv512 / tmp512 given): X does not hold the right-hand
+    // sides; every update product generates its C tile (gemm_nt_launch_gen) -- the ragged last block's too, which then leaves
+    // D = X for the 128-column steps inside it.
     // inv512 / tmp512 (left-looking order, col_start == 0): the explicit inverses of the full 512-column blocks
     // (build_inv512) and mpad x 512 scratch, holding X_0 on entry: block J is then two launches -- T = X_J - X_{0:J} L_{J,0:J}^T
     // into the scratch, X_J = T inv(L_JJ)^T -- instead of eight.
@@ -319,12 +323,16 @@ static int trsm_rows_blocked(algp_ctx* c, int klass, T* X, int64_t mpad, int64_t
         T* Xj = X + j0;
         if (inv512 && tmp512 && w == TWB && col_start == 0) {
             // (block 0 has nothing to its left: the caller has copied its right-hand sides into the scratch)
-            if (j0 > 0) ALGP_TRY(gemm_nt_launch<T>(c, klass, mpad, TWB, j0, (T)-1, X, ldx, L + j0 * ldl, ldl, (T)1, Xj, ldx, tmp512, TWB, 0));
+            if (j0 > 0 && gen) ALGP_TRY(gemm_nt_launch_gen<T>(c, klass, mpad, TWB, j0, (T)-1, X, ldx, L + j0 * ldl, ldl, (T)1, *gen, j0, tmp512, TWB));
+            else if (j0 > 0) ALGP_TRY(gemm_nt_launch<T>(c, klass, mpad, TWB, j0, (T)-1, X, ldx, L + j0 * ldl, ldl, (T)1, Xj, ldx, tmp512, TWB, 0));
             ALGP_TRY(gemm_nt_launch_tri<T>(c, klass, mpad, TWB, tmp512, TWB, inv512 + (j0 / TWB) * TWB * TWB, TWB, Xj, ldx,
                                            stat_w ? stat_w + j0 : nullptr, stat_out ? stat_out + 2 * (j0 / NB) * stat_ld : nullptr, stat_ld));
             continue;
         }
-        if (j0 > 0)
+        if (gen && (j0 == 0 || cs != j0)) return fail(c, ALGP_ERR_STATE, "internal: generated right-hand sides outside the scheduled sweep");
+        if (j0 > 0 && gen)
+            ALGP_TRY(gemm_nt_launch_gen<T>(c, klass, mpad, w, j0, (T)-1, X, ldx, L + j0 * ldl, ldl, (T)1, *gen, j0, Xj, ldx));
+        else if (j0 > 0)
             ALGP_TRY(gemm_nt_launch<T>(c, klass, mpad, j0 + w - cs, j0, (T)-1, X, ldx, L + cs * ldl, ldl, (T)1, X + cs,
                                        ldx, X + cs, ldx, 0));
         for (int64_t k0 = cs; k0 < j0 + w; k0 += NB) {
@@ -435,9 +443,10 @@ template int trinv_upper<float>(algp_ctx*, int, float*, int64_t, int64_t, const 
 template <typename T>
 static int trsm_rows(algp_ctx* c, int klass, T* X, int64_t mpad, int64_t ldx, const T* L, int64_t npad,
                      int64_t ldl, const T* invD, int64_t col_start, bool whole_solve, const T* stat_w = nullptr,
-                     T* stat_out = nullptr, int64_t stat_ld = 0, const T* inv512 = nullptr, T* tmp512 = nullptr) {
+                     T* stat_out = nullptr, int64_t stat_ld = 0, const T* inv512 = nullptr, T* tmp512 = nullptr,
+                     const RhsGen* gen = nullptr) {
     return trsm_rows_blocked<T>(c, klass, X, mpad, ldx, L, npad, ldl, invD, col_start, whole_solve, stat_w, stat_out, stat_ld, inv512,
-                                tmp512);
+                                tmp512, gen);
 }
 
 static hipEvent_t sync_event(algp_ctx* c, size_t i) {
@@ -453,9 +462,19 @@ static hipEvent_t sync_event(algp_ctx* c, size_t i) {
 // default, algp_debug_set_trsm_chunks / $ALGP_TRSM_CHUNKS): the tail of every big GEMM of one chunk (1044 workgroups
 // over 512 resident slots: the last round is 4 % full) and its short HBM-bound in-block launches run beside the other
 // chunks' MFMA-bound GEMMs -- 84 % of the fp64 matrix peak against 78.5 % with the launches back to back on one stream.
+// What trsm_blocked asks before it takes the 512-block inverses, and the scheduled launches on top of them -- everything but
+// the buffers, which it can only try to get.  The candidate solve's plan asks the same function (fused right-hand sides).
+static bool trsm_inv512_wanted(const algp_ctx* c, int64_t mpad, int64_t npad, int64_t col_start) {
+    return env_switch("ALGP_TRSM_INV512", true) && col_start == 0 && mpad / NB > TRSM_PUSH_TILES && npad / WB >= 1 && c->cur == c->stream;
+}
+bool trsm_sched_wanted(const algp_ctx* c, int64_t mpad, int64_t npad, int64_t col_start) {
+    return trsm_inv512_wanted(c, mpad, npad, col_start) && !c->trsm_chunks_explicit && c->cu_count > 0 && env_switch("ALGP_TRSM_SCHED", true);
+}
+
 template <typename T>
 int trsm_blocked(algp_ctx* c, int klass, T* X, int64_t mpad, int64_t ldx, const T* L, int64_t npad,
-                 int64_t ldl, const T* invD, int64_t col_start, const T* stat_w, T* stat_out, int64_t stat_ld, bool* stats_done) {
+                 int64_t ldl, const T* invD, int64_t col_start, const T* stat_w, T* stat_out, int64_t stat_ld, bool* stats_done,
+                 const RhsGen* gen) {
     const int64_t tiles = mpad / NB;
     // row statistics ride along where every row goes through the left-looking order from its first column
     const bool stats = stat_out && stat_w && col_start == 0 && tiles > TRSM_PUSH_TILES;
@@ -466,17 +485,13 @@ int trsm_blocked(algp_ctx* c, int klass, T* X, int64_t mpad, int64_t ldx, const 
     const T* inv512 = nullptr;
     T* tmp512 = nullptr;
     {
-        const bool on = env_switch("ALGP_TRSM_INV512", true);                                      // read per call: tests flip it
-        if (on && col_start == 0 && tiles > TRSM_PUSH_TILES && npad / WB >= 1 && c->cur == c->stream &&
+        if (trsm_inv512_wanted(c, mpad, npad, col_start) &&                                         // (switches read per call: tests flip them)
             ensure(c, c->inv512, sizeof(T) * (size_t)(npad / WB) * WB * WB) == ALGP_OK &&
             ensure(c, c->inv512_scr, sizeof(T) * inv512_scratch_elems<T>(npad)) == ALGP_OK &&
             ensure(c, c->trsm_tmp, sizeof(T) * (size_t)mpad * WB) == ALGP_OK) {
             ALGP_TRY(build_inv512<T>(c, klass, L, ldl, invD, npad, (T*)c->inv512.p, (T*)c->inv512_scr.p));
             inv512 = (const T*)c->inv512.p;
             tmp512 = (T*)c->trsm_tmp.p;
-            // block 0's right-hand sides into the scratch: its product with inv(L_00)^T cannot run in place (a workgroup
-            // of column tile c reads the tiles left of it in the same rows)
-            ALGP_HIP(hipMemcpy2DAsync(tmp512, sizeof(T) * WB, X, sizeof(T) * ldx, sizeof(T) * WB, (size_t)mpad, hipMemcpyDeviceToDevice, c->cur));
         }
     }
     // The scheduled sweep (default): the same launches, one after the other on the caller's stream, each as a grid of 2 x CUs
@@ -484,10 +499,24 @@ int trsm_blocked(algp_ctx* c, int klass, T* X, int64_t mpad, int64_t ldx, const 
     // k-tiles under the current tile's epilogue.  An explicit chunk count ($ALGP_TRSM_CHUNKS, algp_debug_set_trsm_chunks) or
     // $ALGP_TRSM_SCHED=0 (read per call: tests flip it) keeps the row chunks below.  The partials scratch of the cut leftover
     // tiles is provided here: nothing is allocated inside the sweep.
-    if (inv512 && !c->trsm_chunks_explicit && c->cu_count > 0 && env_switch("ALGP_TRSM_SCHED", true) &&
-        ensure(c, c->gemm_part, sizeof(T) * 128 * 128 * 2 * (size_t)c->cu_count) == ALGP_OK) {
+    const bool sched = inv512 && trsm_sched_wanted(c, mpad, npad, col_start) &&
+                       ensure(c, c->gemm_part, sizeof(T) * 128 * 128 * 2 * (size_t)c->cu_count) == ALGP_OK;
+    // Right-hand sides that were to be generated (gen): the scheduled sweep takes them as they are; every other order reads
+    // them from X, so they are written there first, all of them, and the solve proceeds as it always has.
+    if (gen && !sched) {
+        ALGP_TRY(gen->window(c, 0, npad, X, ldx));
+        gen = nullptr;
+    }
+    if (inv512) {
+        // block 0's right-hand sides into the scratch: its product with inv(L_00)^T cannot run in place (a workgroup of column
+        // tile c reads the tiles left of it in the same rows).  Generated: a 512-column window of the kernel-matrix build writes
+        // them there; else a strided copy out of X.
+        if (gen) ALGP_TRY(gen->window(c, 0, WB, tmp512, WB));
+        else ALGP_HIP(hipMemcpy2DAsync(tmp512, sizeof(T) * WB, X, sizeof(T) * ldx, sizeof(T) * WB, (size_t)mpad, hipMemcpyDeviceToDevice, c->cur));
+    }
+    if (sched) {
         c->gemm_sched = true;
-        const int rc = trsm_rows<T>(c, klass, X, mpad, ldx, L, npad, ldl, invD, col_start, true, stat_w, stat_out, stat_ld, inv512, tmp512);
+        const int rc = trsm_rows<T>(c, klass, X, mpad, ldx, L, npad, ldl, invD, col_start, true, stat_w, stat_out, stat_ld, inv512, tmp512, gen);
         c->gemm_sched = false;
         return rc;
     }
@@ -518,9 +547,9 @@ int trsm_blocked(algp_ctx* c, int klass, T* X, int64_t mpad, int64_t ldx, const 
     return rc;
 }
 template int trsm_blocked<double>(algp_ctx*, int, double*, int64_t, int64_t, const double*, int64_t, int64_t,
-                                  const double*, int64_t, const double*, double*, int64_t, bool*);
+                                  const double*, int64_t, const double*, double*, int64_t, bool*, const RhsGen*);
 template int trsm_blocked<float>(algp_ctx*, int, float*, int64_t, int64_t, const float*, int64_t, int64_t,
-                                 const float*, int64_t, const float*, float*, int64_t, bool*);
+                                 const float*, int64_t, const float*, float*, int64_t, bool*, const RhsGen*);
 
 // ---------------------------------------------------------------------------------------------
 // C -= X X^T for a short, very wide X (the R <= 512 new rows of a factor update against N kept columns).

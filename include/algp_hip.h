@@ -445,6 +445,10 @@ int algp_selftest_mfma(algp_ctx* ctx, int* mismatches);
  * of D = C - A B^T (beta_one) or D = -A B^T, m x n x k, lower tiles only or all.                      */
 int algp_bench_gemm(algp_ctx* ctx, int64_t m, int64_t n, int64_t k, int lower_only, int beta_one, int reps,
                     double* ms_per_launch);
+/* the same for D = C - A B^T with C not loaded but generated in the epilogue from synthetic coordinates,
+ * as the candidate sweep's update products form the right-hand sides (the scheduled launcher only: an
+ * error where it is switched off).                                                                    */
+int algp_bench_gemm_generated(algp_ctx* ctx, int64_t m, int64_t n, int64_t k, int reps, double* ms_per_launch);
 
 /* ---- resident-buffer access for benchmarks / multi-GPU plumbing --------------------------- */
 int algp_sync(algp_ctx* ctx);
