@@ -88,6 +88,8 @@ SIGNATURES = {
     'algp_score_paths': (C.c_int, [_c_ctx, _i64p, C.c_int, C.c_int, C.c_double, _dblp]),
     'algp_score_paths_mi': (C.c_int, [_c_ctx, _i64p, C.c_int, C.c_int, C.c_double, C.c_double, _dblp, _dblp]),
     'algp_score_paths_vr': (C.c_int, [_c_ctx, _i64p, C.c_int, C.c_int, C.c_double, C.c_int64, _dblp]),
+    'algp_set_target_weights': (C.c_int, [_c_ctx, _dblp, C.c_int64]),
+    'algp_get_target_variance': (C.c_int, [_c_ctx, _dblp]),
     'algp_comm_unique_id': (C.c_int, [C.c_void_p]),
     'algp_comm_init': (C.c_int, [_c_ctx, C.c_int, C.c_int, C.c_void_p]),
     'algp_comm_init_host': (C.c_int, [_c_ctx, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
@@ -451,6 +453,20 @@ class Context(object):
             self._check(self.lib.algp_score_paths_vr(self.h, _i64(sites.ravel()), sites.shape[0], sites.shape[1], float(mobile_std),
                                                      int(max_union), out.ctypes.data_as(_dblp)))
         return out
+
+    def set_target_weights(self, w):
+        """Weight of every pool site as a target of the variance-reduction criterion (len(w) = pool size, finite, >= 0), or
+        None to detach them (algp_set_target_weights).  A new pool drops them."""
+        if w is None:
+            self._check(self.lib.algp_set_target_weights(self.h, None, 0))
+            return
+        w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+        self._check(self.lib.algp_set_target_weights(self.h, w.ctypes.data_as(_dblp), len(w)))
+
+    def target_variance(self):
+        """sum over the targets of weight x posterior variance under the current state, picks included
+        (algp_get_target_variance)."""
+        return self._get_double(self.lib.algp_get_target_variance)
 
     # -- multi-GPU: the collective behind the ABI (RCCL) ---------------------------------------
     @staticmethod

@@ -222,7 +222,57 @@ class Agent(object):
         if self.comm is not None and getattr(self, '_comm_pool', None) != (id(c), c.pool_generation):
             self.comm.attach(c, self.env.num_samples)                # transport + owner map follow the pool
             self._comm_pool = (id(c), c.pool_generation)
+        # the target weights follow the pool too: the library drops them with it (algp_set_target_weights)
+        tw_key = (id(c), c.pool_generation, getattr(self, '_tw_version', 0))
+        if tw_key != getattr(self, '_tw_key', None):
+            w = getattr(self, '_target_weights', None)
+            if w is not None or getattr(self, '_tw_key', None) is not None:
+                c.set_target_weights(w)
+            self._tw_key = tw_key
         return c
+
+    def set_target_weights(self, w):
+        """Weight of every pool site as a target of the variance-reduction criterion: env.num_samples values, finite and
+        >= 0, or None for every site once (algp_set_target_weights).  They are kept on the agent and follow every pool
+        reload.  Agent.greedy / run_greedy_ipp under criterion='variance_reduction' then pick by the weighted utility;
+        path_variance_reduction and strategy='MaxVarRed' use them under any criterion."""
+        if self.comm is not None:
+            raise NotImplementedError("criterion 'variance_reduction' is not sharded: its targets are the whole candidate set, "
+                                      "which no rank of a sharded agent holds; run it on one GPU")
+        if w is not None:
+            w = np.array(w, dtype=np.float64).reshape(-1)
+            if len(w) != self.env.num_samples:
+                raise ValueError('set_target_weights: expected %d values, got %d' % (self.env.num_samples, len(w)))
+            if not (np.all(np.isfinite(w)) and np.all(w >= 0)):
+                raise ValueError('set_target_weights: every weight must be finite and >= 0')
+        self._target_weights = w
+        self._tw_version = getattr(self, '_tw_version', 0) + 1
+
+    def target_variance(self):
+        """The variance-reduction objective for the agent's current train set: the weighted sum of the posterior variances of
+        every unsampled site (algp_get_target_variance), the state set up as path_variance_reduction does."""
+        if self.comm is not None:
+            raise NotImplementedError("criterion 'variance_reduction' is not sharded: its targets are the whole candidate set, "
+                                      "which no rank of a sharded agent holds; run it on one GPU")
+        return self._vr_state(())[0].target_variance()
+
+    def _vr_state(self, static_indices):
+        """(context, static, mobile): the train set in the agent's current form with `static_indices` static-sampled too,
+        every site a candidate (the targets: every unsampled site), the static sites switched off."""
+        c = self._load_pool()
+        static, mobile0 = self._masks()
+        static = static.copy()
+        static[np.asarray(static_indices, dtype=np.int64).reshape(-1)] = True
+        if self._use_rows():
+            A, is_static = self._train_rows(static, mobile0)
+            c.set_train(A, np.zeros(len(A)), self._rows_noise(is_static))
+        else:
+            A = self._train_order(static | mobile0)
+            c.set_train(A, np.zeros(len(A)), self._fused_var(static[A], mobile0[A]))
+        c.factorize(incremental=True)
+        c.set_candidates(np.arange(self.env.num_samples), prior_includes_noise=True)
+        c.solve_candidates(incremental=True, alive=~static)
+        return c, static, mobile0
 
     # ---- planning steps ---------------------------------------------------------------------------
     def _setup_ipp(self, criterion, update=False):
@@ -430,29 +480,18 @@ class Agent(object):
 
     def path_variance_reduction(self, paths_mobile_indices, static_indices):
         """Variance-reduction utility of every path: how much its mobile readings lower the summed posterior variance of every
-        site that stays unsampled (algp_score_paths_vr).  The sites a path changes are those best_path counts -- distinct, on
-        the field, not mobile-sampled already; the train set is in the agent's current form (a row per reading, else one fused
-        row per site).  One factor update, one candidate solve over every site, one scoring call for all paths."""
+        site that stays unsampled, each weighted by set_target_weights (algp_score_paths_vr).  The sites a path changes are
+        those best_path counts -- distinct, on the field, not mobile-sampled already; the train set is in the agent's current
+        form (a row per reading, else one fused row per site).  One factor update, one candidate solve over every site, one
+        scoring call for all paths."""
         if self.comm is not None:
             raise NotImplementedError("the variance-reduction path utility is not sharded: its targets are the whole candidate "
                                       "set, which no rank of a sharded agent holds; run it on one GPU")
-        c = self._load_pool()
-        n = self.env.num_samples
-        static, mobile0 = self._masks()
-        static = static.copy()
-        static[static_indices] = True
+        mobile0 = self._masks()[1]
         clean = [[j for j in dict.fromkeys(int(v) for v in path) if j != -1 and not mobile0[j]] for path in paths_mobile_indices]
         if max((len(p) for p in clean), default=0) > 256:
             raise ValueError('path_variance_reduction: a path changes more than 256 sites, the limit of algp_score_paths_vr')
-        if self._use_rows():
-            A, is_static = self._train_rows(static, mobile0)
-            c.set_train(A, np.zeros(len(A)), self._rows_noise(is_static))
-        else:
-            A = self._train_order(static | mobile0)
-            c.set_train(A, np.zeros(len(A)), self._fused_var(static[A], mobile0[A]))
-        c.factorize(incremental=True)
-        c.set_candidates(np.arange(n), prior_includes_noise=True)     # the targets: every unsampled site
-        c.solve_candidates(incremental=True, alive=~static)
+        c = self._vr_state(static_indices)[0]
         sites = np.full((len(clean), max(1, max((len(p) for p in clean), default=0))), -1, dtype=np.int64)
         for k, pth in enumerate(clean):
             sites[k, :len(pth)] = pth

@@ -140,6 +140,8 @@ struct Impl {
     static int vr_product(algp_ctx* c);
     static int vr_fold(algp_ctx* c, int64_t q);
     static int vr_scores_enqueue(algp_ctx* c, double ss, double delta, double* dst);
+    static int set_target_weights(algp_ctx* c, const double* w);
+    static int target_variance(algp_ctx* c, double* sum);
     static int scores_enqueue(algp_ctx* c, int criterion, double static_std, double mobile_std, double* dst);
     static int scores(algp_ctx* c, int criterion, double static_std, double mobile_std, void* out, int out_is_device);
     static int argmax(algp_ctx* c, int64_t* local_pos, int64_t* pool_idx, double* value);

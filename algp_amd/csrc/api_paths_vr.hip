@@ -4,7 +4,9 @@
 //   Gamma_ss' = C(s, s') - R_s . R_s'      the posterior covariance of the sites (R_s: the site's row of V^T; a site that is train
 //                                          row l already: L[l, :] - var_l * its unit row, as in score_paths)
 //   E_sj      = C(s, j) - R_s . V_j        their cross covariance with the targets
-//   Phi       = E E^T                      summed over the targets.
+//   Phi       = E Omega E^T                summed over the targets, Omega = diag of the pool's target weights (algp_set_target_weights;
+//                                          the identity where none are attached): the E tile carries sqrt(omega_j) E_sj
+// (with weights the first sum is over omega_j var(j | .) as well).
 // Gamma and Phi depend on the sites, not on the path, and the paths of one planning step share most of their sites: both are
 // built once over the union U of a group of consecutive paths, then every path gathers its two k x k blocks.
 //   rows   R_U = the union's rows of V^T (gather_rows_launch, zero rows behind U up to a multiple of 128)
@@ -169,7 +171,8 @@ int Impl<T>::score_paths_vr(algp_ctx* c, const int64_t* sites, int npaths, int m
         for (int64_t n0 = 0; n0 < Mpad; n0 += chunk) {
             const int64_t nc = std::min(chunk, Mpad - n0);
             ALGP_TRY(gemm_nt_launch_pvr<T>(c, ALGP_PROF_GEMM_OTHER, Upad, nc, Npad, R, Npad, p(c->Vt), c->ldv, n0, s, d_uidx, U,
-                                           (const int64_t*)c->Cidx.p, (const int*)c->ckind.p, M, Es, chunk));
+                                           (const int64_t*)c->Cidx.p, (const int*)c->ckind.p, M, c->has_tw ? (const T*)c->tw.p : nullptr,
+                                           Es, chunk));
             ALGP_TRY(gemm_nt_launch<T>(c, ALGP_PROF_GEMM_OTHER, Upad, Upad, nc, (T)1, Es, chunk, Es, chunk, n0 > 0 ? (T)1 : (T)0, Phi, Upad,
                                        Phi, Upad, 1));
         }

@@ -111,16 +111,18 @@ struct MiState {
 };
 
 // The variance-reduction criterion's state (api_vr.hip): w_c = sum over the targets j (the ordinary rows of the candidate
-// set, fixed by the solve) of E_jc^2, E the signed cross term of include/algp_hip.h, for the first npicks committed picks.
+// set, fixed by the solve) of omega_j E_jc^2, E the signed cross term of include/algp_hip.h and omega the target weights of
+// the pool (algp_ctx::tw; 1 where none are attached), for the first npicks committed picks.
 // Built by one fused product per candidate solve (gemm.hip, gemm_nt_kernel_dma4_vr); later picks are folded in by the rank-1
 // identity, one pass over V^T each.  It does not depend on the noise levels (ss, sm): they enter when the utilities are formed.
 struct VrState {
     DevBuf W;                            // w, one entry per candidate row
     DevBuf Part;                         // the product's sums per column tile, for one chunk of column tiles
-    DevBuf R;                            // a pick's column of V^T: [all rows | targets only, zero elsewhere]
-    DevBuf Tp, Tv;                       // t = V_T^T r_T: its partial sums per row block, and t
-    DevBuf Y;                            // [sum_j C(c, j) r_j | V_c . t]
-    DevBuf Nrm;                          // |r_T|^2
+    DevBuf R;                            // a pick's column of V^T: [all rows | omega_j r_j on the targets, zero elsewhere]
+    DevBuf Tp, Tv;                       // t = V_T^T (omega r)_T: its partial sums per row block, and t
+    DevBuf Y;                            // [sum_j C(c, j) omega_j r_j | V_c . t]
+    DevBuf Nrm;                          // sum_{j in T} omega_j r_j^2
+    DevBuf Obj;                          // one double: the objective sum_{j in T} omega_j pv_j (algp_get_target_variance)
     bool valid = false;
     int64_t npicks = 0;                  // picks folded in
 
@@ -225,6 +227,8 @@ struct algp_ctx {
     algp::DevBuf Xs;        // n x DP scaled, zero padded coordinates
     algp::DevBuf Xraw;      // n x D raw coordinates (kept to rescale on a hyper change)
     algp::DevBuf Cp;        // n x n explicit covariance (pool_is_cov)
+    algp::DevBuf tw;        // target weight of every pool site in the context's dtype (algp_set_target_weights), while has_tw
+    bool has_tw = false;    // the weights belong to their pool: a new pool drops them
     std::vector<int64_t> pos_in_train;   // host: pool index -> position in train set or -1
     std::vector<uint64_t> site_hash;     // host: fingerprint of every pool site's coordinates (algp_factorize_from)
 
@@ -477,13 +481,13 @@ int gemm_nt_launch_stats(algp_ctx* c, int klass, int64_t m, int64_t k, T alpha, 
 // part[bn * part_ld + row]; no matrix is written (gemm.hip)
 template <typename T>
 int gemm_nt_launch_vr(algp_ctx* c, int klass, int64_t mpad, int64_t n, int64_t k, const T* Vt, int64_t ldv, int64_t ncol0,
-                      const KmatSrc& s, const int64_t* cidx, const int* ckind, int64_t M, T* part, int64_t part_ld);
+                      const KmatSrc& s, const int64_t* cidx, const int* ckind, int64_t M, const T* tw, T* part, int64_t part_ld);
 // variance reduction of whole paths: E[u][j] = C(uidx[u], cidx[ncol0 + j]) - R_u . V_(ncol0 + j) on the target columns, 0 on the
 // others and on the rows behind U; the E tile is written (upad x n, leading dimension lde), nothing else (gemm.hip)
 template <typename T>
 int gemm_nt_launch_pvr(algp_ctx* c, int klass, int64_t upad, int64_t n, int64_t k, const T* R, int64_t ldr, const T* Vt, int64_t ldv,
                        int64_t ncol0, const KmatSrc& s, const int64_t* uidx, int64_t U, const int64_t* cidx, const int* ckind, int64_t M,
-                       T* E, int64_t lde);
+                       const T* tw, T* E, int64_t lde);
 // C (m x m, lower tiles) -= X X^T for a short, very wide X (m <= 512 rows, k columns): the k range is cut into
 // chunks that run as one batched launch, the partial products are summed in chunk order (deterministic)
 template <typename T>

@@ -114,6 +114,8 @@ __device__ __forceinline__ T row16_sum(T x) {
 // unit row; C from the scaled coordinates of the tile's 128 rows and 128 columns staged in LDS, with the one kernel-value
 // definition kexp, or read from an explicit pool covariance), drops the columns that are not targets (unit rows, padding),
 // squares, and sums over the tile's 128 columns per row exactly as the STATS epilogue does: stat_out[bn * stat_ld + row].
+// With target weights attached (Args = VrWGemmArgs, an instantiation of its own, so that the unweighted one keeps the
+// instructions and the bits it had) every column counts omega_j times (tw, per pool site).
 // Neither a D tile nor a kernel-matrix block is written.  Fixed order: the same bits in every run.
 // ---------------------------------------------------------------------------------------------
 template <typename T>
@@ -127,7 +129,13 @@ struct VrGemmArgs : GemmArgs<T> {
     int64_t n_pool;
     int DP, kernel;
     T os, noise;
+    const T* tw;                   // target weight of every pool site (n_pool entries): VrWGemmArgs; PvrGemmArgs, or null there.
+                                   // LAST: ahead of Xs it moved the fields behind it by 8 bytes in the kernel arguments, and the
+                                   // unweighted product, the same instructions otherwise, took 2 % longer
 };
+
+template <typename T>
+struct VrWGemmArgs : VrGemmArgs<T> {};   // the same launch with tw attached: the weighted epilogue
 
 // C(prow, pcol) for the two epilogues below: read from the explicit pool covariance, or formed from the scaled coordinates
 // of the row (in registers) and of the column (staged in LDS) with the one kernel-value definition kexp, sigma_n^2 added
@@ -151,13 +159,15 @@ __device__ __forceinline__ T vr_pool_cov(const VrGemmArgs<T>& g, int64_t prow, i
     return cv;
 }
 
-template <typename T, typename ACC>
+template <typename T, bool WEIGHTED, typename ACC>
 __device__ __forceinline__ void vr_epilogue(const VrGemmArgs<T>& g, char* smem, const ACC (&acc)[4][4], int64_t m0, int64_t n0, int bn,
                                             int wr, int wc, int lane, int tid) {
     using F = MF<T>;
     const int fr = lane & 15;
     // LDS: [2 column halves][128 rows] sums | coordinates of the rows, of the columns ([128][MAXD], zero padded) | pool
-    // indices of the rows, of the columns | kappa of the rows | target mask of the columns
+    // indices of the rows, of the columns | kappa of the rows | target mask of the columns (int), or WEIGHTED their target
+    // weight (T; 0: not a target).  2 KB + 16 KB + 2 KB + 512 B + at most 128 doubles <= 21.5 KB of the main loop's 64 KB of
+    // stages; the weights start 8-byte aligned.
     T* red = reinterpret_cast<T*>(smem);
     T* xr = reinterpret_cast<T*>(smem + 2048);
     T* xc = reinterpret_cast<T*>(smem + 2048 + 8192);
@@ -165,6 +175,7 @@ __device__ __forceinline__ void vr_epilogue(const VrGemmArgs<T>& g, char* smem, 
     int64_t* pc = pr + 128;
     int* kr = reinterpret_cast<int*>(pc + 128);
     int* mc = kr + 128;
+    T* wcol = reinterpret_cast<T*>(kr + 128);
     __syncthreads();                                               // every wave is done with the last stage
     {
         const int t = tid & 127;
@@ -174,7 +185,12 @@ __device__ __forceinline__ void vr_epilogue(const VrGemmArgs<T>& g, char* smem, 
         const int64_t p = valid ? g.cidx[gi] : 0;
         const int ordinary = (valid && g.ckind[gi] < 0) ? 1 : 0;
         (is_col ? pc : pr)[t] = p;
-        (is_col ? mc : kr)[t] = ordinary;
+        if constexpr (WEIGHTED) {
+            if (is_col) wcol[t] = ordinary ? g.tw[p] : (T)0;
+            else kr[t] = ordinary;
+        } else {
+            (is_col ? mc : kr)[t] = ordinary;
+        }
         if (!g.Cp) {
             T* x = (is_col ? xc : xr) + t * MAXD;
 #pragma unroll
@@ -193,14 +209,34 @@ __device__ __forceinline__ void vr_epilogue(const VrGemmArgs<T>& g, char* smem, 
 #pragma unroll
             for (int d = 0; d < MAXD; ++d) xrow[d] = xr[row * MAXD + d];
             T s2 = (T)0;
+            if constexpr (WEIGHTED) {
+                T es[4], we[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int col = wc * 64 + j * 16 + fr;
-                const int64_t pcol = pc[col];
-                const T cv = vr_pool_cov<T>(g, prow, pcol, xrow, xc + col * MAXD);
-                T e = kap * cv - acc[i][j][r];
-                e = mc[col] ? e : (T)0;
-                s2 += e * e;
+                for (int j = 0; j < 4; ++j) {
+                    const int col = wc * 64 + j * 16 + fr;
+                    const int64_t pcol = pc[col];
+                    const T cv = vr_pool_cov<T>(g, prow, pcol, xrow, xc + col * MAXD);
+                    const T wgt = wcol[col];
+                    const T e = kap * cv - acc[i][j][r];
+                    es[j] = wgt != (T)0 ? e : (T)0;
+                    we[j] = wgt * es[j];
+                }
+                // sum_j (omega_j e_j) e_j, written out: the second square rounded on its own, the first added to it by one fma,
+                // then one fma per column -- what the compiler makes of the unweighted `s2 += e * e` below, so that all-ones
+                // weights leave the unweighted bits (omega e is then e itself; omega (e e) would round every square first)
+                s2 = kfma(we[0], es[0], we[1] * es[1]);
+                s2 = kfma(we[2], es[2], s2);
+                s2 = kfma(we[3], es[3], s2);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int col = wc * 64 + j * 16 + fr;
+                    const int64_t pcol = pc[col];
+                    const T cv = vr_pool_cov<T>(g, prow, pcol, xrow, xc + col * MAXD);
+                    T e = kap * cv - acc[i][j][r];
+                    e = mc[col] ? e : (T)0;
+                    s2 += e * e;
+                }
             }
             s2 = row16_sum<T>(s2);
             if (fr == 0) red[wc * 128 + row] = s2;
@@ -214,8 +250,9 @@ __device__ __forceinline__ void vr_epilogue(const VrGemmArgs<T>& g, char* smem, 
 // with a train row already: its second-row form), B = rows [ncol0, ncol0 + n) of V^T.  The accumulators hold R_u . V_j; the
 // epilogue forms the cross covariance E_uj = C(u, j) - R_u . V_j in registers -- the kernel term as in vr_epilogue, but always
 // present on the row side and with the row's pool index from uidx -- zeroes the columns that are not targets (unit rows,
-// padding) and the padding rows behind U, and WRITES the tile: E[row][n0 + col], the launch's columns only (Phi = E E^T is
-// the caller's next product).  No kernel-matrix block is written.
+// padding) and the padding rows behind U, scales column j by sqrt(omega_j) (tw as above: Phi = E Omega E^T), and WRITES the
+// tile: E[row][n0 + col], the launch's columns only (Phi = E E^T is the caller's next product).  No kernel-matrix block is
+// written.
 // ---------------------------------------------------------------------------------------------
 template <typename T>
 struct PvrGemmArgs : VrGemmArgs<T> {
@@ -231,13 +268,14 @@ __device__ __forceinline__ void pvr_epilogue(const PvrGemmArgs<T>& g, char* smem
     using F = MF<T>;
     const int fr = lane & 15;
     // LDS: coordinates of the rows, of the columns ([128][MAXD], zero padded) | pool indices of the rows, of the columns |
-    // which rows are union sites | target mask of the columns
+    // which rows are union sites | sqrt of the target weight of the columns (0: not a target): 16 KB + 2 KB + 512 B + 128 T
+    // <= 19.5 KB of the main loop's 64 KB of stages; the weights start 8-byte aligned.
     T* xr = reinterpret_cast<T*>(smem);
     T* xc = reinterpret_cast<T*>(smem + 8192);
     int64_t* pr = reinterpret_cast<int64_t*>(smem + 16384);
     int64_t* pc = pr + 128;
     int* kr = reinterpret_cast<int*>(pc + 128);
-    int* mc = kr + 128;
+    T* wcol = reinterpret_cast<T*>(kr + 128);
     __syncthreads();                                               // every wave is done with the last stage
     {
         const int t = tid & 127;
@@ -246,7 +284,8 @@ __device__ __forceinline__ void pvr_epilogue(const PvrGemmArgs<T>& g, char* smem
         const bool valid = is_col ? gi < g.M : gi < g.U;
         const int64_t p = valid ? (is_col ? g.cidx[gi] : g.uidx[gi]) : 0;
         (is_col ? pc : pr)[t] = p;
-        (is_col ? mc : kr)[t] = is_col ? ((valid && g.ckind[gi] < 0) ? 1 : 0) : (valid ? 1 : 0);
+        if (is_col) wcol[t] = (valid && g.ckind[gi] < 0) ? (g.tw ? sqrt(g.tw[p]) : (T)1) : (T)0;
+        else kr[t] = valid ? 1 : 0;
         if (!g.Cp) {
             T* x = (is_col ? xc : xr) + t * MAXD;
 #pragma unroll
@@ -270,7 +309,8 @@ __device__ __forceinline__ void pvr_epilogue(const PvrGemmArgs<T>& g, char* smem
                 const int col = wc * 64 + j * 16 + fr;
                 const int64_t pcol = pc[col];
                 const T cv = vr_pool_cov<T>(g, prow, pcol, xrow, xc + col * MAXD);
-                Er[col] = (rowon && mc[col]) ? cv - acc[i][j][r] : (T)0;
+                const T sw = wcol[col];
+                Er[col] = (rowon && sw != (T)0) ? sw * (cv - acc[i][j][r]) : (T)0;
             }
         }
 }
@@ -294,7 +334,7 @@ __device__ __forceinline__ void pvr_epilogue(const PvrGemmArgs<T>& g, char* smem
 #ifndef ALGP_GEMM_XOR_MASK
 #define ALGP_GEMM_XOR_MASK 2
 #endif
-// Args = VrGemmArgs<T>: the variance-reduction epilogue above instead of a D tile (STATS is then false); Args =
+// Args = VrGemmArgs<T> / VrWGemmArgs<T>: the variance-reduction epilogue above instead of a D tile (STATS is then false); Args =
 // PvrGemmArgs<T>: the path form's epilogue, which writes the E tile.
 //
 // SCHED: the scheduled sibling for the candidate sweep's products.  A grid of G = min(tiles, 2 x CUs) workgroups, each
@@ -510,7 +550,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel_dma4(Args g) {
         pvr_epilogue<T>(g, smem, acc, m0, n0, wr, wc, lane, tid);
         return;
     } else if constexpr (VR) {
-        vr_epilogue<T>(g, smem, acc, m0, n0, cur_bn, wr, wc, lane, tid);
+        vr_epilogue<T, std::is_same<Args, VrWGemmArgs<T>>::value>(g, smem, acc, m0, n0, cur_bn, wr, wc, lane, tid);
         return;
     }
     const T alpha = g.alpha, beta = g.beta;
@@ -849,10 +889,11 @@ template int gemm_nt_launch_gen<float>(algp_ctx*, int, int64_t, int64_t, int64_t
 
 // The variance-reduction column sums of rows [0, mpad) of V^T against its rows [ncol0, ncol0 + n): per row and column
 // tile bn of the launch, part[bn * part_ld + row] = sum over the tile's target columns j of (kappa_row C(row, j) - V_row . V_j)^2,
-// the dot products over the first k columns.  Nothing else is written.
+// the dot products over the first k columns, every column weighted by tw[its pool site] where tw is given.  Nothing else is
+// written.
 template <typename T>
 int gemm_nt_launch_vr(algp_ctx* c, int klass, int64_t mpad, int64_t n, int64_t k, const T* Vt, int64_t ldv, int64_t ncol0,
-                      const KmatSrc& s, const int64_t* cidx, const int* ckind, int64_t M, T* part, int64_t part_ld) {
+                      const KmatSrc& s, const int64_t* cidx, const int* ckind, int64_t M, const T* tw, T* part, int64_t part_ld) {
     if (mpad <= 0 || n <= 0) return ALGP_OK;
     if (mpad % 128 || n % 128 || k % 128 || k <= 0 || ldv % 4 || ncol0 % 128 || ncol0 + n > mpad || k > ldv || s.DP > MAXD)
         return fail(c, ALGP_ERR_BAD_ARG, "gemm_nt_vr: operands must be padded to multiples of 128");
@@ -867,7 +908,7 @@ int gemm_nt_launch_vr(algp_ctx* c, int klass, int64_t mpad, int64_t n, int64_t k
     g.lower_only = 0; g.ktri = 0; g.kcut = 0;
     g.stat_w = nullptr; g.stat_out = part; g.stat_ld = part_ld;
     g.sch = Sched(); g.part = nullptr;
-    g.cidx = cidx; g.ckind = ckind; g.M = M; g.ncol0 = ncol0;
+    g.cidx = cidx; g.ckind = ckind; g.M = M; g.ncol0 = ncol0; g.tw = tw;
     g.Xs = (const T*)s.Xs; g.Cp = (const T*)s.Cp; g.n_pool = s.n_pool; g.DP = s.DP; g.kernel = s.kernel;
     g.os = (T)s.outputscale; g.noise = (T)s.noise;
     const int64_t tiles = (int64_t)g.tiles_m * g.tiles_n;
@@ -878,23 +919,30 @@ int gemm_nt_launch_vr(algp_ctx* c, int klass, int64_t mpad, int64_t n, int64_t k
     hipEvent_t ev_a, ev_b;
     const bool timed = prof_launch_events(c, klass, flops, bytes, &ev_a, &ev_b);
     const dim3 grid((unsigned)tiles);
-    if (timed) hipExtLaunchKernelGGL((gemm_nt_kernel_dma4<T, false, VrGemmArgs<T>>), grid, dim3(256), 0, c->cur, ev_a, ev_b, 0, g);
-    else hipLaunchKernelGGL((gemm_nt_kernel_dma4<T, false, VrGemmArgs<T>>), grid, dim3(256), 0, c->cur, g);
+    if (!tw) {
+        if (timed) hipExtLaunchKernelGGL((gemm_nt_kernel_dma4<T, false, VrGemmArgs<T>>), grid, dim3(256), 0, c->cur, ev_a, ev_b, 0, g);
+        else hipLaunchKernelGGL((gemm_nt_kernel_dma4<T, false, VrGemmArgs<T>>), grid, dim3(256), 0, c->cur, g);
+    } else {
+        VrWGemmArgs<T> gw;
+        static_cast<VrGemmArgs<T>&>(gw) = g;
+        if (timed) hipExtLaunchKernelGGL((gemm_nt_kernel_dma4<T, false, VrWGemmArgs<T>>), grid, dim3(256), 0, c->cur, ev_a, ev_b, 0, gw);
+        else hipLaunchKernelGGL((gemm_nt_kernel_dma4<T, false, VrWGemmArgs<T>>), grid, dim3(256), 0, c->cur, gw);
+    }
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
 template int gemm_nt_launch_vr<double>(algp_ctx*, int, int64_t, int64_t, int64_t, const double*, int64_t, int64_t, const KmatSrc&,
-                                       const int64_t*, const int*, int64_t, double*, int64_t);
+                                       const int64_t*, const int*, int64_t, const double*, double*, int64_t);
 template int gemm_nt_launch_vr<float>(algp_ctx*, int, int64_t, int64_t, int64_t, const float*, int64_t, int64_t, const KmatSrc&,
-                                      const int64_t*, const int*, int64_t, float*, int64_t);
+                                      const int64_t*, const int*, int64_t, const float*, float*, int64_t);
 
 // The cross covariances of the union rows R (upad x k, the rows behind U zero) with rows [ncol0, ncol0 + n) of V^T:
 // E[u][j] = C(uidx[u], cidx[ncol0 + j]) - R_u . V_(ncol0 + j) where column ncol0 + j is a target, 0 elsewhere and on the
-// padding rows; E is upad x n with leading dimension lde.
+// padding rows, times sqrt(tw[pool site of the column]) where tw is given; E is upad x n with leading dimension lde.
 template <typename T>
 int gemm_nt_launch_pvr(algp_ctx* c, int klass, int64_t upad, int64_t n, int64_t k, const T* R, int64_t ldr, const T* Vt, int64_t ldv,
                        int64_t ncol0, const KmatSrc& s, const int64_t* uidx, int64_t U, const int64_t* cidx, const int* ckind, int64_t M,
-                       T* E, int64_t lde) {
+                       const T* tw, T* E, int64_t lde) {
     if (upad <= 0 || n <= 0) return ALGP_OK;
     if (upad % 128 || n % 128 || k % 128 || k <= 0 || ldr % 4 || ldv % 4 || ncol0 % 128 || ncol0 + n > (M + 127) / 128 * 128 || k > ldv || k > ldr || U > upad || lde < n ||
         s.DP > MAXD)
@@ -910,7 +958,7 @@ int gemm_nt_launch_pvr(algp_ctx* c, int klass, int64_t upad, int64_t n, int64_t 
     g.lower_only = 0; g.ktri = 0; g.kcut = 0;
     g.stat_w = nullptr; g.stat_out = nullptr; g.stat_ld = 0;
     g.sch = Sched(); g.part = nullptr;
-    g.cidx = cidx; g.ckind = ckind; g.M = M; g.ncol0 = ncol0;
+    g.cidx = cidx; g.ckind = ckind; g.M = M; g.ncol0 = ncol0; g.tw = tw;
     g.Xs = (const T*)s.Xs; g.Cp = (const T*)s.Cp; g.n_pool = s.n_pool; g.DP = s.DP; g.kernel = s.kernel;
     g.os = (T)s.outputscale; g.noise = (T)s.noise;
     g.uidx = uidx; g.U = U; g.E = E; g.lde = lde;
@@ -928,9 +976,11 @@ int gemm_nt_launch_pvr(algp_ctx* c, int klass, int64_t upad, int64_t n, int64_t 
     return ALGP_OK;
 }
 template int gemm_nt_launch_pvr<double>(algp_ctx*, int, int64_t, int64_t, int64_t, const double*, int64_t, const double*, int64_t, int64_t,
-                                        const KmatSrc&, const int64_t*, int64_t, const int64_t*, const int*, int64_t, double*, int64_t);
+                                        const KmatSrc&, const int64_t*, int64_t, const int64_t*, const int*, int64_t, const double*, double*,
+                                        int64_t);
 template int gemm_nt_launch_pvr<float>(algp_ctx*, int, int64_t, int64_t, int64_t, const float*, int64_t, const float*, int64_t, int64_t,
-                                       const KmatSrc&, const int64_t*, int64_t, const int64_t*, const int*, int64_t, float*, int64_t);
+                                       const KmatSrc&, const int64_t*, int64_t, const int64_t*, const int*, int64_t, const float*, float*,
+                                       int64_t);
 
 template <typename T>
 int gemm_nt_launch(algp_ctx* c, int klass, int64_t m, int64_t n, int64_t k, T alpha, const T* A,

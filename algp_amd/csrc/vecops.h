@@ -10,8 +10,9 @@ template <typename T>
 int score_launch(algp_ctx* c, int64_t M, const int* ckind, const unsigned char* alive, const T* dstat, double ss,
                  double delta, const double* extra, double* out);
 // variance-reduction criterion (vecops.hip): the product's partial sums per column tile added in tile order; the utilities from
-// w; and one pick's rank-1 fold w_c <- w_c - 2 r_c y_c + r_c^2 |r_T|^2 (col: the pick's column of V^T; r, rt, y1, y2: one entry
-// per row; tp: VR_TBLOCKS x ldv; t: ldv; nrm: one entry)
+// w; and one pick's rank-1 fold w_c <- w_c - 2 r_c y_c + r_c^2 sum_T omega_j r_j^2 (col: the pick's column of V^T; r, rt, y1, y2:
+// one entry per row; tp: VR_TBLOCKS x ldv; t: ldv; nrm: one entry; tw: the target weight of every pool site, or null); and the
+// weighted sum of the target rows' variances, sum_{j in T} omega_j dstat_j, into *out (device)
 constexpr int VR_TBLOCKS = 128;
 template <typename T>
 int vr_combine_launch(algp_ctx* c, const T* part, int64_t ld, int ntiles, int64_t rows, int accumulate, T* w);
@@ -20,7 +21,10 @@ int vr_score_launch(algp_ctx* c, int64_t M, const int* ckind, const unsigned cha
                     double delta, double* out);
 template <typename T>
 int vr_fold_launch(algp_ctx* c, int64_t M, const int* ckind, const int64_t* cidx, const T* Vt, int64_t ldv, int64_t col, const T* Xs,
-                   const T* Cp, int64_t n_pool, int DP, int kernel, T os, T noise, T* r, T* rt, T* nrm, T* tp, T* t, T* y1, T* y2, T* w);
+                   const T* Cp, int64_t n_pool, int DP, int kernel, T os, T noise, const T* tw, T* r, T* rt, T* nrm, T* tp, T* t, T* y1,
+                   T* y2, T* w);
+template <typename T>
+int vr_target_sum_launch(algp_ctx* c, int64_t M, const int* ckind, const int64_t* cidx, const T* dstat, const T* tw, double* out);
 int argmax_launch(algp_ctx* c, const double* s, int64_t M, double* out_val, int64_t* out_idx);
 template <typename T>
 int rows_reduce3_launch(algp_ctx* c, const T* Vt, int64_t rows, int64_t ldv, int64_t c0, int64_t c1, const T* u, const T* w,

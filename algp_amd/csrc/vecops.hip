@@ -376,19 +376,21 @@ template int vr_score_launch<double>(algp_ctx*, int64_t, const int*, const unsig
 template int vr_score_launch<float>(algp_ctx*, int64_t, const int*, const unsigned char*, const float*, const float*, double, double,
                                     double*);
 
-// a committed pick's column `col` of V^T: r[c] of every row, rt[c] = r[c] on the targets (ordinary rows) and 0 elsewhere, and
-// *nrm = |r_T|^2 (one workgroup: a thread adds its rows in ascending order, then the shuffle tree, then the waves left to right)
+// a committed pick's column `col` of V^T: r[c] of every row, rt[c] = omega_c r[c] on the targets (ordinary rows; omega = tw at
+// the row's pool site, 1 without weights) and 0 elsewhere, and *nrm = sum_T omega_j r_j^2 (one workgroup: a thread adds its
+// rows in ascending order, then the shuffle tree, then the waves left to right)
 template <typename T>
-__global__ __launch_bounds__(1024) void vr_pick_col_kernel(int64_t M, const int* ckind, const T* Vt, int64_t ldv, int64_t col, T* r, T* rt,
-                                                           T* nrm) {
+__global__ __launch_bounds__(1024) void vr_pick_col_kernel(int64_t M, const int* ckind, const int64_t* cidx, const T* tw, const T* Vt,
+                                                           int64_t ldv, int64_t col, T* r, T* rt, T* nrm) {
     __shared__ T red[16];
     T s = (T)0;
     for (int64_t j = threadIdx.x; j < M; j += 1024) {
         const T v = Vt[j * ldv + col];
         const T vt = ckind[j] < 0 ? v : (T)0;
+        const T wv = tw ? tw[cidx[j]] * vt : vt;               // omega = 1: vt itself, the sum below the bits of vt vt
         r[j] = v;
-        rt[j] = vt;
-        s = __builtin_fma(vt, vt, s);
+        rt[j] = wv;
+        s = __builtin_fma(wv, vt, s);
     }
     s = dot_tree<T>(s);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
@@ -399,7 +401,7 @@ __global__ __launch_bounds__(1024) void vr_pick_col_kernel(int64_t M, const int*
         *nrm = t;
     }
 }
-// t = V_T^T r_T over the first ncols columns: row block b (rows_per rows) leaves its share at tp[b * ld + k] (a thread per
+// t = V_T^T rt over the first ncols columns: row block b (rows_per rows) leaves its share at tp[b * ld + k] (a thread per
 // column, rows in ascending order, rows outside the targets skipped); vr_tsum_kernel adds the blocks in order
 template <typename T>
 __global__ __launch_bounds__(256) void vr_tpart_kernel(int64_t M, int64_t rows_per, const T* Vt, int64_t ldv, int64_t ncols, const T* rt,
@@ -436,7 +438,7 @@ __global__ __launch_bounds__(256) void vr_cov_gemv_kernel(int64_t M, const int64
         if (lane == 0) y1[c0] = s;
     }
 }
-// the rank-1 fold of one pick: y_c = kappa_c (y1_c + noise rt_c) - y2_c, w_c <- w_c - 2 r_c y_c + r_c^2 |r_T|^2
+// the rank-1 fold of one pick: y_c = kappa_c (y1_c + noise rt_c) - y2_c, w_c <- w_c - 2 r_c y_c + r_c^2 nrm
 // (noise: sigma_n^2 of a coordinate pool, which the kernel-GEMV leaves out where the pool indices coincide; 0 for a covariance pool)
 template <typename T>
 __global__ void vr_fold_kernel(int64_t M, const int* ckind, const T* r, const T* rt, const T* y1, const T* y2, const T* nrm, T noise,
@@ -450,11 +452,12 @@ __global__ void vr_fold_kernel(int64_t M, const int* ckind, const T* r, const T*
 
 template <typename T>
 int vr_fold_launch(algp_ctx* c, int64_t M, const int* ckind, const int64_t* cidx, const T* Vt, int64_t ldv, int64_t col, const T* Xs,
-                   const T* Cp, int64_t n_pool, int DP, int kernel, T os, T noise, T* r, T* rt, T* nrm, T* tp, T* t, T* y1, T* y2, T* w) {
+                   const T* Cp, int64_t n_pool, int DP, int kernel, T os, T noise, const T* tw, T* r, T* rt, T* nrm, T* tp, T* t, T* y1,
+                   T* y2, T* w) {
     if (M <= 0) return ALGP_OK;
     {
         ProfScope ps(c, ALGP_PROF_ROWS, 2.0 * M, sizeof(T) * 3.0 * M);
-        hipLaunchKernelGGL(vr_pick_col_kernel<T>, dim3(1), dim3(1024), 0, c->cur, M, ckind, Vt, ldv, col, r, rt, nrm);
+        hipLaunchKernelGGL(vr_pick_col_kernel<T>, dim3(1), dim3(1024), 0, c->cur, M, ckind, cidx, tw, Vt, ldv, col, r, rt, nrm);
         ALGP_HIP(hipGetLastError());
     }
     const int nblocks = (int)std::min<int64_t>(VR_TBLOCKS, (M + 63) / 64);
@@ -487,10 +490,42 @@ int vr_fold_launch(algp_ctx* c, int64_t M, const int* ckind, const int64_t* cidx
     return ALGP_OK;
 }
 template int vr_fold_launch<double>(algp_ctx*, int64_t, const int*, const int64_t*, const double*, int64_t, int64_t, const double*,
-                                    const double*, int64_t, int, int, double, double, double*, double*, double*, double*, double*, double*,
-                                    double*, double*);
+                                    const double*, int64_t, int, int, double, double, const double*, double*, double*, double*, double*,
+                                    double*, double*, double*, double*);
 template int vr_fold_launch<float>(algp_ctx*, int64_t, const int*, const int64_t*, const float*, int64_t, int64_t, const float*, const float*,
-                                   int64_t, int, int, float, float, float*, float*, float*, float*, float*, float*, float*, float*);
+                                   int64_t, int, int, float, float, const float*, float*, float*, float*, float*, float*, float*, float*,
+                                   float*);
+
+// the criterion's objective: *out = sum over the targets j (ordinary rows) of omega_j dstat_j in double (one workgroup, the
+// order of vr_pick_col_kernel: a thread adds its rows in ascending order, then the shuffle tree, then the waves left to right)
+template <typename T>
+__global__ __launch_bounds__(1024) void vr_target_sum_kernel(int64_t M, const int* ckind, const int64_t* cidx, const T* dstat, const T* tw,
+                                                             double* out) {
+    __shared__ double red[16];
+    double s = 0.0;
+    for (int64_t j = threadIdx.x; j < M; j += 1024)
+        if (ckind[j] < 0) {
+            const double wj = tw ? (double)tw[cidx[j]] : 1.0;
+            s = __builtin_fma(wj, (double)dstat[j], s);
+        }
+    s = dot_tree<double>(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = red[0];
+        for (int k = 1; k < 16; ++k) t += red[k];
+        *out = t;
+    }
+}
+template <typename T>
+int vr_target_sum_launch(algp_ctx* c, int64_t M, const int* ckind, const int64_t* cidx, const T* dstat, const T* tw, double* out) {
+    ProfScope ps(c, ALGP_PROF_ROWS, 2.0 * M, (sizeof(T) * 2.0 + 12.0) * M);
+    hipLaunchKernelGGL(vr_target_sum_kernel<T>, dim3(1), dim3(1024), 0, c->cur, M, ckind, cidx, dstat, tw, out);
+    ALGP_HIP(hipGetLastError());
+    return ALGP_OK;
+}
+template int vr_target_sum_launch<double>(algp_ctx*, int64_t, const int*, const int64_t*, const double*, const double*, double*);
+template int vr_target_sum_launch<float>(algp_ctx*, int64_t, const int*, const int64_t*, const float*, const float*, double*);
 
 // first maximum (np.argmax semantics, agent.py:349): larger value wins, ties go to the smaller index
 __global__ __launch_bounds__(1024) void argmax_kernel(const double* s, int64_t M, double* out_val, int64_t* out_idx) {

@@ -228,7 +228,12 @@ int algp_posterior_mean(algp_ctx* ctx, const int64_t* idx, int64_t M, void* mu_o
  * after it is folded in with E' = E - r_T r_c^T (r: the pick's column of V^T): one fused kernel-GEMV and two passes over
  * V^T.  algp_scores, algp_best_candidate (full scoring, as MI) and algp_greedy accept it; algp_greedy_sharded refuses it
  * (ALGP_ERR_BAD_ARG); candidates set with an extra variance, or a candidate set that lists a pool site twice, are refused with
- * ALGP_ERR_STATE. */
+ * ALGP_ERR_STATE.
+ * Target weights (algp_set_target_weights below): with a weight omega_q >= 0 per pool site attached, target j counts omega_j
+ * times -- sum_{j in T} omega_j E_jc^2 in both utilities, i.e. sum_j omega_j var(j | A) - sum_j omega_j var(j | A with c
+ * static-sampled): a region of interest, plots that matter more, the sites a later prediction is read at.  The targets stay
+ * the ordinary rows of the candidate set; every candidate may still be picked.  The fold of a pick reads
+ * w'_c = w_c - 2 r_c y_c + r_c^2 sum_T omega_j r_j^2 with y = E^T (omega r)_T.  The entropy and MI criteria ignore weights. */
 int algp_scores(algp_ctx* ctx, int criterion, double static_std, double mobile_std, void* out,
                 int out_is_device);
 int algp_argmax(algp_ctx* ctx, int64_t* local_pos, int64_t* pool_idx, double* value);
@@ -237,6 +242,22 @@ int algp_best_candidate(algp_ctx* ctx, int criterion, double static_std, double 
 int algp_commit_pick(algp_ctx* ctx, int64_t pool_idx, double static_std, double mobile_std);
 int algp_greedy(algp_ctx* ctx, int criterion, double static_std, double mobile_std, int k,
                 const int64_t* forced_picks, int64_t* picks_out, double* utilities_out);
+/* algp_set_target_weights: the variance-reduction criterion's weight of every pool site as a target (w: n_pool doubles, each
+ * finite and >= 0; n_pool must be the current pool's size: otherwise ALGP_ERR_BAD_ARG with the offending index in the
+ * message, nothing changed; without a pool ALGP_ERR_STATE).  w = NULL detaches the weights: every target counts once again,
+ * with the bits of a context that never had any.  The weights are held on the device in the context's dtype and belong to
+ * their pool: algp_set_pool and algp_set_pool_cov drop them, as they drop an owner map.  Setting, changing or detaching them
+ * drops the criterion's resident sums -- the next scoring is the full product, committed picks included -- but not the
+ * candidate solve.  A weight on a site that is not a target (a unit row, a site outside the candidate set) is accepted and
+ * ignored; all weights zero is legal (every utility 0, -inf where it is today).  algp_scores / algp_greedy under
+ * ALGP_CRIT_VARIANCE_REDUCTION and algp_score_paths_vr (Phi = E Omega E^T) read them; nothing else does.
+ * algp_get_target_variance: the criterion's objective under the current state, committed picks included:
+ *   *sum = sum_{j in T} omega_j pv_j, pv_j the variance algp_get_posterior reports for target row j (omega = 1 without weights).
+ * A pick's utility is this sum before its commit minus the sum after.  Needs a candidate solve (ALGP_ERR_STATE), brings the rows
+ * up to date as algp_get_posterior does, applies the criterion's two refusals (ALGP_ERR_STATE), and is one device reduction in
+ * a fixed order, accumulated in double: the same bits in every run. */
+int algp_set_target_weights(algp_ctx* ctx, const double* w, int64_t n_pool);
+int algp_get_target_variance(algp_ctx* ctx, double* sum);
 
 /* ---- a8 / f3: Agent.best_path (agent.py:358-403), entropy criterion, all paths at once -----------------------------
  * algp_score_paths: dH_out[p] = H(A u path_p) - H(A) for npaths enumerated paths, where path p adds a mobile reading
@@ -275,7 +296,7 @@ int algp_score_paths_mi(algp_ctx* ctx, const int64_t* sites, int npaths, int max
  *   dV_out[p] = sum_{j in T} var(j | A) - sum_{j in T} var(j | A u path_p) = tr((Gamma_SS + sm I)^-1 Phi_SS),
  * S the path's sites, Gamma = C - R R^T their posterior covariance (R_s: the site's row of V^T, second-row form for a train
  * site; C: the pool covariance, sigma_n^2 where the pool indices coincide), E_sj = C(s, j) - R_s . V_j their cross covariance
- * with the targets, Phi = E E^T.  Gamma and Phi are built once over the union U of a group of consecutive paths (max_union:
+ * with the targets, Phi = E E^T (E Omega E^T and sum_j omega_j var(j | .) with target weights attached, algp_set_target_weights).  Gamma and Phi are built once over the union U of a group of consecutive paths (max_union:
  * the most union sites per group, at least 256; <= 0: the library's default, the largest union whose rows of V^T and whose two
  * U x U matrices each stay within ~4 GB -- 15 744 sites in fp64, 22 272 in fp32, fewer beyond N of about 31 000 / 44 000; a site shared by
  * paths of two groups is computed in both, so paths that share sites belong next to each other), then every path costs O(k^3) on its gathered k x k blocks: 2 U M N + 2 U^2 M flop per group (M candidate rows, N

@@ -6,9 +6,11 @@ Every figure is a host clock around an ABI call that ends in a stream synchronis
 warm-up of every kernel involved at a small size in the same process; the product's own time is also read from the
 library's HIP events (class ALGP_PROF_GEMM_OTHER).  The whole sequence (a new candidate solve, the first scoring, picks
 2..4, and pick 2 again by the full product) runs --repeats times; min / median / max of each figure are reported, rates and
-the ratio from the medians.  One JSON line per size on stdout, all of them in --out.
+the ratio from the medians.  One JSON line per size on stdout, all of them in --out.  --weights rand attaches target
+weights uniform in [0.25, 4] (algp_set_target_weights) before the timed sequence: the weighted epilogue and folds.
 
     python tools/vr_time.py --N 10000 --M 20000 100000 --out profiles/vr_time.json
+    ALGP_LIB=ab_tmp/lib_v1.so python tools/vr_time.py --M 20000          # another build of the same ABI, for an A/B
 """
 import argparse
 import json
@@ -53,7 +55,7 @@ def spread(v):
     return {'min': v[0], 'median': v[len(v) // 2], 'max': v[-1], 'n': len(v)}
 
 
-def measure(dtype, N, M, seed, reps):
+def measure(dtype, N, M, seed, reps, weights='none'):
     os.environ.pop('ALGP_VR_RANK1', None)
     rng = np.random.RandomState(seed)
     c = _hip.Context(dtype)
@@ -63,6 +65,8 @@ def measure(dtype, N, M, seed, reps):
     c.scores(_hip.CRIT_VARIANCE_REDUCTION, SS, SM)
     os.environ.pop('ALGP_VR_RANK1')
     cand = setup(c, N, M, rng)
+    if weights == 'rand':
+        c.set_target_weights(np.random.RandomState(seed + 1).uniform(0.25, 4.0, size=c.n_pool))
     Npad = (N + 127) // 128 * 128
     flop = 2.0 * float(len(cand)) ** 2 * Npad
     first, product, full, picks, commits, agree = [], [], [], [[], [], []], [], []
@@ -89,7 +93,7 @@ def measure(dtype, N, M, seed, reps):
                 agree.append(float(np.max(np.abs(u[fin] - u_full[fin]) / np.abs(u_full[fin]))))
     c.close()
     med = lambda v: sorted(v)[len(v) // 2]
-    return {'dtype': np.dtype(dtype).name, 'N': N, 'M': len(cand), 'repeats': reps, 'first_scoring_flop': flop,
+    return {'dtype': np.dtype(dtype).name, 'N': N, 'M': len(cand), 'repeats': reps, 'weights': weights, 'first_scoring_flop': flop,
             'first_scoring_ms': spread(first), 'first_scoring_product_event_ms': spread(product),
             'first_scoring_tflops': flop / (med(first) * 1e-3) / 1e12, 'product_tflops': flop / (med(product) * 1e-3) / 1e12,
             'commit_ms': spread(commits), 'pick2_scoring_ms': spread(picks[0]), 'pick3_scoring_ms': spread(picks[1]),
@@ -104,11 +108,12 @@ def main():
     ap.add_argument('--dtype', default='float64', choices=['float32', 'float64'])
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--repeats', type=int, default=5)
+    ap.add_argument('--weights', default='none', choices=['none', 'rand'])
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     rows = []
     for M in a.M:
-        rows.append(measure(np.dtype(a.dtype).type, a.N, M, a.seed, a.repeats))
+        rows.append(measure(np.dtype(a.dtype).type, a.N, M, a.seed, a.repeats, a.weights))
         print(json.dumps(rows[-1]), flush=True)
     if a.out:
         with open(a.out, 'w') as f:
