@@ -381,8 +381,8 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel_dma4(Args g) {
     int nkt;                                                       // ... and walks
     int slice = -1, nunits = 1, ui = 0;
     if constexpr (SCHED) {
-        nunits = sched_count(g.sch, blockIdx.x);
-        const SchedUnit u = sched_unit(g.sch, blockIdx.x, 0);
+        nunits = sched_count<!GEN>(g.sch, blockIdx.x);
+        const SchedUnit u = sched_unit<!GEN>(g.sch, blockIdx.x, 0);
         bm = u.tile / g.tiles_n;
         bn = u.tile - bm * g.tiles_n;
         kskip = u.kb0 * (128 / BK);
@@ -533,7 +533,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel_dma4(Args g) {
     if constexpr (SCHED) {
         // the next unit's first NST - 1 k-tiles, into the stages after the one read last (a unit has at least 128 / BK >= 8)
         if (++ui < nunits) {
-            const SchedUnit u = sched_unit(g.sch, blockIdx.x, ui);
+            const SchedUnit u = sched_unit<!GEN>(g.sch, blockIdx.x, ui);
             bm = u.tile / g.tiles_n;
             bn = u.tile - bm * g.tiles_n;
             nkt = (u.kb1 - u.kb0) * (128 / BK);
@@ -692,39 +692,117 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel_dma4(Args g) {
 }
 
 // D = beta C + the partial sums of a scheduled launch's leftover tiles, slice by slice in ascending k: a fixed order, the
-// same bits in every run.  One workgroup per leftover tile (tile0 + blockIdx.x of the row-major list).
+// same bits in every run.  A memory-bound pass, shaped for the memory system: FIN_STRIPS workgroups per leftover tile (tile
+// tile0 + blockIdx.x / FIN_STRIPS of the row-major list), each a strip of 128 / FIN_STRIPS = 8 rows -- 56 leftover tiles are 896
+// workgroups, where one workgroup per tile left four CUs in five idle.  A thread owns PPT 16-byte pieces (two fp64 / four fp32
+// adjacent columns; a wave reads 1 KB of a row at a time), in the same columns of rows RSTEP apart, and loads the slices in
+// batches of FIN_BATCH before the first add of a batch: FIN_BATCH * PPT independent 16-byte loads in flight per thread, where
+// the element-by-element loop waited for every 8 bytes.  Per element the arithmetic is what it always was: v = beta * c
+// rounded on its own (contraction is off in these kernels: unrolled, the compiler would make one fma of the multiplication and
+// the first add, which rounds once where the loop rounded twice), then v += P[q] in ascending q, one add per slice.
+constexpr int FIN_STRIPS = 16;
+constexpr int FIN_BATCH = 8;
+template <typename T>
+struct Fin {
+    static constexpr int EPV = 16 / (int)sizeof(T);                        // elements of a piece
+    static constexpr int RPW = 256 * EPV / 128;                            // rows that the 256 threads cover at a time: 4 / 8
+    static constexpr int PPT = (128 / FIN_STRIPS) / RPW;                   // pieces of a thread: 2 / 1
+    static constexpr int RSTEP = RPW;
+    typedef T V __attribute__((ext_vector_type(EPV)));
+    static_assert(PPT >= 1 && PPT * RPW * FIN_STRIPS == 128, "a strip is whole passes of the workgroup");
+};
+
+// v[i] += the pieces of slices 0 .. NB - 1 at P (uniform: the first of them) + off (the thread's first piece), ascending: every
+// load of the batch is issued before its first add (left alone, the scheduler interleaves them to save registers)
+template <typename T, int NB>
+__device__ __forceinline__ void finish_add(const T* P, unsigned off, typename Fin<T>::V (&v)[Fin<T>::PPT]) {
+#pragma clang fp contract(off)
+    using F = Fin<T>;
+    typename F::V p[NB][F::PPT];
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+        for (int i = 0; i < F::PPT; ++i)
+            p[b][i] = *reinterpret_cast<const typename F::V*>(P + b * (128 * 128) + (off + i * F::RSTEP * 128));
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+        for (int i = 0; i < F::PPT; ++i) v[i] += p[b][i];
+}
+
+// all S slices: whole batches, then the remainder as batches of 4, 2 and 1 (still ascending)
+template <typename T>
+__device__ __forceinline__ void finish_sum(const T* P, unsigned off, int S, typename Fin<T>::V (&v)[Fin<T>::PPT]) {
+    int q = 0;
+    for (; q + FIN_BATCH <= S; q += FIN_BATCH) finish_add<T, FIN_BATCH>(P + (int64_t)q * (128 * 128), off, v);
+    static_assert(FIN_BATCH == 8, "the remainder below is 4 + 2 + 1");
+    if ((S - q) & 4) { finish_add<T, 4>(P + (int64_t)q * (128 * 128), off, v); q += 4; }
+    if ((S - q) & 2) { finish_add<T, 2>(P + (int64_t)q * (128 * 128), off, v); q += 2; }
+    if ((S - q) & 1) finish_add<T, 1>(P + (int64_t)q * (128 * 128), off, v);
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void gemm_finish_kernel(const T* part, int S, int tile0, int tiles_n, T beta, const T* C, int64_t ldc,
                                                           T* D, int64_t ldd) {
-    const int tile = tile0 + blockIdx.x, bm = tile / tiles_n, bn = tile - bm * tiles_n;
-    const T* P = part + (int64_t)blockIdx.x * S * (128 * 128);
-    for (int e = threadIdx.x; e < 128 * 128; e += 256) {
-        const int64_t row = (int64_t)bm * 128 + (e >> 7), col = (int64_t)bn * 128 + (e & 127);
-        T v = beta * C[row * ldc + col];
-        for (int q = 0; q < S; ++q) v += P[(int64_t)q * (128 * 128) + e];
-        D[row * ldd + col] = v;
-    }
+#pragma clang fp contract(off)
+    using F = Fin<T>;
+    using V = typename F::V;
+    const int j = blockIdx.x / FIN_STRIPS, strip = blockIdx.x - j * FIN_STRIPS;
+    const int tile = tile0 + j, bm = tile / tiles_n, bn = tile - bm * tiles_n;
+    const int lrow = strip * (128 / FIN_STRIPS) + (int)threadIdx.x / (128 / F::EPV), lcol = ((int)threadIdx.x % (128 / F::EPV)) * F::EPV;
+    const int64_t row = (int64_t)bm * 128 + lrow, col = (int64_t)bn * 128 + lcol;
+    V v[F::PPT];
+#pragma unroll
+    for (int i = 0; i < F::PPT; ++i) v[i] = beta * *reinterpret_cast<const V*>(C + (row + i * F::RSTEP) * ldc + col);
+    finish_sum<T>(part + (int64_t)j * S * (128 * 128), (unsigned)(lrow * 128 + lcol), S, v);
+#pragma unroll
+    for (int i = 0; i < F::PPT; ++i) *reinterpret_cast<V*>(D + (row + i * F::RSTEP) * ldd + col) = v[i];
 }
 
-// The same with the C term generated (GenGemmArgs): the leftover tiles of a scheduled update product with fused right-hand sides
+// The same with the C term generated (GenGemmArgs): the leftover tiles of a scheduled update product with fused right-hand sides.
+// The coordinates of a thread's columns are loaded once, the coordinates and the kind of a row once per piece; one copy of the C
+// term per kernel form, as in the product's epilogue.
 template <typename T, int DP>
 __global__ __launch_bounds__(256) void gemm_finish_gen_kernel(const T* part, int S, int tile0, int tiles_n, T beta, const T* rx, const T* cx,
                                                               const int* rk, int64_t col0, int64_t ncols, int kernel, T os, T* D, int64_t ldd) {
-    const int tile = tile0 + blockIdx.x, bm = tile / tiles_n, bn = tile - bm * tiles_n;
-    const T* P = part + (int64_t)blockIdx.x * S * (128 * 128);
-    const int64_t col = (int64_t)bn * 128 + (threadIdx.x & 127);   // e & 127 is the same in every round of the loop below
-    T xcol[DP];
+#pragma clang fp contract(off)
+    using F = Fin<T>;
+    using V = typename F::V;
+    const int j = blockIdx.x / FIN_STRIPS, strip = blockIdx.x - j * FIN_STRIPS;
+    const int tile = tile0 + j, bm = tile / tiles_n, bn = tile - bm * tiles_n;
+    const int lrow = strip * (128 / FIN_STRIPS) + (int)threadIdx.x / (128 / F::EPV), lcol = ((int)threadIdx.x % (128 / F::EPV)) * F::EPV;
+    const int64_t row = (int64_t)bm * 128 + lrow, col = (int64_t)bn * 128 + lcol;
+    T xcol[F::EPV][DP];
 #pragma unroll
-    for (int d = 0; d < DP; ++d) xcol[d] = cx[(col0 + col) * DP + d];
-    for (int e = threadIdx.x; e < 128 * 128; e += 256) {
-        const int64_t row = (int64_t)bm * 128 + (e >> 7);
-        T xrow[DP];
+    for (int e = 0; e < F::EPV; ++e)
 #pragma unroll
-        for (int d = 0; d < DP; ++d) xrow[d] = rx[row * DP + d];
-        T v = beta * bt_entry<T, DP>(kernel, os, xrow, xcol, rk[row], col0 + col, ncols);
-        for (int q = 0; q < S; ++q) v += P[(int64_t)q * (128 * 128) + e];
-        D[row * ldd + col] = v;
+        for (int d = 0; d < DP; ++d) xcol[e][d] = cx[(col0 + col + e) * DP + d];
+    T xrow[F::PPT][DP];
+    int kind[F::PPT];
+#pragma unroll
+    for (int i = 0; i < F::PPT; ++i) {
+#pragma unroll
+        for (int d = 0; d < DP; ++d) xrow[i][d] = rx[(row + i * F::RSTEP) * DP + d];
+        kind[i] = rk[row + i * F::RSTEP];
     }
+    V v[F::PPT];
+    auto c_term = [&](auto kform) {
+#pragma clang fp contract(off)
+#pragma unroll
+        for (int i = 0; i < F::PPT; ++i) {
+            V cv;
+#pragma unroll
+            for (int e = 0; e < F::EPV; ++e)
+                cv[e] = bt_entry<T, DP>(decltype(kform)::value, os, xrow[i], xcol[e], kind[i], col0 + col + e, ncols);
+            v[i] = beta * cv;
+        }
+    };
+    if (kernel == ALGP_KERNEL_RBF) c_term(std::integral_constant<int, ALGP_KERNEL_RBF>{});
+    else c_term(std::integral_constant<int, ALGP_KERNEL_MATERN15>{});
+    finish_sum<T>(part + (int64_t)j * S * (128 * 128), (unsigned)(lrow * 128 + lcol), S, v);
+#pragma unroll
+    for (int i = 0; i < F::PPT; ++i) *reinterpret_cast<V*>(D + (row + i * F::RSTEP) * ldd + col) = v[i];
 }
 
 // $ALGP_LAUNCH_LOG=<file>: one line per launch of gemm_nt_kernel_dma4 (any instantiation), in enqueue order (class m n k
@@ -796,6 +874,8 @@ int gemm_nt_launch_batched(algp_ctx* c, int klass, int64_t m, int64_t n, int64_t
                            c->gemm_part.cap >= sizeof(T) * 128 * 128 * (size_t)slots;
         g.sch = sched_make(slots, g.tiles_m, g.tiles_n, (int)(k / 128), kcut, split ? 1 : 0);
         g.part = (T*)c->gemm_part.p;
+        if (g.sch.S >= 2 && (ldc % 4 || ldd % 4 || (((uintptr_t)g.C | (uintptr_t)D) & 15)))
+            return fail(c, ALGP_ERR_BAD_ARG, "gemm_nt: the finish kernel reads C and writes D in 16-byte pieces");
         const dim3 sgrid((unsigned)g.sch.G);
         const bool timed = prof_launch_events(c, klass, flops, bytes, &ev_a, &ev_b);
         if (stat_out) {
@@ -809,7 +889,7 @@ int gemm_nt_launch_batched(algp_ctx* c, int klass, int64_t m, int64_t n, int64_t
         if (g.sch.S >= 2) {
             const double fbytes = sizeof(T) * 128.0 * 128.0 * (double)g.sch.left * (g.sch.S + 2.0);
             const bool ftimed = prof_launch_events(c, klass, 0.0, fbytes, &ev_a, &ev_b);
-            const dim3 fgrid((unsigned)g.sch.left);
+            const dim3 fgrid((unsigned)(g.sch.left * FIN_STRIPS));
             if (ftimed) hipExtLaunchKernelGGL(gemm_finish_kernel<T>, fgrid, dim3(256), 0, c->cur, ev_a, ev_b, 0, (const T*)g.part, g.sch.S,
                                               g.sch.full, g.tiles_n, beta, g.C, ldc, D, ldd);
             else hipLaunchKernelGGL(gemm_finish_kernel<T>, fgrid, dim3(256), 0, c->cur, (const T*)g.part, g.sch.S, g.sch.full, g.tiles_n,
@@ -864,6 +944,8 @@ int gemm_nt_launch_gen(algp_ctx* c, int klass, int64_t m, int64_t n, int64_t k, 
     const bool split = beta != (T)0 && c->gemm_part.p && c->gemm_part.cap >= sizeof(T) * 128 * 128 * (size_t)slots;   // as the loading form
     g.sch = sched_make(slots, g.tiles_m, g.tiles_n, (int)(k / 128), 0, split ? 1 : 0);
     g.part = (T*)c->gemm_part.p;
+    if (g.sch.S >= 2 && (ldd % 4 || ((uintptr_t)D & 15)))
+        return fail(c, ALGP_ERR_BAD_ARG, "gemm_nt_gen: the finish kernel writes D in 16-byte pieces");
     hipEvent_t ev_a, ev_b;
     const dim3 sgrid((unsigned)g.sch.G);
     const bool timed = prof_launch_events(c, klass, flops, bytes, &ev_a, &ev_b);
@@ -873,7 +955,7 @@ int gemm_nt_launch_gen(algp_ctx* c, int klass, int64_t m, int64_t n, int64_t k, 
     if (g.sch.S >= 2) {
         const double fbytes = sizeof(T) * 128.0 * 128.0 * (double)g.sch.left * (g.sch.S + 1.0);
         const bool ftimed = prof_launch_events(c, klass, 0.0, fbytes, &ev_a, &ev_b);
-        const dim3 fgrid((unsigned)g.sch.left);
+        const dim3 fgrid((unsigned)(g.sch.left * FIN_STRIPS));
         if (ftimed) hipExtLaunchKernelGGL((gemm_finish_gen_kernel<T, 2>), fgrid, dim3(256), 0, c->cur, ev_a, ev_b, 0, (const T*)g.part, g.sch.S,
                                           g.sch.full, g.tiles_n, beta, g.rx, g.cx, g.rk, col0, g.ncols, g.kernel, g.os, D, ldd);
         else hipLaunchKernelGGL((gemm_finish_gen_kernel<T, 2>), fgrid, dim3(256), 0, c->cur, (const T*)g.part, g.sch.S, g.sch.full, g.tiles_n,
