@@ -186,18 +186,19 @@ struct Impl {
     static int selftest(algp_ctx* c, int* mism);
 };
 
-// Factor a batch of ppad x ppad blocks (ppad = 128 or 256, lower tiles) as 2 x 2 tiles of 128, the way score_paths_big does:
-// L11 and L22 in place, L21 = G21 inv(L11)^T into L21 (NB x NB per block), log det added to logdet[b], first bad pivot to info[b]
+// Factor a batch of ppad x ppad blocks (ppad = 128 or 256, lower tiles) as 2 x 2 tiles of 128, every step one launch for the
+// whole batch: L11 and L22 in place, L21 = G21 inv(L11)^T into L21 (NB x NB per block), log det added to logdet[b], first bad
+// pivot to info[b]
 template <typename T>
 int factor_blocks_batched(algp_ctx* c, T* G, int ppad, T* inv, T* L21, double* logdet, int* info, int B) {
     ALGP_TRY(potrf_diag_batched_launch<T>(c, G, (int64_t)ppad * ppad, ppad, inv, 2 * NB * NB, logdet, info, B));
     if (ppad > NB) {
         T* G21 = G + (int64_t)NB * ppad;
         T* G22 = G21 + NB;
-        ALGP_TRY(gemm_nt_launch_batched<T>(c, ALGP_PROF_GEMM_OTHER, NB, NB, NB, (T)1, G21, ppad, (int64_t)ppad * ppad, inv, NB, 2 * NB * NB,
-                                           (T)0, nullptr, 0, 0, L21, NB, NB * NB, 0, B));
-        ALGP_TRY(gemm_nt_launch_batched<T>(c, ALGP_PROF_GEMM_OTHER, NB, NB, NB, (T)-1, L21, NB, NB * NB, L21, NB, NB * NB, (T)1, G22, ppad,
-                                           (int64_t)ppad * ppad, G22, ppad, (int64_t)ppad * ppad, 0, B));
+        ALGP_TRY(gemm_nt<T>(c, {.klass = ALGP_PROF_GEMM_OTHER, .m = NB, .n = NB, .k = NB, .A = {G21, ppad, (int64_t)ppad * ppad},
+                                .B = {inv, NB, 2 * NB * NB}, .D = {L21, NB, NB * NB}, .batch = B}));
+        ALGP_TRY(gemm_nt<T>(c, {.klass = ALGP_PROF_GEMM_OTHER, .m = NB, .n = NB, .k = NB, .alpha = (T)-1, .beta = (T)1, .A = {L21, NB, NB * NB},
+                                .B = {L21, NB, NB * NB}, .D = {G22, ppad, (int64_t)ppad * ppad}, .batch = B}));
         ALGP_TRY(potrf_diag_batched_launch<T>(c, G22, (int64_t)ppad * ppad, ppad, inv + NB * NB, 2 * NB * NB, logdet, info, B));
     }
     return ALGP_OK;

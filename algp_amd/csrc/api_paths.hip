@@ -9,8 +9,8 @@ namespace algp {
 // Paths of 65 .. 256 distinct sites (cpos / lpos: candidate row and train row per site, packed to the front of each path's
 // maxlen entries).  Per batch of paths: the paths' rows of V^T gathered into a scratch (a site that is a train row
 // already: L[lpos, :] - var_lpos * its unit row, as in the LDS kernel), the Gram matrices as ONE batched lower-tile MFMA
-// product, G = C_PP + sigma_m^2 I - Gram, then the ppad x ppad blocks factored as 2 x 2 tiles of 128: diagonal-block
-// kernel, L21 = G21 inv(L11)^T, G22 -= L21 L21^T, diagonal-block kernel -- every step one launch for the whole batch.
+// product, G = C_PP + sigma_m^2 I - Gram, then the ppad x ppad blocks factored as 2 x 2 tiles of 128
+// (factor_blocks_batched, api_impl.h) -- every step one launch for the whole batch.
 template <typename T>
 int Impl<T>::score_paths_big(algp_ctx* c, const std::vector<int64_t>& cpos, const std::vector<int64_t>& lpos, int npaths, int maxlen,
                                int maxused, double mobile_std, double* dH) {
@@ -58,21 +58,12 @@ int Impl<T>::score_paths_big(algp_ctx* c, const std::vector<int64_t>& cpos, cons
         ALGP_HIP(hipMemsetAsync(d_info, 0, sizeof(int) * B, c->stream));
         ALGP_TRY(gather_rows_launch<T>(c, p(c->Vt), c->ldv, d_src, rows, Npad, (int64_t)nrow, Npad, second ? d_lrow : nullptr,
                                        second ? (const T*)c->auxVar.p : nullptr, p(c->L), c->Lld));
-        ALGP_TRY(gemm_nt_launch_batched<T>(c, ALGP_PROF_GEMM_OTHER, ppad, ppad, Npad, (T)1, rows, Npad, (int64_t)ppad * Npad, rows, Npad,
-                                           (int64_t)ppad * Npad, (T)0, nullptr, 0, 0, G, ppad, (int64_t)ppad * ppad, 1, B));
+        ALGP_TRY(gemm_nt<T>(c, {.klass = ALGP_PROF_GEMM_OTHER, .m = ppad, .n = ppad, .k = Npad, .A = {rows, Npad, (int64_t)ppad * Npad},
+                                .B = {rows, Npad, (int64_t)ppad * Npad}, .D = {G, ppad, (int64_t)ppad * ppad}, .batch = B, .lower_only = 1}));
         ALGP_TRY(path_assemble_launch<T>(c, d_src, B, ppad, (const int64_t*)c->Cidx.p, (const T*)c->Xs.p,
                                          c->pool_is_cov ? (const T*)c->Cp.p : nullptr, c->n_pool, c->hyp.DP, c->hyp.kernel,
                                          c->hyp.outputscale, c->hyp.noise, mobile_std * mobile_std, G));
-        ALGP_TRY(potrf_diag_batched_launch<T>(c, G, (int64_t)ppad * ppad, ppad, inv, 2 * NB * NB, d_ld, d_info, B));
-        if (ppad > NB) {
-            T* G21 = G + (int64_t)NB * ppad;
-            T* G22 = G21 + NB;
-            ALGP_TRY(gemm_nt_launch_batched<T>(c, ALGP_PROF_GEMM_OTHER, NB, NB, NB, (T)1, G21, ppad, (int64_t)ppad * ppad, inv, NB, 2 * NB * NB,
-                                               (T)0, nullptr, 0, 0, L21, NB, NB * NB, 0, B));
-            ALGP_TRY(gemm_nt_launch_batched<T>(c, ALGP_PROF_GEMM_OTHER, NB, NB, NB, (T)-1, L21, NB, NB * NB, L21, NB, NB * NB, (T)1, G22, ppad,
-                                               (int64_t)ppad * ppad, G22, ppad, (int64_t)ppad * ppad, 0, B));
-            ALGP_TRY(potrf_diag_batched_launch<T>(c, G22, (int64_t)ppad * ppad, ppad, inv + NB * NB, 2 * NB * NB, d_ld, d_info, B));
-        }
+        ALGP_TRY(factor_blocks_batched<T>(c, G, ppad, inv, L21, d_ld, d_info, B));
         ALGP_TRY(path_finish_launch(c, d_src, ppad, B, d_ld, d_info, d_out + p0));
         ALGP_TRY(sync(c));                                   // the index vectors are reused by the next batch
     }
@@ -235,20 +226,20 @@ int Impl<T>::score_paths_mi(algp_ctx* c, const int64_t* sites, int npaths, int m
         // P_SS over the new sites (nothing to do when every site is sampled: no path then has a new site)
         if (mb > 0) {
             ALGP_TRY(mi_tri_gather_launch<T>(c, p(c->mi.Xbar), mbpad, d_srcP, rows, mbpad, (int64_t)nrow, mbpad));
-            ALGP_TRY(gemm_nt_launch_batched<T>(c, ALGP_PROF_GEMM_OTHER, ppad, ppad, mbpad, (T)1, rows, mbpad, (int64_t)ppad * mbpad, rows,
-                                               mbpad, (int64_t)ppad * mbpad, (T)0, nullptr, 0, 0, GP, ppad, (int64_t)mat, 1, B));
+            ALGP_TRY(gemm_nt<T>(c, {.klass = ALGP_PROF_GEMM_OTHER, .m = ppad, .n = ppad, .k = mbpad, .A = {rows, mbpad, (int64_t)ppad * mbpad},
+                                    .B = {rows, mbpad, (int64_t)ppad * mbpad}, .D = {GP, ppad, (int64_t)mat}, .batch = B, .lower_only = 1}));
             ALGP_TRY(mi_pad_diag_launch<T>(c, GP, ppad, d_cntP, B));
             ALGP_TRY(factor_blocks_batched<T>(c, GP, ppad, inv, L21, d_ld, d_info, B));
         }
         // Q_SS over all changing sites -> G, then I + G^T D G = I + Lt LtD^T
         ALGP_TRY(mi_tri_gather_launch<T>(c, p(c->mi.Xall), npad, d_srcQ, rows, npad, (int64_t)nrow, npad));
-        ALGP_TRY(gemm_nt_launch_batched<T>(c, ALGP_PROF_GEMM_OTHER, ppad, ppad, npad, (T)1, rows, npad, (int64_t)ppad * npad, rows, npad,
-                                           (int64_t)ppad * npad, (T)0, nullptr, 0, 0, GQ, ppad, (int64_t)mat, 1, B));
+        ALGP_TRY(gemm_nt<T>(c, {.klass = ALGP_PROF_GEMM_OTHER, .m = ppad, .n = ppad, .k = npad, .A = {rows, npad, (int64_t)ppad * npad},
+                                .B = {rows, npad, (int64_t)ppad * npad}, .D = {GQ, ppad, (int64_t)mat}, .batch = B, .lower_only = 1}));
         ALGP_TRY(mi_pad_diag_launch<T>(c, GQ, ppad, d_cntQ, B));
         ALGP_TRY(factor_blocks_batched<T>(c, GQ, ppad, inv, L21, d_ld + bmax, d_info + bmax, B));
         ALGP_TRY(mi_transpose_launch<T>(c, GQ, L21, d_delta, ppad, Lt, LtD, B));
-        ALGP_TRY(gemm_nt_launch_batched<T>(c, ALGP_PROF_GEMM_OTHER, ppad, ppad, ppad, (T)1, Lt, ppad, (int64_t)mat, LtD, ppad, (int64_t)mat,
-                                           (T)1, ident, ppad, 0, GP, ppad, (int64_t)mat, 1, B));
+        ALGP_TRY(gemm_nt<T>(c, {.klass = ALGP_PROF_GEMM_OTHER, .m = ppad, .n = ppad, .k = ppad, .beta = (T)1, .A = {Lt, ppad, (int64_t)mat},
+                                .B = {LtD, ppad, (int64_t)mat}, .C = {ident, ppad}, .D = {GP, ppad, (int64_t)mat}, .batch = B, .lower_only = 1}));
         ALGP_TRY(factor_blocks_batched<T>(c, GP, ppad, inv, L21, d_ld + 2 * bmax, d_info + 2 * bmax, B));
         ALGP_HIP(hipMemcpyAsync(ld.data(), d_ld, sizeof(double) * 3 * (size_t)bmax, hipMemcpyDeviceToHost, c->stream));
         ALGP_HIP(hipMemcpyAsync(info.data(), d_info, sizeof(int) * 3 * (size_t)bmax, hipMemcpyDeviceToHost, c->stream));

@@ -215,14 +215,14 @@ int Impl<T>::score_paths_vr(algp_ctx* c, const int64_t* sites, int npaths, int m
                 ALGP_TRY(pvr_linv_launch<T>(c, inv, L21, ppad, B, Li, tr));
                 if (ppad > NB) {
                     // the lower left tile of L^-1: -inv(L22) L21 inv(L11), two products against the transposed operands
-                    ALGP_TRY(gemm_nt_launch_batched<T>(c, ALGP_PROF_GEMM_OTHER, NB, NB, NB, (T)1, inv + NB * NB, NB, 2 * NB * NB, tr, NB,
-                                                       2 * NB * NB, (T)0, nullptr, 0, 0, X, NB, NB * NB, 0, B));
-                    ALGP_TRY(gemm_nt_launch_batched<T>(c, ALGP_PROF_GEMM_OTHER, NB, NB, NB, (T)-1, X, NB, NB * NB, tr + NB * NB, NB,
-                                                       2 * NB * NB, (T)0, nullptr, 0, 0, Li + (size_t)NB * ppad, ppad, (int64_t)mat, 0, B));
+                    ALGP_TRY(gemm_nt<T>(c, {.klass = ALGP_PROF_GEMM_OTHER, .m = NB, .n = NB, .k = NB, .A = {inv + NB * NB, NB, 2 * NB * NB},
+                                            .B = {tr, NB, 2 * NB * NB}, .D = {X, NB, NB * NB}, .batch = B}));
+                    ALGP_TRY(gemm_nt<T>(c, {.klass = ALGP_PROF_GEMM_OTHER, .m = NB, .n = NB, .k = NB, .alpha = (T)-1, .A = {X, NB, NB * NB},
+                                            .B = {tr + NB * NB, NB, 2 * NB * NB}, .D = {Li + (size_t)NB * ppad, ppad, (int64_t)mat}, .batch = B}));
                 }
                 // W = L^-1 Phi_SS (Phi_SS is symmetric: the NT product's second operand as it is)
-                ALGP_TRY(gemm_nt_launch_batched<T>(c, ALGP_PROF_GEMM_OTHER, ppad, ppad, ppad, (T)1, Li, ppad, (int64_t)mat, F, ppad, (int64_t)mat,
-                                                   (T)0, nullptr, 0, 0, Wm, ppad, (int64_t)mat, 0, B));
+                ALGP_TRY(gemm_nt<T>(c, {.klass = ALGP_PROF_GEMM_OTHER, .m = ppad, .n = ppad, .k = ppad, .A = {Li, ppad, (int64_t)mat},
+                                        .B = {F, ppad, (int64_t)mat}, .D = {Wm, ppad, (int64_t)mat}, .batch = B}));
                 ALGP_TRY(pvr_trace_launch<T>(c, Wm, Li, ppad, B, d_info, d_pid, d_out));
                 ALGP_TRY(sync(c));                              // the index vectors are reused by the next batch
             }

@@ -454,17 +454,39 @@ int kmat_xy_launch(algp_ctx* c, const T* xs1, int64_t n1, const T* xs2, int64_t 
 template <typename T>
 int scale_coords_launch(algp_ctx* c, const T* x, int64_t n, T* xs);
 
-// D = alpha A B^T + beta C.  lower_only: square output, only the tiles on/below the diagonal.
+// One product D = alpha A B^T + beta C of the GEMM tile kernel, described by field name at the call site (designated
+// initialisers: gemm_nt<T>(c, {.klass = ..., .m = ..., .A = {X, ldx}, ...})); a field that a call does not use stays unwritten.
+// The library is built as C++17, where clang takes designated initialisers as an extension and warns: switched off on purpose
+// for every file that includes this header (no push / pop), since the call sites are spread over them.
+#pragma clang diagnostic ignored "-Wc++20-designator"
+template <typename P>
+struct Mat {                       // an operand: element (i, j) of problem b at p[b * stride + i * ld + j]
+    P* p = nullptr;
+    int64_t ld = 0;
+    int64_t stride = 0;
+};
+template <typename T>
+struct GemmNt {
+    int klass = 0;                 // ALGP_PROF_* class the launch is booked under
+    int64_t m = 0, n = 0, k = 0;
+    T alpha = (T)1, beta = (T)0;
+    Mat<const T> A, B, C;          // C left null: D, with D's leading dimension and stride (in place; the kernel reads C only
+                                   // where beta != 0 and C is not generated)
+    Mat<T> D;
+    int batch = 1;                 // independent problems, one operand stride apart each (grid.y)
+    int lower_only = 0;            // square output, only the tiles on / below the diagonal
+    int ktri = 0, kcut = 0;        // GemmArgs::ktri, ::kcut (gemm.hip): the k range of a tile cut by its row / its column tile
+    const T* stat_w = nullptr;     // row statistics (gemm_nt_launch_stats below): written where stat_out is set
+    T* stat_out = nullptr;
+    int64_t stat_ld = 0;
+};
+template <typename T>
+int gemm_nt(algp_ctx* c, const GemmNt<T>& p);
+// the BLAS-shaped call of one product
 template <typename T>
 int gemm_nt_launch(algp_ctx* c, int klass, int64_t m, int64_t n, int64_t k, T alpha, const T* A,
                    int64_t lda, const T* B, int64_t ldb, T beta, const T* C, int64_t ldc, T* D,
                    int64_t ldd, int lower_only);
-// the same product for `batch` independent problems at element strides sA/sB/sC/sD (grid.y = batch)
-template <typename T>
-int gemm_nt_launch_batched(algp_ctx* c, int klass, int64_t m, int64_t n, int64_t k, T alpha, const T* A, int64_t lda,
-                           int64_t sA, const T* B, int64_t ldb, int64_t sB, T beta, const T* C, int64_t ldc, int64_t sC,
-                           T* D, int64_t ldd, int64_t sD, int lower_only, int batch, int ktri = 0, const T* stat_w = nullptr,
-                           T* stat_out = nullptr, int64_t stat_ld = 0, int kcut = 0);
 // D (m x n) = A B^T, B (n x n) lower triangular by 128-tiles (column tile c sums over k < 128 (c + 1)); stat_out or null: the
 // row statistics of every column tile written (stat_out[(2 tile + 0 / 1) * stat_ld + row])
 template <typename T>

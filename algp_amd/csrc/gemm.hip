@@ -815,48 +815,113 @@ static void launch_log_line(int klass, int64_t m, int64_t n, int64_t k, int lowe
     fflush(launch_log);
 }
 
+// ---- the launch side: every form of gemm_nt_kernel_dma4 goes the same way ------------------------------------------------
+// Its launcher describes the product as a GemmNt (common.h), makes the refusals that are its own, and then
+//   gemm_check        refuses what no form can run (padding, k, leading dimensions, grid size) and counts the output tiles,
+//   gemm_fill         sets the GemmArgs base of the form's argument struct from the description,
+//   gemm_book         gives the launch's flop and byte figures and writes its line of the launch log,
+//   dispatch          enqueues a kernel with its arguments on c->cur, timed where the profiler asks for events,
+//   launch_scheduled  is the scheduled route with its finish launch (the loading and the generating form).
+// A new form costs its own fields, its own checks and one dispatch line.
 template <typename T>
-int gemm_nt_launch_batched(algp_ctx* c, int klass, int64_t m, int64_t n, int64_t k, T alpha, const T* A, int64_t lda,
-                           int64_t sA, const T* B, int64_t ldb, int64_t sB, T beta, const T* C, int64_t ldc, int64_t sC,
-                           T* D, int64_t ldd, int64_t sD, int lower_only, int batch, int ktri, const T* stat_w, T* stat_out,
-                           int64_t stat_ld, int kcut) {
-    if (m <= 0 || n <= 0 || batch <= 0) return ALGP_OK;
-    if (stat_out && (beta != (T)0 || batch != 1 || lower_only || ktri))
-        return fail(c, ALGP_ERR_BAD_ARG, "gemm_nt: row statistics need beta = 0, no batch");
-    if (kcut && (k != n || lower_only || ktri)) return fail(c, ALGP_ERR_BAD_ARG, "gemm_nt: kcut needs k == n");
-    if (m % 128 || n % 128 || k % 128 || k <= 0 || lda % 4 || ldb % 4 || sA % 4 || sB % 4)
-        return fail(c, ALGP_ERR_BAD_ARG, "gemm_nt: operands must be padded to multiples of 128");
-    if (lower_only && m != n) return fail(c, ALGP_ERR_BAD_ARG, "gemm_nt: lower_only needs a square output");
-    if (batch > 65535) return fail(c, ALGP_ERR_BAD_ARG, "gemm_nt: batch too large");
-    GemmArgs<T> g;
-    g.A = A; g.B = B; g.C = C ? C : D; g.D = D;
-    g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldd = ldd;
-    g.sA = sA; g.sB = sB; g.sC = sC; g.sD = sD;
-    g.tiles_m = (int)(m / 128);
-    g.tiles_n = (int)(n / 128);
-    g.ktiles = (int)(k / (8 * MF<T>::EPC));
-    g.alpha = alpha; g.beta = beta;
-    g.lower_only = lower_only;
-    g.ktri = ktri;
-    g.stat_w = stat_w;
-    g.stat_out = stat_out;
-    g.stat_ld = stat_ld;
-    g.kcut = kcut;
+static int gemm_check(algp_ctx* c, const char* who, const GemmNt<T>& p, int64_t* tiles) {
+    if (p.m % 128 || p.n % 128 || p.k % 128 || p.k <= 0 || p.A.ld % 4 || p.B.ld % 4 || p.A.stride % 4 || p.B.stride % 4)
+        return fail(c, ALGP_ERR_BAD_ARG, std::string(who) + ": operands must be padded to multiples of 128");
+    const int64_t tm = p.m / 128, tn = p.n / 128;
+    *tiles = p.lower_only ? tm * (tm + 1) / 2 : tm * tn;
+    if (*tiles > 0x7fffffff) return fail(c, ALGP_ERR_BAD_ARG, std::string(who) + ": grid too large");
+    return ALGP_OK;
+}
+
+template <typename T>
+static void gemm_fill(GemmArgs<T>& g, const GemmNt<T>& p) {
+    const bool inplace = !p.C.p;
+    g.A = p.A.p; g.B = p.B.p; g.C = inplace ? p.D.p : p.C.p; g.D = p.D.p;
+    g.lda = p.A.ld; g.ldb = p.B.ld; g.ldc = inplace ? p.D.ld : p.C.ld; g.ldd = p.D.ld;
+    g.sA = p.A.stride; g.sB = p.B.stride; g.sC = inplace ? p.D.stride : p.C.stride; g.sD = p.D.stride;
+    g.tiles_m = (int)(p.m / 128);
+    g.tiles_n = (int)(p.n / 128);
+    g.ktiles = (int)(p.k / (8 * MF<T>::EPC));
+    g.alpha = p.alpha; g.beta = p.beta;
+    g.lower_only = p.lower_only;
+    g.ktri = p.ktri;
+    g.kcut = p.kcut;
+    g.stat_w = p.stat_w;
+    g.stat_out = p.stat_out;
+    g.stat_ld = p.stat_ld;
     g.sch = Sched();
     g.part = nullptr;
-    if (ktri && (!lower_only || k != m)) return fail(c, ALGP_ERR_BAD_ARG, "gemm_nt: ktri needs a square lower-only product with k == m");
-    const int64_t tiles = lower_only ? (int64_t)g.tiles_m * (g.tiles_m + 1) / 2 : (int64_t)g.tiles_m * g.tiles_n;
-    if (tiles > 0x7fffffff) return fail(c, ALGP_ERR_BAD_ARG, "gemm_nt: grid too large");
+}
+
+// Once per launch, behind its refusals: the figures the profile books, and the launch's line of the launch log (written here).
+// tile_elems: what the form's epilogue moves per output tile -- a D tile or an E tile 128 x 128, D and C twice that, row sums
+// only 128
+struct Booking { double flops, bytes; };
+template <typename T>
+static Booking gemm_book(const GemmNt<T>& p, int64_t tiles, double tile_elems) {
     // ktri: tile row bm holds bm + 1 tiles of K = k - 128 bm: sum_bm (bm + 1)(tm - bm) = tm (tm + 1)(tm + 2) / 6 tile-steps of 128
-    const double tm = (double)g.tiles_m;
-    const double flops = ktri ? 2.0 * 128.0 * 128.0 * 128.0 * tm * (tm + 1.0) * (tm + 2.0) / 6.0 * batch
-                         : kcut ? 2.0 * 128.0 * 128.0 * 128.0 * tm * (double)g.tiles_n * (g.tiles_n + 1.0) / 2.0 * batch
-                              : 2.0 * 128.0 * 128.0 * (double)k * (double)tiles * batch;
-    const double bytes = sizeof(T) * batch * ((double)tiles * 128.0 * 128.0 * (beta != (T)0 ? 2.0 : 1.0) +
-                                              (double)k * 128.0 * (double)(g.tiles_m + g.tiles_n));
-    launch_log_line(klass, m, n, k, lower_only, batch, ktri, (int)sizeof(T), kcut);
+    const double tm = (double)(p.m / 128), tn = (double)(p.n / 128);
+    Booking b;
+    b.flops = p.ktri ? 2.0 * 128.0 * 128.0 * 128.0 * tm * (tm + 1.0) * (tm + 2.0) / 6.0 * p.batch
+              : p.kcut ? 2.0 * 128.0 * 128.0 * 128.0 * tm * tn * (tn + 1.0) / 2.0 * p.batch
+                       : 2.0 * 128.0 * 128.0 * (double)p.k * (double)tiles * p.batch;
+    b.bytes = sizeof(T) * p.batch * ((double)tiles * tile_elems + (double)p.k * 128.0 * (tm + tn));
+    launch_log_line(p.klass, p.m, p.n, p.k, p.lower_only, p.batch, p.ktri, (int)sizeof(T), p.kcut);
+    return b;
+}
+
+template <typename X>
+struct as_is { typedef X type; };                                  // the arguments convert to the kernel's parameter types
+template <typename... P>
+static int dispatch(algp_ctx* c, int klass, double flops, double bytes, void (*kernel)(P...), dim3 grid, const typename as_is<P>::type&... args) {
+    hipEvent_t ev_a, ev_b;
+    if (prof_launch_events(c, klass, flops, bytes, &ev_a, &ev_b)) hipExtLaunchKernelGGL(kernel, grid, dim3(256), 0, c->cur, ev_a, ev_b, 0, args...);
+    else hipLaunchKernelGGL(kernel, grid, dim3(256), 0, c->cur, args...);
+    ALGP_HIP(hipGetLastError());
+    return ALGP_OK;
+}
+
+// The scheduled form (the candidate sweep's launches, potrf.hip): 2 x CUs resident workgroups walk the tile list; the leftover
+// tiles of an update product are cut along k where the sweep has provided the partials scratch (row statistics and kcut rule
+// that out), and `finish` (its arguments behind beta: tail) then sums the S slices onto beta C -- S + 2 tile passes where C is
+// loaded, S + 1 where it is generated.
+template <typename T, typename Args, typename... Tail>
+static int launch_scheduled(algp_ctx* c, const char* who, const GemmNt<T>& p, const Booking& bk, Args& g, void (*product)(Args),
+                            void (*finish)(const T*, int, int, int, T, Tail...), bool c_loaded, const typename as_is<Tail>::type&... tail) {
+    const int slots = 2 * c->cu_count;
+    const bool split = p.beta != (T)0 && !p.stat_out && !p.kcut && c->gemm_part.p &&
+                       c->gemm_part.cap >= sizeof(T) * 128 * 128 * (size_t)slots;
+    g.sch = sched_make(slots, g.tiles_m, g.tiles_n, (int)(p.k / 128), p.kcut, split ? 1 : 0);
+    g.part = (T*)c->gemm_part.p;
+    if (g.sch.S >= 2 && (g.ldd % 4 || ((uintptr_t)g.D & 15) || (c_loaded && (g.ldc % 4 || ((uintptr_t)g.C & 15)))))
+        return fail(c, ALGP_ERR_BAD_ARG, std::string(who) + ": the finish kernel moves its tiles in 16-byte pieces");
+    ALGP_TRY(dispatch(c, p.klass, bk.flops, bk.bytes, product, dim3((unsigned)g.sch.G), g));
+    if (g.sch.S >= 2)
+        ALGP_TRY(dispatch(c, p.klass, 0.0, sizeof(T) * 128.0 * 128.0 * (double)g.sch.left * (g.sch.S + (c_loaded ? 2.0 : 1.0)), finish,
+                          dim3((unsigned)(g.sch.left * FIN_STRIPS)), g.part, g.sch.S, g.sch.full, g.tiles_n, g.beta, tail...));
+    return ALGP_OK;
+}
+
+template <typename T>
+int gemm_nt(algp_ctx* c, const GemmNt<T>& p) {
+    if (p.m <= 0 || p.n <= 0 || p.batch <= 0) return ALGP_OK;
+    if (p.stat_out && (p.beta != (T)0 || p.batch != 1 || p.lower_only || p.ktri))
+        return fail(c, ALGP_ERR_BAD_ARG, "gemm_nt: row statistics need beta = 0, no batch");
+    if (p.kcut && (p.k != p.n || p.lower_only || p.ktri)) return fail(c, ALGP_ERR_BAD_ARG, "gemm_nt: kcut needs k == n");
+    int64_t tiles;
+    ALGP_TRY(gemm_check(c, "gemm_nt", p, &tiles));
+    if (p.lower_only && p.m != p.n) return fail(c, ALGP_ERR_BAD_ARG, "gemm_nt: lower_only needs a square output");
+    if (p.batch > 65535) return fail(c, ALGP_ERR_BAD_ARG, "gemm_nt: batch too large");
+    if (p.ktri && (!p.lower_only || p.k != p.m)) return fail(c, ALGP_ERR_BAD_ARG, "gemm_nt: ktri needs a square lower-only product with k == m");
+    GemmArgs<T> g;
+    gemm_fill(g, p);
+    const Booking bk = gemm_book(p, tiles, 128.0 * 128.0 * (p.beta != (T)0 ? 2.0 : 1.0));
+    if (c->gemm_sched && c->cu_count > 0 && !p.lower_only && !p.ktri && p.batch == 1)
+        return launch_scheduled(c, "gemm_nt", p, bk, g,
+                                p.stat_out ? gemm_nt_kernel_dma4<T, true, GemmArgs<T>, true> : gemm_nt_kernel_dma4<T, false, GemmArgs<T>, true>,
+                                gemm_finish_kernel<T>, true, g.C, g.ldc, g.D, g.ldd);
     int64_t gx = tiles;
-    if (ktri) {                                                    // 8 x the largest per-XCD share (rows x, x + 8, ... of XCD x)
+    if (p.ktri) {                                                  // 8 x the largest per-XCD share (rows x, x + 8, ... of XCD x)
         int64_t most = 0;
         for (int x = 0; x < 8; ++x) {
             int64_t cnt = 0;
@@ -865,50 +930,8 @@ int gemm_nt_launch_batched(algp_ctx* c, int klass, int64_t m, int64_t n, int64_t
         }
         gx = 8 * most;
     }
-    hipEvent_t ev_a, ev_b;
-    if (c->gemm_sched && c->cu_count > 0 && !lower_only && !ktri && batch == 1) {
-        // the scheduled form (the candidate sweep's launches, potrf.hip): 2 x CUs resident workgroups walk the tile list; the
-        // leftover tiles of an update product are cut along k where the sweep has provided the partials scratch
-        const int slots = 2 * c->cu_count;
-        const bool split = beta != (T)0 && !stat_out && !kcut && c->gemm_part.p &&
-                           c->gemm_part.cap >= sizeof(T) * 128 * 128 * (size_t)slots;
-        g.sch = sched_make(slots, g.tiles_m, g.tiles_n, (int)(k / 128), kcut, split ? 1 : 0);
-        g.part = (T*)c->gemm_part.p;
-        if (g.sch.S >= 2 && (ldc % 4 || ldd % 4 || (((uintptr_t)g.C | (uintptr_t)D) & 15)))
-            return fail(c, ALGP_ERR_BAD_ARG, "gemm_nt: the finish kernel reads C and writes D in 16-byte pieces");
-        const dim3 sgrid((unsigned)g.sch.G);
-        const bool timed = prof_launch_events(c, klass, flops, bytes, &ev_a, &ev_b);
-        if (stat_out) {
-            if (timed) hipExtLaunchKernelGGL((gemm_nt_kernel_dma4<T, true, GemmArgs<T>, true>), sgrid, dim3(256), 0, c->cur, ev_a, ev_b, 0, g);
-            else hipLaunchKernelGGL((gemm_nt_kernel_dma4<T, true, GemmArgs<T>, true>), sgrid, dim3(256), 0, c->cur, g);
-        } else {
-            if (timed) hipExtLaunchKernelGGL((gemm_nt_kernel_dma4<T, false, GemmArgs<T>, true>), sgrid, dim3(256), 0, c->cur, ev_a, ev_b, 0, g);
-            else hipLaunchKernelGGL((gemm_nt_kernel_dma4<T, false, GemmArgs<T>, true>), sgrid, dim3(256), 0, c->cur, g);
-        }
-        ALGP_HIP(hipGetLastError());
-        if (g.sch.S >= 2) {
-            const double fbytes = sizeof(T) * 128.0 * 128.0 * (double)g.sch.left * (g.sch.S + 2.0);
-            const bool ftimed = prof_launch_events(c, klass, 0.0, fbytes, &ev_a, &ev_b);
-            const dim3 fgrid((unsigned)(g.sch.left * FIN_STRIPS));
-            if (ftimed) hipExtLaunchKernelGGL(gemm_finish_kernel<T>, fgrid, dim3(256), 0, c->cur, ev_a, ev_b, 0, (const T*)g.part, g.sch.S,
-                                              g.sch.full, g.tiles_n, beta, g.C, ldc, D, ldd);
-            else hipLaunchKernelGGL(gemm_finish_kernel<T>, fgrid, dim3(256), 0, c->cur, (const T*)g.part, g.sch.S, g.sch.full, g.tiles_n,
-                                    beta, g.C, ldc, D, ldd);
-            ALGP_HIP(hipGetLastError());
-        }
-        return ALGP_OK;
-    }
-    const dim3 grid((unsigned)gx, (unsigned)batch);
-    const bool timed = prof_launch_events(c, klass, flops, bytes, &ev_a, &ev_b);
-    if (stat_out) {
-        if (timed) hipExtLaunchKernelGGL((gemm_nt_kernel_dma4<T, true>), grid, dim3(256), 0, c->cur, ev_a, ev_b, 0, g);
-        else hipLaunchKernelGGL((gemm_nt_kernel_dma4<T, true>), grid, dim3(256), 0, c->cur, g);
-    } else {
-        if (timed) hipExtLaunchKernelGGL((gemm_nt_kernel_dma4<T, false>), grid, dim3(256), 0, c->cur, ev_a, ev_b, 0, g);
-        else hipLaunchKernelGGL((gemm_nt_kernel_dma4<T, false>), grid, dim3(256), 0, c->cur, g);
-    }
-    ALGP_HIP(hipGetLastError());
-    return ALGP_OK;
+    return dispatch(c, p.klass, bk.flops, bk.bytes, p.stat_out ? gemm_nt_kernel_dma4<T, true> : gemm_nt_kernel_dma4<T, false>,
+                    dim3((unsigned)gx, (unsigned)p.batch), g);
 }
 
 bool rhs_gen_supported(int DP, bool pool_is_cov) { return DP == 2 && !pool_is_cov; }
@@ -921,53 +944,29 @@ int gemm_nt_launch_gen(algp_ctx* c, int klass, int64_t m, int64_t n, int64_t k, 
     if (m <= 0 || n <= 0) return ALGP_OK;
     if (!c->gemm_sched || c->cu_count <= 0 || !rhs_gen_supported(gen.DP, false) || !gen.rx || !gen.cx || !gen.rk)
         return fail(c, ALGP_ERR_BAD_ARG, "gemm_nt_gen: the scheduled form with two gathered coordinates only");
-    if (m % 128 || n % 128 || k % 128 || k <= 0 || lda % 4 || ldb % 4 || col0 < 0)
-        return fail(c, ALGP_ERR_BAD_ARG, "gemm_nt_gen: operands must be padded to multiples of 128");
+    if (col0 < 0) return fail(c, ALGP_ERR_BAD_ARG, "gemm_nt_gen: operands must be padded to multiples of 128");
+    const GemmNt<T> p = {.klass = klass, .m = m, .n = n, .k = k, .alpha = alpha, .beta = beta, .A = {A, lda}, .B = {B, ldb}, .D = {D, ldd}};
+    int64_t tiles;
+    ALGP_TRY(gemm_check(c, "gemm_nt_gen", p, &tiles));
     GenGemmArgs<T, 2> g;
-    g.A = A; g.B = B; g.C = nullptr; g.D = D;
-    g.lda = lda; g.ldb = ldb; g.ldc = 0; g.ldd = ldd;
-    g.sA = g.sB = g.sC = g.sD = 0;
-    g.tiles_m = (int)(m / 128);
-    g.tiles_n = (int)(n / 128);
-    g.ktiles = (int)(k / (8 * MF<T>::EPC));
-    g.alpha = alpha; g.beta = beta;
-    g.lower_only = 0; g.ktri = 0; g.kcut = 0;
-    g.stat_w = nullptr; g.stat_out = nullptr; g.stat_ld = 0;
+    gemm_fill(g, p);                                               // (C, not read by this form, is D's pointer and strides)
     g.rx = (const T*)gen.rx; g.cx = (const T*)gen.cx; g.rk = gen.rk;
     g.col0 = col0; g.ncols = gen.ncols; g.kernel = gen.kernel; g.os = (T)gen.outputscale;
-    const int64_t tiles = (int64_t)g.tiles_m * g.tiles_n;
-    if (tiles > 0x7fffffff) return fail(c, ALGP_ERR_BAD_ARG, "gemm_nt_gen: grid too large");
-    const double flops = 2.0 * 128.0 * 128.0 * (double)k * (double)tiles;
-    const double bytes = sizeof(T) * ((double)tiles * 128.0 * 128.0 + (double)k * 128.0 * (double)(g.tiles_m + g.tiles_n));
-    launch_log_line(klass, m, n, k, 0, 1, 0, (int)sizeof(T), 0);
-    const int slots = 2 * c->cu_count;
-    const bool split = beta != (T)0 && c->gemm_part.p && c->gemm_part.cap >= sizeof(T) * 128 * 128 * (size_t)slots;   // as the loading form
-    g.sch = sched_make(slots, g.tiles_m, g.tiles_n, (int)(k / 128), 0, split ? 1 : 0);
-    g.part = (T*)c->gemm_part.p;
-    if (g.sch.S >= 2 && (ldd % 4 || ((uintptr_t)D & 15)))
-        return fail(c, ALGP_ERR_BAD_ARG, "gemm_nt_gen: the finish kernel writes D in 16-byte pieces");
-    hipEvent_t ev_a, ev_b;
-    const dim3 sgrid((unsigned)g.sch.G);
-    const bool timed = prof_launch_events(c, klass, flops, bytes, &ev_a, &ev_b);
-    if (timed) hipExtLaunchKernelGGL((gemm_nt_kernel_dma4<T, false, GenGemmArgs<T, 2>, true>), sgrid, dim3(256), 0, c->cur, ev_a, ev_b, 0, g);
-    else hipLaunchKernelGGL((gemm_nt_kernel_dma4<T, false, GenGemmArgs<T, 2>, true>), sgrid, dim3(256), 0, c->cur, g);
-    ALGP_HIP(hipGetLastError());
-    if (g.sch.S >= 2) {
-        const double fbytes = sizeof(T) * 128.0 * 128.0 * (double)g.sch.left * (g.sch.S + 1.0);
-        const bool ftimed = prof_launch_events(c, klass, 0.0, fbytes, &ev_a, &ev_b);
-        const dim3 fgrid((unsigned)(g.sch.left * FIN_STRIPS));
-        if (ftimed) hipExtLaunchKernelGGL((gemm_finish_gen_kernel<T, 2>), fgrid, dim3(256), 0, c->cur, ev_a, ev_b, 0, (const T*)g.part, g.sch.S,
-                                          g.sch.full, g.tiles_n, beta, g.rx, g.cx, g.rk, col0, g.ncols, g.kernel, g.os, D, ldd);
-        else hipLaunchKernelGGL((gemm_finish_gen_kernel<T, 2>), fgrid, dim3(256), 0, c->cur, (const T*)g.part, g.sch.S, g.sch.full, g.tiles_n,
-                                beta, g.rx, g.cx, g.rk, col0, g.ncols, g.kernel, g.os, D, ldd);
-        ALGP_HIP(hipGetLastError());
-    }
-    return ALGP_OK;
+    return launch_scheduled(c, "gemm_nt_gen", p, gemm_book(p, tiles, 128.0 * 128.0), g, gemm_nt_kernel_dma4<T, false, GenGemmArgs<T, 2>, true>,
+                            gemm_finish_gen_kernel<T, 2>, false, g.rx, g.cx, g.rk, col0, g.ncols, g.kernel, g.os, D, ldd);
 }
 template int gemm_nt_launch_gen<double>(algp_ctx*, int, int64_t, int64_t, int64_t, double, const double*, int64_t, const double*, int64_t,
                                         double, const RhsGen&, int64_t, double*, int64_t);
 template int gemm_nt_launch_gen<float>(algp_ctx*, int, int64_t, int64_t, int64_t, float, const float*, int64_t, const float*, int64_t, float,
                                        const RhsGen&, int64_t, float*, int64_t);
+
+// the fields the two variance-reduction forms share
+template <typename T>
+static void vr_fill(VrGemmArgs<T>& g, const KmatSrc& s, const int64_t* cidx, const int* ckind, int64_t M, int64_t ncol0, const T* tw) {
+    g.cidx = cidx; g.ckind = ckind; g.M = M; g.ncol0 = ncol0; g.tw = tw;
+    g.Xs = (const T*)s.Xs; g.Cp = (const T*)s.Cp; g.n_pool = s.n_pool; g.DP = s.DP; g.kernel = s.kernel;
+    g.os = (T)s.outputscale; g.noise = (T)s.noise;
+}
 
 // The variance-reduction column sums of rows [0, mpad) of V^T against its rows [ncol0, ncol0 + n): per row and column
 // tile bn of the launch, part[bn * part_ld + row] = sum over the tile's target columns j of (kappa_row C(row, j) - V_row . V_j)^2,
@@ -977,41 +976,19 @@ template <typename T>
 int gemm_nt_launch_vr(algp_ctx* c, int klass, int64_t mpad, int64_t n, int64_t k, const T* Vt, int64_t ldv, int64_t ncol0,
                       const KmatSrc& s, const int64_t* cidx, const int* ckind, int64_t M, const T* tw, T* part, int64_t part_ld) {
     if (mpad <= 0 || n <= 0) return ALGP_OK;
-    if (mpad % 128 || n % 128 || k % 128 || k <= 0 || ldv % 4 || ncol0 % 128 || ncol0 + n > mpad || k > ldv || s.DP > MAXD)
+    if (ncol0 % 128 || ncol0 + n > mpad || k > ldv || s.DP > MAXD)
         return fail(c, ALGP_ERR_BAD_ARG, "gemm_nt_vr: operands must be padded to multiples of 128");
+    const GemmNt<T> p = {.klass = klass, .m = mpad, .n = n, .k = k, .A = {Vt, ldv}, .B = {Vt + ncol0 * ldv, ldv}, .stat_out = part, .stat_ld = part_ld};
+    int64_t tiles;
+    ALGP_TRY(gemm_check(c, "gemm_nt_vr", p, &tiles));
     VrGemmArgs<T> g;
-    g.A = Vt; g.B = Vt + ncol0 * ldv; g.C = nullptr; g.D = nullptr;
-    g.lda = ldv; g.ldb = ldv; g.ldc = 0; g.ldd = 0;
-    g.sA = g.sB = g.sC = g.sD = 0;
-    g.tiles_m = (int)(mpad / 128);
-    g.tiles_n = (int)(n / 128);
-    g.ktiles = (int)(k / (8 * MF<T>::EPC));
-    g.alpha = (T)1; g.beta = (T)0;
-    g.lower_only = 0; g.ktri = 0; g.kcut = 0;
-    g.stat_w = nullptr; g.stat_out = part; g.stat_ld = part_ld;
-    g.sch = Sched(); g.part = nullptr;
-    g.cidx = cidx; g.ckind = ckind; g.M = M; g.ncol0 = ncol0; g.tw = tw;
-    g.Xs = (const T*)s.Xs; g.Cp = (const T*)s.Cp; g.n_pool = s.n_pool; g.DP = s.DP; g.kernel = s.kernel;
-    g.os = (T)s.outputscale; g.noise = (T)s.noise;
-    const int64_t tiles = (int64_t)g.tiles_m * g.tiles_n;
-    if (tiles > 0x7fffffff) return fail(c, ALGP_ERR_BAD_ARG, "gemm_nt_vr: grid too large");
-    const double flops = 2.0 * 128.0 * 128.0 * (double)k * (double)tiles;
-    const double bytes = sizeof(T) * ((double)k * 128.0 * (double)(g.tiles_m + g.tiles_n) + 128.0 * (double)tiles);
-    launch_log_line(klass, mpad, n, k, 0, 1, 0, (int)sizeof(T), 0);
-    hipEvent_t ev_a, ev_b;
-    const bool timed = prof_launch_events(c, klass, flops, bytes, &ev_a, &ev_b);
-    const dim3 grid((unsigned)tiles);
-    if (!tw) {
-        if (timed) hipExtLaunchKernelGGL((gemm_nt_kernel_dma4<T, false, VrGemmArgs<T>>), grid, dim3(256), 0, c->cur, ev_a, ev_b, 0, g);
-        else hipLaunchKernelGGL((gemm_nt_kernel_dma4<T, false, VrGemmArgs<T>>), grid, dim3(256), 0, c->cur, g);
-    } else {
-        VrWGemmArgs<T> gw;
-        static_cast<VrGemmArgs<T>&>(gw) = g;
-        if (timed) hipExtLaunchKernelGGL((gemm_nt_kernel_dma4<T, false, VrWGemmArgs<T>>), grid, dim3(256), 0, c->cur, ev_a, ev_b, 0, gw);
-        else hipLaunchKernelGGL((gemm_nt_kernel_dma4<T, false, VrWGemmArgs<T>>), grid, dim3(256), 0, c->cur, gw);
-    }
-    ALGP_HIP(hipGetLastError());
-    return ALGP_OK;
+    gemm_fill(g, p);
+    vr_fill(g, s, cidx, ckind, M, ncol0, tw);
+    const Booking bk = gemm_book(p, tiles, 128.0);
+    if (!tw) return dispatch(c, klass, bk.flops, bk.bytes, gemm_nt_kernel_dma4<T, false, VrGemmArgs<T>>, dim3((unsigned)tiles), g);
+    VrWGemmArgs<T> gw;
+    static_cast<VrGemmArgs<T>&>(gw) = g;
+    return dispatch(c, klass, bk.flops, bk.bytes, gemm_nt_kernel_dma4<T, false, VrWGemmArgs<T>>, dim3((unsigned)tiles), gw);
 }
 template int gemm_nt_launch_vr<double>(algp_ctx*, int, int64_t, int64_t, int64_t, const double*, int64_t, int64_t, const KmatSrc&,
                                        const int64_t*, const int*, int64_t, const double*, double*, int64_t);
@@ -1026,36 +1003,17 @@ int gemm_nt_launch_pvr(algp_ctx* c, int klass, int64_t upad, int64_t n, int64_t 
                        int64_t ncol0, const KmatSrc& s, const int64_t* uidx, int64_t U, const int64_t* cidx, const int* ckind, int64_t M,
                        const T* tw, T* E, int64_t lde) {
     if (upad <= 0 || n <= 0) return ALGP_OK;
-    if (upad % 128 || n % 128 || k % 128 || k <= 0 || ldr % 4 || ldv % 4 || ncol0 % 128 || ncol0 + n > (M + 127) / 128 * 128 || k > ldv || k > ldr || U > upad || lde < n ||
-        s.DP > MAXD)
+    if (ncol0 % 128 || ncol0 + n > (M + 127) / 128 * 128 || k > ldv || k > ldr || U > upad || lde < n || s.DP > MAXD)
         return fail(c, ALGP_ERR_BAD_ARG, "gemm_nt_pvr: operands must be padded to multiples of 128");
+    const GemmNt<T> p = {.klass = klass, .m = upad, .n = n, .k = k, .A = {R, ldr}, .B = {Vt + ncol0 * ldv, ldv}};
+    int64_t tiles;
+    ALGP_TRY(gemm_check(c, "gemm_nt_pvr", p, &tiles));
     PvrGemmArgs<T> g;
-    g.A = R; g.B = Vt + ncol0 * ldv; g.C = nullptr; g.D = nullptr;
-    g.lda = ldr; g.ldb = ldv; g.ldc = 0; g.ldd = 0;
-    g.sA = g.sB = g.sC = g.sD = 0;
-    g.tiles_m = (int)(upad / 128);
-    g.tiles_n = (int)(n / 128);
-    g.ktiles = (int)(k / (8 * MF<T>::EPC));
-    g.alpha = (T)1; g.beta = (T)0;
-    g.lower_only = 0; g.ktri = 0; g.kcut = 0;
-    g.stat_w = nullptr; g.stat_out = nullptr; g.stat_ld = 0;
-    g.sch = Sched(); g.part = nullptr;
-    g.cidx = cidx; g.ckind = ckind; g.M = M; g.ncol0 = ncol0; g.tw = tw;
-    g.Xs = (const T*)s.Xs; g.Cp = (const T*)s.Cp; g.n_pool = s.n_pool; g.DP = s.DP; g.kernel = s.kernel;
-    g.os = (T)s.outputscale; g.noise = (T)s.noise;
+    gemm_fill(g, p);
+    vr_fill(g, s, cidx, ckind, M, ncol0, tw);
     g.uidx = uidx; g.U = U; g.E = E; g.lde = lde;
-    const int64_t tiles = (int64_t)g.tiles_m * g.tiles_n;
-    if (tiles > 0x7fffffff) return fail(c, ALGP_ERR_BAD_ARG, "gemm_nt_pvr: grid too large");
-    const double flops = 2.0 * 128.0 * 128.0 * (double)k * (double)tiles;
-    const double bytes = sizeof(T) * ((double)k * 128.0 * (double)(g.tiles_m + g.tiles_n) + 128.0 * 128.0 * (double)tiles);
-    launch_log_line(klass, upad, n, k, 0, 1, 0, (int)sizeof(T), 0);
-    hipEvent_t ev_a, ev_b;
-    const bool timed = prof_launch_events(c, klass, flops, bytes, &ev_a, &ev_b);
-    const dim3 grid((unsigned)tiles);
-    if (timed) hipExtLaunchKernelGGL((gemm_nt_kernel_dma4<T, false, PvrGemmArgs<T>>), grid, dim3(256), 0, c->cur, ev_a, ev_b, 0, g);
-    else hipLaunchKernelGGL((gemm_nt_kernel_dma4<T, false, PvrGemmArgs<T>>), grid, dim3(256), 0, c->cur, g);
-    ALGP_HIP(hipGetLastError());
-    return ALGP_OK;
+    const Booking bk = gemm_book(p, tiles, 128.0 * 128.0);
+    return dispatch(c, klass, bk.flops, bk.bytes, gemm_nt_kernel_dma4<T, false, PvrGemmArgs<T>>, dim3((unsigned)tiles), g);
 }
 template int gemm_nt_launch_pvr<double>(algp_ctx*, int, int64_t, int64_t, int64_t, const double*, int64_t, const double*, int64_t, int64_t,
                                         const KmatSrc&, const int64_t*, int64_t, const int64_t*, const int*, int64_t, const double*, double*,
@@ -1068,23 +1026,23 @@ template <typename T>
 int gemm_nt_launch(algp_ctx* c, int klass, int64_t m, int64_t n, int64_t k, T alpha, const T* A,
                    int64_t lda, const T* B, int64_t ldb, T beta, const T* C, int64_t ldc, T* D,
                    int64_t ldd, int lower_only) {
-    return gemm_nt_launch_batched<T>(c, klass, m, n, k, alpha, A, lda, 0, B, ldb, 0, beta, C, ldc, 0, D, ldd, 0,
-                                     lower_only, 1, 0, nullptr, nullptr, 0, 0);
+    return gemm_nt<T>(c, {.klass = klass, .m = m, .n = n, .k = k, .alpha = alpha, .beta = beta, .A = {A, lda}, .B = {B, ldb}, .C = {C, ldc},
+                          .D = {D, ldd}, .lower_only = lower_only});
 }
 // D = alpha A B^T for ONE column tile (n = 128), and per output row the sums of d^2 and d * w[column] over the tile
 template <typename T>
 int gemm_nt_launch_stats(algp_ctx* c, int klass, int64_t m, int64_t k, T alpha, const T* A, int64_t lda, const T* B, int64_t ldb,
                          T* D, int64_t ldd, const T* w, T* stat_out, int64_t stat_ld) {
-    return gemm_nt_launch_batched<T>(c, klass, m, 128, k, alpha, A, lda, 0, B, ldb, 0, (T)0, nullptr, 0, 0, D, ldd, 0, 0, 1, 0, w,
-                                     stat_out, stat_ld, 0);
+    return gemm_nt<T>(c, {.klass = klass, .m = m, .n = 128, .k = k, .alpha = alpha, .A = {A, lda}, .B = {B, ldb}, .D = {D, ldd},
+                          .stat_w = w, .stat_out = stat_out, .stat_ld = stat_ld});
 }
 // D (m x n) = A B^T with B (n x n) lower triangular by 128-tiles -- X_J = T inv(L_JJ)^T with the explicit inverse of a 512-column
 // block: column tile c walks k < 128 (c + 1) only; stat_out (or null): the row statistics of every column tile as above
 template <typename T>
 int gemm_nt_launch_tri(algp_ctx* c, int klass, int64_t m, int64_t n, const T* A, int64_t lda, const T* B, int64_t ldb, T* D,
                        int64_t ldd, const T* w, T* stat_out, int64_t stat_ld) {
-    return gemm_nt_launch_batched<T>(c, klass, m, n, n, (T)1, A, lda, 0, B, ldb, 0, (T)0, nullptr, 0, 0, D, ldd, 0, 0, 1, 0,
-                                     stat_out ? w : nullptr, stat_out, stat_ld, 1);
+    return gemm_nt<T>(c, {.klass = klass, .m = m, .n = n, .k = n, .A = {A, lda}, .B = {B, ldb}, .D = {D, ldd}, .kcut = 1,
+                          .stat_w = stat_out ? w : nullptr, .stat_out = stat_out, .stat_ld = stat_ld});
 }
 template int gemm_nt_launch_tri<double>(algp_ctx*, int, int64_t, int64_t, const double*, int64_t, const double*, int64_t, double*,
                                         int64_t, const double*, double*, int64_t);
@@ -1099,12 +1057,9 @@ template int gemm_nt_launch<double>(algp_ctx*, int, int64_t, int64_t, int64_t, d
                                     const double*, int64_t, double, const double*, int64_t, double*, int64_t, int);
 template int gemm_nt_launch<float>(algp_ctx*, int, int64_t, int64_t, int64_t, float, const float*, int64_t,
                                    const float*, int64_t, float, const float*, int64_t, float*, int64_t, int);
-template int gemm_nt_launch_batched<double>(algp_ctx*, int, int64_t, int64_t, int64_t, double, const double*, int64_t,
-                                            int64_t, const double*, int64_t, int64_t, double, const double*, int64_t,
-                                            int64_t, double*, int64_t, int64_t, int, int, int, const double*, double*, int64_t, int);
-template int gemm_nt_launch_batched<float>(algp_ctx*, int, int64_t, int64_t, int64_t, float, const float*, int64_t,
-                                           int64_t, const float*, int64_t, int64_t, float, const float*, int64_t, int64_t,
-                                           float*, int64_t, int64_t, int, int, int, const float*, float*, int64_t, int);
+// (last: the object file holds the kernels in the order in which these instantiations first name them)
+template int gemm_nt<double>(algp_ctx*, const GemmNt<double>&);
+template int gemm_nt<float>(algp_ctx*, const GemmNt<float>&);
 
 // ---------------------------------------------------------------------------------------------
 // MFMA fragment-layout probe (exact integer data, asymmetric B).

@@ -200,19 +200,19 @@ static int build_inv512(algp_ctx* c, int klass, const T* L, int64_t ldl, const T
     // level 1: tiles (1, 0) and (3, 2)
     for (int lo = 0; lo < 4; lo += 2) {
         const int hi = lo + 1;
-        ALGP_TRY(gemm_nt_launch_batched<T>(c, klass, NB, NB, NB, (T)1, DT + (int64_t)lo * NB * NB, NB, sD, L1 + (int64_t)(NB * hi) * ldl + NB * lo,
-                                           ldl, sL, (T)0, nullptr, 0, 0, PT1, NB, (int64_t)NB * NB, 0, nb));
-        ALGP_TRY(gemm_nt_launch_batched<T>(c, klass, NB, NB, NB, (T)-1, D1 + (int64_t)hi * NB * NB, NB, sD, PT1, NB, (int64_t)NB * NB, (T)0,
-                                           nullptr, 0, 0, out + (int64_t)(NB * hi) * WB + NB * lo, WB, sO, 0, nb));
+        ALGP_TRY(gemm_nt<T>(c, {.klass = klass, .m = NB, .n = NB, .k = NB, .A = {DT + (int64_t)lo * NB * NB, NB, sD},
+                                .B = {L1 + (int64_t)(NB * hi) * ldl + NB * lo, ldl, sL}, .D = {PT1, NB, (int64_t)NB * NB}, .batch = nb}));
+        ALGP_TRY(gemm_nt<T>(c, {.klass = klass, .m = NB, .n = NB, .k = NB, .alpha = (T)-1, .A = {D1 + (int64_t)hi * NB * NB, NB, sD},
+                                .B = {PT1, NB, (int64_t)NB * NB}, .D = {out + (int64_t)(NB * hi) * WB + NB * lo, WB, sO}, .batch = nb}));
     }
     // level 2: the 256 x 256 block (2..3, 0..1)
     hipLaunchKernelGGL(transpose_tiles_kernel<T>, dim3(8, 8, (unsigned)nb), dim3(256), 0, c->cur, out, (int64_t)WB, sO, XT, (int64_t)256,
                        (int64_t)256 * 256);
     ALGP_HIP(hipGetLastError());
-    ALGP_TRY(gemm_nt_launch_batched<T>(c, klass, 256, 256, 256, (T)1, XT, 256, (int64_t)256 * 256, L1 + (int64_t)256 * ldl, ldl, sL, (T)0,
-                                       nullptr, 0, 0, PT2, 256, (int64_t)256 * 256, 0, nb));
-    ALGP_TRY(gemm_nt_launch_batched<T>(c, klass, 256, 256, 256, (T)-1, out + (int64_t)256 * WB + 256, WB, sO, PT2, 256, (int64_t)256 * 256, (T)0,
-                                       nullptr, 0, 0, out + (int64_t)256 * WB, WB, sO, 0, nb));
+    ALGP_TRY(gemm_nt<T>(c, {.klass = klass, .m = 256, .n = 256, .k = 256, .A = {XT, 256, (int64_t)256 * 256},
+                            .B = {L1 + (int64_t)256 * ldl, ldl, sL}, .D = {PT2, 256, (int64_t)256 * 256}, .batch = nb}));
+    ALGP_TRY(gemm_nt<T>(c, {.klass = klass, .m = 256, .n = 256, .k = 256, .alpha = (T)-1, .A = {out + (int64_t)256 * WB + 256, WB, sO},
+                            .B = {PT2, 256, (int64_t)256 * 256}, .D = {out + (int64_t)256 * WB, WB, sO}, .batch = nb}));
     return ALGP_OK;
 }
 template <typename T>
@@ -431,7 +431,7 @@ template int trinv_upper_inplace<float>(algp_ctx*, int, float*, int64_t, int64_t
 // 512-wide column panels of X, 20 launches whose first few hold fewer tiles than the machine has slots.)
 template <typename T>
 int syrk_upper(algp_ctx* c, int klass, const T* X, int64_t npad, int64_t ldx, T* C, int64_t ldc) {
-    return gemm_nt_launch_batched<T>(c, klass, npad, npad, npad, (T)1, X, ldx, 0, X, ldx, 0, (T)0, nullptr, ldc, 0, C, ldc, 0, 1, 1, 1);
+    return gemm_nt<T>(c, {.klass = klass, .m = npad, .n = npad, .k = npad, .A = {X, ldx}, .B = {X, ldx}, .D = {C, ldc}, .lower_only = 1, .ktri = 1});
 }
 template int syrk_upper<double>(algp_ctx*, int, const double*, int64_t, int64_t, double*, int64_t);
 template int syrk_upper<float>(algp_ctx*, int, const float*, int64_t, int64_t, float*, int64_t);
@@ -588,8 +588,8 @@ int syrk_skinny_sub(algp_ctx* c, int klass, const T* X, int64_t m, int64_t k, in
         return gemm_nt_launch<T>(c, klass, m, m, k, (T)-1, X, ldx, X, ldx, (T)1, C, ldc, C, ldc, 1);
     ALGP_TRY(ensure(c, scratch, sizeof(T) * (size_t)(nfull + 1) * m * m));
     T* P = (T*)scratch.p;
-    ALGP_TRY(gemm_nt_launch_batched<T>(c, klass, m, m, per * NB, (T)1, X, ldx, per * NB, X, ldx, per * NB, (T)0, nullptr, m,
-                                       m * m, P, m, m * m, 1, (int)nfull));
+    ALGP_TRY(gemm_nt<T>(c, {.klass = klass, .m = m, .n = m, .k = per * NB, .A = {X, ldx, per * NB}, .B = {X, ldx, per * NB},
+                            .D = {P, m, m * m}, .batch = (int)nfull, .lower_only = 1}));
     int nch = (int)nfull;
     if (rem > 0) {
         ALGP_TRY(gemm_nt_launch<T>(c, klass, m, m, rem * NB, (T)1, X + nfull * per * NB, ldx, X + nfull * per * NB, ldx,
@@ -618,8 +618,8 @@ int gemm_splitk_sub(algp_ctx* c, int klass, int64_t m, int64_t n, int64_t k, con
         return gemm_nt_launch<T>(c, klass, m, n, k, (T)-1, A, lda, B, ldb, (T)1, C, ldc, C, ldc, 0);
     ALGP_TRY(ensure(c, scratch, sizeof(T) * (size_t)(nfull + 1) * m * n));
     T* P = (T*)scratch.p;
-    ALGP_TRY(gemm_nt_launch_batched<T>(c, klass, m, n, per * NB, (T)1, A, lda, per * NB, B, ldb, per * NB, (T)0, nullptr, n,
-                                       m * n, P, n, m * n, 0, (int)nfull));
+    ALGP_TRY(gemm_nt<T>(c, {.klass = klass, .m = m, .n = n, .k = per * NB, .A = {A, lda, per * NB}, .B = {B, ldb, per * NB},
+                            .D = {P, n, m * n}, .batch = (int)nfull}));
     int nch = (int)nfull;
     if (rem > 0) {
         ALGP_TRY(gemm_nt_launch<T>(c, klass, m, n, rem * NB, (T)1, A + nfull * per * NB, lda, B + nfull * per * NB, ldb,
