@@ -96,6 +96,7 @@ SIGNATURES = {
     'algp_comm_destroy': (C.c_int, [_c_ctx]),
     'algp_comm_set_owners': (C.c_int, [_c_ctx, C.POINTER(C.c_int32), C.c_int64]),
     'algp_comm_set_mi_groups': (C.c_int, [_c_ctx, C.c_int]),
+    'algp_comm_set_vr_exchange': (C.c_int, [_c_ctx, C.c_int64]),
     'algp_debug_first_max': (C.c_int, [_c_ctx, _dblp, C.c_int, _dblp]),
     'algp_debug_fail_next_pick': (C.c_int, [_c_ctx, C.c_int]),
     'algp_debug_set_trsm_chunks': (C.c_int, [_c_ctx, C.c_int]),
@@ -525,6 +526,14 @@ class Context(object):
         comm_init[_host] (algp_comm_set_mi_groups)."""
         self._check(self.lib.algp_comm_set_mi_groups(self.h, int(n_complement_ranks)))
 
+    def comm_set_vr_exchange(self, rows_per_round=-1):
+        """The variance-reduction criterion's layout over the ranks: how many rows of its V^T every rank contributes to each
+        all-gather of the build (rounded up to 128; -1: the library's default, a staging buffer within 1 GiB; 0 detaches).
+        Every rank, the same value, after comm_init[_host].  With it attached and more than one rank, greedy_sharded accepts the
+        criterion, its targets are the ordinary rows of every rank's shard, and scores() under it is a collective that returns
+        this rank's rows' utilities against all of them (algp_comm_set_vr_exchange)."""
+        self._check(self.lib.algp_comm_set_vr_exchange(self.h, int(rows_per_round)))
+
     def counter(self, which):
         """algp_debug_counter: 0 stream synchronisations so far | 1 rows of L the last factor update placed without a
         triangular solve | 2 how many of them arrived from other ranks | 3 row exchanges so far | 4 agreed fall-backs."""
@@ -547,7 +556,8 @@ class Context(object):
     def debug_fail_at(self, where, code):
         """Inject `code` into this rank's next greedy pick: where = 0 resolving its best, 1 committing the winner (after the
         exchange), 2 packing its contribution, 3 the agreement word of its next sharded factor update, 4 the next step of the
-        sharded MI state -- its build after a solve, else the fold of a committed pick (algp_debug_fail_at)."""
+        sharded MI state -- its build after a solve, else the fold of a committed pick --, 5 the same for the
+        variance-reduction state over the ranks (algp_debug_fail_at)."""
         self._check(self.lib.algp_debug_fail_at(self.h, int(where), int(code)))
 
     def debug_trsv_stall(self, block):
@@ -579,7 +589,8 @@ class Context(object):
 
     def greedy_sharded(self, criterion, static_std, mobile_std, k, want_utilities=False):
         """k picks over the candidate shards of all ranks (one all-gather per pick inside the library; the MI criterion also
-        needs comm_set_mi_groups and adds two per pick)."""
+        needs comm_set_mi_groups and adds two per pick, the variance-reduction criterion comm_set_vr_exchange and adds the
+        build's gathers at the first pick and one per pick after it)."""
         picks = np.empty(int(k), dtype=np.int64)
         ut = np.empty(int(k), dtype=np.float64) if want_utilities else None
         self._check(self.lib.algp_greedy_sharded(self.h, int(criterion), float(static_std), float(mobile_std), int(k),

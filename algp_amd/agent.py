@@ -237,8 +237,8 @@ class Agent(object):
         reload.  Agent.greedy / run_greedy_ipp under criterion='variance_reduction' then pick by the weighted utility;
         path_variance_reduction and strategy='MaxVarRed' use them under any criterion."""
         if self.comm is not None:
-            raise NotImplementedError("criterion 'variance_reduction' is not sharded: its targets are the whole candidate set, "
-                                      "which no rank of a sharded agent holds; run it on one GPU")
+            raise NotImplementedError("target weights are not sharded in the Agent: a sharded agent scores the variance-reduction "
+                                      "criterion unweighted (attach weights through Context.set_target_weights on every rank)")
         if w is not None:
             w = np.array(w, dtype=np.float64).reshape(-1)
             if len(w) != self.env.num_samples:
@@ -252,8 +252,8 @@ class Agent(object):
         """The variance-reduction objective for the agent's current train set: the weighted sum of the posterior variances of
         every unsampled site (algp_get_target_variance), the state set up as path_variance_reduction does."""
         if self.comm is not None:
-            raise NotImplementedError("criterion 'variance_reduction' is not sharded: its targets are the whole candidate set, "
-                                      "which no rank of a sharded agent holds; run it on one GPU")
+            raise NotImplementedError("the variance-reduction objective is not sharded in the Agent: a rank's "
+                                      "algp_get_target_variance is its own share, the objective the sum over the ranks")
         return self._vr_state(())[0].target_variance()
 
     def _vr_state(self, static_indices):
@@ -422,14 +422,12 @@ class Agent(object):
 
     def greedy(self, num_samples):
         """k most informative static sampling sites, greedily (agent.py:295-356)."""
-        if self.criterion == 'variance_reduction' and self.comm is not None:
-            raise NotImplementedError("criterion 'variance_reduction' is not sharded: its targets are the whole candidate set, "
-                                      "which no rank of a sharded agent holds; run it on one GPU")
         c = self._load_pool()
         static, mobile = self._masks()
         sampled = static | mobile
         # sharded: this rank scores its share of the pool (the factor is replicated); one all-gather per pick inside
-        # algp_greedy_sharded, and the factor update below takes the new sites' rows from their owners' V^T
+        # algp_greedy_sharded (the MI and variance-reduction criteria add their state's own, ShardLink.attach), and the factor
+        # update below takes the new sites' rows from their owners' V^T
         cand = np.arange(self.env.num_samples) if self.comm is None else self._shard()
         if self._use_rows():
             A, is_static = self._train_rows(static, mobile)
@@ -485,8 +483,8 @@ class Agent(object):
         form (a row per reading, else one fused row per site).  One factor update, one candidate solve over every site, one
         scoring call for all paths."""
         if self.comm is not None:
-            raise NotImplementedError("the variance-reduction path utility is not sharded: its targets are the whole candidate "
-                                      "set, which no rank of a sharded agent holds; run it on one GPU")
+            raise NotImplementedError("the variance-reduction path utility is not sharded: a rank's algp_score_paths_vr would "
+                                      "count the targets of its own shard only; run it on one GPU")
         mobile0 = self._masks()[1]
         clean = [[j for j in dict.fromkeys(int(v) for v in path) if j != -1 and not mobile0[j]] for path in paths_mobile_indices]
         if max((len(p) for p in clean), default=0) > 256:

@@ -39,6 +39,10 @@ int Impl<T>::scores_enqueue(algp_ctx* c, int criterion, double static_std, doubl
 
 template <typename T>
 int Impl<T>::scores(algp_ctx* c, int criterion, double static_std, double mobile_std, void* out, int out_is_device) {
+    // the variance-reduction criterion over the ranks of a communicator: algp_scores is a collective there.  The state's build
+    // or folds come first, with this rank's refusals as its status word (vr_shard_step makes the ones scores_enqueue would
+    // make), so that nothing rank-local returns before a collective the peers enter; scores_enqueue then only forms the utilities
+    if (criterion == ALGP_CRIT_VARIANCE_REDUCTION && vr_over_ranks(c)) ALGP_TRY(vr_shard_step(c, ALGP_OK, true));
     ALGP_TRY(scores_enqueue(c, criterion, static_std, mobile_std, out_is_device ? (double*)out : nullptr));
     if (!out_is_device && out)
         ALGP_HIP(hipMemcpyAsync(out, c->scores.p, sizeof(double) * c->M, hipMemcpyDeviceToHost, c->stream));
@@ -319,6 +323,11 @@ int Impl<T>::greedy_picks(algp_ctx* c, int criterion, double static_std, double 
                 // one-GPU state (mi_build, in place: two pool-sized matrices), built and folded by ensure_bounds below.
                 ALGP_TRY(mi_shard_step(c, ss, sm, st, pck == 0));
             }
+            if (criterion == ALGP_CRIT_VARIANCE_REDUCTION && round == 0 && vr_over_ranks(c)) {
+                // the same for the variance-reduction state over the ranks (api_vr.hip): the build at the first pick of a call, then
+                // one gather per pick folded; a world of one keeps the one-GPU state (vr_product / vr_fold)
+                ALGP_TRY(vr_shard_step(c, st, pck == 0));
+            }
             if (st == ALGP_OK && c->M > 0) st = ensure_bounds(c, criterion, static_std, mobile_std, ss, delta);
             if (st == ALGP_OK && c->M > 0) st = enqueue_local_best(c, ss, delta);
             const bool have = st == ALGP_OK && c->M > 0;             // an empty shard offers nothing; that is not an error
@@ -403,6 +412,9 @@ int algp_argmax(algp_ctx* c, int64_t* local_pos, int64_t* pool_idx, double* valu
 int algp_best_candidate(algp_ctx* c, int criterion, double static_std, double mobile_std, int64_t* local_pos,
                         int64_t* pool_idx, double* value) {
     CHECK_CTX(c);
+    if (criterion == ALGP_CRIT_VARIANCE_REDUCTION && vr_over_ranks(c))
+        return fail(c, ALGP_ERR_STATE, "best_candidate: this context scores the variance-reduction criterion over the ranks of its "
+                                       "communicator; use algp_greedy_sharded (or the collective algp_scores)");
     FINISH(c, DISPATCH(c, best_candidate(c, criterion, static_std, mobile_std, local_pos, pool_idx, value)));
 }
 
@@ -415,6 +427,9 @@ int algp_greedy(algp_ctx* c, int criterion, double static_std, double mobile_std
                 int64_t* picks_out, double* ut_out) {
     CHECK_CTX(c);
     if (k < 0 || k > MAX_APPEND) return fail(c, ALGP_ERR_BAD_ARG, "greedy: 0 <= k <= 128");
+    if (criterion == ALGP_CRIT_VARIANCE_REDUCTION && vr_over_ranks(c))
+        return fail(c, ALGP_ERR_STATE, "greedy: this context scores the variance-reduction criterion over the ranks of its communicator; "
+                                       "use algp_greedy_sharded (or the collective algp_scores with algp_commit_pick)");
     FINISH(c, DISPATCH(c, greedy(c, criterion, static_std, mobile_std, k, forced, picks_out, ut_out)));
 }
 
@@ -495,7 +510,9 @@ int algp_debug_fail_at(algp_ctx* c, int where, int code) {
     else if (where == 2) c->debug_fail_next_pack = code;
     else if (where == 3) c->debug_fail_next_rowx = code;
     else if (where == 4) c->debug_fail_next_mi = code;
-    else return fail(c, ALGP_ERR_BAD_ARG, "debug_fail_at: where = 0 (pick), 1 (commit), 2 (pack), 3 (row exchange), 4 (sharded MI step)");
+    else if (where == 5) c->debug_fail_next_vr = code;
+    else return fail(c, ALGP_ERR_BAD_ARG, "debug_fail_at: where = 0 (pick), 1 (commit), 2 (pack), 3 (row exchange), 4 (sharded MI step), "
+                                          "5 (variance-reduction step over the ranks)");
     return ALGP_OK;
 }
 #endif
@@ -511,8 +528,11 @@ int algp_greedy_sharded(algp_ctx* c, int criterion, double static_std, double mo
                         double* utilities_out) {
     CHECK_CTX(c);
     if (k < 0 || k > MAX_APPEND) return fail(c, ALGP_ERR_BAD_ARG, "greedy_sharded: 0 <= k <= 128");
-    if (criterion != ALGP_CRIT_ENTROPY && criterion != ALGP_CRIT_MUTUAL_INFORMATION)
+    if (criterion != ALGP_CRIT_ENTROPY && criterion != ALGP_CRIT_MUTUAL_INFORMATION && criterion != ALGP_CRIT_VARIANCE_REDUCTION)
         return fail(c, ALGP_ERR_BAD_ARG, "greedy_sharded: unknown criterion");
+    if (criterion == ALGP_CRIT_VARIANCE_REDUCTION && c->vr.xrows == 0)
+        return fail(c, ALGP_ERR_BAD_ARG, "greedy_sharded: the variance-reduction criterion counts the targets of every rank only with a "
+                                         "layout attached: call algp_comm_set_vr_exchange on every rank first (or use algp_greedy)");
     if (criterion == ALGP_CRIT_MUTUAL_INFORMATION && c->mi.ncomp <= 0)
         return fail(c, ALGP_ERR_BAD_ARG, "greedy_sharded: the MI criterion shards its pool-wide inverses over the ranks only with "
                                          "a layout attached: call algp_comm_set_mi_groups on every rank first (or use algp_greedy)");

@@ -25,6 +25,9 @@ hipEvent_t sync_event_api(algp_ctx* c, size_t i);
 KmatSrc make_src(algp_ctx* c);
 int sync(algp_ctx* c);
 int sync_checked(algp_ctx* c, const char* what);
+// the variance-reduction criterion is scored over the ranks of the communicator: a layout is attached (algp_comm_set_vr_exchange)
+// and there is more than one rank (a world of one keeps the one-GPU state, as under the MI criterion)
+inline bool vr_over_ranks(const algp_ctx* c) { return c->vr.xrows != 0 && c->comm_nranks > 1; }
 
 // how the candidate solve runs (Impl::SolvePlan): the new columns only (tail.hip), one task-list launch (chol_dag.hip),
 // the sweep (trsm_blocked, potrf.hip), or folded into the factorisation's own launch (fit_and_solve)
@@ -140,6 +143,11 @@ struct Impl {
     static int vr_product(algp_ctx* c);
     static int vr_fold(algp_ctx* c, int64_t q);
     static int vr_scores_enqueue(algp_ctx* c, double ss, double delta, double* dst);
+    // over the ranks of a communicator (algp_comm_set_vr_exchange): collectives, every rank calls them with its status st
+    static int vr_zero_picks_block(algp_ctx* c, int64_t q);
+    static int vr_shard_build(algp_ctx* c, int64_t max_rows, int st = 0);
+    static int vr_shard_fold(algp_ctx* c, int st);
+    static int vr_shard_step(algp_ctx* c, int st, bool first_of_call);
     static int set_target_weights(algp_ctx* c, const double* w);
     static int target_variance(algp_ctx* c, double* sum);
     static int scores_enqueue(algp_ctx* c, int criterion, double static_std, double mobile_std, double* dst);

@@ -12,7 +12,7 @@
 // and factors the group's matrix (replicated, no communication), computes only its own 128-row blocks of X (blocks member,
 // member + g, ...: mi_trinv_rows, mi_shard.hip) and releases the factor.  The diagonals, the rank-1 lists U / W, their signs
 // and the three entropies stay WHOLE on every rank, so scoring is mi_score_launch on each rank's own candidates.
-// Collectives, all of them all-gathers through comm_agree / comm_rows_gather (RCCL or the caller's host transport):
+// Collectives, all of them all-gathers through comm_agree / comm_exchange (comm.hip) (RCCL or the caller's host transport):
 //   first pick of an algp_greedy_sharded call: a 32-byte agreement word (status, whether a build is needed, picks so far);
 //     then, when any rank needs it, the build and ONE gather of every rank's diagonal pieces and entropies;
 //   every pick folded: a gather of the owners' rows at the pick ([header | row of X_bar | row of X_all] per rank), then a
@@ -216,34 +216,10 @@ static void mi_payloads(const algp_ctx* c, int64_t mb, int64_t mbpad, int64_t np
     *cbytes = 32 + es * (size_t)NB * (size_t)(Gb.maxloc + Ga.maxloc);
 }
 
-// this rank's header (status, three values) in front of its payload at rowx, the all-gather of `bytes` per rank, every header
-// back to the host (hdr: 4 doubles per rank); code / bad: the first non-zero status in rank order and its rank (0 / -1: none)
-static int mi_exchange(algp_ctx* c, size_t bytes, int st, const double* v3, std::vector<double>& hdr, int& code, int& bad) {
-    const int nr = c->comm_nranks;
-    c->mi.hdr[0] = (double)st;
-    for (int i = 0; i < 3; ++i) c->mi.hdr[1 + i] = v3 ? v3[i] : 0.0;
-    char* own = (char*)c->rowx.p;
-    ALGP_HIP(hipMemcpyAsync(own, c->mi.hdr, 32, hipMemcpyHostToDevice, c->stream));
-    ALGP_TRY(comm_rows_gather(c, bytes));
-    hdr.assign((size_t)nr * 4, 0.0);
-    ALGP_HIP(hipMemcpy2DAsync(hdr.data(), 32, own + bytes, bytes, 32, (size_t)nr, hipMemcpyDeviceToHost, c->stream));
-    ALGP_TRY(sync(c));
-    code = 0;
-    bad = -1;
-    for (int r = 0; r < nr && bad < 0; ++r)
-        if (hdr[(size_t)r * 4] != 0.0) {
-            bad = r;
-            code = hdr[(size_t)r * 4] == hdr[(size_t)r * 4] ? (int)hdr[(size_t)r * 4] : ALGP_ERR_HIP;
-        }
-    return ALGP_OK;
-}
-
-// an agreed failure: the failing rank keeps its own message, the others name it; the state is rebuilt by the next call
+// an agreed failure (comm_agreed_fail, comm.hip) drops the state: the next call rebuilds it
 static int mi_agreed_fail(algp_ctx* c, int code, int bad, const std::string& local_err, const char* what) {
     c->mi.valid = false;
-    if (bad == c->comm_rank && !local_err.empty()) return fail(c, code, local_err);
-    return fail(c, code, "greedy_sharded: rank " + std::to_string(bad) + " failed with error " + std::to_string(code) + " in " + what +
-                             " of the mutual-information state; every rank returns it");
+    return comm_agreed_fail(c, code, bad, local_err, what, "the mutual-information state");
 }
 
 // host side of a build: the sets, the payload sizes, and this rank's memory check -- nothing allocated yet
@@ -362,7 +338,7 @@ int Impl<T>::mi_shard_fold(algp_ctx* c, int st) {
     std::string local_err = st != ALGP_OK ? c->err : std::string();
     std::vector<double> hdr;
     int code = 0, bad = -1;
-    ALGP_TRY(mi_exchange(c, rbytes, st, nullptr, hdr, code, bad));
+    ALGP_TRY(comm_exchange(c, rbytes, st, nullptr, hdr, code, bad));
     if (code) return mi_agreed_fail(c, code, bad, local_err, "the row exchange of a pick");
     // 2. this rank's entries of the pick's columns, the earlier picks' terms removed
     const char* rows = own + rbytes;
@@ -384,7 +360,7 @@ int Impl<T>::mi_shard_fold(algp_ctx* c, int st) {
                                          Hs + 3 + MAX_APPEND, r, pk.pool_idx, (T*)(own + 32 + es * NB * (size_t)Gb.maxloc));
     }
     local_err = st != ALGP_OK ? c->err : std::string();
-    ALGP_TRY(mi_exchange(c, cbytes, st, nullptr, hdr, code, bad));
+    ALGP_TRY(comm_exchange(c, cbytes, st, nullptr, hdr, code, bad));
     if (code) return mi_agreed_fail(c, code, bad, local_err, "the column exchange of a pick");
     // 3. on every rank: the whole columns, folded into both diagonals (mi_rank1_kernel at the next slot of each list)
     const char* pcs = own + cbytes;
@@ -451,7 +427,7 @@ int Impl<T>::mi_shard_step(algp_ctx* c, double ss, double sm, int st, bool first
             int bst = mi_shard_build(c, pl, H3);
             const std::string berr = bst != ALGP_OK ? c->err : std::string();
             std::vector<double> hdr;
-            ALGP_TRY(mi_exchange(c, pl.cbytes, bst, H3, hdr, code, bad));
+            ALGP_TRY(comm_exchange(c, pl.cbytes, bst, H3, hdr, code, bad));
             if (code) return mi_agreed_fail(c, code, bad, berr, "the build");
             // whole diagonals from the pieces, the entropies from the first rank of each group
             const MiGroup Gb = mi_group(c, 0, pl.mb, pl.mbpad), Ga = mi_group(c, 1, c->n_pool, pl.npad);

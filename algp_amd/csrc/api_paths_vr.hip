@@ -245,6 +245,9 @@ int algp_score_paths_vr(algp_ctx* c, const int64_t* sites, int npaths, int maxle
     CHECK_CTX(c);
     if (npaths < 0 || maxlen < 1 || (npaths > 0 && (!sites || !dV_out)) || !(mobile_std > 0))
         return fail(c, ALGP_ERR_BAD_ARG, "score_paths_vr: bad arguments");
+    if (vr_over_ranks(c))
+        return fail(c, ALGP_ERR_STATE, "score_paths_vr: this context scores the variance-reduction criterion over the ranks of its "
+                                       "communicator, and a path's targets here would be this rank's own only; not sharded");
     if (npaths == 0) return ALGP_OK;
     FINISH(c, DISPATCH(c, score_paths_vr(c, sites, npaths, maxlen, mobile_std, max_union, dV_out)));
 }

@@ -181,6 +181,7 @@ int comm_init(algp_ctx* c, int nranks, int rank, const void* unique_id128) {
     c->comm = comm;
     c->host_gather = nullptr;
     c->mi.drop_layout();
+    c->vr.drop_layout();
     c->comm_nranks = nranks;
     c->comm_rank = rank;
     return comm_reserve(c);
@@ -245,7 +246,8 @@ void comm_destroy(algp_ctx* c) {
     c->rowx_host = nullptr;
     c->rowx_host_cap = 0;
     c->site_owner.clear();
-    c->mi.drop_layout();                                     // the MI layout belongs to the communicator
+    c->mi.drop_layout();                                     // the MI layout belongs to the communicator,
+    c->vr.drop_layout();                                     // and so does the variance-reduction criterion's
     c->comm = nullptr;
     c->host_gather = nullptr;
     c->host_gather_user = nullptr;
@@ -352,25 +354,26 @@ int comm_pick_exchange(algp_ctx* c, const double* val_dev, const int64_t* pos_de
 // size, a hash of the plan -- so that every rank takes the same branch, and a rank that cannot take part says so instead
 // of leaving its peers in the second collective), then ONE all-gather of the rows (`cap` rows per rank, cap = the largest
 // number any rank owns; the plan is computed identically everywhere from the train set and the owner map).
-int comm_agree(algp_ctx* c, const double mine[4], std::vector<double>& all) {
+int comm_agree(algp_ctx* c, const double* mine, std::vector<double>& all, int nd) {
     const int nr = c->comm_nranks;
-    all.assign((size_t)nr * 4, 0.0);
+    const size_t wb = sizeof(double) * (size_t)nd;               // 32 bytes, or a wider word (the variance-reduction criterion's: 80)
+    all.assign((size_t)nr * nd, 0.0);
     if (c->host_gather) {
-        std::vector<double> send(mine, mine + 4);
-        const int rc = c->host_gather(c->host_gather_user, send.data(), all.data(), 32);
+        std::vector<double> send(mine, mine + nd);
+        const int rc = c->host_gather(c->host_gather_user, send.data(), all.data(), (int64_t)wb);
         if (rc != 0) return fail(c, ALGP_ERR_HIP, "factorize_update: the caller's all-gather returned " + std::to_string(rc));
         return ALGP_OK;
     }
     if (!c->comm) return fail(c, ALGP_ERR_STATE, "factorize_update: no communicator");
     RcclApi* api = rccl_api(nullptr);
     if (!api) return fail(c, ALGP_ERR_STATE, "factorize_update: the RCCL communicator has no library behind it");
-    ALGP_TRY(ensure(c, c->commbuf, std::max<size_t>(c->commbuf.cap, 32 * (size_t)(nr + 1))));
+    ALGP_TRY(ensure(c, c->commbuf, std::max<size_t>(c->commbuf.cap, wb * (size_t)(nr + 1))));
     char* own = (char*)c->commbuf.p;
-    ALGP_HIP(hipMemcpyAsync(own, mine, 32, hipMemcpyHostToDevice, c->stream));
-    const ncclResult_t r = api->AllGather(own, own + 32, 32, ncclChar, (ncclComm_t)c->comm, c->stream);
+    ALGP_HIP(hipMemcpyAsync(own, mine, wb, hipMemcpyHostToDevice, c->stream));
+    const ncclResult_t r = api->AllGather(own, own + wb, wb, ncclChar, (ncclComm_t)c->comm, c->stream);
     if (r != ncclSuccess)
         return fail(c, ALGP_ERR_HIP, std::string("ncclAllGather: ") + (api->GetErrorString ? api->GetErrorString(r) : "failed"));
-    ALGP_HIP(hipMemcpyAsync(all.data(), own + 32, 32 * (size_t)nr, hipMemcpyDeviceToHost, c->stream));
+    ALGP_HIP(hipMemcpyAsync(all.data(), own + wb, wb * (size_t)nr, hipMemcpyDeviceToHost, c->stream));
     ALGP_HIP(hipStreamSynchronize(c->stream));
     c->n_syncs++;
     return ALGP_OK;
@@ -427,6 +430,38 @@ int comm_rows_gather(algp_ctx* c, size_t bytes_per_rank, const size_t* used_byte
         else ALGP_HIP(hipMemcpyAsync(all + bytes_per_rank * (size_t)r, hr + bytes_per_rank * (size_t)r, ub, hipMemcpyHostToDevice, c->stream));
     }
     return ALGP_OK;
+}
+
+// ---- the gathers of a criterion's state dealt over the ranks (api_mi.hip, api_vr.hip) -------------------------------------
+// Every such gather carries each rank's status word in a 32-byte header in front of its payload: a rank that failed still
+// takes part, and every rank returns the first failing rank's code from the same call.
+int comm_exchange(algp_ctx* c, size_t bytes, int st, const double* v3, std::vector<double>& hdr, int& code, int& bad) {
+    const int nr = c->comm_nranks;
+    c->xhdr[0] = (double)st;
+    for (int i = 0; i < 3; ++i) c->xhdr[1 + i] = v3 ? v3[i] : 0.0;
+    char* own = (char*)c->rowx.p;
+    ALGP_HIP(hipMemcpyAsync(own, c->xhdr, 32, hipMemcpyHostToDevice, c->stream));
+    ALGP_TRY(comm_rows_gather(c, bytes));
+    hdr.assign((size_t)nr * 4, 0.0);
+    ALGP_HIP(hipMemcpy2DAsync(hdr.data(), 32, own + bytes, bytes, 32, (size_t)nr, hipMemcpyDeviceToHost, c->stream));
+    ALGP_HIP(hipStreamSynchronize(c->stream));
+    c->n_syncs++;
+    code = 0;
+    bad = -1;
+    for (int r = 0; r < nr && bad < 0; ++r)
+        if (hdr[(size_t)r * 4] != 0.0) {
+            bad = r;
+            code = hdr[(size_t)r * 4] == hdr[(size_t)r * 4] ? (int)hdr[(size_t)r * 4] : ALGP_ERR_HIP;
+        }
+    return ALGP_OK;
+}
+
+// an agreed failure: the failing rank keeps its own message, the others name it; the caller drops the state, which the next
+// call rebuilds
+int comm_agreed_fail(algp_ctx* c, int code, int bad, const std::string& local_err, const char* what, const char* state) {
+    if (bad == c->comm_rank && !local_err.empty()) return fail(c, code, local_err);
+    return fail(c, code, "greedy_sharded: rank " + std::to_string(bad) + " failed with error " + std::to_string(code) + " in " + what +
+                             " of " + state + "; every rank returns it");
 }
 
 // test hook: first_max_kernel over a caller-made buffer of `nranks` triples (fabricated 8-rank cases on one GPU)

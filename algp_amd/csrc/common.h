@@ -94,7 +94,6 @@ struct MiState {
     int64_t mb = 0, mbpad = 0, npad = 0;
     double ss = 0, sm = 0;
     int ncomp = 0;                       // ranks [0, ncomp) hold P, the others Q (0: no layout; a world of one: 1, both)
-    double hdr[4] = {0, 0, 0, 0};        // this rank's header of the next gather (host memory that outlives the copy)
 
     bool holds(int f) const { return valid && form == f; }
     // holds(f) for (ss, sm) with at most npicks_now picks folded in: catching up folds the later picks, nothing is rebuilt.
@@ -123,10 +122,23 @@ struct VrState {
     DevBuf Y;                            // [sum_j C(c, j) omega_j r_j | V_c . t]
     DevBuf Nrm;                          // sum_{j in T} omega_j r_j^2
     DevBuf Obj;                          // one double: the objective sum_{j in T} omega_j pv_j (algp_get_target_variance)
+    // over the ranks of a communicator (algp_comm_set_vr_exchange): the local candidates' marks by pool site and the hit flag of
+    // the build's disjointness check; the gathered (pool index, omega r) pairs of a fold, made contiguous
+    DevBuf Mark, Tidx, Trt;
     bool valid = false;
+    bool over_ranks = false;             // w counts the targets of every rank (built by vr_shard_build), not this context's own
     int64_t npicks = 0;                  // picks folded in
+    int64_t xrows = 0;                   // the layout: rows of V^T per rank and all-gather of the build (0: none, -1: the default)
+    int64_t max_rows = 0;                // the largest shard's rows when the state was built (the padding of a fold's pairs)
+    bool every_time = false;             // some rank of the last agreement runs with ALGP_VR_RANK1=0: every scoring builds
 
     void drop() { valid = false; npicks = 0; }
+    // the communicator's layout goes, and with it a state built over its ranks
+    void drop_layout() {
+        xrows = 0;
+        if (over_ranks) drop();
+        over_ranks = false;
+    }
 };
 
 }  // namespace algp
@@ -229,6 +241,7 @@ struct algp_ctx {
     algp::DevBuf Cp;        // n x n explicit covariance (pool_is_cov)
     algp::DevBuf tw;        // target weight of every pool site in the context's dtype (algp_set_target_weights), while has_tw
     bool has_tw = false;    // the weights belong to their pool: a new pool drops them
+    uint64_t tw_hash = 0;   // FNV-1a of the weights as attached (while has_tw): ranks scoring together must hold the same ones
     std::vector<int64_t> pos_in_train;   // host: pool index -> position in train set or -1
     std::vector<uint64_t> site_hash;     // host: fingerprint of every pool site's coordinates (algp_factorize_from)
 
@@ -330,6 +343,8 @@ struct algp_ctx {
     int debug_fail_next_commit = 0; // algp_debug_fail_at(1): the next commit of a greedy pick fails with this code (after the exchange)
     int debug_fail_next_pack = 0;   // algp_debug_fail_at(2): the next pick's pack launch counts as failed
     int debug_fail_next_mi = 0;     // algp_debug_fail_at(4): the next step of the sharded MI state (its build or a pick's fold) fails
+    int debug_fail_next_vr = 0;     // algp_debug_fail_at(5): the next step of the variance-reduction state over ranks (build, else a fold) fails
+    double xhdr[4] = {0, 0, 0, 0};  // comm_exchange: this rank's header of the next gather (host memory that outlives the copy)
 
     // scratch for auxiliary factorizations (entropy_from_cov, set entropies, MI terms, posterior cov)
     algp::DevBuf auxA, auxInv, auxW, auxIdx, auxVar, auxD, hostStage;
@@ -504,6 +519,13 @@ int gemm_nt_launch_stats(algp_ctx* c, int klass, int64_t m, int64_t k, T alpha, 
 template <typename T>
 int gemm_nt_launch_vr(algp_ctx* c, int klass, int64_t mpad, int64_t n, int64_t k, const T* Vt, int64_t ldv, int64_t ncol0,
                       const KmatSrc& s, const int64_t* cidx, const int* ckind, int64_t M, const T* tw, T* part, int64_t part_ld);
+// its rectangular form (the criterion over ranks): rows [0, mpad) of V^T against `nslices` blocks of n gathered rows B (leading
+// dimension ldb; slice s starts slice_bytes * s behind B, and its n pool indices -- negative: not a target -- behind cpool by the same
+// step) in ONE launch; slice s, column tile bn -> part[(s * n / 128 + bn) * part_ld + row]
+template <typename T>
+int gemm_nt_launch_vrx(algp_ctx* c, int klass, int64_t mpad, int64_t n, int64_t k, const T* Vt, int64_t ldv, const T* B, int64_t ldb,
+                       const int64_t* cpool, int nslices, int64_t slice_bytes, const KmatSrc& s, const int64_t* cidx, const int* ckind,
+                       int64_t M, const T* tw, T* part, int64_t part_ld);
 // variance reduction of whole paths: E[u][j] = C(uidx[u], cidx[ncol0 + j]) - R_u . V_(ncol0 + j) on the target columns, 0 on the
 // others and on the rows behind U; the E tile is written (upad x n, leading dimension lde), nothing else (gemm.hip)
 template <typename T>
@@ -532,9 +554,16 @@ int comm_init_host(algp_ctx* c, int nranks, int rank, algp_allgather_fn fn, void
 int comm_pick_exchange(algp_ctx* c, const double* val_dev, const int64_t* pos_dev, const int64_t* cidx_dev,
                        const int* fresh_dev, int npicks, int status, double* rec5, const char** winner_payload);
 int comm_reserve(algp_ctx* c);
-int comm_agree(algp_ctx* c, const double mine[4], std::vector<double>& all);
+// every rank's `nd` doubles (an agreement word: 4, or more where a protocol compares more), in rank order
+int comm_agree(algp_ctx* c, const double* mine, std::vector<double>& all, int nd = 4);
 int comm_rows_reserve(algp_ctx* c, size_t bytes_per_rank);
 int comm_rows_gather(algp_ctx* c, size_t bytes_per_rank, const size_t* used_bytes = nullptr);
+// The gather of a sharded criterion's state (MI: api_mi.hip; variance reduction: api_vr.hip): this rank's 32-byte header
+// (status st, three values v3 or zeros) in front of its payload at rowx, comm_rows_gather of `bytes` per rank, every header
+// back to the host (hdr: 4 doubles per rank); code / bad: the first non-zero status in rank order and its rank (0 / -1: none).
+// comm_agreed_fail: the failing rank keeps its own message, the others name it (what: the step, state: whose state it is).
+int comm_exchange(algp_ctx* c, size_t bytes, int st, const double* v3, std::vector<double>& hdr, int& code, int& bad);
+int comm_agreed_fail(algp_ctx* c, int code, int bad, const std::string& local_err, const char* what, const char* state);
 size_t comm_payload_bytes(const algp_ctx* c);
 int comm_debug_first_max(algp_ctx* c, const double* triples, int nranks, double* out5);
 void dag_release(algp_ctx* c);   // frees the cached task lists of the dependency-driven Cholesky

@@ -123,7 +123,10 @@ struct VrGemmArgs : GemmArgs<T> {
     const int64_t* cidx;           // pool index of every candidate row (M entries)
     const int* ckind;              // >= 0: a unit row
     int64_t M;                     // rows / columns beyond M are padding
-    int64_t ncol0;                 // candidate row that column 0 of this launch's B is
+    union {
+        int64_t ncol0;             // candidate row that column 0 of this launch's B is
+        const int64_t* cpool;      // VrxGemmArgs: the pool index of every column of B (negative: not a target), B being rows of its own
+    };
     const T* Xs;                   // scaled coordinates, DP per site (coordinate pool)
     const T* Cp;                   // or the explicit pool covariance (n_pool x n_pool)
     int64_t n_pool;
@@ -136,6 +139,15 @@ struct VrGemmArgs : GemmArgs<T> {
 
 template <typename T>
 struct VrWGemmArgs : VrGemmArgs<T> {};   // the same launch with tw attached: the weighted epilogue
+// The rectangular form (the criterion over the ranks of a communicator, api_vr.hip): the rows are this rank's V^T as above,
+// the columns gathered rows of every rank's V^T -- B and ldb of their own, and on the column side cpool in the place of
+// cidx / ckind / M.  The launch is batched over the ranks' slices (blockIdx.y): slice s of B lies sB elements further, its
+// pool indices the same number of bytes behind cpool (they travel in front of their rows), and its column tile bn leaves its
+// sums at stat_out[(s * tiles_n + bn) * stat_ld + row].  The same fields at the same offsets, tw still last.
+template <typename T>
+struct VrxGemmArgs : VrGemmArgs<T> {};
+template <typename T>
+struct VrxWGemmArgs : VrxGemmArgs<T> {};
 
 // C(prow, pcol) for the two epilogues below: read from the explicit pool covariance, or formed from the scaled coordinates
 // of the row (in registers) and of the column (staged in LDS) with the one kernel-value definition kexp, sigma_n^2 added
@@ -159,9 +171,10 @@ __device__ __forceinline__ T vr_pool_cov(const VrGemmArgs<T>& g, int64_t prow, i
     return cv;
 }
 
-template <typename T, bool WEIGHTED, typename ACC>
+// RECT: the columns are described by cpool (this slice's 128 x tiles_n pool indices) instead of cidx / ckind / M
+template <typename T, bool WEIGHTED, bool RECT, typename ACC>
 __device__ __forceinline__ void vr_epilogue(const VrGemmArgs<T>& g, char* smem, const ACC (&acc)[4][4], int64_t m0, int64_t n0, int bn,
-                                            int wr, int wc, int lane, int tid) {
+                                            int wr, int wc, int lane, int tid, const int64_t* cpool = nullptr) {
     using F = MF<T>;
     const int fr = lane & 15;
     // LDS: [2 column halves][128 rows] sums | coordinates of the rows, of the columns ([128][MAXD], zero padded) | pool
@@ -180,10 +193,18 @@ __device__ __forceinline__ void vr_epilogue(const VrGemmArgs<T>& g, char* smem, 
     {
         const int t = tid & 127;
         const bool is_col = tid >= 128;
-        const int64_t gi = is_col ? g.ncol0 + n0 + t : m0 + t;
-        const bool valid = gi < g.M;
-        const int64_t p = valid ? g.cidx[gi] : 0;
-        const int ordinary = (valid && g.ckind[gi] < 0) ? 1 : 0;
+        int64_t p;
+        int ordinary;
+        if (RECT && is_col) {
+            const int64_t hp = cpool[n0 + t];
+            ordinary = hp >= 0 ? 1 : 0;
+            p = ordinary ? hp : 0;
+        } else {
+            const int64_t gi = (!RECT && is_col) ? g.ncol0 + n0 + t : m0 + t;
+            const bool valid = gi < g.M;
+            p = valid ? g.cidx[gi] : 0;
+            ordinary = (valid && g.ckind[gi] < 0) ? 1 : 0;
+        }
         (is_col ? pc : pr)[t] = p;
         if constexpr (WEIGHTED) {
             if (is_col) wcol[t] = ordinary ? g.tw[p] : (T)0;
@@ -550,7 +571,13 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel_dma4(Args g) {
         pvr_epilogue<T>(g, smem, acc, m0, n0, wr, wc, lane, tid);
         return;
     } else if constexpr (VR) {
-        vr_epilogue<T, std::is_same<Args, VrWGemmArgs<T>>::value>(g, smem, acc, m0, n0, cur_bn, wr, wc, lane, tid);
+        constexpr bool WEIGHTED = std::is_same<Args, VrWGemmArgs<T>>::value || std::is_same<Args, VrxWGemmArgs<T>>::value;
+        if constexpr (std::is_base_of<VrxGemmArgs<T>, Args>::value)
+            vr_epilogue<T, WEIGHTED, true>(g, smem, acc, m0, n0, (int)bz * g.tiles_n + cur_bn, wr, wc, lane, tid,
+                                           reinterpret_cast<const int64_t*>(reinterpret_cast<const char*>(g.cpool) +
+                                                                            bz * g.sB * (int64_t)sizeof(T)));
+        else
+            vr_epilogue<T, WEIGHTED, false>(g, smem, acc, m0, n0, cur_bn, wr, wc, lane, tid);
         return;
     }
     const T alpha = g.alpha, beta = g.beta;
@@ -994,6 +1021,40 @@ template int gemm_nt_launch_vr<double>(algp_ctx*, int, int64_t, int64_t, int64_t
                                        const int64_t*, const int*, int64_t, const double*, double*, int64_t);
 template int gemm_nt_launch_vr<float>(algp_ctx*, int, int64_t, int64_t, int64_t, const float*, int64_t, int64_t, const KmatSrc&,
                                       const int64_t*, const int*, int64_t, const float*, float*, int64_t);
+
+// The rectangular form: rows [0, mpad) of V^T (cidx / ckind / M describe them) against nslices blocks of n rows each, slice s at
+// B + s * slice_bytes (leading dimension ldb) with its n pool indices at cpool + s * slice_bytes (negative: the column is no target);
+// part[(s * n / 128 + bn) * part_ld + row] = the sum over the target columns j of slice s, tile bn, of
+// (kappa_row C(row, j) - V_row . B_j)^2, weighted by tw[pool index of j] where tw is given.  One batched launch.
+template <typename T>
+int gemm_nt_launch_vrx(algp_ctx* c, int klass, int64_t mpad, int64_t n, int64_t k, const T* Vt, int64_t ldv, const T* B, int64_t ldb,
+                       const int64_t* cpool, int nslices, int64_t slice_bytes, const KmatSrc& s, const int64_t* cidx, const int* ckind,
+                       int64_t M, const T* tw, T* part, int64_t part_ld) {
+    if (mpad <= 0 || n <= 0 || nslices <= 0) return ALGP_OK;
+    if (k > ldv || k > ldb || s.DP > MAXD || !cpool || slice_bytes % 16 || ((uintptr_t)B & 15) || ((uintptr_t)cpool & 7) || nslices > 65535 ||
+        (nslices > 1 && slice_bytes < (int64_t)sizeof(T) * n * ldb))
+        return fail(c, ALGP_ERR_BAD_ARG, "gemm_nt_vrx: operands must be padded to multiples of 128, the slices 16-byte aligned");
+    const GemmNt<T> p = {.klass = klass, .m = mpad, .n = n, .k = k, .A = {Vt, ldv}, .B = {B, ldb, slice_bytes / (int64_t)sizeof(T)},
+                         .batch = nslices, .stat_out = part, .stat_ld = part_ld};
+    int64_t tiles;
+    ALGP_TRY(gemm_check(c, "gemm_nt_vrx", p, &tiles));
+    VrxGemmArgs<T> g;
+    gemm_fill(g, p);
+    vr_fill(g, s, cidx, ckind, M, 0, tw);
+    g.cpool = cpool;
+    const Booking bk = gemm_book(p, tiles, 128.0);
+    const dim3 grid((unsigned)tiles, (unsigned)nslices);
+    if (!tw) return dispatch(c, klass, bk.flops, bk.bytes, gemm_nt_kernel_dma4<T, false, VrxGemmArgs<T>>, grid, g);
+    VrxWGemmArgs<T> gw;
+    static_cast<VrGemmArgs<T>&>(gw) = g;
+    return dispatch(c, klass, bk.flops, bk.bytes, gemm_nt_kernel_dma4<T, false, VrxWGemmArgs<T>>, grid, gw);
+}
+template int gemm_nt_launch_vrx<double>(algp_ctx*, int, int64_t, int64_t, int64_t, const double*, int64_t, const double*, int64_t,
+                                        const int64_t*, int, int64_t, const KmatSrc&, const int64_t*, const int*, int64_t, const double*,
+                                        double*, int64_t);
+template int gemm_nt_launch_vrx<float>(algp_ctx*, int, int64_t, int64_t, int64_t, const float*, int64_t, const float*, int64_t,
+                                       const int64_t*, int, int64_t, const KmatSrc&, const int64_t*, const int*, int64_t, const float*,
+                                       float*, int64_t);
 
 // The cross covariances of the union rows R (upad x k, the rows behind U zero) with rows [ncol0, ncol0 + n) of V^T:
 // E[u][j] = C(uidx[u], cidx[ncol0 + j]) - R_u . V_(ncol0 + j) where column ncol0 + j is a target, 0 elsewhere and on the

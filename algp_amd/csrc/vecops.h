@@ -23,6 +23,27 @@ template <typename T>
 int vr_fold_launch(algp_ctx* c, int64_t M, const int* ckind, const int64_t* cidx, const T* Vt, int64_t ldv, int64_t col, const T* Xs,
                    const T* Cp, int64_t n_pool, int DP, int kernel, T os, T noise, const T* tw, T* r, T* rt, T* nrm, T* tp, T* t, T* y1,
                    T* y2, T* w);
+// the same fold cut at its sums over the targets (local half; then the update from a list of N (pool index, rt) target pairs),
+// and the pieces of the criterion over the ranks of a communicator: a round's packed rows, the disjointness marks, a fold's
+// pairs, and its gathered sums and pair list (vecops.hip)
+template <typename T>
+int vr_fold_local_launch(algp_ctx* c, int64_t M, const int* ckind, const int64_t* cidx, const T* Vt, int64_t ldv, int64_t col, const T* tw,
+                         T* r, T* rt, T* nrm, T* tp, T* t);
+template <typename T>
+int vr_fold_apply_launch(algp_ctx* c, int64_t M, const int* ckind, const int64_t* cidx, const T* Vt, int64_t ldv, int64_t col, const T* Xs,
+                         const T* Cp, int64_t n_pool, int DP, int kernel, T os, T noise, int64_t N, const int64_t* tidx, const T* tval,
+                         const T* r, const T* rt, const T* nrm, const T* t, T* y1, T* y2, T* w);
+template <typename T>
+int vr_pack_rows_launch(algp_ctx* c, int64_t M, int64_t row0, int64_t B, const int* ckind, const int64_t* cidx, const T* Vt, int64_t ldv,
+                        int64_t K, int64_t kvalid, int64_t* head, T* rows);
+int vr_mark_launch(algp_ctx* c, int64_t M, const int64_t* cidx, int64_t n_pool, int* mark);
+int vr_overlap_launch(algp_ctx* c, const char* gathered_heads, int64_t slice_bytes, int nranks, int self, int64_t B, int64_t n_pool,
+                      int* mark);
+template <typename T>
+int vr_pairs_launch(algp_ctx* c, int64_t M, int64_t cap, const int* ckind, const int64_t* cidx, const T* rt, int64_t* idx, T* val);
+template <typename T>
+int vr_fold_gathered_launch(algp_ctx* c, const char* gathered, int64_t stride, int nranks, int64_t ncols, int64_t cap, int64_t off_nrm,
+                            int64_t off_t, int64_t off_idx, int64_t off_val, T* t, T* nrm, int64_t* tidx, T* tval);
 template <typename T>
 int vr_target_sum_launch(algp_ctx* c, int64_t M, const int* ckind, const int64_t* cidx, const T* dstat, const T* tw, double* out);
 int argmax_launch(algp_ctx* c, const double* s, int64_t M, double* out_val, int64_t* out_idx);

@@ -424,16 +424,18 @@ __global__ __launch_bounds__(256) void vr_tsum_kernel(int nblocks, const T* tp, 
     for (int b = 0; b < nblocks; ++b) s += tp[(int64_t)b * ld + k];
     t[k] = s;
 }
-// explicit pool covariance: y1[c] = sum_j Cp[pool(c)][pool(j)] rt[j] (a wave per row, as kgemv_kernel for a coordinate pool)
+// explicit pool covariance: y1[c] = sum_j Cp[pool(c)][aidx[j]] rt[j] over the N listed targets (a wave per row, as kgemv_kernel
+// for a coordinate pool; on one GPU the targets are the rows themselves: N = M, aidx = cidx)
 template <typename T>
-__global__ __launch_bounds__(256) void vr_cov_gemv_kernel(int64_t M, const int64_t* cidx, const T* Cp, int64_t n_pool, const T* rt, T* y1) {
+__global__ __launch_bounds__(256) void vr_cov_gemv_kernel(int64_t M, const int64_t* cidx, const T* Cp, int64_t n_pool, int64_t N,
+                                                          const int64_t* aidx, const T* rt, T* y1) {
     const int lane = threadIdx.x & 63;
     const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int64_t nw = (int64_t)gridDim.x * 4;
     for (int64_t c0 = wave; c0 < M; c0 += nw) {
         const T* row = Cp + cidx[c0] * n_pool;
         T s = (T)0;
-        for (int64_t j = lane; j < M; j += 64) s = __builtin_fma(row[cidx[j]], rt[j], s);
+        for (int64_t j = lane; j < N; j += 64) s = __builtin_fma(row[aidx[j]], rt[j], s);
         s = dot_tree<T>(s);
         if (lane == 0) y1[c0] = s;
     }
@@ -450,10 +452,13 @@ __global__ void vr_fold_kernel(int64_t M, const int* ckind, const T* r, const T*
     w[j] = w[j] - (T)2 * rj * y + rj * rj * *nrm;
 }
 
+// The fold in two halves, cut at its sums over the targets.  The first is local: the pick's column (r, rt, *nrm) and
+// t = V_T^T rt over the columns left of it.  The second takes the targets as a list of (pool index, rt) pairs -- this context's
+// own rows on one GPU, every rank's gathered pairs over a communicator, with t and *nrm summed over the ranks in between
+// (vr_fold_gathered_kernel) -- and updates w.
 template <typename T>
-int vr_fold_launch(algp_ctx* c, int64_t M, const int* ckind, const int64_t* cidx, const T* Vt, int64_t ldv, int64_t col, const T* Xs,
-                   const T* Cp, int64_t n_pool, int DP, int kernel, T os, T noise, const T* tw, T* r, T* rt, T* nrm, T* tp, T* t, T* y1,
-                   T* y2, T* w) {
+int vr_fold_local_launch(algp_ctx* c, int64_t M, const int* ckind, const int64_t* cidx, const T* Vt, int64_t ldv, int64_t col, const T* tw,
+                         T* r, T* rt, T* nrm, T* tp, T* t) {
     if (M <= 0) return ALGP_OK;
     {
         ProfScope ps(c, ALGP_PROF_ROWS, 2.0 * M, sizeof(T) * 3.0 * M);
@@ -473,21 +478,49 @@ int vr_fold_launch(algp_ctx* c, int64_t M, const int* ckind, const int64_t* cidx
         hipLaunchKernelGGL(vr_tsum_kernel<T>, dim3((unsigned)((col + 255) / 256)), dim3(256), 0, c->cur, nblocks, (const T*)tp, ldv, col, t);
         ALGP_HIP(hipGetLastError());
     }
-    ALGP_TRY(rows_reduce_launch<T>(c, Vt, M, ldv, col, (const T*)t, (T*)nullptr, y2));
+    return ALGP_OK;
+}
+template int vr_fold_local_launch<double>(algp_ctx*, int64_t, const int*, const int64_t*, const double*, int64_t, int64_t, const double*,
+                                          double*, double*, double*, double*, double*);
+template int vr_fold_local_launch<float>(algp_ctx*, int64_t, const int*, const int64_t*, const float*, int64_t, int64_t, const float*, float*,
+                                         float*, float*, float*, float*);
+
+template <typename T>
+int vr_fold_apply_launch(algp_ctx* c, int64_t M, const int* ckind, const int64_t* cidx, const T* Vt, int64_t ldv, int64_t col, const T* Xs,
+                         const T* Cp, int64_t n_pool, int DP, int kernel, T os, T noise, int64_t N, const int64_t* tidx, const T* tval,
+                         const T* r, const T* rt, const T* nrm, const T* t, T* y1, T* y2, T* w) {
+    if (M <= 0) return ALGP_OK;
+    ALGP_TRY(rows_reduce_launch<T>(c, Vt, M, ldv, col, t, (T*)nullptr, y2));
     if (Cp) {
         int64_t g = (M + 3) / 4;
         if (g > 8192) g = 8192;
-        ProfScope ps(c, ALGP_PROF_KMAT, 2.0 * M * M, sizeof(T) * (double)M * M);
-        hipLaunchKernelGGL(vr_cov_gemv_kernel<T>, dim3((unsigned)g), dim3(256), 0, c->cur, M, cidx, Cp, n_pool, (const T*)rt, y1);
+        ProfScope ps(c, ALGP_PROF_KMAT, 2.0 * M * N, sizeof(T) * (double)M * N);
+        hipLaunchKernelGGL(vr_cov_gemv_kernel<T>, dim3((unsigned)g), dim3(256), 0, c->cur, M, cidx, Cp, n_pool, N, tidx, tval, y1);
         ALGP_HIP(hipGetLastError());
     } else {
-        ALGP_TRY(kgemv_launch<T>(c, M, cidx, Xs, DP, M, cidx, (const T*)rt, kernel, os, (T)0, y1));
+        ALGP_TRY(kgemv_launch<T>(c, M, cidx, Xs, DP, N, tidx, tval, kernel, os, (T)0, y1));
     }
     ProfScope ps(c, ALGP_PROF_SCORE, 6.0 * M, sizeof(T) * 6.0 * M);
-    hipLaunchKernelGGL(vr_fold_kernel<T>, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, c->cur, M, ckind, (const T*)r, (const T*)rt,
-                       (const T*)y1, (const T*)y2, (const T*)nrm, Cp ? (T)0 : noise, w);
+    hipLaunchKernelGGL(vr_fold_kernel<T>, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, c->cur, M, ckind, r, rt, (const T*)y1,
+                       (const T*)y2, nrm, Cp ? (T)0 : noise, w);
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
+}
+template int vr_fold_apply_launch<double>(algp_ctx*, int64_t, const int*, const int64_t*, const double*, int64_t, int64_t, const double*,
+                                          const double*, int64_t, int, int, double, double, int64_t, const int64_t*, const double*,
+                                          const double*, const double*, const double*, const double*, double*, double*, double*);
+template int vr_fold_apply_launch<float>(algp_ctx*, int64_t, const int*, const int64_t*, const float*, int64_t, int64_t, const float*,
+                                         const float*, int64_t, int, int, float, float, int64_t, const int64_t*, const float*, const float*,
+                                         const float*, const float*, const float*, float*, float*, float*);
+
+// one GPU: the targets are this context's own ordinary rows (rt is zero on the others)
+template <typename T>
+int vr_fold_launch(algp_ctx* c, int64_t M, const int* ckind, const int64_t* cidx, const T* Vt, int64_t ldv, int64_t col, const T* Xs,
+                   const T* Cp, int64_t n_pool, int DP, int kernel, T os, T noise, const T* tw, T* r, T* rt, T* nrm, T* tp, T* t, T* y1,
+                   T* y2, T* w) {
+    ALGP_TRY(vr_fold_local_launch<T>(c, M, ckind, cidx, Vt, ldv, col, tw, r, rt, nrm, tp, t));
+    return vr_fold_apply_launch<T>(c, M, ckind, cidx, Vt, ldv, col, Xs, Cp, n_pool, DP, kernel, os, noise, M, cidx, (const T*)rt,
+                                   (const T*)r, (const T*)rt, (const T*)nrm, (const T*)t, y1, y2, w);
 }
 template int vr_fold_launch<double>(algp_ctx*, int64_t, const int*, const int64_t*, const double*, int64_t, int64_t, const double*,
                                     const double*, int64_t, int, int, double, double, const double*, double*, double*, double*, double*,
@@ -495,6 +528,141 @@ template int vr_fold_launch<double>(algp_ctx*, int64_t, const int*, const int64_
 template int vr_fold_launch<float>(algp_ctx*, int64_t, const int*, const int64_t*, const float*, int64_t, int64_t, const float*, const float*,
                                    int64_t, int, int, float, float, const float*, float*, float*, float*, float*, float*, float*, float*,
                                    float*);
+
+// ---- the criterion over the ranks of a communicator (api_vr.hip: vr_shard_build, vr_shard_fold) --------------------------
+// A round's contribution of this rank: rows [row0, row0 + B) of V^T over K columns behind one header entry per row: its pool
+// index p where the row is a target; -2 - p where it is a unit row (no target: the product reads any negative entry so, but the
+// disjointness check below still learns the site); -1 behind M.  Rows that are no targets travel as zeros.  Columns from
+// kvalid on (the part of the picks' block no pick has written) are zeros.  16-byte loads and stores.
+template <typename T>
+__global__ __launch_bounds__(256) void vr_pack_rows_kernel(int64_t M, int64_t row0, int64_t B, const int* ckind, const int64_t* cidx,
+                                                           const T* Vt, int64_t ldv, int64_t K, int64_t kvalid, int64_t* head, T* rows) {
+    constexpr int EPV = 16 / (int)sizeof(T);
+    typedef T vec_t __attribute__((ext_vector_type(EPV)));
+    const int64_t pieces = K / EPV;
+    const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (id < B) {
+        const int64_t src = row0 + id;
+        head[id] = src < M ? (ckind[src] < 0 ? cidx[src] : -2 - cidx[src]) : (int64_t)-1;
+    }
+    if (id >= B * pieces) return;
+    const int64_t row = id / pieces, col = (id - row * pieces) * EPV;
+    const int64_t src = row0 + row;
+    vec_t v;
+#pragma unroll
+    for (int e = 0; e < EPV; ++e) v[e] = (T)0;
+    if (src < M && ckind[src] < 0) {
+        v = *reinterpret_cast<const vec_t*>(Vt + src * ldv + col);
+#pragma unroll
+        for (int e = 0; e < EPV; ++e)
+            if (col + e >= kvalid) v[e] = (T)0;
+    }
+    *reinterpret_cast<vec_t*>(rows + row * K + col) = v;
+}
+template <typename T>
+int vr_pack_rows_launch(algp_ctx* c, int64_t M, int64_t row0, int64_t B, const int* ckind, const int64_t* cidx, const T* Vt, int64_t ldv,
+                        int64_t K, int64_t kvalid, int64_t* head, T* rows) {
+    const int64_t n = B * (K / (16 / (int64_t)sizeof(T)));
+    ProfScope ps(c, ALGP_PROF_ROWS, 0.0, sizeof(T) * 2.0 * (double)B * K);
+    hipLaunchKernelGGL(vr_pack_rows_kernel<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->cur, M, row0, B, ckind, cidx, Vt, ldv, K,
+                       kvalid, head, rows);
+    ALGP_HIP(hipGetLastError());
+    return ALGP_OK;
+}
+template int vr_pack_rows_launch<double>(algp_ctx*, int64_t, int64_t, int64_t, const int*, const int64_t*, const double*, int64_t, int64_t,
+                                         int64_t, int64_t*, double*);
+template int vr_pack_rows_launch<float>(algp_ctx*, int64_t, int64_t, int64_t, const int*, const int64_t*, const float*, int64_t, int64_t,
+                                        int64_t, int64_t*, float*);
+
+// The shards must be disjoint: mark[pool site] = 1 for this rank's candidates, and a gathered row of ANOTHER rank, target or
+// unit row, whose site lands on a mark (or outside the pool) raises mark[n_pool], which the build reads back before its last
+// exchange
+__global__ void vr_mark_kernel(int64_t M, const int64_t* cidx, int* mark) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < M) mark[cidx[j]] = 1;
+}
+__global__ void vr_overlap_kernel(const char* gathered, int64_t slice_bytes, int nranks, int self, int64_t B, int64_t n_pool, int* mark) {
+    const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (id >= (int64_t)nranks * B) return;
+    const int r = (int)(id / B);
+    if (r == self) return;
+    const int64_t h = reinterpret_cast<const int64_t*>(gathered + (int64_t)r * slice_bytes)[id - (int64_t)r * B];
+    if (h == -1) return;                                          // padding
+    const int64_t p = h >= 0 ? h : -2 - h;
+    if (p >= n_pool || mark[p]) mark[n_pool] = 1;
+}
+int vr_mark_launch(algp_ctx* c, int64_t M, const int64_t* cidx, int64_t n_pool, int* mark) {
+    ALGP_HIP(hipMemsetAsync(mark, 0, sizeof(int) * (size_t)(n_pool + 1), c->cur));
+    if (M <= 0) return ALGP_OK;
+    hipLaunchKernelGGL(vr_mark_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, c->cur, M, cidx, mark);
+    ALGP_HIP(hipGetLastError());
+    return ALGP_OK;
+}
+int vr_overlap_launch(algp_ctx* c, const char* gathered_heads, int64_t slice_bytes, int nranks, int self, int64_t B, int64_t n_pool,
+                      int* mark) {
+    const int64_t n = (int64_t)nranks * B;
+    hipLaunchKernelGGL(vr_overlap_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->cur, gathered_heads, slice_bytes, nranks, self,
+                       B, n_pool, mark);
+    ALGP_HIP(hipGetLastError());
+    return ALGP_OK;
+}
+
+// A fold's pairs of this rank, padded to the largest shard: (pool index, rt) of its targets, (-1, 0) elsewhere
+template <typename T>
+__global__ void vr_pairs_kernel(int64_t M, int64_t cap, const int* ckind, const int64_t* cidx, const T* rt, int64_t* idx, T* val) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= cap) return;
+    const bool target = j < M && ckind[j] < 0;
+    idx[j] = target ? cidx[j] : (int64_t)-1;
+    val[j] = target ? rt[j] : (T)0;
+}
+template <typename T>
+int vr_pairs_launch(algp_ctx* c, int64_t M, int64_t cap, const int* ckind, const int64_t* cidx, const T* rt, int64_t* idx, T* val) {
+    if (cap <= 0) return ALGP_OK;
+    hipLaunchKernelGGL(vr_pairs_kernel<T>, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, c->cur, M, cap, ckind, cidx, rt, idx, val);
+    ALGP_HIP(hipGetLastError());
+    return ALGP_OK;
+}
+template int vr_pairs_launch<double>(algp_ctx*, int64_t, int64_t, const int*, const int64_t*, const double*, int64_t*, double*);
+template int vr_pairs_launch<float>(algp_ctx*, int64_t, int64_t, const int*, const int64_t*, const float*, int64_t*, float*);
+
+// After a fold's gather (per rank: *nrm at off_nrm, t over ncols columns at off_t, cap pool indices at off_idx, cap values at
+// off_val of its `stride` bytes): t and *nrm summed in rank order, the pairs in one list (padding: site 0 with value 0)
+template <typename T>
+__global__ void vr_fold_gathered_kernel(const char* gathered, int64_t stride, int nranks, int64_t ncols, int64_t cap, int64_t off_nrm,
+                                        int64_t off_t, int64_t off_idx, int64_t off_val, T* t, T* nrm, int64_t* tidx, T* tval) {
+    const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (id < ncols) {
+        T s = (T)0;
+        for (int r = 0; r < nranks; ++r) s += reinterpret_cast<const T*>(gathered + (int64_t)r * stride + off_t)[id];
+        t[id] = s;
+    }
+    if (id == 0) {
+        T s = (T)0;
+        for (int r = 0; r < nranks; ++r) s += *reinterpret_cast<const T*>(gathered + (int64_t)r * stride + off_nrm);
+        *nrm = s;
+    }
+    if (id < (int64_t)nranks * cap) {
+        const int64_t r = id / cap, j = id - r * cap;
+        const int64_t p = reinterpret_cast<const int64_t*>(gathered + r * stride + off_idx)[j];
+        tidx[id] = p >= 0 ? p : 0;
+        tval[id] = p >= 0 ? reinterpret_cast<const T*>(gathered + r * stride + off_val)[j] : (T)0;
+    }
+}
+template <typename T>
+int vr_fold_gathered_launch(algp_ctx* c, const char* gathered, int64_t stride, int nranks, int64_t ncols, int64_t cap, int64_t off_nrm,
+                            int64_t off_t, int64_t off_idx, int64_t off_val, T* t, T* nrm, int64_t* tidx, T* tval) {
+    const int64_t n = std::max<int64_t>(std::max<int64_t>(ncols, (int64_t)nranks * cap), 1);
+    ProfScope ps(c, ALGP_PROF_ROWS, (double)nranks * ncols, (sizeof(T) * (double)ncols + (sizeof(T) + 8.0) * cap) * nranks);
+    hipLaunchKernelGGL(vr_fold_gathered_kernel<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->cur, gathered, stride, nranks, ncols,
+                       cap, off_nrm, off_t, off_idx, off_val, t, nrm, tidx, tval);
+    ALGP_HIP(hipGetLastError());
+    return ALGP_OK;
+}
+template int vr_fold_gathered_launch<double>(algp_ctx*, const char*, int64_t, int, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
+                                             double*, double*, int64_t*, double*);
+template int vr_fold_gathered_launch<float>(algp_ctx*, const char*, int64_t, int, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
+                                            float*, float*, int64_t*, float*);
 
 // the criterion's objective: *out = sum over the targets j (ordinary rows) of omega_j dstat_j in double (one workgroup, the
 // order of vr_pick_col_kernel: a thread adds its rows in ascending order, then the shuffle tree, then the waves left to right)

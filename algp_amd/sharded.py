@@ -40,7 +40,8 @@ class ShardLink(object):
     rank's place in the job, the transport of the library's collectives, and which rank holds which pool site as a
     candidate.  `Agent(env, args, comm=ShardLink(...))` then scores only its share of the pool in `greedy`
     (algp_greedy_sharded: one all-gather per pick; under the MI criterion the pool-wide inverses are dealt over the ranks
-    too, algp_comm_set_mi_groups) and its factor updates take the rows of the new train sites from
+    too, algp_comm_set_mi_groups; under the variance-reduction criterion the targets are every rank's, their rows of V^T
+    exchanged in the build, algp_comm_set_vr_exchange) and its factor updates take the rows of the new train sites from
     their owners (algp_comm_set_owners: one all-gather per planning step) -- agent.py:125-229 with the loop of
     agent.py:313-354 cut into shards; every rank ends each step with the same picks and the same factor.
 
@@ -53,9 +54,12 @@ class ShardLink(object):
     the smaller pool index, which is np.argmax's first maximum (agent.py:349).
     mi_complement_ranks: under the MI criterion, how many ranks (the first ones) hold the complement's pool-wide inverse;
     the others hold the whole pool's (algp_comm_set_mi_groups).  Default: half of them, and both on the one rank of a
-    world of one."""
+    world of one.
+    vr_rows_per_round: under the variance-reduction criterion, how many rows of its V^T a rank contributes to each all-gather
+    of the build (algp_comm_set_vr_exchange; -1: the library's default, a staging buffer within 1 GiB)."""
 
-    def __init__(self, rank, world_size, unique_id=None, all_gather=None, layout='strided', mi_complement_ranks=None):
+    def __init__(self, rank, world_size, unique_id=None, all_gather=None, layout='strided', mi_complement_ranks=None,
+                 vr_rows_per_round=-1):
         if (unique_id is None) == (all_gather is None):
             raise ValueError('give exactly one transport: unique_id (RCCL) or all_gather (host)')
         if layout not in ('strided', 'contiguous'):
@@ -67,6 +71,9 @@ class ShardLink(object):
         if not (self.world_size == 1 and mi_complement_ranks == 1) and not 1 <= mi_complement_ranks < self.world_size:
             raise ValueError('mi_complement_ranks: 1 <= n < world_size (a world of one: 1)')
         self.mi_complement_ranks = int(mi_complement_ranks)
+        if int(vr_rows_per_round) < -1 or int(vr_rows_per_round) == 0:
+            raise ValueError('vr_rows_per_round: a positive number of rows, or -1 for the default')
+        self.vr_rows_per_round = int(vr_rows_per_round)
         self._id_used = False
 
     def owners(self, n_pool):
@@ -101,6 +108,7 @@ class ShardLink(object):
             ctx._shard_link = self
         ctx.comm_set_owners(self.owners(n_pool))
         ctx.comm_set_mi_groups(self.mi_complement_ranks)
+        ctx.comm_set_vr_exchange(self.vr_rows_per_round)
 
 
 class LocalComm(object):
@@ -231,6 +239,10 @@ class ShardedGreedy(object):
 
     def step(self, criterion, static_std, mobile_std):
         """One pick: returns (pool index of the winner, its utility)."""
+        if criterion == 2:
+            # every rank's scores() would count its own shard's targets only: another quantity than the criterion's
+            raise ValueError('ShardedGreedy: the variance-reduction criterion (2) needs the targets of every rank; use the ABI '
+                             'route, Context.comm_set_vr_exchange + greedy_sharded (algp_greedy_sharded)')
         if self.lazy and criterion == 0 and hasattr(self.b, 'best_candidate') and hasattr(self.comm, 'all_gather_pairs'):
             best_pos, best_v = self._step_pairs(criterion, static_std, mobile_std)
             winner = int(self.all_idx[best_pos])

@@ -226,9 +226,15 @@ int algp_posterior_mean(algp_ctx* ctx, const int64_t* idx, int64_t M, void* mu_o
  * static-sampled and switched-off rows get -inf, as for the entropy criterion.  The first scoring after a candidate solve is
  * one fused M x M x (N + picks) product on the matrix cores (2 M^2 K flop; no M x M matrix is written); each pick committed
  * after it is folded in with E' = E - r_T r_c^T (r: the pick's column of V^T): one fused kernel-GEMV and two passes over
- * V^T.  algp_scores, algp_best_candidate (full scoring, as MI) and algp_greedy accept it; algp_greedy_sharded refuses it
- * (ALGP_ERR_BAD_ARG); candidates set with an extra variance, or a candidate set that lists a pool site twice, are refused with
- * ALGP_ERR_STATE.
+ * V^T.  algp_scores, algp_best_candidate (full scoring, as MI) and algp_greedy accept it; algp_greedy_sharded accepts it with a
+ * layout of algp_comm_set_vr_exchange (below) and refuses it without one (ALGP_ERR_BAD_ARG); candidates set with an extra
+ * variance, or a candidate set that lists a pool site twice, are refused with ALGP_ERR_STATE.
+ * On a context with that layout attached and more than one rank the targets are the ordinary rows of EVERY rank's shard, and
+ * under this criterion algp_scores is a COLLECTIVE: every rank calls it, in the same sequence; it brings the state over the
+ * ranks up to the committed picks (a build, or one fold per pick) and returns the utilities of this rank's own rows against
+ * the targets of all ranks.  With algp_commit_pick on every rank that is how forced picks are driven.  algp_greedy and
+ * algp_best_candidate under this criterion, and algp_score_paths_vr, return ALGP_ERR_STATE there (they would count this rank's
+ * targets only).
  * Target weights (algp_set_target_weights below): with a weight omega_q >= 0 per pool site attached, target j counts omega_j
  * times -- sum_{j in T} omega_j E_jc^2 in both utilities, i.e. sum_j omega_j var(j | A) - sum_j omega_j var(j | A with c
  * static-sampled): a region of interest, plots that matter more, the sites a later prediction is read at.  The targets stay
@@ -255,7 +261,10 @@ int algp_greedy(algp_ctx* ctx, int criterion, double static_std, double mobile_s
  *   *sum = sum_{j in T} omega_j pv_j, pv_j the variance algp_get_posterior reports for target row j (omega = 1 without weights).
  * A pick's utility is this sum before its commit minus the sum after.  Needs a candidate solve (ALGP_ERR_STATE), brings the rows
  * up to date as algp_get_posterior does, applies the criterion's two refusals (ALGP_ERR_STATE), and is one device reduction in
- * a fixed order, accumulated in double: the same bits in every run. */
+ * a fixed order, accumulated in double: the same bits in every run.  It stays LOCAL on a context that scores the criterion over
+ * ranks (algp_comm_set_vr_exchange) and is no collective: *sum = this rank's share, over the targets of its own shard; the
+ * objective is the sum over the ranks.  The weights are per pool site, so every rank attaches all of them; a hash of what was
+ * attached travels in the criterion's agreement word, and ranks holding different weights all get ALGP_ERR_BAD_ARG. */
 int algp_set_target_weights(algp_ctx* ctx, const double* w, int64_t n_pool);
 int algp_get_target_variance(algp_ctx* ctx, double* sum);
 
@@ -326,7 +335,8 @@ int algp_score_paths_vr(algp_ctx* ctx, const int64_t* sites, int npaths, int max
  *   (the winner is then chosen on the host and only its row goes back to the device).
  *   This is also how two ranks can share one card.
  * Both reserve the exchange's buffers for the current train set; algp_set_train re-reserves them when its size changes.
- * algp_greedy_sharded: k picks (entropy criterion; the MI criterion with a layout of algp_comm_set_mi_groups, below).  Per pick, stream-ordered and with
+ * algp_greedy_sharded: k picks (entropy criterion; the MI criterion with a layout of algp_comm_set_mi_groups, the
+ *   variance-reduction criterion with one of algp_comm_set_vr_exchange, both below).  Per pick, stream-ordered and with
  *   a single read-back (40 bytes): each rank's best candidate resolved on the device (argmax, refresh of the rows
  *   whose bound can still win, argmax), the all-gather, the first maximum in rank order (= np.argmax over the
  *   concatenated scores, agent.py:349, shards being contiguous in rank order), then the commit of the winner on every
@@ -394,6 +404,33 @@ int algp_greedy_sharded(algp_ctx* ctx, int criterion, double static_std, double 
  * come from differently blocked products).  algp_scores with the MI criterion on such a context scores from the sharded
  * state while it is current; with picks committed outside algp_greedy_sharded it builds the whole inverses on this GPU. */
 int algp_comm_set_mi_groups(algp_ctx* ctx, int n_complement_ranks);
+/* algp_comm_set_vr_exchange: the layout under which the VARIANCE-REDUCTION criterion is scored over the ranks (without it
+ * algp_greedy_sharded refuses that criterion with ALGP_ERR_BAD_ARG).  The targets become the union over the ranks of the
+ * ordinary rows of each rank's candidate set -- the shards must be disjoint: a pool site listed by two ranks, as a target or as
+ * a unit row, makes every rank return ALGP_ERR_STATE from the build; empty shards are legal -- and a rank keeps w_c = sum_{j in T_all} omega_j E_jc^2 for its
+ * own rows c only.  rows_per_round > 0: every rank contributes that many rows of its V^T (rounded up to a multiple of 128) to
+ * each all-gather of the build; -1: the library's default,
+ *   B = max(128, floor(((2^30 / (world + 1) - 32) / (8 + es (Npad + 128))) / 128) * 128),   es = the element size,
+ * the largest multiple of 128 for which the (world + 1) slices [32-byte header | 8-byte pool index and Npad + 128 elements per
+ * row] of the staging buffer stay within 1 GiB (config 4, 8 ranks, fp64: 1 408 rows, 9 rounds); either is capped at the largest
+ * shard, rounded up to 128.  0 detaches the layout.  After algp_comm_init[_host] (else ALGP_ERR_STATE), which drops a layout
+ * attached before; the same value on every rank: differing values make every rank return ALGP_ERR_BAD_ARG from its next
+ * collective scoring (they are compared in the agreement word, before any payload travels).  A world of one keeps the
+ * one-GPU state, bit for bit.
+ * Collectives (all-gathers through the attached transport only), on the context's stream, a gather and the product behind it
+ * one after the other: at the first scoring of a call an 80-byte agreement word per rank (status, rows, picks committed and
+ * folded, whether it needs a build -- no valid state, another solve, new weights, ALGP_VR_RANK1=0; any rank's need is every
+ * rank's -- the rows per round, the weights' hash, Npad, n_pool); a build is a 32-byte word (allocations), R = ceil(largest
+ * shard / B) gathers of 32 + B (8 + es K) bytes per rank (per row its pool site -- tagged where the row is a unit row, which
+ * travels as zeros -- and its K columns) (K = Npad, or Npad + 128 once picks are committed), each followed by
+ * ONE rectangular product of the rank's whole V^T against the world x B gathered rows (2 M_loc_pad world B K flop), and a last
+ * 32-byte gather with the outcome of the disjointness check; every committed pick folded is one gather of
+ * 48 + es (Npad + 128) + (8 + es) max_shard bytes per rank (the rank's partial sums over its targets and its targets' (pool
+ * index, omega r) pairs).  The partial sums are added in a fixed order (round, rank, tile; rank): the same bits in every run
+ * for a given world, partition and rows per round; across worlds the utilities differ by rounding only.  Every gather carries
+ * each rank's status word: a rank that fails still takes part, every rank returns its code from the same call, and the state
+ * is rebuilt by the next call.  Ranks with different numbers of committed picks: ALGP_ERR_STATE. */
+int algp_comm_set_vr_exchange(algp_ctx* ctx, int64_t rows_per_round);
 /* ---- test hooks -----------------------------------------------------------------------------------------------------
  * Compiled in when ALGP_TEST_HOOKS is 1 -- the default of algp_amd/csrc/Makefile, and what this repository's tests and
  * bench.py (its one-stream leg, the strong-scaling emulation) need; `make TEST_HOOKS=0` builds the library without them
@@ -426,7 +463,10 @@ int algp_comm_set_mi_groups(algp_ctx* ctx, int n_complement_ranks);
  * 2 = the launch that packs its contribution counts as failed (ALGP_ERR_HIP in its status word, the gather still runs),
  * 3 = this rank's agreement word of its next sharded algp_factorize_update carries `code`: every rank returns it,
  * 4 = the next step of the sharded MI criterion on this rank (its build after a solve, else the fold of a committed pick) fails
- * with `code`; every rank returns it from that algp_greedy_sharded call (a world of one has no such step). */
+ * with `code`; every rank returns it from that algp_greedy_sharded call (a world of one has no such step),
+ * 5 = the same for the variance-reduction criterion over the ranks (algp_comm_set_vr_exchange): this rank's next step (the
+ * build, else the fold of a committed pick) fails with `code`; every rank returns it from that algp_scores or
+ * algp_greedy_sharded call. */
 int algp_debug_fail_at(algp_ctx* ctx, int where, int code);
 int algp_debug_trsv_stall(algp_ctx* ctx, int block);
 int algp_debug_get_pick(algp_ctx* ctx, int q, void* row_out, int64_t row_capacity, int64_t* ncols_out, double* d_out);
