@@ -19,6 +19,7 @@ LIB_PATH = os.environ.get('ALGP_LIB') or os.path.join(_HERE, 'lib', 'libalgp_hip
 
 F32, F64 = 0, 1
 KERNEL_RBF, KERNEL_MATERN15 = 0, 1
+KERNEL_MATERN05, KERNEL_MATERN25 = 2, 3
 CRIT_ENTROPY, CRIT_MUTUAL_INFORMATION, CRIT_VARIANCE_REDUCTION = 0, 1, 2
 OK, ERR_BAD_ARG, ERR_HIP, ERR_NOT_PD, ERR_OOM, ERR_STATE, ERR_NO_DEVICE = range(7)
 PROF = dict(kmat=0, gemm_chol=1, gemm_trsm=2, potrf_diag=3, trsv=4, rows=5, score=6, gemm_other=7, cholesky=8, trsm=9,

@@ -80,7 +80,7 @@ class Agent(object):
     # ---- model plumbing (agent.py:34-45) --------------------------------------------------------
     def _init_model(self, args):
         self.gp = GPR(latent=args.latent, lr=args.lr, max_iterations=args.max_iterations,
-                      kernel_params={'type': args.kernel}, learn_likelihood_noise=self.learn_likelihood_noise,
+                      kernel_params={'type': args.kernel, 'nu': getattr(args, 'matern_nu', 1.5)}, learn_likelihood_noise=self.learn_likelihood_noise,
                       dtype=getattr(args, 'dtype', np.float64), device=getattr(args, 'device', 0))
 
     def load_model(self, parent_agent):

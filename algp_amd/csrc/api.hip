@@ -562,7 +562,7 @@ int algp_dtype(const algp_ctx* c) { return c ? c->dtype : -1; }
 int algp_set_hypers(algp_ctx* c, int kernel, int D, const double* log_ls, double log_os, double log_noise) {
     CHECK_CTX(c);
     if (D < 1 || D > MAXD || !log_ls) return fail(c, ALGP_ERR_BAD_ARG, "set_hypers: 1 <= D <= 8 required");
-    if (kernel != ALGP_KERNEL_RBF && kernel != ALGP_KERNEL_MATERN15) return fail(c, ALGP_ERR_BAD_ARG, "set_hypers: unknown kernel");
+    if (kernel < ALGP_KERNEL_RBF || kernel > ALGP_KERNEL_MATERN25) return fail(c, ALGP_ERR_BAD_ARG, "set_hypers: unknown kernel");
     if (c->hyp.set && c->hyp.D != D && c->n_pool > 0 && !c->pool_is_cov) {
         // the resident coordinates have another width: drop the pool, the caller sets a new one
         c->n_pool = 0;

@@ -144,7 +144,7 @@ struct VrState {
 }  // namespace algp
 
 namespace algp {
-// exp(x) for the kernel values, x <= 0 in every use (-r^2/2, -sqrt(3) r): ONE definition for every kernel that evaluates
+// exp(x) for the kernel values, x <= 0 in every use (-r^2/2, -r, -sqrt(3) r, -sqrt(5) r): ONE definition for every kernel that evaluates
 // k(x, x') -- the matrix build, the lazy refresh's b', the path scores, the mean-only posterior, the MLL gradient -- so
 // that a value recomputed later has the bits of the one stored earlier.  fp64: Cody-Waite reduction x = k ln2 + r,
 // |r| <= ln2 / 2, Taylor to r^13 (truncation 4e-18), v_ldexp: ~20 instructions where the library routine takes ~55 (the
@@ -174,19 +174,62 @@ __device__ __forceinline__ double kexp(double x) {
 
 __device__ __forceinline__ float kfma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 __device__ __forceinline__ double kfma(double a, double b, double c) { return __builtin_fma(a, b, c); }
-// ScaleKernel(RBF) / ScaleKernel(Matern-1.5) of a squared scaled distance
+// Matern-1/2 and Matern-5/2 of a squared scaled distance, and their derivative factors (kdk below): written once, here, with
+// contraction off and the one fused multiply-add spelled out, so that every site that inlines them -- the matrix build, the
+// product epilogues, the criteria, the gradient -- rounds the same way whatever surrounds the call.
+//   nu = 1/2: os e^-r, dk = os e^-r / r (0 at r = 0: the limit of u_d^2 / r);  nu = 5/2, a = sqrt(5) r: os (1 + a + a^2/3) e^-a,
+//   dk = 5/3 os (1 + a) e^-a
+// One body for both: a = c r with c = 1 or sqrt 5 by the (uniform) form, one square root and one exponential, then the value
+// os e^-a alone or times the polynomial.  A site that takes the form at run time thus holds one square root and one exponential
+// for the two, not two of each (the variance-reduction epilogues inline this 64 times).
 template <typename T>
+__device__ __forceinline__ T kval_matern_05_25(int kernel, T os, T r2, T* dk) {
+#pragma clang fp contract(off)
+    const bool m25 = kernel == ALGP_KERNEL_MATERN25;
+    const T r = sqrt(r2);
+    const T a = r * (m25 ? (T)2.2360679774997896 : (T)1);
+    const T oe = os * kexp(-a);
+    const T a1 = (T)1 + a;
+    if (dk) *dk = m25 ? (T)1.6666666666666667 * (a1 * oe) : (r > (T)0 ? oe / r : (T)0);
+    // (selected, not multiplied by a run-time 0: a coordinate difference that overflows gives a = inf, e^-a = 0 and the value 0
+    // for nu = 1/2 as os * kexp(-r) alone would, not 0 * inf)
+    return m25 ? kfma(a * (T)0.33333333333333333, a, a1) * oe : oe;
+}
+// The forms come in two families: 0 = RBF and Matern-3/2, 1 = Matern-1/2 and Matern-5/2.  A kernel whose inner loop selects the
+// form at run time is compiled once per family (kmat_kernel, the generating GEMM epilogues), so that the copy the first two forms
+// run is the code it was before the second family existed: with all four in one loop the fp64 matrix build took 20 more VGPRs,
+// and the fp64 gradient kernel (whose nu = 1/2 factor holds a division) 4 more, which cost it a wave of occupancy.
+__host__ __device__ inline int kernel_family(int kernel) { return kernel == ALGP_KERNEL_MATERN05 || kernel == ALGP_KERNEL_MATERN25 ? 1 : 0; }
+// ScaleKernel(RBF) / ScaleKernel(Matern-nu), nu = 1/2, 3/2, 5/2, of a squared scaled distance.  FAM: the family `kernel` is known
+// to belong to (only its two forms are compiled in), or -1: any of the four
+template <typename T, int FAM = -1>
 __device__ __forceinline__ T kval(int kernel, T os, T r2) {
-    if (kernel == ALGP_KERNEL_RBF) return os * kexp((T)-0.5 * r2);
+    if (FAM != 1 && kernel == ALGP_KERNEL_RBF) return os * kexp((T)-0.5 * r2);
+    if (FAM != 0 && (FAM == 1 || kernel_family(kernel) == 1)) return kval_matern_05_25<T>(kernel, os, r2, nullptr);
     const T r = sqrt(r2) * (T)1.7320508075688772;
     return os * ((T)1 + r) * kexp(-r);
+}
+// The kernel value (returned) and the factor dk of its length-scale derivative, dk * u_d^2 = dk/dlog ls_d with
+// u_d = (x_d - x'_d) / ls_d, i.e. dk = -2 dk/dr^2: the MLL gradient (fit.hip).  FAM as for kval
+template <typename T, int FAM = -1>
+__device__ __forceinline__ T kdk(int kernel, T os, T r2, T& dk) {
+    if (FAM != 1 && kernel == ALGP_KERNEL_RBF) {
+        const T kv = os * kexp((T)-0.5 * r2);
+        dk = kv;
+        return kv;
+    }
+    if (FAM != 0 && (FAM == 1 || kernel_family(kernel) == 1)) return kval_matern_05_25<T>(kernel, os, r2, &dk);
+    const T a = sqrt(r2) * (T)1.7320508075688772;
+    const T e = kexp(-a);
+    dk = (T)3 * os * e;
+    return os * ((T)1 + a) * e;
 }
 // k(x, x') from the scaled, zero-padded coordinates of the two sites: ONE definition for the kernel-matrix build (kmat.hip)
 // and for the product epilogue that forms the candidates' right-hand sides in registers (gemm.hip, GEN), which must leave the
 // same bits.  Two coordinates (the form with two call sites): r^2 = fma(d0, d0, d1 * d1), the second square rounded on its own --
 // what the compiler has always made of `r2 = 0; r2 += d0 * d0; r2 += d1 * d1` in the matrix build, written out so that no call
 // site can be contracted differently.  Wider coordinates keep the plain sum (the matrix build is their only caller).
-template <typename T, int DP>
+template <typename T, int DP, int FAM = -1>
 __device__ __forceinline__ T kmat_value(int kernel, T os, const T (&xr)[DP], const T (&xc)[DP]) {
     T r2;
     if constexpr (DP == 2) {
@@ -201,7 +244,7 @@ __device__ __forceinline__ T kmat_value(int kernel, T os, const T (&xr)[DP], con
             r2 += df * df;
         }
     }
-    return kval<T>(kernel, os, r2);
+    return kval<T, FAM>(kernel, os, r2);
 }
 // Entry (row, global column gcol) of the candidates' right-hand side B^T = K(candidates, train) as the matrix build writes it:
 // kind -1: an ordinary row, k(x_row, x_col) in the columns of the train set (gcol < ncols), 0 in the padding behind them;

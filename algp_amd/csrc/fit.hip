@@ -3,7 +3,8 @@
 //
 //   MLL = -1/2 y0' S^-1 y0 - 1/2 log det S - N/2 log 2pi,   S = K + diag(var) + sigma_n^2 I
 //   dMLL/dtheta = 1/2 tr(W dS/dtheta),  W = alpha alpha' - S^-1
-//   dS/dlog os = K ; dS/dlog ls_d = K .* u_d^2 (RBF) | 3 os e^{-a} u_d^2 (Matern-1.5), u_d = (x_d-x'_d)/ls_d
+//   dS/dlog os = K ; dS/dlog ls_d = dk u_d^2, u_d = (x_d-x'_d)/ls_d, dk = -2 dk/dr^2 (kdk, common.h): K (RBF) | os e^-r / r, 0 where
+//   r = 0 (Matern-1/2) | 3 os e^-a, a = sqrt(3) r (Matern-3/2) | 5/3 os (1 + a) e^-a, a = sqrt(5) r (Matern-5/2)
 //   dS/dlog sigma_n^2 = sigma_n^2 E,  E_ij = 1 where rows i and j are the same pool site (I unless a site is listed more than
 //   once: the kernel matrix gives such rows' cross entries sigma_n^2 too, algp_hip.h at algp_set_train)
 // S^-1 = X X' with X = L^-T (trinv_upper + syrk_upper on the MFMA GEMM, both skipping X's zero half:
@@ -14,7 +15,8 @@
 
 namespace algp {
 
-template <typename T, int DP>
+// FAM: the family of `kernel` (kernel_family, common.h): one copy of the kernel per family
+template <typename T, int DP, int FAM>
 __global__ __launch_bounds__(256) void mll_grad_kernel(const T* Sinv, int64_t ld, int64_t N, const T* Xs,
                                                        const int64_t* aidx, const T* alpha, int kernel, T os,
                                                        int repeats /* a pool site occurs in more than one row */,
@@ -74,16 +76,8 @@ __global__ __launch_bounds__(256) void mll_grad_kernel(const T* Sinv, int64_t ld
             }
             const T w = s_a[li] * aj - sv[rr];
             const double m = (i == j) ? 1.0 : 2.0;               // symmetric: off-diagonal pairs count twice
-            T kv, dk;                                            // dk * u_d^2 = dK/dlog ls_d
-            if (kernel == ALGP_KERNEL_RBF) {
-                kv = os * kexp((T)-0.5 * r2);
-                dk = kv;
-            } else {
-                const T a = sqrt(r2) * (T)1.7320508075688772;
-                const T e = kexp(-a);
-                kv = os * ((T)1 + a) * e;
-                dk = (T)3 * os * e;
-            }
+            T dk;                                                // dk * u_d^2 = dK/dlog ls_d (kdk, common.h; 0 at r = 0 for nu = 1/2)
+            const T kv = kdk<T, FAM>(kernel, os, r2, dk);
             g_os += m * (double)(w * kv);
             if (i == j) g_tr += (double)w;
             else if (repeats && s_p[li] == pj) g_tr += 2.0 * (double)w;   // a second row of the same site: S_ij holds sigma_n^2 too
@@ -136,9 +130,14 @@ int mll_grad_launch(algp_ctx* c, const T* Sinv, int64_t ld, int64_t N, const T* 
     const unsigned nb = (unsigned)((N + 63) / 64);
     ProfScope ps(c, ALGP_PROF_KMAT, 0.5 * (double)N * N * (3.0 * DP + 8.0), sizeof(T) * 0.5 * (double)N * N);
     dim3 grid(nb * (nb + 1) / 2), blk(256);
-    if (DP == 2) hipLaunchKernelGGL((mll_grad_kernel<T, 2>), grid, blk, 0, c->cur, Sinv, ld, N, Xs, aidx, alpha, kernel, os, rp, partial);
-    else if (DP == 4) hipLaunchKernelGGL((mll_grad_kernel<T, 4>), grid, blk, 0, c->cur, Sinv, ld, N, Xs, aidx, alpha, kernel, os, rp, partial);
-    else hipLaunchKernelGGL((mll_grad_kernel<T, 8>), grid, blk, 0, c->cur, Sinv, ld, N, Xs, aidx, alpha, kernel, os, rp, partial);
+    auto launch = [&](auto fam) {
+        constexpr int FAM = decltype(fam)::value;
+        if (DP == 2) hipLaunchKernelGGL((mll_grad_kernel<T, 2, FAM>), grid, blk, 0, c->cur, Sinv, ld, N, Xs, aidx, alpha, kernel, os, rp, partial);
+        else if (DP == 4) hipLaunchKernelGGL((mll_grad_kernel<T, 4, FAM>), grid, blk, 0, c->cur, Sinv, ld, N, Xs, aidx, alpha, kernel, os, rp, partial);
+        else hipLaunchKernelGGL((mll_grad_kernel<T, 8, FAM>), grid, blk, 0, c->cur, Sinv, ld, N, Xs, aidx, alpha, kernel, os, rp, partial);
+    };
+    if (kernel_family(kernel)) launch(std::integral_constant<int, 1>{});
+    else launch(std::integral_constant<int, 0>{});
     ALGP_HIP(hipGetLastError());
     hipLaunchKernelGGL(mll_grad_reduce_kernel, dim3(1), dim3(256), 0, c->cur, partial, (int64_t)grid.x, 2 + DP, out_dev);
     ALGP_HIP(hipGetLastError());

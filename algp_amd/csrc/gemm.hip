@@ -66,10 +66,15 @@ struct GemmArgs {
 
 // GEN kernels only (the scheduled update products of the candidate sweep with fused right-hand sides, RhsGen in common.h): C is
 // not read -- entry (row, column) of the C tile is the B^T entry (row, col0 + column), formed in the epilogue by bt_entry from
-// the gathered coordinates rx / cx (DP per row / column) and the rows' kinds rk
-template <typename T, int DP_>
+// the gathered coordinates rx / cx (DP per row / column) and the rows' kinds rk.  FAM: which kernel forms the instantiation holds
+// a copy of its store loop for -- 0: RBF and Matern-3/2, 1: Matern-1/2 and Matern-5/2 (kernel_family, common.h).  Two forms per kernel and
+// not four: the epilogue shares its registers with the k loop, and with four copies in one kernel the allocation of the whole
+// kernel moved (fp64 256 -> 246 VGPRs, profiles/kernel_forms_resources.md): the RBF copy, which the headline step runs, would no
+// longer be the code it was, in the one kernel here with no register to spare.
+template <typename T, int DP_, int FAM_ = 0>
 struct GenGemmArgs : GemmArgs<T> {
     static constexpr int DP = DP_;
+    static constexpr int FAM = FAM_;
     const T* rx;
     const T* cx;
     const int* rk;
@@ -80,8 +85,8 @@ struct GenGemmArgs : GemmArgs<T> {
 };
 template <typename A>
 struct gen_dp { static constexpr int value = 0; };
-template <typename T, int DP>
-struct gen_dp<GenGemmArgs<T, DP>> { static constexpr int value = DP; };
+template <typename T, int DP, int FAM>
+struct gen_dp<GenGemmArgs<T, DP, FAM>> { static constexpr int value = DP; };
 
 typedef __attribute__((address_space(3))) void* lds_vp;
 typedef const __attribute__((address_space(1))) void* glb_vp;
@@ -163,10 +168,10 @@ __device__ __forceinline__ T vr_pool_cov(const VrGemmArgs<T>& g, int64_t prow, i
     }
     T cv;
     if (g.kernel == ALGP_KERNEL_RBF) cv = g.os * kexp((T)-0.5 * r2);
-    else {
+    else if (g.kernel == ALGP_KERNEL_MATERN15) {
         const T rr = sqrt(r2) * (T)1.7320508075688772;
         cv = g.os * ((T)1 + rr) * kexp(-rr);
-    }
+    } else cv = kval<T, 1>(g.kernel, g.os, r2);
     if (prow == pcol) cv += g.noise;
     return cv;
 }
@@ -615,8 +620,8 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel_dma4(Args g) {
         const int64_t gc = g.col0 + n0 + wc * 64 + gfr;            // global column of this lane's column j = 0; + 16 j
         const T os = g.os;
         const int64_t ncols = g.ncols;
-        // one copy of the loop per kernel form: the form is uniform, and as a run-time argument of kval both forms' arithmetic
-        // (a square root per value) would be done and selected
+        // one copy of the loop per kernel form of this instantiation's family: the form is uniform, and as a run-time argument of
+        // kval every form's arithmetic (a square root per value) would be done and selected
         auto tile_out = [&](auto kform) {
 #pragma unroll
             for (int i = 0; i < 4; ++i)
@@ -637,8 +642,13 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel_dma4(Args g) {
                     }
                 }
         };
-        if (g.kernel == ALGP_KERNEL_RBF) tile_out(std::integral_constant<int, ALGP_KERNEL_RBF>{});
-        else tile_out(std::integral_constant<int, ALGP_KERNEL_MATERN15>{});
+        if constexpr (Args::FAM == 0) {
+            if (g.kernel == ALGP_KERNEL_RBF) tile_out(std::integral_constant<int, ALGP_KERNEL_RBF>{});
+            else tile_out(std::integral_constant<int, ALGP_KERNEL_MATERN15>{});
+        } else {
+            if (g.kernel == ALGP_KERNEL_MATERN05) tile_out(std::integral_constant<int, ALGP_KERNEL_MATERN05>{});
+            else tile_out(std::integral_constant<int, ALGP_KERNEL_MATERN25>{});
+        }
     } else if (beta != (T)0) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -789,8 +799,8 @@ __global__ __launch_bounds__(256) void gemm_finish_kernel(const T* part, int S, 
 
 // The same with the C term generated (GenGemmArgs): the leftover tiles of a scheduled update product with fused right-hand sides.
 // The coordinates of a thread's columns are loaded once, the coordinates and the kind of a row once per piece; one copy of the C
-// term per kernel form, as in the product's epilogue.
-template <typename T, int DP>
+// term per kernel form of the family FAM, as in the product's epilogue.
+template <typename T, int DP, int FAM>
 __global__ __launch_bounds__(256) void gemm_finish_gen_kernel(const T* part, int S, int tile0, int tiles_n, T beta, const T* rx, const T* cx,
                                                               const int* rk, int64_t col0, int64_t ncols, int kernel, T os, T* D, int64_t ldd) {
 #pragma clang fp contract(off)
@@ -825,8 +835,13 @@ __global__ __launch_bounds__(256) void gemm_finish_gen_kernel(const T* part, int
             v[i] = beta * cv;
         }
     };
-    if (kernel == ALGP_KERNEL_RBF) c_term(std::integral_constant<int, ALGP_KERNEL_RBF>{});
-    else c_term(std::integral_constant<int, ALGP_KERNEL_MATERN15>{});
+    if constexpr (FAM == 0) {
+        if (kernel == ALGP_KERNEL_RBF) c_term(std::integral_constant<int, ALGP_KERNEL_RBF>{});
+        else c_term(std::integral_constant<int, ALGP_KERNEL_MATERN15>{});
+    } else {
+        if (kernel == ALGP_KERNEL_MATERN05) c_term(std::integral_constant<int, ALGP_KERNEL_MATERN05>{});
+        else c_term(std::integral_constant<int, ALGP_KERNEL_MATERN25>{});
+    }
     finish_sum<T>(part + (int64_t)j * S * (128 * 128), (unsigned)(lrow * 128 + lcol), S, v);
 #pragma unroll
     for (int i = 0; i < F::PPT; ++i) *reinterpret_cast<V*>(D + (row + i * F::RSTEP) * ldd + col) = v[i];
@@ -975,12 +990,17 @@ int gemm_nt_launch_gen(algp_ctx* c, int klass, int64_t m, int64_t n, int64_t k, 
     const GemmNt<T> p = {.klass = klass, .m = m, .n = n, .k = k, .alpha = alpha, .beta = beta, .A = {A, lda}, .B = {B, ldb}, .D = {D, ldd}};
     int64_t tiles;
     ALGP_TRY(gemm_check(c, "gemm_nt_gen", p, &tiles));
-    GenGemmArgs<T, 2> g;
-    gemm_fill(g, p);                                               // (C, not read by this form, is D's pointer and strides)
-    g.rx = (const T*)gen.rx; g.cx = (const T*)gen.cx; g.rk = gen.rk;
-    g.col0 = col0; g.ncols = gen.ncols; g.kernel = gen.kernel; g.os = (T)gen.outputscale;
-    return launch_scheduled(c, "gemm_nt_gen", p, gemm_book(p, tiles, 128.0 * 128.0), g, gemm_nt_kernel_dma4<T, false, GenGemmArgs<T, 2>, true>,
-                            gemm_finish_gen_kernel<T, 2>, false, g.rx, g.cx, g.rk, col0, g.ncols, g.kernel, g.os, D, ldd);
+    auto launch = [&](auto fam) {
+        constexpr int FAM = decltype(fam)::value;
+        GenGemmArgs<T, 2, FAM> g;
+        gemm_fill(g, p);                                           // (C, not read by this form, is D's pointer and strides)
+        g.rx = (const T*)gen.rx; g.cx = (const T*)gen.cx; g.rk = gen.rk;
+        g.col0 = col0; g.ncols = gen.ncols; g.kernel = gen.kernel; g.os = (T)gen.outputscale;
+        return launch_scheduled(c, "gemm_nt_gen", p, gemm_book(p, tiles, 128.0 * 128.0), g,
+                                gemm_nt_kernel_dma4<T, false, GenGemmArgs<T, 2, FAM>, true>, gemm_finish_gen_kernel<T, 2, FAM>, false, g.rx,
+                                g.cx, g.rk, col0, g.ncols, g.kernel, g.os, D, ldd);
+    };
+    return kernel_family(gen.kernel) ? launch(std::integral_constant<int, 1>{}) : launch(std::integral_constant<int, 0>{});
 }
 template int gemm_nt_launch_gen<double>(algp_ctx*, int, int64_t, int64_t, int64_t, double, const double*, int64_t, const double*, int64_t,
                                         double, const RhsGen&, int64_t, double*, int64_t);

@@ -58,7 +58,8 @@ struct KmatArgs {
 // EQ: entries whose row and column address the same pool site receive a diagonal term (the symmetric builds); without it
 // (the candidates' B^T, cross matrices) the index comparisons are not even compiled in -- they and the other per-element
 // bookkeeping were half of the kernel's VALU instructions, and the kernel is VALU-issue bound (profiles/r04_valu_by_kernel.json).
-template <typename T, int DP, bool EQ>
+// FAM: the family of a.kernel (kernel_family, common.h): one copy of the kernel per family, the form selected inside it
+template <typename T, int DP, bool EQ, int FAM>
 __global__ __launch_bounds__(256) void kmat_kernel(KmatArgs<T> a) {
     constexpr int VEC = Vec16<T>::N;
     using vec_t = typename Vec16<T>::type;
@@ -128,7 +129,7 @@ __global__ __launch_bounds__(256) void kmat_kernel(KmatArgs<T> a) {
                 for (int d = 0; d < DP; ++d) xr[d] = s_x[rr][d];
 #pragma unroll
                 for (int v = 0; v < VEC; ++v) {
-                    const T val = kmat_value<T, DP>(a.kernel, a.outputscale, xr, xc[v]);
+                    const T val = kmat_value<T, DP, FAM>(a.kernel, a.outputscale, xr, xc[v]);
                     o[v] = live[v] ? val : (T)0;
                 }
             }
@@ -177,15 +178,20 @@ static int kmat_dispatch(algp_ctx* c, const KmatArgs<T>& a, int DP) {
         b.row_base = y0 * 32;
         dim3 grid((unsigned)gx, (unsigned)ny);
         const bool eq = a.same_pool && (a.noise_on_equal != (T)0 || a.diag_add != nullptr);
-        if (eq) {
-            if (DP == 2) hipLaunchKernelGGL((kmat_kernel<T, 2, true>), grid, dim3(256), 0, c->cur, b);
-            else if (DP == 4) hipLaunchKernelGGL((kmat_kernel<T, 4, true>), grid, dim3(256), 0, c->cur, b);
-            else hipLaunchKernelGGL((kmat_kernel<T, 8, true>), grid, dim3(256), 0, c->cur, b);
-        } else {
-            if (DP == 2) hipLaunchKernelGGL((kmat_kernel<T, 2, false>), grid, dim3(256), 0, c->cur, b);
-            else if (DP == 4) hipLaunchKernelGGL((kmat_kernel<T, 4, false>), grid, dim3(256), 0, c->cur, b);
-            else hipLaunchKernelGGL((kmat_kernel<T, 8, false>), grid, dim3(256), 0, c->cur, b);
-        }
+        auto launch = [&](auto fam) {
+            constexpr int FAM = decltype(fam)::value;
+            if (eq) {
+                if (DP == 2) hipLaunchKernelGGL((kmat_kernel<T, 2, true, FAM>), grid, dim3(256), 0, c->cur, b);
+                else if (DP == 4) hipLaunchKernelGGL((kmat_kernel<T, 4, true, FAM>), grid, dim3(256), 0, c->cur, b);
+                else hipLaunchKernelGGL((kmat_kernel<T, 8, true, FAM>), grid, dim3(256), 0, c->cur, b);
+            } else {
+                if (DP == 2) hipLaunchKernelGGL((kmat_kernel<T, 2, false, FAM>), grid, dim3(256), 0, c->cur, b);
+                else if (DP == 4) hipLaunchKernelGGL((kmat_kernel<T, 4, false, FAM>), grid, dim3(256), 0, c->cur, b);
+                else hipLaunchKernelGGL((kmat_kernel<T, 8, false, FAM>), grid, dim3(256), 0, c->cur, b);
+            }
+        };
+        if (kernel_family(a.kernel)) launch(std::integral_constant<int, 1>{});
+        else launch(std::integral_constant<int, 0>{});
     }
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;

@@ -803,10 +803,10 @@ __device__ __forceinline__ T pick_bprime(bool unit, int64_t pj, const T* Xs, con
                 r2 += df * df;
             }
             if (kernel == ALGP_KERNEL_RBF) bp = os * kexp((T)-0.5 * r2);
-            else {
+            else if (kernel == ALGP_KERNEL_MATERN15) {
                 const T r = sqrt(r2) * (T)1.7320508075688772;
                 bp = os * ((T)1 + r) * kexp(-r);
-            }
+            } else bp = kval<T, 1>(kernel, os, r2);
             if (pj == pick_pool) bp += noise;
         }
     }
@@ -1242,10 +1242,10 @@ __global__ __launch_bounds__(256) void path_score_kernel(const int64_t* cpos, co
                     r2 += df * df;
                 }
                 if (kernel == ALGP_KERNEL_RBF) cab = os * kexp(-0.5 * r2);
-                else {
+                else if (kernel == ALGP_KERNEL_MATERN15) {
                     const double r = sqrt(r2) * 1.7320508075688772;
                     cab = os * (1.0 + r) * kexp(-r);
-                }
+                } else cab = kval<double, 1>(kernel, os, r2);
                 if (pa == pb) cab += noise;
             }
             G[a][b] = cab + (a == b ? sm : 0.0) - acc[i][j];
@@ -1332,10 +1332,10 @@ __global__ __launch_bounds__(256) void path_assemble_kernel(const int64_t* cpos,
                     r2 += df * df;
                 }
                 if (kernel == ALGP_KERNEL_RBF) cab = os * kexp(-0.5 * r2);
-                else {
+                else if (kernel == ALGP_KERNEL_MATERN15) {
                     const double r = sqrt(r2) * 1.7320508075688772;
                     cab = os * (1.0 + r) * kexp(-r);
-                }
+                } else cab = kval<double, 1>(kernel, os, r2);
                 if (pa == pb) cab += noise;
             }
             v = (T)(cab + (a == b ? sm : 0.0) - (double)Gp[e]);
@@ -1408,10 +1408,10 @@ __global__ __launch_bounds__(256) void pvr_assemble_kernel(const int64_t* uidx, 
                 r2 += df * df;
             }
             if (kernel == ALGP_KERNEL_RBF) cab = os * kexp(-0.5 * r2);
-            else {
+            else if (kernel == ALGP_KERNEL_MATERN15) {
                 const double r = sqrt(r2) * 1.7320508075688772;
                 cab = os * (1.0 + r) * kexp(-r);
-            }
+            } else cab = kval<double, 1>(kernel, os, r2);
             if (pa == pb) cab += noise;
         }
         G[a * ld + b] = (T)(cab - (double)G[a * ld + b]);
@@ -1653,10 +1653,10 @@ __global__ __launch_bounds__(256) void kgemv_kernel(int64_t M, const int64_t* qi
             }
             T kv;
             if (kernel == ALGP_KERNEL_RBF) kv = os * kexp((T)-0.5 * r2);
-            else {
+            else if (kernel == ALGP_KERNEL_MATERN15) {
                 const T r = sqrt(r2) * (T)1.7320508075688772;
                 kv = os * ((T)1 + r) * kexp(-r);
-            }
+            } else kv = kval<T, 1>(kernel, os, r2);
             s += kv * alpha[a];
         }
         for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);

@@ -12,9 +12,11 @@ Same constructor, methods, properties and parameter names as the reference so th
 What differs, deliberately:
   * arithmetic runs on the GPU in `dtype` (float64 by default; the reference is float32 through
     utils.py:19) -- pass dtype=np.float32 for the reference's precision;
-  * only the identity latent function and the rbf / matern(nu=1.5) kernels exist (north_star scope;
-    the reference also has linear / non_linear latents and a spectral mixture kernel,
-    models.py:23-44, 221-223): anything else raises NotImplementedError like models.py:227, 248;
+  * only the identity latent function and the rbf / matern kernels exist, the latter with
+    kernel_params['nu'] = 0.5, 1.5 (the default when 'nu' is absent) or 2.5; 'nu' is ignored for
+    rbf (north_star scope; the reference also has linear / non_linear latents and a spectral
+    mixture kernel, models.py:23-44, 221-223): anything else, another nu included, raises
+    NotImplementedError like models.py:227, 248;
   * `fit` uses the analytic MLL gradient computed on the device with the reference's own optimiser
     objects (torch.optim.Adam + ReduceLROnPlateau(patience=50), models.py:121-124).
 """
@@ -25,6 +27,7 @@ import torch.nn as nn
 from . import _hip
 
 _KERNELS = {None: _hip.KERNEL_RBF, 'rbf': _hip.KERNEL_RBF, 'matern': _hip.KERNEL_MATERN15}
+_MATERN_NU = {0.5: _hip.KERNEL_MATERN05, 1.5: _hip.KERNEL_MATERN15, 2.5: _hip.KERNEL_MATERN25}
 
 
 class IdentityLatentFunction(nn.Module):
@@ -59,8 +62,8 @@ class _GaussianLikelihood(nn.Module):
 
 class ExactGPModel(nn.Module):
     """Parameter container with the reference's names (models.py:206-254): zero mean on
-    mean-centred targets, ScaleKernel(RBF-ARD | Matern-1.5), per-point white noise, Gaussian
-    likelihood.  It holds no arithmetic: the GPU library reads the parameters."""
+    mean-centred targets, ScaleKernel(RBF-ARD | Matern-nu, nu = 1/2, 3/2, 5/2), per-point white
+    noise, Gaussian likelihood.  It holds no arithmetic: the GPU library reads the parameters."""
 
     def __init__(self, train_x, train_y, likelihood, var=None, latent=None, kernel_params=None, latent_params=None):
         super(ExactGPModel, self).__init__()
@@ -71,6 +74,11 @@ class ExactGPModel(nn.Module):
         if kernel not in _KERNELS:
             raise NotImplementedError(kernel)
         self.kernel_type = _KERNELS[kernel]
+        if kernel == 'matern' and 'nu' in kernel_params:
+            nu = kernel_params['nu']
+            if nu not in _MATERN_NU:
+                raise NotImplementedError('matern nu=%r: nu is one of 0.5, 1.5, 2.5' % (nu,))
+            self.kernel_type = _MATERN_NU[nu]
         self.kernel_covar_module = _ScaleKernel(int(np.shape(train_x)[-1]))
         self.likelihood = likelihood
 

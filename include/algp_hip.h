@@ -34,7 +34,7 @@ extern "C" {
 typedef struct algp_ctx algp_ctx;
 
 enum { ALGP_F32 = 0, ALGP_F64 = 1 };
-enum { ALGP_KERNEL_RBF = 0, ALGP_KERNEL_MATERN15 = 1 };          /* models.py:217-220 */
+enum { ALGP_KERNEL_RBF = 0, ALGP_KERNEL_MATERN15 = 1, ALGP_KERNEL_MATERN05 = 2, ALGP_KERNEL_MATERN25 = 3 };  /* models.py:217-222 */
 enum { ALGP_CRIT_ENTROPY = 0, ALGP_CRIT_MUTUAL_INFORMATION = 1, ALGP_CRIT_VARIANCE_REDUCTION = 2 };  /* agent.py:128; 2: below */
 enum {
     ALGP_OK = 0,
@@ -81,7 +81,12 @@ double algp_last_jitter(const algp_ctx* ctx);
 int algp_dtype(const algp_ctx* ctx);
 
 /* ---- hyper-parameters: ExactGPModel's D+2 scalars (models.py:206-254; names run.py:35-37) ---
- * k(x,x') = exp(log_outputscale) * exp(-1/2 sum_d ((x_d-x'_d)/exp(log_lengthscale[d]))^2)  (RBF)
+ * With os = exp(log_outputscale), r^2 = sum_d ((x_d-x'_d)/exp(log_lengthscale[d]))^2 and r = sqrt(r^2), k(x,x') is
+ *   ALGP_KERNEL_RBF       os exp(-r^2 / 2)
+ *   ALGP_KERNEL_MATERN05  os exp(-r)                                    (nu = 1/2, the exponential kernel)
+ *   ALGP_KERNEL_MATERN15  os (1 + a) exp(-a),           a = sqrt(3) r   (nu = 3/2)
+ *   ALGP_KERNEL_MATERN25  os (1 + a + a^2 / 3) exp(-a), a = sqrt(5) r   (nu = 5/2)
+ * (gpytorch's ScaleKernel(RBFKernel | MaternKernel(nu), ard_num_dims = D)); any other id is ALGP_ERR_BAD_ARG.
  * sigma_n^2 = exp(log_noise) (models.py:180).                                                  */
 int algp_set_hypers(algp_ctx* ctx, int kernel, int D, const double* log_lengthscale,
                     double log_outputscale, double log_noise);
