@@ -475,9 +475,8 @@ int Impl<T>::posterior_mean(algp_ctx* c, const int64_t* idx, int64_t M, void* mu
     ALGP_TRY(ensure(c, c->auxD, sizeof(T) * M));
     ALGP_HIP(hipMemcpyAsync(c->auxIdx.p, idx, sizeof(int64_t) * M, hipMemcpyHostToDevice, c->stream));
     ALGP_TRY(need_alpha(c));
-    ALGP_TRY(kgemv_launch<T>(c, M, (const int64_t*)c->auxIdx.p, (const T*)c->Xs.p, c->hyp.DP, c->N,
-                             (const int64_t*)c->Aidx.p, (const T*)c->alpha.p, c->hyp.kernel, (T)c->hyp.outputscale,
-                             (T)c->ybar, p(c->auxD)));
+    ALGP_TRY(kgemv_launch<T>(c, M, (const int64_t*)c->auxIdx.p, make_src(c), c->N, (const int64_t*)c->Aidx.p,
+                             (const T*)c->alpha.p, (T)c->ybar, p(c->auxD)));
     ALGP_HIP(hipMemcpyAsync(mu_out, c->auxD.p, sizeof(T) * M, hipMemcpyDeviceToHost, c->stream));
     const int rc = sync_checked(c, "posterior_mean");
     if (rc != ALGP_OK) c->alpha_valid = false;

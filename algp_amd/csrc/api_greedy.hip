@@ -103,9 +103,7 @@ int Impl<T>::remote_row(algp_ctx* c, int64_t pool_idx, int in_train) {
                                      (const T*)nullptr, r.ss, r.dot, (T)0, r.dstat, r.mu, r.alive));
     if (!c->picks.empty())
         ALGP_TRY(lazy_refresh_launch<T>(c, 1, 2, 0, (const LazyPick*)c->lazypicks.p, (int)c->picks.size(), r.ckind, r.cidx,
-                                        (const T*)c->Xs.p, c->pool_is_cov ? (const T*)c->Cp.p : nullptr, c->n_pool,
-                                        c->hyp.DP, c->hyp.kernel, (T)c->hyp.outputscale, (T)c->hyp.noise, p(c->prevrows),
-                                        ldv, l, r.dstat, r.fresh, r.alive, r.score, c->lazy_ss, c->lazy_delta));
+                                        s, p(c->prevrows), ldv, l, r.dstat, r.fresh, r.alive, r.score, c->lazy_ss, c->lazy_delta));
     return ALGP_OK;
 }
 
@@ -196,9 +194,7 @@ int Impl<T>::commit_pick(algp_ctx* c, int64_t pool_idx, double static_std, doubl
 template <typename T>
 int Impl<T>::lazy_launch(algp_ctx* c, int mode, int64_t pos, double ss, double delta, const int64_t* pos_dev) {
     return lazy_refresh_launch<T>(c, c->M, mode, pos, (const LazyPick*)c->lazypicks.p, (int)c->picks.size(),
-                                  (const int*)c->ckind.p, (const int64_t*)c->Cidx.p, (const T*)c->Xs.p,
-                                  c->pool_is_cov ? (const T*)c->Cp.p : nullptr, c->n_pool, c->hyp.DP, c->hyp.kernel,
-                                  (T)c->hyp.outputscale, (T)c->hyp.noise, p(c->prevrows), c->ldv, p(c->Vt),
+                                  (const int*)c->ckind.p, (const int64_t*)c->Cidx.p, make_src(c), p(c->prevrows), c->ldv, p(c->Vt),
                                   p(c->dstat), (int*)c->fresh.p, (const unsigned char*)c->alive.p,
                                   (double*)c->scores.p, ss, delta, pos_dev);
 }

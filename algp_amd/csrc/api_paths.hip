@@ -60,9 +60,7 @@ int Impl<T>::score_paths_big(algp_ctx* c, const std::vector<int64_t>& cpos, cons
                                        second ? (const T*)c->auxVar.p : nullptr, p(c->L), c->Lld));
         ALGP_TRY(gemm_nt<T>(c, {.klass = ALGP_PROF_GEMM_OTHER, .m = ppad, .n = ppad, .k = Npad, .A = {rows, Npad, (int64_t)ppad * Npad},
                                 .B = {rows, Npad, (int64_t)ppad * Npad}, .D = {G, ppad, (int64_t)ppad * ppad}, .batch = B, .lower_only = 1}));
-        ALGP_TRY(path_assemble_launch<T>(c, d_src, B, ppad, (const int64_t*)c->Cidx.p, (const T*)c->Xs.p,
-                                         c->pool_is_cov ? (const T*)c->Cp.p : nullptr, c->n_pool, c->hyp.DP, c->hyp.kernel,
-                                         c->hyp.outputscale, c->hyp.noise, mobile_std * mobile_std, G));
+        ALGP_TRY(path_assemble_launch<T>(c, d_src, B, ppad, (const int64_t*)c->Cidx.p, make_src(c), mobile_std * mobile_std, G));
         ALGP_TRY(factor_blocks_batched<T>(c, G, ppad, inv, L21, d_ld, d_info, B));
         ALGP_TRY(path_finish_launch(c, d_src, ppad, B, d_ld, d_info, d_out + p0));
         ALGP_TRY(sync(c));                                   // the index vectors are reused by the next batch
@@ -109,9 +107,7 @@ int Impl<T>::score_paths(algp_ctx* c, const int64_t* sites, int npaths, int maxl
     ALGP_HIP(hipMemcpyAsync(d_c, cpos.data(), sizeof(int64_t) * tot, hipMemcpyHostToDevice, c->stream));
     ALGP_HIP(hipMemcpyAsync(d_l, lpos.data(), sizeof(int64_t) * tot, hipMemcpyHostToDevice, c->stream));
     ALGP_TRY(path_score_launch<T>(c, d_c, d_l, npaths, maxlen, (const int64_t*)c->Cidx.p, p(c->Vt), c->ldv, c->ncols, p(c->L),
-                                  c->Lld, (const T*)c->varA.p, (const T*)c->Xs.p, c->pool_is_cov ? (const T*)c->Cp.p : nullptr,
-                                  c->n_pool, c->hyp.DP, c->hyp.kernel, c->hyp.outputscale, c->hyp.noise,
-                                  mobile_std * mobile_std, (double*)c->hostStage.p));
+                                  c->Lld, (const T*)c->varA.p, make_src(c), mobile_std * mobile_std, (double*)c->hostStage.p));
     ALGP_HIP(hipMemcpyAsync(dH, c->hostStage.p, sizeof(double) * npaths, hipMemcpyDeviceToHost, c->stream));
     return sync(c);
 }

@@ -166,8 +166,7 @@ int Impl<T>::score_paths_vr(algp_ctx* c, const int64_t* sites, int npaths, int m
         ALGP_TRY(gather_rows_launch<T>(c, p(c->Vt), c->ldv, d_src, R, Npad, Upad, Npad, second ? d_lrow : nullptr,
                                        second ? (const T*)c->auxVar.p : nullptr, p(c->L), c->Lld));
         ALGP_TRY(gemm_nt_launch<T>(c, ALGP_PROF_GEMM_OTHER, Upad, Upad, Npad, (T)1, R, Npad, R, Npad, (T)0, nullptr, 0, Gam, Upad, 1));
-        ALGP_TRY(pvr_assemble_launch<T>(c, d_uidx, U, Upad, (const T*)c->Xs.p, c->pool_is_cov ? (const T*)c->Cp.p : nullptr, c->n_pool,
-                                        c->hyp.DP, c->hyp.kernel, c->hyp.outputscale, c->hyp.noise, Gam));
+        ALGP_TRY(pvr_assemble_launch<T>(c, d_uidx, U, Upad, s, Gam));
         for (int64_t n0 = 0; n0 < Mpad; n0 += chunk) {
             const int64_t nc = std::min(chunk, Mpad - n0);
             ALGP_TRY(gemm_nt_launch_pvr<T>(c, ALGP_PROF_GEMM_OTHER, Upad, nc, Npad, R, Npad, p(c->Vt), c->ldv, n0, s, d_uidx, U,

@@ -97,9 +97,8 @@ int Impl<T>::vr_fold(algp_ctx* c, int64_t q) {
     ALGP_TRY(ensure(c, vr.Tp, sizeof(T) * (size_t)VR_TBLOCKS * ldv));
     ALGP_TRY(ensure(c, vr.Tv, sizeof(T) * ldv));
     ALGP_TRY(ensure(c, vr.Nrm, sizeof(T)));
-    return vr_fold_launch<T>(c, M, (const int*)c->ckind.p, (const int64_t*)c->Cidx.p, p(c->Vt), ldv, c->Npad + q, (const T*)c->Xs.p,
-                             c->pool_is_cov ? (const T*)c->Cp.p : nullptr, c->n_pool, c->hyp.DP, c->hyp.kernel,
-                             (T)c->hyp.outputscale, (T)c->hyp.noise, c->has_tw ? (const T*)c->tw.p : nullptr, p(vr.R), p(vr.R) + Mpad,
+    return vr_fold_launch<T>(c, M, (const int*)c->ckind.p, (const int64_t*)c->Cidx.p, p(c->Vt), ldv, c->Npad + q, make_src(c),
+                             c->has_tw ? (const T*)c->tw.p : nullptr, p(vr.R), p(vr.R) + Mpad,
                              p(vr.Nrm), p(vr.Tp), p(vr.Tv), p(vr.Y), p(vr.Y) + Mpad, p(vr.W));
 }
 
@@ -295,9 +294,8 @@ int Impl<T>::vr_shard_fold(algp_ctx* c, int st) {
     const int rc = [&]() {
         ALGP_TRY(vr_fold_gathered_launch<T>(c, own + bytes, (int64_t)bytes, nr, col, cap, 32, off_t, off_idx, off_val, p(vr.Tv), p(vr.Nrm),
                                             (int64_t*)vr.Tidx.p, p(vr.Trt)));
-        return vr_fold_apply_launch<T>(c, M, (const int*)c->ckind.p, (const int64_t*)c->Cidx.p, p(c->Vt), ldv, col, (const T*)c->Xs.p,
-                                       c->pool_is_cov ? (const T*)c->Cp.p : nullptr, c->n_pool, c->hyp.DP, c->hyp.kernel,
-                                       (T)c->hyp.outputscale, (T)c->hyp.noise, (int64_t)nr * cap, (const int64_t*)vr.Tidx.p,
+        return vr_fold_apply_launch<T>(c, M, (const int*)c->ckind.p, (const int64_t*)c->Cidx.p, p(c->Vt), ldv, col, make_src(c),
+                                       (int64_t)nr * cap, (const int64_t*)vr.Tidx.p,
                                        (const T*)vr.Trt.p, (const T*)vr.R.p, (const T*)vr.R.p + Mpad, (const T*)vr.Nrm.p, (const T*)vr.Tv.p,
                                        p(vr.Y), p(vr.Y) + Mpad, p(vr.W));
     }();

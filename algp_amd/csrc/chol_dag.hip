@@ -1054,8 +1054,7 @@ int cholesky_dag(algp_ctx* c, T* A, int64_t npad, int64_t ld, T* invD, double* l
     sh.nt = (int)(npad / NB);
     return dag_launch<T>(c, sh, A, ld, invD, (T*)nullptr, 0, logdet_acc, info);
 }
-template int cholesky_dag<double>(algp_ctx*, double*, int64_t, int64_t, double*, double*, int*);
-template int cholesky_dag<float>(algp_ctx*, float*, int64_t, int64_t, float*, double*, int*);
+ALGP_INSTANTIATE(cholesky_dag);
 
 // The factorisation of A and P <- P L^-T in ONE launch: the mpad rows of P ride along as extra block rows of the task list
 // (mode 1: dense rows, the candidates' B^T -> V^T; mode 2: P = I, npad x npad -> L^-T, zero tiles never touched).
@@ -1069,8 +1068,7 @@ int cholesky_dag_panel(algp_ctx* c, T* A, int64_t npad, int64_t ld, T* invD, dou
     sh.pshort = mode == 1 ? pshort : 0;
     return dag_launch<T>(c, sh, A, ld, invD, P, ldp, logdet_acc, info);
 }
-template int cholesky_dag_panel<double>(algp_ctx*, double*, int64_t, int64_t, double*, double*, int*, double*, int64_t, int64_t, int, int);
-template int cholesky_dag_panel<float>(algp_ctx*, float*, int64_t, int64_t, float*, double*, int*, float*, int64_t, int64_t, int, int);
+ALGP_INSTANTIATE(cholesky_dag_panel);
 
 // P <- P L^-T against a factor that is final (same task list without the factorisation's own tasks)
 template <typename T>
@@ -1084,8 +1082,7 @@ int solve_dag_panel(algp_ctx* c, const T* L, int64_t npad, int64_t ld, const T* 
     sh.solve_only = true;
     return dag_launch<T>(c, sh, const_cast<T*>(L), ld, const_cast<T*>(invD), P, ldp, (double*)nullptr, info);
 }
-template int solve_dag_panel<double>(algp_ctx*, const double*, int64_t, int64_t, const double*, int*, double*, int64_t, int64_t, int, int);
-template int solve_dag_panel<float>(algp_ctx*, const float*, int64_t, int64_t, const float*, int*, float*, int64_t, int64_t, int, int);
+ALGP_INSTANTIATE(solve_dag_panel);
 
 void dag_release(algp_ctx* c) {
     for (auto& e : c->dag_cache) {

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include "../../include/algp_hip.h"
 
@@ -201,13 +202,16 @@ __device__ __forceinline__ T kval_matern_05_25(int kernel, T os, T r2, T* dk) {
 // and the fp64 gradient kernel (whose nu = 1/2 factor holds a division) 4 more, which cost it a wave of occupancy.
 __host__ __device__ inline int kernel_family(int kernel) { return kernel == ALGP_KERNEL_MATERN05 || kernel == ALGP_KERNEL_MATERN25 ? 1 : 0; }
 // ScaleKernel(RBF) / ScaleKernel(Matern-nu), nu = 1/2, 3/2, 5/2, of a squared scaled distance.  FAM: the family `kernel` is known
-// to belong to (only its two forms are compiled in), or -1: any of the four
+// to belong to (only its two forms are compiled in), or -1: any of the four, tested in the order RBF, Matern-3/2, second family
+// (the order the criteria's kernels have always tested them in: pool_cov below keeps their instructions)
 template <typename T, int FAM = -1>
 __device__ __forceinline__ T kval(int kernel, T os, T r2) {
     if (FAM != 1 && kernel == ALGP_KERNEL_RBF) return os * kexp((T)-0.5 * r2);
-    if (FAM != 0 && (FAM == 1 || kernel_family(kernel) == 1)) return kval_matern_05_25<T>(kernel, os, r2, nullptr);
-    const T r = sqrt(r2) * (T)1.7320508075688772;
-    return os * ((T)1 + r) * kexp(-r);
+    if (FAM != 1 && (FAM == 0 || kernel == ALGP_KERNEL_MATERN15)) {
+        const T r = sqrt(r2) * (T)1.7320508075688772;
+        return os * ((T)1 + r) * kexp(-r);
+    }
+    return kval_matern_05_25<T>(kernel, os, r2, nullptr);
 }
 // The kernel value (returned) and the factor dk of its length-scale derivative, dk * u_d^2 = dk/dlog ls_d with
 // u_d = (x_d - x'_d) / ls_d, i.e. dk = -2 dk/dr^2: the MLL gradient (fit.hip).  FAM as for kval
@@ -255,6 +259,50 @@ __device__ __forceinline__ T bt_entry(int kernel, T os, const T (&xr)[DP], const
     const T ordinary = (kind == -1 && gcol < ncols) ? v : (T)0;
     const T unit = gcol == (int64_t)kind ? (T)1 : (T)0;
     return kind >= 0 ? unit : ordinary;
+}
+
+// The pool covariance as the vector kernels and the criteria's epilogues see it: KmatSrc (below) in the storage type T, with
+// the outputscale and the noise in the type the site computes in (C: double in the path kernels, whatever T is).  DP stays a
+// template argument of the kernels.  Made on the host by cov_src.
+template <typename T, typename C = T>
+struct CovSrc {
+    const T* Xs;         // n x DP scaled, zero padded coordinates (coordinate pool)
+    const T* Cp;         // n x n explicit covariance, or null
+    int64_t n_pool;
+    int kernel;
+    C os, noise;         // noise: sigma_n^2 where the pool indices coincide; 0 for an explicit covariance, which holds it already
+};
+// C(pa, pb), ONE definition for every site outside the matrix build: the lazy refresh's b', the path kernels, the kernel-GEMV,
+// the variance-reduction epilogues.  The entry of the explicit covariance if there is one; else r^2 as the plain sum from zero
+// over the DP coordinate differences, the kernel value (kval), and sigma_n^2 where the pool indices coincide (NOISE = false: left
+// out -- the kernel-GEMV, whose callers add that term themselves or have none).  The plain sum is NOT kmat_value's r^2: under
+// contraction two coordinates come out as fma(d1, d1, d0 * d0) here and fma(d0, d0, d1 * d1) there, which round differently, and
+// each side's stored results hold its own bits -- the two are not to be merged.
+// xa, xb: the two sites' coordinates wherever the kernel holds them (registers, LDS, memory), in any type; computed in the type
+// of s.os.  S: a CovSrc, or any argument struct with its fields (the GEMM's VrGemmArgs, read in place: a CovSrc made from it in
+// the epilogue moved the address arithmetic around it).
+template <int DP, bool NOISE = true, typename S, typename XA, typename XB>
+__device__ __forceinline__ auto pool_cov(const S& s, int64_t pa, int64_t pb, const XA* xa, const XB* xb) {
+    using C = decltype(s.os);
+    if (s.Cp) return (C)s.Cp[pa * s.n_pool + pb];
+    C r2 = (C)0;
+#pragma unroll
+    for (int d = 0; d < DP; ++d) {
+        const C df = (C)xa[d] - (C)xb[d];
+        r2 += df * df;
+    }
+    C v = kval<C>(s.kernel, s.os, r2);
+    if (NOISE && pa == pb) v += s.noise;
+    return v;
+}
+// the row's coordinates in registers, the column's read from the pool; both read from the pool
+template <int DP, bool NOISE = true, typename S, typename XA>
+__device__ __forceinline__ auto pool_cov(const S& s, int64_t pa, int64_t pb, const XA* xa) {
+    return pool_cov<DP, NOISE>(s, pa, pb, xa, s.Xs + pb * DP);
+}
+template <int DP, typename S>
+__device__ __forceinline__ auto pool_cov(const S& s, int64_t pa, int64_t pb) {
+    return pool_cov<DP>(s, pa, pb, s.Xs + pa * DP, s.Xs + pb * DP);
 }
 }  // namespace algp
 
@@ -468,6 +516,24 @@ struct KmatSrc {
     double outputscale;
     double noise;        // sigma_n^2 added when pool indices coincide (coords mode only)
 };
+// the device-side view of a source (CovSrc above).  The one place that says what `noise` means per pool kind: an explicit
+// covariance carries sigma_n^2 on its diagonal already, so nothing is added to it anywhere
+template <typename T, typename C = T>
+inline CovSrc<T, C> cov_src(const KmatSrc& s) {
+    return {(const T*)s.Xs, (const T*)s.Cp, s.n_pool, s.kernel, (C)s.outputscale, (C)(s.Cp ? 0.0 : s.noise)};
+}
+// The padded coordinate width (2, 4 or 8) as a compile-time constant: f(std::integral_constant<int, DP>{}), one launch line
+// per kernel instead of three
+template <typename F>
+inline void with_dp(int DP, F&& f) {
+    if (DP == 2) f(std::integral_constant<int, 2>{});
+    else if (DP == 4) f(std::integral_constant<int, 4>{});
+    else f(std::integral_constant<int, 8>{});
+}
+// explicit instantiation of a typed launcher for both element types, by name: the signature is the template's own
+#define ALGP_INSTANTIATE(f) \
+    template decltype(f<double>) f<double>; \
+    template decltype(f<float>) f<float>
 
 // The candidates' right-hand sides as a generator instead of a matrix (the scheduled sweep, potrf.hip: trsm_blocked): the update
 // product of a column block forms its C tile in registers from these (gemm.hip, GEN), so B^T is never written to V^T and read

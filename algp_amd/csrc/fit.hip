@@ -132,9 +132,10 @@ int mll_grad_launch(algp_ctx* c, const T* Sinv, int64_t ld, int64_t N, const T* 
     dim3 grid(nb * (nb + 1) / 2), blk(256);
     auto launch = [&](auto fam) {
         constexpr int FAM = decltype(fam)::value;
-        if (DP == 2) hipLaunchKernelGGL((mll_grad_kernel<T, 2, FAM>), grid, blk, 0, c->cur, Sinv, ld, N, Xs, aidx, alpha, kernel, os, rp, partial);
-        else if (DP == 4) hipLaunchKernelGGL((mll_grad_kernel<T, 4, FAM>), grid, blk, 0, c->cur, Sinv, ld, N, Xs, aidx, alpha, kernel, os, rp, partial);
-        else hipLaunchKernelGGL((mll_grad_kernel<T, 8, FAM>), grid, blk, 0, c->cur, Sinv, ld, N, Xs, aidx, alpha, kernel, os, rp, partial);
+        with_dp(DP, [&](auto dp) {
+            hipLaunchKernelGGL((mll_grad_kernel<T, decltype(dp)::value, FAM>), grid, blk, 0, c->cur, Sinv, ld, N, Xs, aidx, alpha, kernel, os,
+                               rp, partial);
+        });
     };
     if (kernel_family(kernel)) launch(std::integral_constant<int, 1>{});
     else launch(std::integral_constant<int, 0>{});
@@ -143,9 +144,6 @@ int mll_grad_launch(algp_ctx* c, const T* Sinv, int64_t ld, int64_t N, const T* 
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int mll_grad_launch<double>(algp_ctx*, const double*, int64_t, int64_t, const double*, int, const int64_t*,
-                                     const double*, int, double, double*, double*);
-template int mll_grad_launch<float>(algp_ctx*, const float*, int64_t, int64_t, const float*, int, const int64_t*,
-                                    const float*, int, float, double*, double*);
+ALGP_INSTANTIATE(mll_grad_launch);
 
 }  // namespace algp

@@ -154,26 +154,11 @@ struct VrxGemmArgs : VrGemmArgs<T> {};
 template <typename T>
 struct VrxWGemmArgs : VrxGemmArgs<T> {};
 
-// C(prow, pcol) for the two epilogues below: read from the explicit pool covariance, or formed from the scaled coordinates
-// of the row (in registers) and of the column (staged in LDS) with the one kernel-value definition kexp, sigma_n^2 added
-// where the pool indices coincide
+// C(prow, pcol) for the two epilogues below: pool_cov (common.h) over the launch's own source fields, the coordinates of the
+// row in registers and of the column staged in LDS, both at width MAXD
 template <typename T>
 __device__ __forceinline__ T vr_pool_cov(const VrGemmArgs<T>& g, int64_t prow, int64_t pcol, const T (&xrow)[MAXD], const T* xcol) {
-    if (g.Cp) return g.Cp[prow * g.n_pool + pcol];
-    T r2 = (T)0;
-#pragma unroll
-    for (int d = 0; d < MAXD; ++d) {
-        const T df = xrow[d] - xcol[d];
-        r2 += df * df;
-    }
-    T cv;
-    if (g.kernel == ALGP_KERNEL_RBF) cv = g.os * kexp((T)-0.5 * r2);
-    else if (g.kernel == ALGP_KERNEL_MATERN15) {
-        const T rr = sqrt(r2) * (T)1.7320508075688772;
-        cv = g.os * ((T)1 + rr) * kexp(-rr);
-    } else cv = kval<T, 1>(g.kernel, g.os, r2);
-    if (prow == pcol) cv += g.noise;
-    return cv;
+    return pool_cov<MAXD>(g, prow, pcol, &xrow[0], xcol);
 }
 
 // RECT: the columns are described by cpool (this slice's 128 x tiles_n pool indices) instead of cidx / ckind / M
@@ -1002,10 +987,7 @@ int gemm_nt_launch_gen(algp_ctx* c, int klass, int64_t m, int64_t n, int64_t k, 
     };
     return kernel_family(gen.kernel) ? launch(std::integral_constant<int, 1>{}) : launch(std::integral_constant<int, 0>{});
 }
-template int gemm_nt_launch_gen<double>(algp_ctx*, int, int64_t, int64_t, int64_t, double, const double*, int64_t, const double*, int64_t,
-                                        double, const RhsGen&, int64_t, double*, int64_t);
-template int gemm_nt_launch_gen<float>(algp_ctx*, int, int64_t, int64_t, int64_t, float, const float*, int64_t, const float*, int64_t, float,
-                                       const RhsGen&, int64_t, float*, int64_t);
+ALGP_INSTANTIATE(gemm_nt_launch_gen);
 
 // the fields the two variance-reduction forms share
 template <typename T>
@@ -1037,10 +1019,7 @@ int gemm_nt_launch_vr(algp_ctx* c, int klass, int64_t mpad, int64_t n, int64_t k
     static_cast<VrGemmArgs<T>&>(gw) = g;
     return dispatch(c, klass, bk.flops, bk.bytes, gemm_nt_kernel_dma4<T, false, VrWGemmArgs<T>>, dim3((unsigned)tiles), gw);
 }
-template int gemm_nt_launch_vr<double>(algp_ctx*, int, int64_t, int64_t, int64_t, const double*, int64_t, int64_t, const KmatSrc&,
-                                       const int64_t*, const int*, int64_t, const double*, double*, int64_t);
-template int gemm_nt_launch_vr<float>(algp_ctx*, int, int64_t, int64_t, int64_t, const float*, int64_t, int64_t, const KmatSrc&,
-                                      const int64_t*, const int*, int64_t, const float*, float*, int64_t);
+ALGP_INSTANTIATE(gemm_nt_launch_vr);
 
 // The rectangular form: rows [0, mpad) of V^T (cidx / ckind / M describe them) against nslices blocks of n rows each, slice s at
 // B + s * slice_bytes (leading dimension ldb) with its n pool indices at cpool + s * slice_bytes (negative: the column is no target);
@@ -1069,12 +1048,7 @@ int gemm_nt_launch_vrx(algp_ctx* c, int klass, int64_t mpad, int64_t n, int64_t 
     static_cast<VrGemmArgs<T>&>(gw) = g;
     return dispatch(c, klass, bk.flops, bk.bytes, gemm_nt_kernel_dma4<T, false, VrxWGemmArgs<T>>, grid, gw);
 }
-template int gemm_nt_launch_vrx<double>(algp_ctx*, int, int64_t, int64_t, int64_t, const double*, int64_t, const double*, int64_t,
-                                        const int64_t*, int, int64_t, const KmatSrc&, const int64_t*, const int*, int64_t, const double*,
-                                        double*, int64_t);
-template int gemm_nt_launch_vrx<float>(algp_ctx*, int, int64_t, int64_t, int64_t, const float*, int64_t, const float*, int64_t,
-                                       const int64_t*, int, int64_t, const KmatSrc&, const int64_t*, const int*, int64_t, const float*,
-                                       float*, int64_t);
+ALGP_INSTANTIATE(gemm_nt_launch_vrx);
 
 // The cross covariances of the union rows R (upad x k, the rows behind U zero) with rows [ncol0, ncol0 + n) of V^T:
 // E[u][j] = C(uidx[u], cidx[ncol0 + j]) - R_u . V_(ncol0 + j) where column ncol0 + j is a target, 0 elsewhere and on the
@@ -1096,12 +1070,7 @@ int gemm_nt_launch_pvr(algp_ctx* c, int klass, int64_t upad, int64_t n, int64_t 
     const Booking bk = gemm_book(p, tiles, 128.0 * 128.0);
     return dispatch(c, klass, bk.flops, bk.bytes, gemm_nt_kernel_dma4<T, false, PvrGemmArgs<T>>, dim3((unsigned)tiles), g);
 }
-template int gemm_nt_launch_pvr<double>(algp_ctx*, int, int64_t, int64_t, int64_t, const double*, int64_t, const double*, int64_t, int64_t,
-                                        const KmatSrc&, const int64_t*, int64_t, const int64_t*, const int*, int64_t, const double*, double*,
-                                        int64_t);
-template int gemm_nt_launch_pvr<float>(algp_ctx*, int, int64_t, int64_t, int64_t, const float*, int64_t, const float*, int64_t, int64_t,
-                                       const KmatSrc&, const int64_t*, int64_t, const int64_t*, const int*, int64_t, const float*, float*,
-                                       int64_t);
+ALGP_INSTANTIATE(gemm_nt_launch_pvr);
 
 template <typename T>
 int gemm_nt_launch(algp_ctx* c, int klass, int64_t m, int64_t n, int64_t k, T alpha, const T* A,
@@ -1125,22 +1094,12 @@ int gemm_nt_launch_tri(algp_ctx* c, int klass, int64_t m, int64_t n, const T* A,
     return gemm_nt<T>(c, {.klass = klass, .m = m, .n = n, .k = n, .A = {A, lda}, .B = {B, ldb}, .D = {D, ldd}, .kcut = 1,
                           .stat_w = stat_out ? w : nullptr, .stat_out = stat_out, .stat_ld = stat_ld});
 }
-template int gemm_nt_launch_tri<double>(algp_ctx*, int, int64_t, int64_t, const double*, int64_t, const double*, int64_t, double*,
-                                        int64_t, const double*, double*, int64_t);
-template int gemm_nt_launch_tri<float>(algp_ctx*, int, int64_t, int64_t, const float*, int64_t, const float*, int64_t, float*, int64_t,
-                                       const float*, float*, int64_t);
-template int gemm_nt_launch_stats<double>(algp_ctx*, int, int64_t, int64_t, double, const double*, int64_t, const double*, int64_t,
-                                          double*, int64_t, const double*, double*, int64_t);
-template int gemm_nt_launch_stats<float>(algp_ctx*, int, int64_t, int64_t, float, const float*, int64_t, const float*, int64_t, float*,
-                                         int64_t, const float*, float*, int64_t);
+ALGP_INSTANTIATE(gemm_nt_launch_tri);
+ALGP_INSTANTIATE(gemm_nt_launch_stats);
 
-template int gemm_nt_launch<double>(algp_ctx*, int, int64_t, int64_t, int64_t, double, const double*, int64_t,
-                                    const double*, int64_t, double, const double*, int64_t, double*, int64_t, int);
-template int gemm_nt_launch<float>(algp_ctx*, int, int64_t, int64_t, int64_t, float, const float*, int64_t,
-                                   const float*, int64_t, float, const float*, int64_t, float*, int64_t, int);
+ALGP_INSTANTIATE(gemm_nt_launch);
 // (last: the object file holds the kernels in the order in which these instantiations first name them)
-template int gemm_nt<double>(algp_ctx*, const GemmNt<double>&);
-template int gemm_nt<float>(algp_ctx*, const GemmNt<float>&);
+ALGP_INSTANTIATE(gemm_nt);
 
 // ---------------------------------------------------------------------------------------------
 // MFMA fragment-layout probe (exact integer data, asymmetric B).
@@ -1171,8 +1130,7 @@ int test_mfma_launch(algp_ctx* c, int* mismatches_dev) {
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int test_mfma_launch<double>(algp_ctx*, int*);
-template int test_mfma_launch<float>(algp_ctx*, int*);
+ALGP_INSTANTIATE(test_mfma_launch);
 
 
 // ---------------------------------------------------------------------------------------------
@@ -1242,7 +1200,6 @@ int bench_gemm(algp_ctx* c, int64_t m, int64_t n, int64_t k, int lower_only, int
     c->dev_bytes -= (int64_t)(a.cap + b.cap + cc.cap + grx.cap + gcx.cap + grk.cap);
     return rc;
 }
-template int bench_gemm<double>(algp_ctx*, int64_t, int64_t, int64_t, int, int, int, double*, bool);
-template int bench_gemm<float>(algp_ctx*, int64_t, int64_t, int64_t, int, int, int, double*, bool);
+ALGP_INSTANTIATE(bench_gemm);
 
 }  // namespace algp

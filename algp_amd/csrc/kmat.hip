@@ -180,15 +180,10 @@ static int kmat_dispatch(algp_ctx* c, const KmatArgs<T>& a, int DP) {
         const bool eq = a.same_pool && (a.noise_on_equal != (T)0 || a.diag_add != nullptr);
         auto launch = [&](auto fam) {
             constexpr int FAM = decltype(fam)::value;
-            if (eq) {
-                if (DP == 2) hipLaunchKernelGGL((kmat_kernel<T, 2, true, FAM>), grid, dim3(256), 0, c->cur, b);
-                else if (DP == 4) hipLaunchKernelGGL((kmat_kernel<T, 4, true, FAM>), grid, dim3(256), 0, c->cur, b);
-                else hipLaunchKernelGGL((kmat_kernel<T, 8, true, FAM>), grid, dim3(256), 0, c->cur, b);
-            } else {
-                if (DP == 2) hipLaunchKernelGGL((kmat_kernel<T, 2, false, FAM>), grid, dim3(256), 0, c->cur, b);
-                else if (DP == 4) hipLaunchKernelGGL((kmat_kernel<T, 4, false, FAM>), grid, dim3(256), 0, c->cur, b);
-                else hipLaunchKernelGGL((kmat_kernel<T, 8, false, FAM>), grid, dim3(256), 0, c->cur, b);
-            }
+            with_dp(DP, [&](auto dp) {
+                if (eq) hipLaunchKernelGGL((kmat_kernel<T, decltype(dp)::value, true, FAM>), grid, dim3(256), 0, c->cur, b);
+                else hipLaunchKernelGGL((kmat_kernel<T, decltype(dp)::value, false, FAM>), grid, dim3(256), 0, c->cur, b);
+            });
         };
         if (kernel_family(a.kernel)) launch(std::integral_constant<int, 1>{});
         else launch(std::integral_constant<int, 0>{});
@@ -222,10 +217,7 @@ int kmat_launch(algp_ctx* c, const KmatSrc& s, const int64_t* ridx, int64_t rows
     a.ldo = ldo;
     return kmat_dispatch<T>(c, a, s.DP);
 }
-template int kmat_launch<double>(algp_ctx*, const KmatSrc&, const int64_t*, int64_t, int64_t, const int64_t*, int64_t,
-                                 int64_t, const double*, int, const int*, int, double*, int64_t, int64_t, int64_t);
-template int kmat_launch<float>(algp_ctx*, const KmatSrc&, const int64_t*, int64_t, int64_t, const int64_t*, int64_t,
-                                int64_t, const float*, int, const int*, int, float*, int64_t, int64_t, int64_t);
+ALGP_INSTANTIATE(kmat_launch);
 
 template <typename T>
 int kmat_xy_launch(algp_ctx* c, const T* xs1, int64_t n1, const T* xs2, int64_t n2, int symmetric,
@@ -251,10 +243,7 @@ int kmat_xy_launch(algp_ctx* c, const T* xs1, int64_t n1, const T* xs2, int64_t 
     a.ldo = ldo;
     return kmat_dispatch<T>(c, a, c->hyp.DP);
 }
-template int kmat_xy_launch<double>(algp_ctx*, const double*, int64_t, const double*, int64_t, int, const double*,
-                                    double, double*, int64_t);
-template int kmat_xy_launch<float>(algp_ctx*, const float*, int64_t, const float*, int64_t, int, const float*, double,
-                                   float*, int64_t);
+ALGP_INSTANTIATE(kmat_xy_launch);
 
 // The candidates' right-hand sides as a generator (RhsGen, common.h): the coordinates of the candidate rows and of the train
 // columns gathered into two contiguous arrays, once per solve, so that the product epilogue that forms B^T entries has no
@@ -286,10 +275,7 @@ int rhs_gather_launch(algp_ctx* c, const T* Xs, int DP, const int64_t* ridx, int
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int rhs_gather_launch<double>(algp_ctx*, const double*, int, const int64_t*, int64_t, int64_t, const int*, const int64_t*,
-                                       int64_t, int64_t, double*, double*, int*);
-template int rhs_gather_launch<float>(algp_ctx*, const float*, int, const int64_t*, int64_t, int64_t, const int*, const int64_t*, int64_t,
-                                      int64_t, float*, float*, int*);
+ALGP_INSTANTIATE(rhs_gather_launch);
 
 // xs[i][d] = x[i][d] / lengthscale_d for d < D, 0 for D <= d < DP
 struct InvLs {
@@ -316,7 +302,6 @@ int scale_coords_launch(algp_ctx* c, const T* x, int64_t n, T* xs) {
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int scale_coords_launch<double>(algp_ctx*, const double*, int64_t, double*);
-template int scale_coords_launch<float>(algp_ctx*, const float*, int64_t, float*);
+ALGP_INSTANTIATE(scale_coords_launch);
 
 }  // namespace algp

@@ -60,8 +60,7 @@ int mi_trinv_rows(algp_ctx* c, int klass, T* X, int64_t ldx, int64_t nloc, int g
     }
     return ALGP_OK;
 }
-template int mi_trinv_rows<double>(algp_ctx*, int, double*, int64_t, int64_t, int, int, const double*, int64_t, int64_t, const double*);
-template int mi_trinv_rows<float>(algp_ctx*, int, float*, int64_t, int64_t, int, int, const float*, int64_t, int64_t, const float*);
+ALGP_INSTANTIATE(mi_trinv_rows);
 
 // The local form of mi_rank1_kernel's first half: raw[t] = (X X_c^T) at local row t (rows_reduce_kernel) -> the entry of the
 // pick's column at that row's global index with the earlier picks' rank-1 terms removed, into this rank's piece `out`
@@ -88,10 +87,7 @@ int mi_cols_local_launch(algp_ctx* c, int64_t rows, int g, int member, int64_t m
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int mi_cols_local_launch<double>(algp_ctx*, int64_t, int, int, int64_t, const double*, const double*, int64_t, const double*,
-                                          int, int64_t, double*);
-template int mi_cols_local_launch<float>(algp_ctx*, int64_t, int, int, int64_t, const float*, const float*, int64_t, const double*, int,
-                                         int64_t, float*);
+ALGP_INSTANTIATE(mi_cols_local_launch);
 
 // dst[j] (j < m) <- the piece of the rank that owns global row j: rank first + (j / 128) mod g, its local row
 // (j / 128) / g * 128 + j mod 128, in its payload at gathered + rank * stride + off bytes
@@ -112,7 +108,6 @@ int mi_assemble_launch(algp_ctx* c, int64_t m, int g, int first, const char* gat
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int mi_assemble_launch<double>(algp_ctx*, int64_t, int, int, const char*, int64_t, int64_t, double*);
-template int mi_assemble_launch<float>(algp_ctx*, int64_t, int, int, const char*, int64_t, int64_t, float*);
+ALGP_INSTANTIATE(mi_assemble_launch);
 
 }  // namespace algp

@@ -42,8 +42,7 @@ int mi_tri_gather_launch(algp_ctx* c, const T* X, int64_t ldx, const int64_t* sr
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int mi_tri_gather_launch<double>(algp_ctx*, const double*, int64_t, const int64_t*, double*, int64_t, int64_t, int64_t);
-template int mi_tri_gather_launch<float>(algp_ctx*, const float*, int64_t, const int64_t*, float*, int64_t, int64_t, int64_t);
+ALGP_INSTANTIATE(mi_tri_gather_launch);
 
 // G[b][a][a] = 1 for cnt[b] <= a < ppad (the Gram of the zero rows behind a path's sites is exactly 0 there)
 template <typename T>
@@ -61,8 +60,7 @@ int mi_pad_diag_launch(algp_ctx* c, T* G, int ppad, const int* cnt, int batch) {
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int mi_pad_diag_launch<double>(algp_ctx*, double*, int, const int*, int);
-template int mi_pad_diag_launch<float>(algp_ctx*, float*, int, const int*, int);
+ALGP_INSTANTIATE(mi_pad_diag_launch);
 
 // Lt[a][b] = G[b][a] (b >= a, else 0) and LtD[a][b] = G[b][a] delta[b], per ppad x ppad block of the batch.  G is the
 // factor of the 2 x 2 tiled block: L11 and L22 in the block's diagonal tiles (their strict upper parts are not read),
@@ -111,7 +109,6 @@ int mi_transpose_launch(algp_ctx* c, const T* G, const T* L21, const T* delta, i
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int mi_transpose_launch<double>(algp_ctx*, const double*, const double*, const double*, int, double*, double*, int);
-template int mi_transpose_launch<float>(algp_ctx*, const float*, const float*, const float*, int, float*, float*, int);
+ALGP_INSTANTIATE(mi_transpose_launch);
 
 }  // namespace algp

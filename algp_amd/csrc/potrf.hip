@@ -36,8 +36,7 @@ int potrf_diag_launch(algp_ctx* c, T* A, int64_t lda, T* inv_out, double* logdet
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int potrf_diag_launch<double>(algp_ctx*, double*, int64_t, double*, double*, int*, int64_t);
-template int potrf_diag_launch<float>(algp_ctx*, float*, int64_t, float*, double*, int*, int64_t);
+ALGP_INSTANTIATE(potrf_diag_launch);
 
 // `batch` independent 128 x 128 blocks (block b at A + b * sA): factor + inverse + log det (to logdet[b], added) + first bad
 // pivot (info[b], 1-based) -- the per-path blocks of algp_score_paths
@@ -56,8 +55,7 @@ int potrf_diag_batched_launch(algp_ctx* c, T* A, int64_t sA, int64_t lda, T* inv
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int potrf_diag_batched_launch<double>(algp_ctx*, double*, int64_t, int64_t, double*, int64_t, double*, int*, int);
-template int potrf_diag_batched_launch<float>(algp_ctx*, float*, int64_t, int64_t, float*, int64_t, double*, int*, int);
+ALGP_INSTANTIATE(potrf_diag_batched_launch);
 
 template <typename T>
 int trinv_diag_launch(algp_ctx* c, const T* A, int64_t lda, T* inv_out) {
@@ -66,8 +64,7 @@ int trinv_diag_launch(algp_ctx* c, const T* A, int64_t lda, T* inv_out) {
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int trinv_diag_launch<double>(algp_ctx*, const double*, int64_t, double*);
-template int trinv_diag_launch<float>(algp_ctx*, const float*, int64_t, float*);
+ALGP_INSTANTIATE(trinv_diag_launch);
 
 // ---------------------------------------------------------------------------------------------
 // Two-level blocking.  The GEMM tile is 128 wide, but updating with K = 128 re-reads and re-writes
@@ -144,8 +141,7 @@ int cholesky_blocked(algp_ctx* c, T* A, int64_t npad, int64_t ld, T* invD, doubl
     if (dag_enabled() && nt >= DAG_MIN_TILES && nt <= DAG_MAX_TILES) return cholesky_dag<T>(c, A, npad, ld, invD, logdet_acc, info);
     return cholesky_serial<T>(c, A, npad, ld, invD, logdet_acc, info);
 }
-template int cholesky_blocked<double>(algp_ctx*, double*, int64_t, int64_t, double*, double*, int*);
-template int cholesky_blocked<float>(algp_ctx*, float*, int64_t, int64_t, float*, double*, int*);
+ALGP_INSTANTIATE(cholesky_blocked);
 
 // ---------------------------------------------------------------------------------------------
 // Explicit inverses of the factor's full 512 x 512 diagonal blocks, for the left-looking candidate solve: with
@@ -422,8 +418,7 @@ int trinv_upper_inplace(algp_ctx* c, int klass, T* XL, int64_t npad, int64_t ld,
     }
     return ALGP_OK;
 }
-template int trinv_upper_inplace<double>(algp_ctx*, int, double*, int64_t, int64_t, const double*);
-template int trinv_upper_inplace<float>(algp_ctx*, int, float*, int64_t, int64_t, const float*);
+ALGP_INSTANTIATE(trinv_upper_inplace);
 
 // C (lower tiles) <- X X^T for the upper-triangular X above: ONE launch in which output tile (a, b <= a) sums over the
 // columns k >= 128 a only (row tile a of X is zero left of them; GemmArgs::ktri).  The tiles are dealt out by ascending a,
@@ -433,10 +428,8 @@ template <typename T>
 int syrk_upper(algp_ctx* c, int klass, const T* X, int64_t npad, int64_t ldx, T* C, int64_t ldc) {
     return gemm_nt<T>(c, {.klass = klass, .m = npad, .n = npad, .k = npad, .A = {X, ldx}, .B = {X, ldx}, .D = {C, ldc}, .lower_only = 1, .ktri = 1});
 }
-template int syrk_upper<double>(algp_ctx*, int, const double*, int64_t, int64_t, double*, int64_t);
-template int syrk_upper<float>(algp_ctx*, int, const float*, int64_t, int64_t, float*, int64_t);
-template int trinv_upper<double>(algp_ctx*, int, double*, int64_t, int64_t, const double*, int64_t, const double*);
-template int trinv_upper<float>(algp_ctx*, int, float*, int64_t, int64_t, const float*, int64_t, const float*);
+ALGP_INSTANTIATE(syrk_upper);
+ALGP_INSTANTIATE(trinv_upper);
 
 // (A divide-and-conquer order of this sweep was measured in round 1: same time, 339 GB instead of 200 GB of HBM
 // traffic per solve at N = 10 000, M = 100 000 -- the big off-diagonal blocks of L fall out of the 4 MB L2s -- and removed.)
@@ -546,10 +539,7 @@ int trsm_blocked(algp_ctx* c, int klass, T* X, int64_t mpad, int64_t ldx, const 
     }
     return rc;
 }
-template int trsm_blocked<double>(algp_ctx*, int, double*, int64_t, int64_t, const double*, int64_t, int64_t,
-                                  const double*, int64_t, const double*, double*, int64_t, bool*, const RhsGen*);
-template int trsm_blocked<float>(algp_ctx*, int, float*, int64_t, int64_t, const float*, int64_t, int64_t,
-                                 const float*, int64_t, const float*, float*, int64_t, bool*, const RhsGen*);
+ALGP_INSTANTIATE(trsm_blocked);
 
 // ---------------------------------------------------------------------------------------------
 // C -= X X^T for a short, very wide X (the R <= 512 new rows of a factor update against N kept columns).
@@ -632,8 +622,7 @@ int gemm_splitk_sub(algp_ctx* c, int klass, int64_t m, int64_t n, int64_t k, con
     return ALGP_OK;
 }
 
-template int syrk_skinny_sub<double>(algp_ctx*, int, const double*, int64_t, int64_t, int64_t, double*, int64_t, DevBuf&);
-template int syrk_skinny_sub<float>(algp_ctx*, int, const float*, int64_t, int64_t, int64_t, float*, int64_t, DevBuf&);
+ALGP_INSTANTIATE(syrk_skinny_sub);
 
 // ---------------------------------------------------------------------------------------------
 // Vector solves (HBM-bound: each reads the lower triangle of L once): forward b <- L^-1 b and backward b <- L^-T b,
@@ -708,8 +697,7 @@ int tail_gemv2_launch(algp_ctx* c, const T* L, int64_t ldl, int64_t k, int64_t n
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int tail_gemv2_launch<double>(algp_ctx*, const double*, int64_t, int64_t, int64_t, double*, double*);
-template int tail_gemv2_launch<float>(algp_ctx*, const float*, int64_t, int64_t, int64_t, float*, float*);
+ALGP_INSTANTIATE(tail_gemv2_launch);
 
 // ---------------------------------------------------------------------------------------------
 // Forward substitution b <- L^-1 b as ONE launch (one or two right-hand sides at once).  The launch sequence above it
@@ -952,8 +940,7 @@ template <typename T>
 int trsv_forward2(algp_ctx* c, const T* L, int64_t npad, int64_t ldl, const T* invD, T* b0, T* b1, int64_t kb_start) {
     return trsv_chain_launch<T>(c, L, npad, ldl, invD, b0, b1, kb_start);
 }
-template int trsv_forward2<double>(algp_ctx*, const double*, int64_t, int64_t, const double*, double*, double*, int64_t);
-template int trsv_forward2<float>(algp_ctx*, const float*, int64_t, int64_t, const float*, float*, float*, int64_t);
+ALGP_INSTANTIATE(trsv_forward2);
 template <typename T>
 int trsv_backward(algp_ctx* c, const T* L, int64_t npad, int64_t ldl, const T* invD, T* b) {
     const int nblk = (int)(npad / NB);
@@ -967,9 +954,7 @@ int trsv_backward(algp_ctx* c, const T* L, int64_t npad, int64_t ldl, const T* i
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int trsv_forward<double>(algp_ctx*, const double*, int64_t, int64_t, const double*, double*, int64_t);
-template int trsv_forward<float>(algp_ctx*, const float*, int64_t, int64_t, const float*, float*, int64_t);
-template int trsv_backward<double>(algp_ctx*, const double*, int64_t, int64_t, const double*, double*);
-template int trsv_backward<float>(algp_ctx*, const float*, int64_t, int64_t, const float*, float*);
+ALGP_INSTANTIATE(trsv_forward);
+ALGP_INSTANTIATE(trsv_backward);
 
 }  // namespace algp

@@ -425,9 +425,6 @@ int tail_cols_launch(algp_ctx* c, int klass, T* X, int64_t mpad, int64_t ldx, co
     // 128 candidate rows per workgroup, two workgroups per CU (64 rows at three or four per CU: the same time, EXPERIMENTS.md)
     return tail_dispatch<T, 2>(c, g, mpad, nkt, w);
 }
-template int tail_cols_launch<double>(algp_ctx*, int, double*, int64_t, int64_t, const double*, int64_t, int64_t, const double*, int64_t, int,
-                                      const double*);
-template int tail_cols_launch<float>(algp_ctx*, int, float*, int64_t, int64_t, const float*, int64_t, int64_t, const float*, int64_t, int,
-                                     const float*);
+ALGP_INSTANTIATE(tail_cols_launch);
 
 }  // namespace algp

@@ -1,4 +1,6 @@
-// launchers defined in vecops.hip
+// launchers defined in vecops.hip.  A launcher whose kernel evaluates the pool covariance takes the source as a KmatSrc
+// (make_src(c) at the call site) and hands its kernel the typed device view (cov_src -> CovSrc, common.h); every entry C(pa, pb)
+// is pool_cov (common.h), whatever the kernel holds the two sites' coordinates in.
 #pragma once
 #include "common.h"
 namespace algp {
@@ -20,9 +22,8 @@ template <typename T>
 int vr_score_launch(algp_ctx* c, int64_t M, const int* ckind, const unsigned char* alive, const T* dstat, const T* w, double ss,
                     double delta, double* out);
 template <typename T>
-int vr_fold_launch(algp_ctx* c, int64_t M, const int* ckind, const int64_t* cidx, const T* Vt, int64_t ldv, int64_t col, const T* Xs,
-                   const T* Cp, int64_t n_pool, int DP, int kernel, T os, T noise, const T* tw, T* r, T* rt, T* nrm, T* tp, T* t, T* y1,
-                   T* y2, T* w);
+int vr_fold_launch(algp_ctx* c, int64_t M, const int* ckind, const int64_t* cidx, const T* Vt, int64_t ldv, int64_t col, const KmatSrc& s,
+                   const T* tw, T* r, T* rt, T* nrm, T* tp, T* t, T* y1, T* y2, T* w);
 // the same fold cut at its sums over the targets (local half; then the update from a list of N (pool index, rt) target pairs),
 // and the pieces of the criterion over the ranks of a communicator: a round's packed rows, the disjointness marks, a fold's
 // pairs, and its gathered sums and pair list (vecops.hip)
@@ -30,9 +31,9 @@ template <typename T>
 int vr_fold_local_launch(algp_ctx* c, int64_t M, const int* ckind, const int64_t* cidx, const T* Vt, int64_t ldv, int64_t col, const T* tw,
                          T* r, T* rt, T* nrm, T* tp, T* t);
 template <typename T>
-int vr_fold_apply_launch(algp_ctx* c, int64_t M, const int* ckind, const int64_t* cidx, const T* Vt, int64_t ldv, int64_t col, const T* Xs,
-                         const T* Cp, int64_t n_pool, int DP, int kernel, T os, T noise, int64_t N, const int64_t* tidx, const T* tval,
-                         const T* r, const T* rt, const T* nrm, const T* t, T* y1, T* y2, T* w);
+int vr_fold_apply_launch(algp_ctx* c, int64_t M, const int* ckind, const int64_t* cidx, const T* Vt, int64_t ldv, int64_t col,
+                         const KmatSrc& s, int64_t N, const int64_t* tidx, const T* tval, const T* r, const T* rt, const T* nrm,
+                         const T* t, T* y1, T* y2, T* w);
 template <typename T>
 int vr_pack_rows_launch(algp_ctx* c, int64_t M, int64_t row0, int64_t B, const int* ckind, const int64_t* cidx, const T* Vt, int64_t ldv,
                         int64_t K, int64_t kvalid, int64_t* head, T* rows);
@@ -72,19 +73,17 @@ int gather_rows_launch(algp_ctx* c, const T* src, int64_t lds, const int64_t* sr
 // pos_dev != null: the row index is read from the device (what an argmax kernel left there; < 0 = nothing to do)
 template <typename T>
 int lazy_refresh_launch(algp_ctx* c, int64_t M, int mode, int64_t pos, const LazyPick* picks, int npicks, const int* ckind,
-                        const int64_t* cidx, const T* Xs, const T* Cp, int64_t n_pool, int DP, int kernel, T os, T noise,
-                        const T* prevrows, int64_t ldv, T* Vt, T* dstat, int* fresh, const unsigned char* alive,
-                        double* scores, double ss, double delta, const int64_t* pos_dev = nullptr);
+                        const int64_t* cidx, const KmatSrc& s, const T* prevrows, int64_t ldv, T* Vt, T* dstat, int* fresh,
+                        const unsigned char* alive, double* scores, double ss, double delta, const int64_t* pos_dev = nullptr);
 // best_path block scoring: dH of every path from the resident rows of V^T (one workgroup per path, <= 64 sites each)
 template <typename T>
 int path_score_launch(algp_ctx* c, const int64_t* cpos, const int64_t* lpos, int npaths, int maxlen, const int64_t* cidx,
-                      const T* Vt, int64_t ldv, int64_t ncols, const T* L, int64_t ldl, const T* varA, const T* Xs,
-                      const T* Cp, int64_t n_pool, int DP, int kernel, double os, double noise, double sm, double* out);
+                      const T* Vt, int64_t ldv, int64_t ncols, const T* L, int64_t ldl, const T* varA, const KmatSrc& s, double sm,
+                      double* out);
 // paths of 65 .. 256 sites: G = C_PP + sigma_m^2 I - Gram in place for a batch of ppad x ppad blocks (sites packed to the front
 // of each path's ppad entries of cpos, -1 behind them); out[p] = P CONST + 1/2 logdet[p] (NaN where info[p] != 0)
 template <typename T>
-int path_assemble_launch(algp_ctx* c, const int64_t* cpos, int batch, int ppad, const int64_t* cidx, const T* Xs, const T* Cp,
-                         int64_t n_pool, int DP, int kernel, double os, double noise, double sm, T* G);
+int path_assemble_launch(algp_ctx* c, const int64_t* cpos, int batch, int ppad, const int64_t* cidx, const KmatSrc& s, double sm, T* G);
 int path_finish_launch(algp_ctx* c, const int64_t* cpos, int ppad, int batch, const double* logdet, const int* info, double* out);
 // variance reduction of whole paths (api_paths_vr.hip), over Gamma and Phi of a group's union sites (ld apart, lower tiles
 // valid): Gamma = C(U, U) - Gram in place; the paths of at most 64 sites, one workgroup each (upos: stride union positions per
@@ -93,8 +92,7 @@ int path_finish_launch(algp_ctx* c, const int64_t* cpos, int ppad, int batch, co
 // inverse tiles and, at ppad = 256, tr = [L21^T | inv(L11)^T] per block for the products of its lower left tile; and
 // out[pid[b]] = sum over the lower triangle of W_ij Li_ij (NaN where info[b] != 0)
 template <typename T>
-int pvr_assemble_launch(algp_ctx* c, const int64_t* uidx, int64_t U, int64_t ld, const T* Xs, const T* Cp, int64_t n_pool, int DP,
-                        int kernel, double os, double noise, T* G);
+int pvr_assemble_launch(algp_ctx* c, const int64_t* uidx, int64_t U, int64_t ld, const KmatSrc& s, T* G);
 template <typename T>
 int pvr_small_launch(algp_ctx* c, const int* upos, int stride, const int* pid, int npaths, const T* Gam, const T* Phi, int64_t ld,
                      double sm, double* out);
@@ -136,9 +134,11 @@ int mi_cols_local_launch(algp_ctx* c, int64_t rows, int g, int member, int64_t m
                          const double* sgn, int q, int64_t cpos, T* out);
 template <typename T>
 int mi_assemble_launch(algp_ctx* c, int64_t m, int g, int first, const char* gathered, int64_t stride, int64_t off, T* dst);
+// mu[j] = ybar + sum_a C(qidx[j], aidx[a]) alpha[a] over N listed sites, sigma_n^2 of coinciding sites left out (the mean-only
+// posterior; the variance-reduction fold's sum over its targets, for either pool kind)
 template <typename T>
-int kgemv_launch(algp_ctx* c, int64_t M, const int64_t* qidx, const T* Xs, int DP, int64_t N, const int64_t* aidx,
-                 const T* alpha, int kernel, T os, T ybar, T* mu);
+int kgemv_launch(algp_ctx* c, int64_t M, const int64_t* qidx, const KmatSrc& s, int64_t N, const int64_t* aidx, const T* alpha, T ybar,
+                 T* mu);
 template <typename T>
 int pad_identity_launch(algp_ctx* c, T* A, int64_t n, int64_t npad, int64_t ld);
 template <typename T>

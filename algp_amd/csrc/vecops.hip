@@ -190,12 +190,8 @@ int combine3_launch(algp_ctx* c, int64_t M, const T* acc, const T* tmp, int64_t 
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int rows_reduce3_launch<double>(algp_ctx*, const double*, int64_t, int64_t, int64_t, int64_t, const double*,
-                                         const double*, double*, int64_t, int);
-template int rows_reduce3_launch<float>(algp_ctx*, const float*, int64_t, int64_t, int64_t, int64_t, const float*, const float*,
-                                        float*, int64_t, int);
-template int combine3_launch<double>(algp_ctx*, int64_t, const double*, const double*, int64_t, double, double*, double*);
-template int combine3_launch<float>(algp_ctx*, int64_t, const float*, const float*, int64_t, float, float*, float*);
+ALGP_INSTANTIATE(rows_reduce3_launch);
+ALGP_INSTANTIATE(combine3_launch);
 
 template <typename T>
 int rows_reduce_launch(algp_ctx* c, const T* Vt, int64_t rows, int64_t ldv, int64_t ncols, const T* w, T* ss,
@@ -212,8 +208,7 @@ int rows_reduce_launch(algp_ctx* c, const T* Vt, int64_t rows, int64_t ldv, int6
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int rows_reduce_launch<double>(algp_ctx*, const double*, int64_t, int64_t, int64_t, const double*, double*, double*, int64_t);
-template int rows_reduce_launch<float>(algp_ctx*, const float*, int64_t, int64_t, int64_t, const float*, float*, float*, int64_t);
+ALGP_INSTANTIATE(rows_reduce_launch);
 
 // The row statistics the candidate solve left per column tile (gemm.hip, STATS: stat[(2 t + 0 / 1) * ld + row]) summed over
 // the tiles in ascending order: ss = sum v^2, dot = sum v z of every row, without a second pass over V^T.
@@ -243,8 +238,7 @@ int rowstat_combine_launch(algp_ctx* c, const T* stat, int64_t ld, int ntiles, i
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int rowstat_combine_launch<double>(algp_ctx*, const double*, int64_t, int, int64_t, double*, double*);
-template int rowstat_combine_launch<float>(algp_ctx*, const float*, int64_t, int, int64_t, float*, float*);
+ALGP_INSTANTIATE(rowstat_combine_launch);
 
 // ---------------------------------------------------------------------------------------------
 // candidate finalize: dstat = prior - ss (ordinary) | ss (unit row: [S^-1]_jj); mu = ybar + dot
@@ -273,10 +267,7 @@ int cand_finalize_launch(algp_ctx* c, int64_t M, const int* ckind, const int64_t
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int cand_finalize_launch<double>(algp_ctx*, int64_t, const int*, const int64_t*, const double*, int64_t, double,
-                                          const double*, const double*, const double*, double, double*, double*, unsigned char*);
-template int cand_finalize_launch<float>(algp_ctx*, int64_t, const int*, const int64_t*, const float*, int64_t, float,
-                                         const float*, const float*, const float*, float, float*, float*, unsigned char*);
+ALGP_INSTANTIATE(cand_finalize_launch);
 
 // ---------------------------------------------------------------------------------------------
 // scores (entropy gain per candidate, agent.py:341 after telescoping)
@@ -310,10 +301,7 @@ int score_launch(algp_ctx* c, int64_t M, const int* ckind, const unsigned char* 
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int score_launch<double>(algp_ctx*, int64_t, const int*, const unsigned char*, const double*, double, double,
-                                  const double*, double*);
-template int score_launch<float>(algp_ctx*, int64_t, const int*, const unsigned char*, const float*, double, double,
-                                 const double*, double*);
+ALGP_INSTANTIATE(score_launch);
 
 // ---------------------------------------------------------------------------------------------
 // Variance-reduction criterion (include/algp_hip.h; state and driver: api_vr.hip).  w_c = sum over the targets j of E_jc^2
@@ -345,8 +333,7 @@ int vr_combine_launch(algp_ctx* c, const T* part, int64_t ld, int ntiles, int64_
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int vr_combine_launch<double>(algp_ctx*, const double*, int64_t, int, int64_t, int, double*);
-template int vr_combine_launch<float>(algp_ctx*, const float*, int64_t, int, int64_t, int, float*);
+ALGP_INSTANTIATE(vr_combine_launch);
 
 // u_c = w_c / (pv_c + ss) (ordinary row) | -delta w_c / (1 + delta s_cc) (unit row); -inf where the row is not selectable
 template <typename T>
@@ -371,10 +358,7 @@ int vr_score_launch(algp_ctx* c, int64_t M, const int* ckind, const unsigned cha
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int vr_score_launch<double>(algp_ctx*, int64_t, const int*, const unsigned char*, const double*, const double*, double, double,
-                                     double*);
-template int vr_score_launch<float>(algp_ctx*, int64_t, const int*, const unsigned char*, const float*, const float*, double, double,
-                                    double*);
+ALGP_INSTANTIATE(vr_score_launch);
 
 // a committed pick's column `col` of V^T: r[c] of every row, rt[c] = omega_c r[c] on the targets (ordinary rows; omega = tw at
 // the row's pool site, 1 without weights) and 0 elsewhere, and *nrm = sum_T omega_j r_j^2 (one workgroup: a thread adds its
@@ -424,24 +408,8 @@ __global__ __launch_bounds__(256) void vr_tsum_kernel(int nblocks, const T* tp, 
     for (int b = 0; b < nblocks; ++b) s += tp[(int64_t)b * ld + k];
     t[k] = s;
 }
-// explicit pool covariance: y1[c] = sum_j Cp[pool(c)][aidx[j]] rt[j] over the N listed targets (a wave per row, as kgemv_kernel
-// for a coordinate pool; on one GPU the targets are the rows themselves: N = M, aidx = cidx)
-template <typename T>
-__global__ __launch_bounds__(256) void vr_cov_gemv_kernel(int64_t M, const int64_t* cidx, const T* Cp, int64_t n_pool, int64_t N,
-                                                          const int64_t* aidx, const T* rt, T* y1) {
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int64_t nw = (int64_t)gridDim.x * 4;
-    for (int64_t c0 = wave; c0 < M; c0 += nw) {
-        const T* row = Cp + cidx[c0] * n_pool;
-        T s = (T)0;
-        for (int64_t j = lane; j < N; j += 64) s = __builtin_fma(row[aidx[j]], rt[j], s);
-        s = dot_tree<T>(s);
-        if (lane == 0) y1[c0] = s;
-    }
-}
 // the rank-1 fold of one pick: y_c = kappa_c (y1_c + noise rt_c) - y2_c, w_c <- w_c - 2 r_c y_c + r_c^2 nrm
-// (noise: sigma_n^2 of a coordinate pool, which the kernel-GEMV leaves out where the pool indices coincide; 0 for a covariance pool)
+// (y1: the kernel-GEMV over the targets, kgemv_launch, which leaves the source's noise term out; noise: CovSrc::noise)
 template <typename T>
 __global__ void vr_fold_kernel(int64_t M, const int* ckind, const T* r, const T* rt, const T* y1, const T* y2, const T* nrm, T noise,
                                T* w) {
@@ -480,54 +448,32 @@ int vr_fold_local_launch(algp_ctx* c, int64_t M, const int* ckind, const int64_t
     }
     return ALGP_OK;
 }
-template int vr_fold_local_launch<double>(algp_ctx*, int64_t, const int*, const int64_t*, const double*, int64_t, int64_t, const double*,
-                                          double*, double*, double*, double*, double*);
-template int vr_fold_local_launch<float>(algp_ctx*, int64_t, const int*, const int64_t*, const float*, int64_t, int64_t, const float*, float*,
-                                         float*, float*, float*, float*);
+ALGP_INSTANTIATE(vr_fold_local_launch);
 
 template <typename T>
-int vr_fold_apply_launch(algp_ctx* c, int64_t M, const int* ckind, const int64_t* cidx, const T* Vt, int64_t ldv, int64_t col, const T* Xs,
-                         const T* Cp, int64_t n_pool, int DP, int kernel, T os, T noise, int64_t N, const int64_t* tidx, const T* tval,
-                         const T* r, const T* rt, const T* nrm, const T* t, T* y1, T* y2, T* w) {
+int vr_fold_apply_launch(algp_ctx* c, int64_t M, const int* ckind, const int64_t* cidx, const T* Vt, int64_t ldv, int64_t col,
+                         const KmatSrc& s, int64_t N, const int64_t* tidx, const T* tval, const T* r, const T* rt, const T* nrm,
+                         const T* t, T* y1, T* y2, T* w) {
     if (M <= 0) return ALGP_OK;
     ALGP_TRY(rows_reduce_launch<T>(c, Vt, M, ldv, col, t, (T*)nullptr, y2));
-    if (Cp) {
-        int64_t g = (M + 3) / 4;
-        if (g > 8192) g = 8192;
-        ProfScope ps(c, ALGP_PROF_KMAT, 2.0 * M * N, sizeof(T) * (double)M * N);
-        hipLaunchKernelGGL(vr_cov_gemv_kernel<T>, dim3((unsigned)g), dim3(256), 0, c->cur, M, cidx, Cp, n_pool, N, tidx, tval, y1);
-        ALGP_HIP(hipGetLastError());
-    } else {
-        ALGP_TRY(kgemv_launch<T>(c, M, cidx, Xs, DP, N, tidx, tval, kernel, os, (T)0, y1));
-    }
+    ALGP_TRY(kgemv_launch<T>(c, M, cidx, s, N, tidx, tval, (T)0, y1));
     ProfScope ps(c, ALGP_PROF_SCORE, 6.0 * M, sizeof(T) * 6.0 * M);
     hipLaunchKernelGGL(vr_fold_kernel<T>, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, c->cur, M, ckind, r, rt, (const T*)y1,
-                       (const T*)y2, nrm, Cp ? (T)0 : noise, w);
+                       (const T*)y2, nrm, cov_src<T>(s).noise, w);
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int vr_fold_apply_launch<double>(algp_ctx*, int64_t, const int*, const int64_t*, const double*, int64_t, int64_t, const double*,
-                                          const double*, int64_t, int, int, double, double, int64_t, const int64_t*, const double*,
-                                          const double*, const double*, const double*, const double*, double*, double*, double*);
-template int vr_fold_apply_launch<float>(algp_ctx*, int64_t, const int*, const int64_t*, const float*, int64_t, int64_t, const float*,
-                                         const float*, int64_t, int, int, float, float, int64_t, const int64_t*, const float*, const float*,
-                                         const float*, const float*, const float*, float*, float*, float*);
+ALGP_INSTANTIATE(vr_fold_apply_launch);
 
 // one GPU: the targets are this context's own ordinary rows (rt is zero on the others)
 template <typename T>
-int vr_fold_launch(algp_ctx* c, int64_t M, const int* ckind, const int64_t* cidx, const T* Vt, int64_t ldv, int64_t col, const T* Xs,
-                   const T* Cp, int64_t n_pool, int DP, int kernel, T os, T noise, const T* tw, T* r, T* rt, T* nrm, T* tp, T* t, T* y1,
-                   T* y2, T* w) {
+int vr_fold_launch(algp_ctx* c, int64_t M, const int* ckind, const int64_t* cidx, const T* Vt, int64_t ldv, int64_t col, const KmatSrc& s,
+                   const T* tw, T* r, T* rt, T* nrm, T* tp, T* t, T* y1, T* y2, T* w) {
     ALGP_TRY(vr_fold_local_launch<T>(c, M, ckind, cidx, Vt, ldv, col, tw, r, rt, nrm, tp, t));
-    return vr_fold_apply_launch<T>(c, M, ckind, cidx, Vt, ldv, col, Xs, Cp, n_pool, DP, kernel, os, noise, M, cidx, (const T*)rt,
-                                   (const T*)r, (const T*)rt, (const T*)nrm, (const T*)t, y1, y2, w);
+    return vr_fold_apply_launch<T>(c, M, ckind, cidx, Vt, ldv, col, s, M, cidx, (const T*)rt, (const T*)r, (const T*)rt, (const T*)nrm,
+                                   (const T*)t, y1, y2, w);
 }
-template int vr_fold_launch<double>(algp_ctx*, int64_t, const int*, const int64_t*, const double*, int64_t, int64_t, const double*,
-                                    const double*, int64_t, int, int, double, double, const double*, double*, double*, double*, double*,
-                                    double*, double*, double*, double*);
-template int vr_fold_launch<float>(algp_ctx*, int64_t, const int*, const int64_t*, const float*, int64_t, int64_t, const float*, const float*,
-                                   int64_t, int, int, float, float, const float*, float*, float*, float*, float*, float*, float*, float*,
-                                   float*);
+ALGP_INSTANTIATE(vr_fold_launch);
 
 // ---- the criterion over the ranks of a communicator (api_vr.hip: vr_shard_build, vr_shard_fold) --------------------------
 // A round's contribution of this rank: rows [row0, row0 + B) of V^T over K columns behind one header entry per row: its pool
@@ -569,10 +515,7 @@ int vr_pack_rows_launch(algp_ctx* c, int64_t M, int64_t row0, int64_t B, const i
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int vr_pack_rows_launch<double>(algp_ctx*, int64_t, int64_t, int64_t, const int*, const int64_t*, const double*, int64_t, int64_t,
-                                         int64_t, int64_t*, double*);
-template int vr_pack_rows_launch<float>(algp_ctx*, int64_t, int64_t, int64_t, const int*, const int64_t*, const float*, int64_t, int64_t,
-                                        int64_t, int64_t*, float*);
+ALGP_INSTANTIATE(vr_pack_rows_launch);
 
 // The shards must be disjoint: mark[pool site] = 1 for this rank's candidates, and a gathered row of ANOTHER rank, target or
 // unit row, whose site lands on a mark (or outside the pool) raises mark[n_pool], which the build reads back before its last
@@ -623,8 +566,7 @@ int vr_pairs_launch(algp_ctx* c, int64_t M, int64_t cap, const int* ckind, const
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int vr_pairs_launch<double>(algp_ctx*, int64_t, int64_t, const int*, const int64_t*, const double*, int64_t*, double*);
-template int vr_pairs_launch<float>(algp_ctx*, int64_t, int64_t, const int*, const int64_t*, const float*, int64_t*, float*);
+ALGP_INSTANTIATE(vr_pairs_launch);
 
 // After a fold's gather (per rank: *nrm at off_nrm, t over ncols columns at off_t, cap pool indices at off_idx, cap values at
 // off_val of its `stride` bytes): t and *nrm summed in rank order, the pairs in one list (padding: site 0 with value 0)
@@ -659,10 +601,7 @@ int vr_fold_gathered_launch(algp_ctx* c, const char* gathered, int64_t stride, i
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int vr_fold_gathered_launch<double>(algp_ctx*, const char*, int64_t, int, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
-                                             double*, double*, int64_t*, double*);
-template int vr_fold_gathered_launch<float>(algp_ctx*, const char*, int64_t, int, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
-                                            float*, float*, int64_t*, float*);
+ALGP_INSTANTIATE(vr_fold_gathered_launch);
 
 // the criterion's objective: *out = sum over the targets j (ordinary rows) of omega_j dstat_j in double (one workgroup, the
 // order of vr_pick_col_kernel: a thread adds its rows in ascending order, then the shuffle tree, then the waves left to right)
@@ -692,8 +631,7 @@ int vr_target_sum_launch(algp_ctx* c, int64_t M, const int* ckind, const int64_t
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int vr_target_sum_launch<double>(algp_ctx*, int64_t, const int*, const int64_t*, const double*, const double*, double*);
-template int vr_target_sum_launch<float>(algp_ctx*, int64_t, const int*, const int64_t*, const float*, const float*, double*);
+ALGP_INSTANTIATE(vr_target_sum_launch);
 
 // first maximum (np.argmax semantics, agent.py:349): larger value wins, ties go to the smaller index
 __global__ __launch_bounds__(1024) void argmax_kernel(const double* s, int64_t M, double* out_val, int64_t* out_idx) {
@@ -789,28 +727,8 @@ int argmax_launch(algp_ctx* c, const double* s, int64_t M, double* out_val, int6
 // ---------------------------------------------------------------------------------------------
 // b'_j = C(pick, j) when the pick is a new site and row j is ordinary, else 0
 template <typename T, int DP>
-__device__ __forceinline__ T pick_bprime(bool unit, int64_t pj, const T* Xs, const T* Cp, int64_t n_pool,
-                                         int64_t pick_pool, int pick_in_train, int kernel, T os, T noise) {
-    T bp = (T)0;
-    if (!pick_in_train && !unit) {
-        if (Cp) {
-            bp = Cp[pick_pool * n_pool + pj];
-        } else {
-            T r2 = (T)0;
-#pragma unroll
-            for (int d = 0; d < DP; ++d) {
-                const T df = Xs[pick_pool * DP + d] - Xs[pj * DP + d];
-                r2 += df * df;
-            }
-            if (kernel == ALGP_KERNEL_RBF) bp = os * kexp((T)-0.5 * r2);
-            else if (kernel == ALGP_KERNEL_MATERN15) {
-                const T r = sqrt(r2) * (T)1.7320508075688772;
-                bp = os * ((T)1 + r) * kexp(-r);
-            } else bp = kval<T, 1>(kernel, os, r2);
-            if (pj == pick_pool) bp += noise;
-        }
-    }
-    return bp;
+__device__ __forceinline__ T pick_bprime(bool unit, int64_t pj, const CovSrc<T>& src, int64_t pick_pool, int pick_in_train) {
+    return (!pick_in_train && !unit) ? pool_cov<DP>(src, pick_pool, pj) : (T)0;
 }
 
 // z = u - ybar w ; rhs initialisation for the resumed substitutions: u[i] = y[i], w[i] = (i < n) for i >= k
@@ -839,10 +757,8 @@ int uw_combine_launch(algp_ctx* c, T* z, const T* u, const T* w, T ybar, int64_t
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int uw_init_launch<double>(algp_ctx*, double*, double*, const double*, int64_t, int64_t, int64_t);
-template int uw_init_launch<float>(algp_ctx*, float*, float*, const float*, int64_t, int64_t, int64_t);
-template int uw_combine_launch<double>(algp_ctx*, double*, const double*, const double*, double, int64_t);
-template int uw_combine_launch<float>(algp_ctx*, float*, const float*, const float*, float, int64_t);
+ALGP_INSTANTIATE(uw_init_launch);
+ALGP_INSTANTIATE(uw_combine_launch);
 
 // dst[r][0:ncols] = src[src_row[r]][0:ncols], or zeros where src_row[r] < 0 (one workgroup per row and 2048 columns: the
 // row exchange of the sharded loop packs a handful of rows of 50 000).
@@ -880,10 +796,7 @@ int gather_rows_launch(algp_ctx* c, const T* src, int64_t lds, const int64_t* sr
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int gather_rows_launch<double>(algp_ctx*, const double*, int64_t, const int64_t*, double*, int64_t, int64_t, int64_t,
-                                        const int64_t*, const double*, const double*, int64_t);
-template int gather_rows_launch<float>(algp_ctx*, const float*, int64_t, const int64_t*, float*, int64_t, int64_t, int64_t,
-                                       const int64_t*, const float*, const float*, int64_t);
+ALGP_INSTANTIATE(gather_rows_launch);
 
 // ---------------------------------------------------------------------------------------------
 // Lazy greedy (entropy criterion).  The gain of a candidate never grows when more sites are sampled
@@ -902,8 +815,7 @@ template <typename T, int DP, bool COOP>
 __global__ __launch_bounds__(COOP ? 1024 : 256) void lazy_refresh_kernel(int64_t M, int mode, int64_t pos, const int64_t* pos_dev,
                                                            const LazyPick* picks,
                                                            int npicks, const int* ckind, const int64_t* cidx,
-                                                           const T* Xs, const T* Cp, int64_t n_pool, int kernel, T os,
-                                                           T noise, const T* prevrows, int64_t ldv, T* Vt, T* dstat,
+                                                           CovSrc<T> src, const T* prevrows, int64_t ldv, T* Vt, T* dstat,
                                                            int* fresh, const unsigned char* alive, double* scores,
                                                            double ss, double delta) {
     const int lane = threadIdx.x & 63;
@@ -930,7 +842,7 @@ __global__ __launch_bounds__(COOP ? 1024 : 256) void lazy_refresh_kernel(int64_t
             T sd = red[0];
 #pragma unroll
             for (int k = 1; k < 16; ++k) sd += red[k];
-            const T bp = pick_bprime<T, DP>(unit, pj, Xs, Cp, n_pool, pk.pool_idx, (int)pk.in_train, kernel, os, noise);
+            const T bp = pick_bprime<T, DP>(unit, pj, src, pk.pool_idx, (int)pk.in_train);
             const T r = (bp - sd) * (T)pk.scale;
             d += unit ? r * r : -(r * r);
             if (threadIdx.x == 0) row[pk.ncols] = r;
@@ -959,7 +871,7 @@ __global__ __launch_bounds__(COOP ? 1024 : 256) void lazy_refresh_kernel(int64_t
             const LazyPick pk = picks[q];
             T sd = row_dot_one_wave<T>(row, prevrows + (int64_t)q * ldv, pk.ncols, lane);
             sd = __shfl(sd, 0, 64);
-            const T bp = pick_bprime<T, DP>(unit, pj, Xs, Cp, n_pool, pk.pool_idx, (int)pk.in_train, kernel, os, noise);
+            const T bp = pick_bprime<T, DP>(unit, pj, src, pk.pool_idx, (int)pk.in_train);
             const T r = (bp - sd) * (T)pk.scale;
             d += unit ? r * r : -(r * r);
             if (lane == 0) row[pk.ncols] = r;
@@ -975,38 +887,26 @@ __global__ __launch_bounds__(COOP ? 1024 : 256) void lazy_refresh_kernel(int64_t
 
 template <typename T>
 int lazy_refresh_launch(algp_ctx* c, int64_t M, int mode, int64_t pos, const LazyPick* picks, int npicks, const int* ckind,
-                        const int64_t* cidx, const T* Xs, const T* Cp, int64_t n_pool, int DP, int kernel, T os, T noise,
-                        const T* prevrows, int64_t ldv, T* Vt, T* dstat, int* fresh, const unsigned char* alive,
-                        double* scores, double ss, double delta, const int64_t* pos_dev) {
+                        const int64_t* cidx, const KmatSrc& s, const T* prevrows, int64_t ldv, T* Vt, T* dstat, int* fresh,
+                        const unsigned char* alive, double* scores, double ss, double delta, const int64_t* pos_dev) {
     if (M <= 0 || npicks <= 0) return ALGP_OK;
     const bool coop = (mode == 0 || (mode == 2 && M == 1));      // one row: sixteen waves share its dot products
     int64_t g = coop ? 1 : (M + 3) / 4;
     if (g > 65536) g = 65536;
     ProfScope ps(c, ALGP_PROF_ROWS, 0.0, 13.0 * M);
     dim3 grid((unsigned)g), blk(coop ? 1024 : 256);
-#define ALGP_LR(DPV, CO)                                                                                          \
-    hipLaunchKernelGGL((lazy_refresh_kernel<T, DPV, CO>), grid, blk, 0, c->cur, M, mode, pos, pos_dev, picks, npicks, ckind, \
-                       cidx, Xs, Cp, n_pool, kernel, os, noise, prevrows, ldv, Vt, dstat, fresh, alive, scores, ss, delta)
-#define ALGP_LR2(DPV)                                                                                             \
-    do {                                                                                                          \
-        if (coop) ALGP_LR(DPV, true);                                                                             \
-        else ALGP_LR(DPV, false);                                                                                 \
-    } while (0)
-    if (DP == 2) ALGP_LR2(2);
-    else if (DP == 4) ALGP_LR2(4);
-    else ALGP_LR2(8);
-#undef ALGP_LR2
-#undef ALGP_LR
+    auto launch = [&](auto dp, auto co) {
+        hipLaunchKernelGGL((lazy_refresh_kernel<T, decltype(dp)::value, decltype(co)::value>), grid, blk, 0, c->cur, M, mode, pos, pos_dev,
+                           picks, npicks, ckind, cidx, cov_src<T>(s), prevrows, ldv, Vt, dstat, fresh, alive, scores, ss, delta);
+    };
+    with_dp(s.DP, [&](auto dp) {
+        if (coop) launch(dp, std::true_type{});
+        else launch(dp, std::false_type{});
+    });
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int lazy_refresh_launch<double>(algp_ctx*, int64_t, int, int64_t, const LazyPick*, int, const int*, const int64_t*,
-                                         const double*, const double*, int64_t, int, int, double, double, const double*,
-                                         int64_t, double*, double*, int*, const unsigned char*, double*, double, double,
-                                         const int64_t*);
-template int lazy_refresh_launch<float>(algp_ctx*, int64_t, int, int64_t, const LazyPick*, int, const int*, const int64_t*,
-                                        const float*, const float*, int64_t, int, int, float, float, const float*, int64_t,
-                                        float*, float*, int*, const unsigned char*, double*, double, double, const int64_t*);
+ALGP_INSTANTIATE(lazy_refresh_launch);
 
 // ---------------------------------------------------------------------------------------------
 // greedy commit bookkeeping on the device (one thread): from the winner's statistic d_c (posterior variance, or
@@ -1043,10 +943,7 @@ int commit_finalize_launch(algp_ctx* c, const T* dsrc, int in_train, double ss, 
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int commit_finalize_launch<double>(algp_ctx*, const double*, int, double, double, LazyPick*, int64_t, int64_t,
-                                            unsigned char*, double*, double*);
-template int commit_finalize_launch<float>(algp_ctx*, const float*, int, double, double, LazyPick*, int64_t, int64_t,
-                                           unsigned char*, double*, double*);
+ALGP_INSTANTIATE(commit_finalize_launch);
 
 // ---------------------------------------------------------------------------------------------
 // MI criterion (agent.py:330-339).  Besides the entropy gain, the utility of candidate i needs H(Abar \ i) and H(all_i):
@@ -1103,10 +1000,7 @@ int mi_rank1_launch(algp_ctx* c, int64_t m, const T* col0, T* U, int64_t ldu, do
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int mi_rank1_launch<double>(algp_ctx*, int64_t, const double*, double*, int64_t, double*, int, int64_t, int, double, double*,
-                                     double*, double*, const LazyPick*);
-template int mi_rank1_launch<float>(algp_ctx*, int64_t, const float*, float*, int64_t, double*, int, int64_t, int, double, float*,
-                                    double*, double*, const LazyPick*);
+ALGP_INSTANTIATE(mi_rank1_launch);
 
 // MI utility of every candidate from the device-resident terms: entropy gain + H(A) + H(Abar \ i) - H(all_i)
 // Hs = (H(A), H(Abar), H(all)); posbar: pool index -> row of the complement matrix
@@ -1136,10 +1030,7 @@ int mi_score_launch(algp_ctx* c, int64_t M, const int* ckind, const int64_t* cid
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int mi_score_launch<double>(algp_ctx*, int64_t, const int*, const int64_t*, const unsigned char*, const double*, double,
-                                     double, const int64_t*, const double*, const double*, const double*, double*);
-template int mi_score_launch<float>(algp_ctx*, int64_t, const int*, const int64_t*, const unsigned char*, const float*, double,
-                                    double, const int64_t*, const float*, const float*, const double*, double*);
+ALGP_INSTANTIATE(mi_score_launch);
 
 // out[0] = fresh[*idx] (as a double; -1 when *idx < 0): rides with the argmax read-back of the lazy greedy
 __global__ void fresh_at_kernel(const int* fresh, const int64_t* idx, double* out) {
@@ -1164,8 +1055,7 @@ constexpr int PATH_SITES = 64;
 template <typename T, int DP>
 __global__ __launch_bounds__(256) void path_score_kernel(const int64_t* cpos, const int64_t* lpos, int maxlen, const int64_t* cidx,
                                                          const T* Vt, int64_t ldv, int64_t ncols, const T* L, int64_t ldl,
-                                                         const T* varA, const T* Xs, const T* Cp, int64_t n_pool, int kernel,
-                                                         double os, double noise, double sm, double* out) {
+                                                         const T* varA, CovSrc<T, double> src, double sm, double* out) {
     __shared__ double G[PATH_SITES][PATH_SITES + 1];
     __shared__ double R[PATH_SITES][33];
     __shared__ int64_t s_c[PATH_SITES], s_l[PATH_SITES];
@@ -1230,25 +1120,7 @@ __global__ __launch_bounds__(256) void path_score_kernel(const int64_t* cpos, co
         for (int j = 0; j < 4; ++j) {
             const int b = tx + 16 * j;
             if (b > a) continue;
-            const int64_t pa = cidx[s_c[a]], pb = cidx[s_c[b]];
-            double cab;
-            if (Cp) {
-                cab = (double)Cp[pa * n_pool + pb];
-            } else {
-                double r2 = 0.0;
-#pragma unroll
-                for (int d = 0; d < DP; ++d) {
-                    const double df = (double)Xs[pa * DP + d] - (double)Xs[pb * DP + d];
-                    r2 += df * df;
-                }
-                if (kernel == ALGP_KERNEL_RBF) cab = os * kexp(-0.5 * r2);
-                else if (kernel == ALGP_KERNEL_MATERN15) {
-                    const double r = sqrt(r2) * 1.7320508075688772;
-                    cab = os * (1.0 + r) * kexp(-r);
-                } else cab = kval<double, 1>(kernel, os, r2);
-                if (pa == pb) cab += noise;
-            }
-            G[a][b] = cab + (a == b ? sm : 0.0) - acc[i][j];
+            G[a][b] = pool_cov<DP>(src, cidx[s_c[a]], cidx[s_c[b]]) + (a == b ? sm : 0.0) - acc[i][j];
         }
     }
     __syncthreads();
@@ -1273,26 +1145,17 @@ __global__ __launch_bounds__(256) void path_score_kernel(const int64_t* cpos, co
 
 template <typename T>
 int path_score_launch(algp_ctx* c, const int64_t* cpos, const int64_t* lpos, int npaths, int maxlen, const int64_t* cidx,
-                      const T* Vt, int64_t ldv, int64_t ncols, const T* L, int64_t ldl, const T* varA, const T* Xs,
-                      const T* Cp, int64_t n_pool, int DP, int kernel, double os, double noise, double sm, double* out) {
+                      const T* Vt, int64_t ldv, int64_t ncols, const T* L, int64_t ldl, const T* varA, const KmatSrc& s, double sm,
+                      double* out) {
     if (npaths <= 0) return ALGP_OK;
-    dim3 grid((unsigned)npaths), blk(256);
-#define ALGP_PS(DPV)                                                                                                    \
-    hipLaunchKernelGGL((path_score_kernel<T, DPV>), grid, blk, 0, c->cur, cpos, lpos, maxlen, cidx, Vt, ldv, ncols, L, ldl, \
-                       varA, Xs, Cp, n_pool, kernel, os, noise, sm, out)
-    if (DP == 2) ALGP_PS(2);
-    else if (DP == 4) ALGP_PS(4);
-    else ALGP_PS(8);
-#undef ALGP_PS
+    with_dp(s.DP, [&](auto dp) {
+        hipLaunchKernelGGL((path_score_kernel<T, decltype(dp)::value>), dim3((unsigned)npaths), dim3(256), 0, c->cur, cpos, lpos, maxlen,
+                           cidx, Vt, ldv, ncols, L, ldl, varA, cov_src<T, double>(s), sm, out);
+    });
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int path_score_launch<double>(algp_ctx*, const int64_t*, const int64_t*, int, int, const int64_t*, const double*, int64_t,
-                                       int64_t, const double*, int64_t, const double*, const double*, const double*, int64_t, int,
-                                       int, double, double, double, double*);
-template int path_score_launch<float>(algp_ctx*, const int64_t*, const int64_t*, int, int, const int64_t*, const float*, int64_t,
-                                      int64_t, const float*, int64_t, const float*, const float*, const float*, int64_t, int, int,
-                                      double, double, double, double*);
+ALGP_INSTANTIATE(path_score_launch);
 
 // ---- paths of 65 .. 256 sites (config 5's field rows: up to ~250 sites on a 250 x 200 field, env.py:197-310) -------------
 // The path's posterior block no longer fits LDS: its rows of V^T are gathered into a scratch (gather_rows_kernel, the
@@ -1300,8 +1163,8 @@ template int path_score_launch<float>(algp_ctx*, const int64_t*, const int64_t*,
 // kernel turns each into G = C_PP + sigma_m^2 I - Gram (identity on the padding) in place, and the blocks are factored
 // as 2 x 2 tiles of 128 by the diagonal-block kernel + two batched tile products (api.hip: score_paths_big).
 template <typename T, int DP>
-__global__ __launch_bounds__(256) void path_assemble_kernel(const int64_t* cpos, int ppad, const int64_t* cidx, const T* Xs, const T* Cp,
-                                                            int64_t n_pool, int kernel, double os, double noise, double sm, T* G) {
+__global__ __launch_bounds__(256) void path_assemble_kernel(const int64_t* cpos, int ppad, const int64_t* cidx, CovSrc<T, double> src,
+                                                            double sm, T* G) {
     __shared__ int64_t s_p[256];
     __shared__ int s_n;
     const int tid = threadIdx.x;
@@ -1320,25 +1183,7 @@ __global__ __launch_bounds__(256) void path_assemble_kernel(const int64_t* cpos,
         if ((a >> 7) < (b >> 7)) continue;                         // tiles above the diagonal are never read
         T v;
         if (a < P && b < P) {
-            const int64_t pa = s_p[a], pb = s_p[b];
-            double cab;
-            if (Cp) {
-                cab = (double)Cp[pa * n_pool + pb];
-            } else {
-                double r2 = 0.0;
-#pragma unroll
-                for (int d = 0; d < DP; ++d) {
-                    const double df = (double)Xs[pa * DP + d] - (double)Xs[pb * DP + d];
-                    r2 += df * df;
-                }
-                if (kernel == ALGP_KERNEL_RBF) cab = os * kexp(-0.5 * r2);
-                else if (kernel == ALGP_KERNEL_MATERN15) {
-                    const double r = sqrt(r2) * 1.7320508075688772;
-                    cab = os * (1.0 + r) * kexp(-r);
-                } else cab = kval<double, 1>(kernel, os, r2);
-                if (pa == pb) cab += noise;
-            }
-            v = (T)(cab + (a == b ? sm : 0.0) - (double)Gp[e]);
+            v = (T)(pool_cov<DP>(src, s_p[a], s_p[b]) + (a == b ? sm : 0.0) - (double)Gp[e]);
         } else {
             v = a == b ? (T)1 : (T)0;
         }
@@ -1346,23 +1191,16 @@ __global__ __launch_bounds__(256) void path_assemble_kernel(const int64_t* cpos,
     }
 }
 template <typename T>
-int path_assemble_launch(algp_ctx* c, const int64_t* cpos, int batch, int ppad, const int64_t* cidx, const T* Xs, const T* Cp,
-                         int64_t n_pool, int DP, int kernel, double os, double noise, double sm, T* G) {
+int path_assemble_launch(algp_ctx* c, const int64_t* cpos, int batch, int ppad, const int64_t* cidx, const KmatSrc& s, double sm, T* G) {
     if (batch <= 0) return ALGP_OK;
-    dim3 grid((unsigned)batch), blk(256);
-#define ALGP_PA(DPV)                                                                                                      \
-    hipLaunchKernelGGL((path_assemble_kernel<T, DPV>), grid, blk, 0, c->cur, cpos, ppad, cidx, Xs, Cp, n_pool, kernel, os, noise, sm, G)
-    if (DP == 2) ALGP_PA(2);
-    else if (DP == 4) ALGP_PA(4);
-    else ALGP_PA(8);
-#undef ALGP_PA
+    with_dp(s.DP, [&](auto dp) {
+        hipLaunchKernelGGL((path_assemble_kernel<T, decltype(dp)::value>), dim3((unsigned)batch), dim3(256), 0, c->cur, cpos, ppad, cidx,
+                           cov_src<T, double>(s), sm, G);
+    });
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int path_assemble_launch<double>(algp_ctx*, const int64_t*, int, int, const int64_t*, const double*, const double*, int64_t, int, int,
-                                          double, double, double, double*);
-template int path_assemble_launch<float>(algp_ctx*, const int64_t*, int, int, const int64_t*, const float*, const float*, int64_t, int, int,
-                                         double, double, double, float*);
+ALGP_INSTANTIATE(path_assemble_launch);
 // out[p] = P CONST + 1/2 log det (NaN where a pivot was not positive)
 __global__ void path_finish_kernel(const int64_t* cpos, int ppad, int batch, const double* logdet, const int* info, double* out) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1388,53 +1226,25 @@ int path_finish_launch(algp_ctx* c, const int64_t* cpos, int ppad, int batch, co
 // ---------------------------------------------------------------------------------------------
 // Gamma = C(U, U) - Gram in place, on and below the diagonal (one workgroup per row; sm is added per path)
 template <typename T, int DP>
-__global__ __launch_bounds__(256) void pvr_assemble_kernel(const int64_t* uidx, int64_t U, int64_t ld, const T* Xs, const T* Cp, int64_t n_pool,
-                                                           int kernel, double os, double noise, T* G) {
+__global__ __launch_bounds__(256) void pvr_assemble_kernel(const int64_t* uidx, int64_t U, int64_t ld, CovSrc<T, double> src, T* G) {
     const int64_t a = blockIdx.x;
     const int64_t pa = uidx[a];
     double xa[DP];
 #pragma unroll
-    for (int d = 0; d < DP; ++d) xa[d] = Cp ? 0.0 : (double)Xs[pa * DP + d];
-    for (int64_t b = threadIdx.x; b <= a; b += 256) {
-        const int64_t pb = uidx[b];
-        double cab;
-        if (Cp) {
-            cab = (double)Cp[pa * n_pool + pb];
-        } else {
-            double r2 = 0.0;
-#pragma unroll
-            for (int d = 0; d < DP; ++d) {
-                const double df = xa[d] - (double)Xs[pb * DP + d];
-                r2 += df * df;
-            }
-            if (kernel == ALGP_KERNEL_RBF) cab = os * kexp(-0.5 * r2);
-            else if (kernel == ALGP_KERNEL_MATERN15) {
-                const double r = sqrt(r2) * 1.7320508075688772;
-                cab = os * (1.0 + r) * kexp(-r);
-            } else cab = kval<double, 1>(kernel, os, r2);
-            if (pa == pb) cab += noise;
-        }
-        G[a * ld + b] = (T)(cab - (double)G[a * ld + b]);
-    }
+    for (int d = 0; d < DP; ++d) xa[d] = src.Cp ? 0.0 : (double)src.Xs[pa * DP + d];
+    for (int64_t b = threadIdx.x; b <= a; b += 256) G[a * ld + b] = (T)(pool_cov<DP>(src, pa, uidx[b], xa) - (double)G[a * ld + b]);
 }
 template <typename T>
-int pvr_assemble_launch(algp_ctx* c, const int64_t* uidx, int64_t U, int64_t ld, const T* Xs, const T* Cp, int64_t n_pool, int DP,
-                        int kernel, double os, double noise, T* G) {
+int pvr_assemble_launch(algp_ctx* c, const int64_t* uidx, int64_t U, int64_t ld, const KmatSrc& s, T* G) {
     if (U <= 0) return ALGP_OK;
-    dim3 grid((unsigned)U), blk(256);
-#define ALGP_PVA(DPV) \
-    hipLaunchKernelGGL((pvr_assemble_kernel<T, DPV>), grid, blk, 0, c->cur, uidx, U, ld, Xs, Cp, n_pool, kernel, os, noise, G)
-    if (DP == 2) ALGP_PVA(2);
-    else if (DP == 4) ALGP_PVA(4);
-    else ALGP_PVA(8);
-#undef ALGP_PVA
+    with_dp(s.DP, [&](auto dp) {
+        hipLaunchKernelGGL((pvr_assemble_kernel<T, decltype(dp)::value>), dim3((unsigned)U), dim3(256), 0, c->cur, uidx, U, ld,
+                           cov_src<T, double>(s), G);
+    });
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int pvr_assemble_launch<double>(algp_ctx*, const int64_t*, int64_t, int64_t, const double*, const double*, int64_t, int, int, double,
-                                         double, double*);
-template int pvr_assemble_launch<float>(algp_ctx*, const int64_t*, int64_t, int64_t, const float*, const float*, int64_t, int, int, double,
-                                        double, float*);
+ALGP_INSTANTIATE(pvr_assemble_launch);
 
 // Paths of at most 64 sites, one workgroup per path, fp64 in LDS for either dtype like path_score_kernel: both k x k blocks
 // gathered by union position, sm on Gamma's diagonal, the column Cholesky L L^T = Gamma_SS + sm I, W = L^-1 Phi_SS (a thread
@@ -1512,8 +1322,7 @@ int pvr_small_launch(algp_ctx* c, const int* upos, int stride, const int* pid, i
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int pvr_small_launch<double>(algp_ctx*, const int*, int, const int*, int, const double*, const double*, int64_t, double, double*);
-template int pvr_small_launch<float>(algp_ctx*, const int*, int, const int*, int, const float*, const float*, int64_t, double, double*);
+ALGP_INSTANTIATE(pvr_small_launch);
 
 // Paths of 65 .. 256 sites, a batch of ppad x ppad blocks (ppad = 128 or 256).  Gather: G = Gamma_SS + sm I on its lower
 // tiles, the identity behind the path's sites; F = Phi_SS in both triangles, zero behind them.
@@ -1547,8 +1356,7 @@ int pvr_gather_launch(algp_ctx* c, const int* upos, int ppad, int batch, const T
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int pvr_gather_launch<double>(algp_ctx*, const int*, int, int, const double*, const double*, int64_t, double, double*, double*);
-template int pvr_gather_launch<float>(algp_ctx*, const int*, int, int, const float*, const float*, int64_t, double, float*, float*);
+ALGP_INSTANTIATE(pvr_gather_launch);
 
 // The block's L^-1 from its 2 x 2 tiled factor: the two inverse tiles (inv: [inv(L11) | inv(L22)], zeros above their
 // diagonals) go to the diagonal tiles of Li, zeros above them; ppad = 256: tr = [L21^T | inv(L11)^T] are the transposed
@@ -1592,8 +1400,7 @@ int pvr_linv_launch(algp_ctx* c, const T* inv, const T* L21, int ppad, int batch
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int pvr_linv_launch<double>(algp_ctx*, const double*, const double*, int, int, double*, double*);
-template int pvr_linv_launch<float>(algp_ctx*, const float*, const float*, int, int, float*, float*);
+ALGP_INSTANTIATE(pvr_linv_launch);
 
 // u = sum over the lower triangle of W_ij (L^-1)_ij = tr(L^-1 Phi_SS L^-T), W = L^-1 Phi_SS; fp64 sums in a fixed order (a
 // thread's strided share, then a tree over the 256 threads); NaN where the factorisation met a bad pivot
@@ -1623,17 +1430,16 @@ int pvr_trace_launch(algp_ctx* c, const T* W, const T* Li, int ppad, int batch, 
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int pvr_trace_launch<double>(algp_ctx*, const double*, const double*, int, int, const int*, const int*, double*);
-template int pvr_trace_launch<float>(algp_ctx*, const float*, const float*, int, int, const int*, const int*, double*);
+ALGP_INSTANTIATE(pvr_trace_launch);
 
 // ---------------------------------------------------------------------------------------------
-// fused kernel-GEMV: mu_j = ybar + sum_a k(x_j, x_a) alpha_a, K never materialised (utils.py:301).
+// fused kernel-GEMV: mu_j = ybar + sum_a C(q_j, a) alpha_a WITHOUT the noise term of coinciding sites, the matrix never
+// materialised (utils.py:301; for an explicit covariance a gather of its entries).
 // One wave per output; lanes stride over the train set (coordinates and alpha are L2 resident).
 // ---------------------------------------------------------------------------------------------
 template <typename T, int DP>
-__global__ __launch_bounds__(256) void kgemv_kernel(int64_t M, const int64_t* qidx, const T* Xs, int64_t N,
-                                                    const int64_t* aidx, const T* alpha, int kernel, T os, T ybar,
-                                                    T* mu) {
+__global__ __launch_bounds__(256) void kgemv_kernel(int64_t M, const int64_t* qidx, CovSrc<T> src, int64_t N, const int64_t* aidx,
+                                                    const T* alpha, T ybar, T* mu) {
     const int lane = threadIdx.x & 63;
     const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int64_t nw = (int64_t)gridDim.x * 4;
@@ -1641,47 +1447,30 @@ __global__ __launch_bounds__(256) void kgemv_kernel(int64_t M, const int64_t* qi
         const int64_t pj = qidx[j];
         T xj[DP];
 #pragma unroll
-        for (int d = 0; d < DP; ++d) xj[d] = Xs[pj * DP + d];
+        for (int d = 0; d < DP; ++d) xj[d] = src.Cp ? (T)0 : src.Xs[pj * DP + d];
         T s = (T)0;
-        for (int64_t a = lane; a < N; a += 64) {
-            const int64_t pa = aidx[a];
-            T r2 = (T)0;
-#pragma unroll
-            for (int d = 0; d < DP; ++d) {
-                const T df = xj[d] - Xs[pa * DP + d];
-                r2 += df * df;
-            }
-            T kv;
-            if (kernel == ALGP_KERNEL_RBF) kv = os * kexp((T)-0.5 * r2);
-            else if (kernel == ALGP_KERNEL_MATERN15) {
-                const T r = sqrt(r2) * (T)1.7320508075688772;
-                kv = os * ((T)1 + r) * kexp(-r);
-            } else kv = kval<T, 1>(kernel, os, r2);
-            s += kv * alpha[a];
-        }
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+        for (int64_t a = lane; a < N; a += 64) s += pool_cov<DP, false>(src, pj, aidx[a], xj) * alpha[a];
+        s = dot_tree<T>(s);
         if (lane == 0) mu[j] = ybar + s;
     }
 }
 
 template <typename T>
-int kgemv_launch(algp_ctx* c, int64_t M, const int64_t* qidx, const T* Xs, int DP, int64_t N, const int64_t* aidx,
-                 const T* alpha, int kernel, T os, T ybar, T* mu) {
+int kgemv_launch(algp_ctx* c, int64_t M, const int64_t* qidx, const KmatSrc& s, int64_t N, const int64_t* aidx, const T* alpha, T ybar,
+                 T* mu) {
     if (M <= 0) return ALGP_OK;
     int64_t g = (M + 3) / 4;
     if (g > 8192) g = 8192;
-    ProfScope ps(c, ALGP_PROF_KMAT, (double)M * N * (3.0 * DP + 4.0), sizeof(T) * (double)(M + N) * (DP + 1));
-    dim3 grid((unsigned)g), blk(256);
-    if (DP == 2) hipLaunchKernelGGL((kgemv_kernel<T, 2>), grid, blk, 0, c->cur, M, qidx, Xs, N, aidx, alpha, kernel, os, ybar, mu);
-    else if (DP == 4) hipLaunchKernelGGL((kgemv_kernel<T, 4>), grid, blk, 0, c->cur, M, qidx, Xs, N, aidx, alpha, kernel, os, ybar, mu);
-    else hipLaunchKernelGGL((kgemv_kernel<T, 8>), grid, blk, 0, c->cur, M, qidx, Xs, N, aidx, alpha, kernel, os, ybar, mu);
+    ProfScope ps(c, ALGP_PROF_KMAT, (double)M * N * (s.Cp ? 2.0 : 3.0 * s.DP + 4.0),
+                 sizeof(T) * (s.Cp ? (double)M * N : (double)(M + N) * (s.DP + 1)));
+    with_dp(s.DP, [&](auto dp) {
+        hipLaunchKernelGGL((kgemv_kernel<T, decltype(dp)::value>), dim3((unsigned)g), dim3(256), 0, c->cur, M, qidx, cov_src<T>(s), N, aidx,
+                           alpha, ybar, mu);
+    });
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int kgemv_launch<double>(algp_ctx*, int64_t, const int64_t*, const double*, int, int64_t, const int64_t*,
-                                  const double*, int, double, double, double*);
-template int kgemv_launch<float>(algp_ctx*, int64_t, const int64_t*, const float*, int, int64_t, const int64_t*,
-                                 const float*, int, float, float, float*);
+ALGP_INSTANTIATE(kgemv_launch);
 
 // ---------------------------------------------------------------------------------------------
 // small helpers
@@ -1701,8 +1490,7 @@ int pad_identity_launch(algp_ctx* c, T* A, int64_t n, int64_t npad, int64_t ld) 
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int pad_identity_launch<double>(algp_ctx*, double*, int64_t, int64_t, int64_t);
-template int pad_identity_launch<float>(algp_ctx*, float*, int64_t, int64_t, int64_t);
+ALGP_INSTANTIATE(pad_identity_launch);
 
 // A[i][i] += v for i < n
 template <typename T>
@@ -1717,8 +1505,7 @@ int add_diag_launch(algp_ctx* c, T* A, int64_t n, int64_t ld, T v) {
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int add_diag_launch<double>(algp_ctx*, double*, int64_t, int64_t, double);
-template int add_diag_launch<float>(algp_ctx*, float*, int64_t, int64_t, float);
+ALGP_INSTANTIATE(add_diag_launch);
 
 template <typename T>
 __global__ void set_identity_kernel(T* A, int64_t npad, int64_t ld) {
@@ -1734,8 +1521,7 @@ int set_identity_launch(algp_ctx* c, T* A, int64_t npad, int64_t ld) {
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int set_identity_launch<double>(algp_ctx*, double*, int64_t, int64_t);
-template int set_identity_launch<float>(algp_ctx*, float*, int64_t, int64_t);
+ALGP_INSTANTIATE(set_identity_launch);
 
 // sum_i log L[i][i] for i < n, accumulated into *out (double)
 // out[i] = sum_{k >= 128 (i / 128)} X[i][k] z[k] for an upper-triangular X (zero tiles left of the diagonal tile are never read):
@@ -1771,8 +1557,7 @@ int upper_gemv_launch(algp_ctx* c, const T* X, int64_t ld, int64_t n, const T* z
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int upper_gemv_launch<double>(algp_ctx*, const double*, int64_t, int64_t, const double*, double*);
-template int upper_gemv_launch<float>(algp_ctx*, const float*, int64_t, int64_t, const float*, float*);
+ALGP_INSTANTIATE(upper_gemv_launch);
 
 // acc3[q * stride + rows[e]] = 0 for q < 3: the carried row sums of candidates whose kept columns were zeroed
 template <typename T>
@@ -1787,8 +1572,7 @@ int zero_rows3_launch(algp_ctx* c, T* acc3, int64_t stride, const int64_t* rows,
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int zero_rows3_launch<double>(algp_ctx*, double*, int64_t, const int64_t*, int64_t);
-template int zero_rows3_launch<float>(algp_ctx*, float*, int64_t, const int64_t*, int64_t);
+ALGP_INSTANTIATE(zero_rows3_launch);
 
 // X[rows[r]][0:ncols] = 0 for n listed rows (a workgroup per row and 2048 columns): the candidates that became train sites
 // in an incremental step restart as unit rows (one memset per row before: ~30 per step of config 5's loop, 0.2 ms in all).
@@ -1805,8 +1589,7 @@ int zero_listed_rows_launch(algp_ctx* c, T* X, int64_t ldx, const int64_t* rows,
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int zero_listed_rows_launch<double>(algp_ctx*, double*, int64_t, const int64_t*, int64_t, int64_t);
-template int zero_listed_rows_launch<float>(algp_ctx*, float*, int64_t, const int64_t*, int64_t, int64_t);
+ALGP_INSTANTIATE(zero_listed_rows_launch);
 
 // Fixed assignment and fixed summation order: the log-determinant of an updated factor is the same number in every run.
 // Workgroup b takes entries i = 256 (b + G q) + thread; its 4 wave sums go to part[4 b ..]; logdiag_sum_kernel adds the 4 G
@@ -1835,8 +1618,7 @@ int logdiag_launch(algp_ctx* c, const T* L, int64_t ld, int64_t n, double* out) 
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int logdiag_launch<double>(algp_ctx*, const double*, int64_t, int64_t, double*);
-template int logdiag_launch<float>(algp_ctx*, const float*, int64_t, int64_t, double*);
+ALGP_INSTANTIATE(logdiag_launch);
 
 template <typename T>
 __global__ void add_doubles_kernel(double* dst, const T* src, int64_t n) {
@@ -1850,7 +1632,6 @@ int to_double_launch(algp_ctx* c, double* dst, const T* src, int64_t n) {
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
 }
-template int to_double_launch<double>(algp_ctx*, double*, const double*, int64_t);
-template int to_double_launch<float>(algp_ctx*, double*, const float*, int64_t);
+ALGP_INSTANTIATE(to_double_launch);
 
 }  // namespace algp
