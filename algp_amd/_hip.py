@@ -65,6 +65,7 @@ SIGNATURES = {
     'algp_get_posterior': (C.c_int, [_c_ctx, C.c_void_p, C.c_void_p]),
     'algp_get_posterior_cov': (C.c_int, [_c_ctx, C.c_void_p, _dblp]),
     'algp_posterior_mean': (C.c_int, [_c_ctx, _i64p, C.c_int64, C.c_void_p]),
+    'algp_sample_posterior': (C.c_int, [_c_ctx, C.c_int, C.c_int, _dblp, _dblp, _dblp, _dblp, _dblp, C.c_void_p]),
     'algp_scores': (C.c_int, [_c_ctx, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_int]),
     'algp_argmax': (C.c_int, [_c_ctx, _i64p, _i64p, _dblp]),
     'algp_best_candidate': (C.c_int, [_c_ctx, C.c_int, C.c_double, C.c_double, _i64p, _i64p, _dblp]),
@@ -369,6 +370,38 @@ class Context(object):
         mu = np.empty(len(idx), dtype=self.dtype)
         self._check(self.lib.algp_posterior_mean(self.h, _i64(idx), len(idx), _ptr(mu)))
         return mu
+
+    def sample_posterior(self, eps, weights=None, omega=None, phase=None, prior=None):
+        """(S, M) joint draws of the latent field at the candidates, in the context's dtype (algp_sample_posterior).  The
+        library draws nothing: eps (S, N) are the standard-normal draws of the train noise, and the prior draw is either
+        random Fourier features -- weights (S, F) standard normal, omega (F, D) unit-lengthscale frequencies, phase (F,);
+        see utils.spectral_draws -- or prior (S, n_pool) values at every pool site.  Raises ValueError for a bad combination
+        of arguments and for the states the ABI refuses (no solve, picks committed, a unit row, a repeated train site)."""
+        def dbl(a, shape, what):
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.shape != tuple(shape):
+                raise ValueError('%s: expected shape %s, got %s' % (what, tuple(shape), a.shape))
+            return a
+        eps = np.ascontiguousarray(eps, dtype=np.float64)
+        if eps.ndim != 2 or eps.shape[0] < 1 or eps.shape[1] != self.N:
+            raise ValueError('eps: expected shape (S >= 1, %d), got %s' % (self.N, eps.shape))
+        S = eps.shape[0]
+        if (prior is None) == (weights is None) or (weights is None) != (omega is None) or (weights is None) != (phase is None):
+            raise ValueError('pass either weights, omega and phase (random features) or prior (values at every pool site)')
+        F = 0
+        if prior is None:
+            weights = np.ascontiguousarray(weights, dtype=np.float64)
+            if weights.ndim != 2 or weights.shape[0] != S or weights.shape[1] < 1:
+                raise ValueError('weights: expected shape (%d, F >= 1), got %s' % (S, weights.shape))
+            F = weights.shape[1]
+            omega = dbl(omega, (F, self.D), 'omega')
+            phase = dbl(phase, (F,), 'phase')
+        else:
+            prior = dbl(prior, (S, self.n_pool), 'prior')
+        out = np.empty((S, self.M), dtype=self.dtype)
+        dp = lambda a: None if a is None else a.ctypes.data_as(_dblp)
+        self._check(self.lib.algp_sample_posterior(self.h, S, F, dp(omega), dp(phase), dp(weights), dp(prior), dp(eps), _ptr(out)))
+        return out
 
     # -- greedy ----------------------------------------------------------------
     def scores(self, criterion, static_std, mobile_std, out_device_ptr=None):

@@ -21,7 +21,8 @@ import torch
 
 from . import _hip
 from .models import GPR
-from .utils import CONST, compute_mae, find_equi_sample_path, find_shortest_path, predictive_distribution
+from .utils import (CONST, compute_mae, find_equi_sample_path, find_shortest_path, posterior_samples,
+                    predictive_distribution)
 
 _CRIT = {'entropy': _hip.CRIT_ENTROPY, 'mutual_information': _hip.CRIT_MUTUAL_INFORMATION,
          'variance_reduction': _hip.CRIT_VARIANCE_REDUCTION}
@@ -287,6 +288,15 @@ class Agent(object):
         self._pool_key = None                                       # predictive_distribution reloads the pool
         return predictive_distribution(self.gp, self.env.X[ind], y, x, var, return_var=return_var,
                                        return_cov=return_cov, return_mi=return_mi)
+
+    def sample_posterior(self, x=None, n_samples=1, n_features=2048, rng=None):
+        """(n_samples, len(x)) joint draws of the latent field at env.test_X (or `x`) given the sampled dataset: the
+        from-scratch branch of predict with utils.posterior_samples in place of the moments.  Local on a sharded agent: no
+        collective."""
+        ind, y, var = self.get_sampled_dataset()
+        x = self.env.test_X if x is None else x
+        self._pool_key = None                                       # posterior_samples reloads the pool
+        return posterior_samples(self.gp, self.env.X[ind], y, x, var, n_samples=n_samples, n_features=n_features, rng=rng)
 
     def _predict_incremental(self, ind, y, var, return_var, return_cov, return_mi):
         """utils.predictive_distribution on the held-out set, with the factor kept across calls."""

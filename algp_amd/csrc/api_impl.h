@@ -3,7 +3,7 @@
 // factor of the train set and its updates), api_candidates.hip (candidate solve and posterior), api_greedy.hip (scoring,
 // picks, the sharded exchange), api_mi.hip (the MI criterion's state, on one GPU and over the ranks), api_vr.hip (the
 // variance-reduction criterion), api_paths.hip (best_path block scoring), api_paths_vr.hip (the variance-reduction utility of
-// whole paths), api_fit.hip (MLL gradient, one fit iteration).
+// whole paths), api_fit.hip (MLL gradient, one fit iteration), api_sample.hip (joint posterior draws).
 // Every file defines its members of Impl<T> and instantiates Impl<float> / Impl<double> for them.
 #pragma once
 #include <limits.h>
@@ -111,6 +111,9 @@ struct Impl {
     static int get_posterior(algp_ctx* c, void* mu, void* var);
     static int get_posterior_cov(algp_ctx* c, void* cov_out, double* mi_out);
     static int posterior_mean(algp_ctx* c, const int64_t* idx, int64_t M, void* mu_out);
+    // joint draws of the latent field at the candidates by pathwise conditioning (api_sample.hip)
+    static int sample_posterior(algp_ctx* c, int S, int F, const double* omega, const double* phase, const double* weights,
+                                const double* prior, const double* eps, void* out);
     static int build_set_matrix(algp_ctx* c, const int64_t* idx, int64_t m, const void* var, int64_t* mpad_out, T* dst = nullptr);
     static int set_entropy(algp_ctx* c, const int64_t* idx, int64_t m, const void* var, double* H);
     static int inverse_diag_resident(algp_ctx* c, int64_t m, int64_t mpad, void* diag_out);

@@ -1,0 +1,127 @@
+// api_sample.hip -- algp_sample_posterior: joint draws of the latent field at the candidates by pathwise conditioning
+// (Matheron's rule) on the resident candidate solve.  With V^T = B^T L^-T on the device a prior draw g becomes a posterior draw,
+//     f_s(j) = ybar + g_s(j) + V_j . L^-1 (y - ybar - g_s(A) - sqrt(v) o eps_s),      v_i = var_i + sigma_n^2,
+// by one triangular solve of the S right-hand sides and one product against V^T.  The prior draw is either a random-Fourier-
+// feature sum (sample.hip: an M x S x F product whose A operand is generated in registers) or values the caller supplies.  The
+// library draws nothing: frequencies, phases, weights and the noise draws are arguments.  Samples go through in tiles of 128:
+//   R^T (128 x Npad)  = the train rows' epilogue of the prior draw                 sample_features_launch / sample_values_launch
+//   Z^T               = R^T L^-T, in place                                          trsm_blocked
+//   out (128 x Mpad)  = ybar + G_X + Z^T (V^T)^T                                    gemm_nt_launch, beta = 1 on the prior draw
+// Nothing of the resident state is written; the scratch is one buffer of the context (algp_ctx::smp).
+#include "api_impl.h"
+
+using namespace algp;
+
+namespace algp {
+
+template <typename T>
+int Impl<T>::sample_posterior(algp_ctx* c, int S, int F, const double* omega, const double* phase, const double* weights,
+                              const double* prior, const double* eps, void* out) {
+    if (!c->solved) return fail(c, ALGP_ERR_STATE, "sample_posterior: call algp_solve_candidates first");
+    const int64_t N = c->N, Npad = c->Npad, M = c->M, Mpad = c->Mpad, n_pool = c->n_pool;
+    // the two states algp_get_posterior_cov refuses, for its reasons: V_j . z is the conditional update only for ordinary rows
+    // solved against the train set alone
+    if (c->prior_noise)
+        for (int64_t j = 0; j < M; ++j)
+            if (c->vt_kind[j] >= 0)
+                return fail(c, ALGP_ERR_STATE,
+                            "sample_posterior: candidate " + std::to_string(j) + " (pool index " + std::to_string(c->cand_idx[j]) +
+                                ") is a train site and was solved as a unit row (prior_includes_noise = 1): set the "
+                                "candidates with prior_includes_noise = 0");
+    if (!c->picks.empty())
+        return fail(c, ALGP_ERR_STATE, "sample_posterior: " + std::to_string(c->picks.size()) +
+                                           " pick(s) were committed since the candidate solve, which the draws would not "
+                                           "include: solve the candidates again");
+    // rows of one site share its sigma_n^2 term (algp_set_train): independent eps cannot describe their noise
+    if (c->train_has_repeats)
+        return fail(c, ALGP_ERR_STATE, "sample_posterior: the train set lists a pool site in more than one row");
+    if (F > 0 && c->pool_is_cov) return fail(c, ALGP_ERR_BAD_ARG, "sample_posterior: random features need a coordinate pool (pass prior values)");
+    if (N > 0 && !eps) return fail(c, ALGP_ERR_BAD_ARG, "sample_posterior: eps is NULL");
+    if (M > 0 && !out) return fail(c, ALGP_ERR_BAD_ARG, "sample_posterior: out is NULL");
+    if (M == 0) return ALGP_OK;
+
+    // (An explicit covariance takes prior_includes_noise = 1 only, so a train site among its candidates is a unit row and was
+    // refused above: every row that arrives here was solved from K_Aj, on either pool kind.)
+    const int DP = c->hyp.DP, D = c->hyp.D;
+    const int64_t Fpad = round_up(F, SAMPLE_KT);
+    // the scratch, carved out of one allocation
+    size_t total = 0;
+    auto take = [&](size_t bytes) { const size_t off = total; total += (bytes + 255) / 256 * 256; return off; };
+    const size_t o_stA = take(sizeof(double) * (size_t)SAMPLE_TILE * (size_t)(F > 0 ? F : n_pool));   // weights / prior values
+    const size_t o_stB = take(sizeof(double) * (size_t)SAMPLE_TILE * (size_t)N);                      // eps
+    const size_t o_stC = take(sizeof(double) * (size_t)F * (size_t)(D + 1));                          // omega, phase
+    const size_t o_G = take(sizeof(T) * (size_t)SAMPLE_TILE * (size_t)(F > 0 ? Fpad : n_pool));       // W^T (Fpad x 128) / prior (128 x n_pool)
+    const size_t o_om = take(sizeof(T) * (size_t)Fpad * DP);
+    const size_t o_ph = take(sizeof(T) * (size_t)Fpad);
+    const size_t o_E = take(sizeof(T) * (size_t)SAMPLE_TILE * (size_t)Npad);
+    const size_t o_R = take(sizeof(T) * (size_t)SAMPLE_TILE * (size_t)Npad);
+    const size_t o_O = take(sizeof(T) * (size_t)SAMPLE_TILE * (size_t)Mpad);
+    if (total > c->smp.cap) {
+        size_t free_b = 0, total_b = 0;
+        ALGP_HIP(hipMemGetInfo(&free_b, &total_b));
+        if (total > c->smp.cap + free_b)
+            return fail(c, ALGP_ERR_OOM, "sample_posterior: the scratch of one tile of 128 samples takes " + std::to_string(total) +
+                                             " bytes, " + std::to_string(c->smp.cap + free_b) + " available");
+    }
+    ALGP_TRY(ensure(c, c->smp, total));
+    char* base = (char*)c->smp.p;
+    double *stA = (double*)(base + o_stA), *stB = (double*)(base + o_stB), *stC = (double*)(base + o_stC);
+    T *G = (T*)(base + o_G), *om = (T*)(base + o_om), *ph = (T*)(base + o_ph), *E = (T*)(base + o_E), *R = (T*)(base + o_R);
+    T* O = (T*)(base + o_O);
+
+    if (F > 0) {
+        ALGP_HIP(hipMemcpyAsync(stC, omega, sizeof(double) * (size_t)F * D, hipMemcpyHostToDevice, c->stream));
+        ALGP_HIP(hipMemcpyAsync(stC + (size_t)F * D, phase, sizeof(double) * (size_t)F, hipMemcpyHostToDevice, c->stream));
+        ALGP_TRY(sample_convert_launch<T>(c, stC, F, D, om, Fpad, DP, DP, 0));
+        ALGP_TRY(sample_convert_launch<T>(c, stC + (size_t)F * D, 1, F, ph, 1, Fpad, Fpad, 0));
+    }
+    const T scale = F > 0 ? (T)sqrt(2.0 * c->hyp.outputscale / (double)F) : (T)1;
+    for (int64_t s0 = 0; s0 < S; s0 += SAMPLE_TILE) {
+        const int sl = (int)std::min<int64_t>(SAMPLE_TILE, S - s0);
+        if (F > 0) {
+            ALGP_HIP(hipMemcpyAsync(stA, weights + s0 * F, sizeof(double) * (size_t)sl * F, hipMemcpyHostToDevice, c->stream));
+            ALGP_TRY(sample_convert_launch<T>(c, stA, sl, F, G, SAMPLE_TILE, Fpad, SAMPLE_TILE, 1));
+        } else {
+            ALGP_HIP(hipMemcpyAsync(stA, prior + s0 * n_pool, sizeof(double) * (size_t)sl * n_pool, hipMemcpyHostToDevice, c->stream));
+            ALGP_TRY(sample_convert_launch<T>(c, stA, sl, n_pool, G, SAMPLE_TILE, n_pool, n_pool, 0));
+        }
+        auto draw = [&](const int64_t* idx, const SampleEpi<T>& e) {
+            return F > 0 ? sample_features_launch<T>(c, (const T*)c->Xs.p, DP, idx, G, om, ph, Fpad, F, scale, e)
+                         : sample_values_launch<T>(c, G, n_pool, idx, e);
+        };
+        if (N > 0) {
+            ALGP_HIP(hipMemcpyAsync(stB, eps + s0 * N, sizeof(double) * (size_t)sl * N, hipMemcpyHostToDevice, c->stream));
+            ALGP_TRY(sample_convert_launch<T>(c, stB, sl, N, E, SAMPLE_TILE, Npad, Npad, 0));
+            ALGP_TRY(draw((const int64_t*)c->Aidx.p, {R, Npad, N, sl, (T)0, (const T*)c->y0.p, (const T*)c->varA.p, E, (T)c->hyp.noise}));
+            ALGP_TRY(trsm_blocked<T>(c, ALGP_PROF_GEMM_TRSM, R, SAMPLE_TILE, Npad, p(c->L), Npad, c->Lld, p(c->invD)));
+        }
+        ALGP_TRY(draw((const int64_t*)c->Cidx.p, {O, Mpad, M, sl, (T)c->ybar, nullptr, nullptr, nullptr, (T)0}));
+        if (N > 0) {
+            ALGP_TRY(gemm_nt_launch<T>(c, ALGP_PROF_GEMM_OTHER, SAMPLE_TILE, Mpad, Npad, (T)1, R, Npad, p(c->Vt), c->ldv, (T)1, O, Mpad,
+                                       O, Mpad, 0));
+        }
+        ALGP_HIP(hipMemcpy2DAsync((T*)out + s0 * M, sizeof(T) * M, O, sizeof(T) * Mpad, sizeof(T) * M, (size_t)sl, hipMemcpyDeviceToHost,
+                                  c->stream));
+        ALGP_TRY(sync(c));                                           // the staging is reused by the next tile
+    }
+    return ALGP_OK;
+}
+
+template struct Impl<float>;
+template struct Impl<double>;
+
+}  // namespace algp
+
+extern "C" {
+
+int algp_sample_posterior(algp_ctx* c, int S, int F, const double* omega, const double* phase, const double* weights,
+                          const double* prior, const double* eps, void* out) {
+    CHECK_CTX(c);
+    if (S < 1 || F < 0) return fail(c, ALGP_ERR_BAD_ARG, "sample_posterior: S >= 1 and F >= 0 required");
+    if (F > 0 ? (!omega || !phase || !weights || prior) : (omega || phase || weights || !prior))
+        return fail(c, ALGP_ERR_BAD_ARG, F > 0 ? "sample_posterior: F > 0 takes omega, phase and weights, and no prior values"
+                                               : "sample_posterior: F == 0 takes prior values, and no omega, phase or weights");
+    FINISH(c, DISPATCH(c, sample_posterior(c, S, F, omega, phase, weights, prior, eps, out)));
+}
+
+}  // extern "C"

@@ -439,6 +439,7 @@ struct algp_ctx {
 
     // scratch for auxiliary factorizations (entropy_from_cov, set entropies, MI terms, posterior cov)
     algp::DevBuf auxA, auxInv, auxW, auxIdx, auxVar, auxD, hostStage;
+    algp::DevBuf smp;                    // algp_sample_posterior's scratch, one allocation carved up per call (api_sample.hip)
 
     // profiling
     bool prof_on = false;
@@ -734,6 +735,38 @@ int trsv_backward(algp_ctx* c, const T* L, int64_t npad, int64_t ldl, const T* i
 template <typename T>
 int rows_reduce_launch(algp_ctx* c, const T* Vt, int64_t rows, int64_t ldv, int64_t ncols, const T* w, T* ss, T* dot,
                        int64_t tri_c0 = -1);
+
+// ---- joint posterior draws (sample.hip; algp_sample_posterior, api_sample.hip) ----
+// Where a launch of the two kernels below leaves the prior draw g of (row, sample s), for one tile of at most 128 samples,
+// sample-major: out[s * ld + row], every row < ld and every s < 128 written.
+//   candidates (y0 == null): ybar + g for row < nrows, 0 behind
+//   train rows: y0[row] - g - sqrt(var[row] + noise) eps[s * ld + row] for row < nrows and s < slive, 0 elsewhere -- the
+//   right-hand side R^T of Z^T = R^T L^-T
+template <typename T>
+struct SampleEpi {
+    T* out;
+    int64_t ld, nrows;
+    int slive;
+    T ybar;
+    const T* y0;
+    const T* var;
+    const T* eps;
+    T noise;
+};
+constexpr int SAMPLE_TILE = 128;   // samples per pass
+constexpr int SAMPLE_KT = 32;      // features per staged k-tile: F is padded to it with zero weights
+// g[row][s] = scale sum_f cos(Xs[idx[row]] . om[f] + ph[f]) Wt[f][s] on the matrix cores, the A operand generated in registers;
+// om: Fpad x DP, ph: Fpad, Wt: Fpad x 128 (feature-major, zero behind F and behind the live samples); flop_f: the true F
+template <typename T>
+int sample_features_launch(algp_ctx* c, const T* Xs, int DP, const int64_t* idx, const T* Wt, const T* om, const T* ph,
+                           int64_t Fpad, int64_t flop_f, T scale, const SampleEpi<T>& e);
+// g[row][s] = prior[s * n_pool + idx[row]] (prior: 128 x n_pool, zero rows behind the live samples)
+template <typename T>
+int sample_values_launch(algp_ctx* c, const T* prior, int64_t n_pool, const int64_t* idx, const SampleEpi<T>& e);
+// dst (rows_pad x cols_pad, leading dimension ldd; transposed: cols_pad x rows_pad) = src (rows x cols doubles), zero padded
+template <typename T>
+int sample_convert_launch(algp_ctx* c, const double* src, int64_t rows, int64_t cols, T* dst, int64_t rows_pad, int64_t cols_pad,
+                          int64_t ldd, int transposed);
 
 template <typename T>
 int test_mfma_launch(algp_ctx* c, int* mismatches_dev);

@@ -252,5 +252,12 @@ class GPR(object):
         cov, _ = c.posterior_cov()
         return mu, cov + self.dtype.type(noise) * np.eye(M, dtype=self.dtype)
 
+    def sample_posterior(self, x, n_samples=1, n_features=2048, rng=None):
+        """(n_samples, len(x)) joint draws of the latent field f at `x` (no observation noise), conditioned on the stored
+        training data: utils.posterior_samples."""
+        from .utils import posterior_samples
+        return posterior_samples(self, self._train_x, self._train_y, x, self._train_var, n_samples=n_samples,
+                                 n_features=n_features, rng=rng)
+
     def get_embeddings(self, x):
         return np.asarray(x)                                                     # identity latent (models.py:199-203)

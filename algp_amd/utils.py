@@ -74,6 +74,55 @@ def predictive_distribution(gp, train_x, train_y, test_x, train_var=None, test_v
     return res
 
 
+_MATERN_NU = {_hip.KERNEL_MATERN05: 0.5, _hip.KERNEL_MATERN15: 1.5, _hip.KERNEL_MATERN25: 2.5}
+
+
+def _rng(rng):
+    return rng if isinstance(rng, np.random.RandomState) else np.random.RandomState(rng)
+
+
+def spectral_draws(kernel_id, D, n_features, rng):
+    """(omega, phase): n_features random Fourier frequencies of the kernel's spectral density for UNIT lengthscale,
+    (n_features, D) float64, and phases ~ U[0, 2 pi), (n_features,) float64, so that with x scaled by 1 / lengthscale
+    E[2 os cos(omega . x + phase) cos(omega . x' + phase)] = k(x, x').  RBF: omega ~ N(0, I); Matern-nu: a multivariate
+    Student-t with 2 nu degrees of freedom, omega = z sqrt(2 nu / c), z ~ N(0, I), c ~ chi^2(2 nu), one c per feature.
+    Drawn from `rng` (a RandomState or a seed) in this order: z, c (Matern only), phase."""
+    rng = _rng(rng)
+    D, F = int(D), int(n_features)
+    omega = rng.standard_normal((F, D))
+    if kernel_id != _hip.KERNEL_RBF:
+        if kernel_id not in _MATERN_NU:
+            raise NotImplementedError('spectral_draws: kernel id %r' % (kernel_id,))
+        nu = _MATERN_NU[kernel_id]
+        omega = omega * np.sqrt(2.0 * nu / rng.chisquare(2.0 * nu, size=F))[:, None]
+    phase = rng.uniform(0.0, 2.0 * np.pi, size=F)
+    return np.ascontiguousarray(omega, dtype=np.float64), np.ascontiguousarray(phase, dtype=np.float64)
+
+
+def posterior_samples(gp, train_x, train_y, test_x, train_var=None, n_samples=1, n_features=2048, rng=None):
+    """(n_samples, len(test_x)) joint draws of the latent field at `test_x` given the train data, by pathwise conditioning
+    on the device (algp_sample_posterior): pool, train set and candidates exactly as predictive_distribution sets them
+    (prior_includes_noise=False), the prior draw from `n_features` random Fourier features of the kernel.  Everything random
+    comes from `rng` (a RandomState or a seed), in this order: spectral_draws(kernel, D, n_features, rng), the weights
+    standard_normal((n_samples, n_features)), the train-noise draws standard_normal((n_samples, N))."""
+    c = gp.ctx
+    gp.sync_hypers()
+    rng = _rng(rng)
+    train_x = np.asarray(train_x, dtype=np.float64)
+    train_x = train_x.reshape(len(train_x), -1)
+    test_x = np.asarray(test_x, dtype=np.float64)
+    test_x = test_x.reshape(len(test_x), -1)
+    N, M = len(train_x), len(test_x)
+    c.set_pool(np.vstack([train_x, test_x]))
+    c.set_train(np.arange(N), train_y, train_var)
+    c.set_candidates(np.arange(N, N + M), prior_includes_noise=False)
+    c.fit_and_solve()
+    omega, phase = spectral_draws(gp.hypers()[3], train_x.shape[1], n_features, rng)
+    weights = rng.standard_normal((int(n_samples), int(n_features)))
+    eps = rng.standard_normal((int(n_samples), N))
+    return c.sample_posterior(eps, weights=weights, omega=omega, phase=phase)
+
+
 def compute_mae(true, pred):
     return np.mean(np.abs(true - pred))                        # utils.py:227-228
 

@@ -188,6 +188,36 @@ int algp_get_posterior_cov(algp_ctx* ctx, void* cov_out, double* mi_out);
 /* mean only, mu = ybar + K_xa alpha with K never materialised (utils.py:301)                   */
 int algp_posterior_mean(algp_ctx* ctx, const int64_t* idx, int64_t M, void* mu_out);
 
+/* ---- joint posterior draws at the candidates: pathwise conditioning (no reference counterpart) ------------------------------
+ * algp_sample_posterior: out[s * M + j] = draw s of the LATENT field f at candidate j (candidate order, the context's dtype; no
+ * observation noise is added).  Matheron's rule on the resident candidate solve (V^T = B^T L^-T): a prior draw g becomes
+ *   f_s(j) = ybar + g_s(j) + V_j . L^-1 (y - ybar - g_s(A) - sqrt(v) o eps_s),     v_i = var_i + sigma_n^2
+ * (v_i: the train row's whole noise, S_ii - K_ii) by one triangular solve of the S right-hand sides and one product against
+ * V^T: 2 (M + N) F S + 2 M N S + N^2 S flop; no M x M and no M x F matrix exists anywhere.  The library draws NO random
+ * numbers: everything random is an argument (host doubles, converted to the context's dtype on the device), so the call is
+ * deterministic.  eps: S x N standard-normal draws for the train noise.  The prior draw G (S x n_pool sites) comes from
+ *   F > 0, features mode: G = sqrt(2 os / F) cos(Xs omega^T + phase) W^T -- random Fourier features of the kernel's spectral
+ *     density: omega (F x D) frequencies for UNIT lengthscale (N(0, I) for RBF; z sqrt(2 nu / c), z ~ N(0, I), c ~ chi^2(2 nu)
+ *     for Matern-nu), phase (F) ~ U[0, 2 pi), weights W (S x F) standard normal; Xs = x / lengthscale is the resident pool.
+ *     prior must be NULL.  Needs a coordinate pool (an explicit covariance: ALGP_ERR_BAD_ARG).  The product runs on the matrix
+ *     cores with its cosines generated in registers; phase and cosine are computed in the context's dtype.
+ *   F == 0, values mode: G = prior (S x n_pool values of a prior draw at EVERY pool site, e.g. chol(K_pool) xi on a small
+ *     pool); omega, phase, weights must be NULL.  Both pool kinds.
+ * Any other combination of NULL / non-NULL, S < 1, F < 0, eps NULL with N > 0, out NULL with M > 0: ALGP_ERR_BAD_ARG.
+ * Preconditions (ALGP_ERR_STATE), those of algp_get_posterior_cov for its reasons: a candidate solve is resident; no pick
+ * committed since; no candidate solved as a unit row (a train site under prior_includes_noise = 1; the message names it: use
+ * prior_includes_noise = 0, where such a row is an ordinary one and is sampled like any other) -- and the train set lists no
+ * pool site in more than one row (such rows share a sigma_n^2 term that independent eps cannot describe; the MI criterion
+ * refuses that state too).  algp_set_candidate_alive masks are ignored: every row gets a value.  M = 0: nothing written,
+ * ALGP_OK.  N = 0: ybar + G, the prior draw.  (An explicit-covariance pool takes prior_includes_noise = 1 only, so there a
+ * candidate that is a train site is always a unit row: leave train sites out of its candidate list.)
+ * The call reads the resident state and writes none of it (V^T, z, the variances, the lazy-greedy bounds, the criteria's
+ * state).  Samples go through in tiles of 128; S has no cap.  The scratch of one tile belongs to the context (counted by
+ * algp_device_bytes, freed by algp_destroy); if it does not fit: ALGP_ERR_OOM with the byte count, before anything is allocated.
+ * Profiling: the feature product and the product against V^T under ALGP_PROF_GEMM_OTHER, the solve under ALGP_PROF_GEMM_TRSM. */
+int algp_sample_posterior(algp_ctx* ctx, int S, int F, const double* omega, const double* phase, const double* weights,
+                          const double* prior, const double* eps, void* out);
+
 /* ---- a7: Agent.greedy (agent.py:295-356) ---------------------------------------------------
  * algp_scores: utilities of every candidate under the current state
  *   entropy: CONST + 1/2 log(pv_j + ss) (unsampled) | 1/2 log(1 + delta s_jj) (mobile-sampled)
