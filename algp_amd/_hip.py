@@ -66,6 +66,7 @@ SIGNATURES = {
     'algp_get_posterior_cov': (C.c_int, [_c_ctx, C.c_void_p, _dblp]),
     'algp_posterior_mean': (C.c_int, [_c_ctx, _i64p, C.c_int64, C.c_void_p]),
     'algp_sample_posterior': (C.c_int, [_c_ctx, C.c_int, C.c_int, _dblp, _dblp, _dblp, _dblp, _dblp, C.c_void_p]),
+    'algp_group_posterior': (C.c_int, [_c_ctx, C.POINTER(C.c_int32), _dblp, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     'algp_scores': (C.c_int, [_c_ctx, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_int]),
     'algp_argmax': (C.c_int, [_c_ctx, _i64p, _i64p, _dblp]),
     'algp_best_candidate': (C.c_int, [_c_ctx, C.c_int, C.c_double, C.c_double, _i64p, _i64p, _dblp]),
@@ -402,6 +403,39 @@ class Context(object):
         dp = lambda a: None if a is None else a.ctypes.data_as(_dblp)
         self._check(self.lib.algp_sample_posterior(self.h, S, F, dp(omega), dp(phase), dp(weights), dp(prior), dp(eps), _ptr(out)))
         return out
+
+    def group_posterior(self, group, weight=None, n_groups=None, want_cov=True, want_cross=False):
+        """(mean, cov or None, cross or None): the joint posterior of the aggregates g_q = sum_{j in q} a_j f(x_j) of the latent
+        field over groups of candidate rows (algp_group_posterior), in the context's dtype.  group (M,): a label in
+        [0, n_groups) per candidate row, -1 for a row in no group; n_groups defaults to max(group) + 1.  weight (M,): the
+        coefficients a_j as given, or None for the plain group means (a_j = 1 / n_q; every group then needs a member).
+        mean (Q,) = A mu, cov (Q, Q) = A Sigma A^T with Sigma the matrix posterior_cov() returns, cross (Q, M) = A Sigma.
+        Raises ValueError for bad shapes, labels or weights and for the states the ABI refuses (no solve, picks committed,
+        a unit row, an explicit-covariance pool)."""
+        group = np.asarray(group)
+        if group.shape != (self.M,):
+            raise ValueError('group: expected shape (%d,), got %s' % (self.M, group.shape))
+        if group.dtype.kind not in 'iu':
+            raise ValueError('group: integer labels expected, got dtype %s' % group.dtype)
+        if n_groups is None:
+            n_groups = int(group.max()) + 1 if self.M else 0
+        Q = int(n_groups)
+        if Q < 1:
+            raise ValueError('n_groups >= 1 required, got %d' % Q)
+        if self.M and (group.min() < -(2 ** 31) or group.max() >= 2 ** 31):
+            raise ValueError('group: a label does not fit 32 bits')
+        group = np.ascontiguousarray(group, dtype=np.int32)
+        if weight is not None:
+            weight = np.ascontiguousarray(weight, dtype=np.float64)
+            if weight.shape != (self.M,):
+                raise ValueError('weight: expected shape (%d,), got %s' % (self.M, weight.shape))
+        mean = np.empty(Q, dtype=self.dtype)
+        cov = np.empty((Q, Q), dtype=self.dtype) if want_cov else None
+        cross = np.empty((Q, self.M), dtype=self.dtype) if want_cross else None
+        self._check(self.lib.algp_group_posterior(self.h, group.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                  None if weight is None else weight.ctypes.data_as(_dblp), Q, _ptr(mean),
+                                                  _ptr(cov), _ptr(cross)))
+        return mean, cov, cross
 
     # -- greedy ----------------------------------------------------------------
     def scores(self, criterion, static_std, mobile_std, out_device_ptr=None):

@@ -21,7 +21,7 @@ import torch
 
 from . import _hip
 from .models import GPR
-from .utils import (CONST, compute_mae, find_equi_sample_path, find_shortest_path, posterior_samples,
+from .utils import (CONST, compute_mae, find_equi_sample_path, find_shortest_path, group_posterior, posterior_samples,
                     predictive_distribution)
 
 _CRIT = {'entropy': _hip.CRIT_ENTROPY, 'mutual_information': _hip.CRIT_MUTUAL_INFORMATION,
@@ -297,6 +297,16 @@ class Agent(object):
         x = self.env.test_X if x is None else x
         self._pool_key = None                                       # posterior_samples reloads the pool
         return posterior_samples(self.gp, self.env.X[ind], y, x, var, n_samples=n_samples, n_features=n_features, rng=rng)
+
+    def group_posterior(self, group, x=None, test_var=None, weight=None, n_groups=None, return_cross=False):
+        """(mean, cov) or (mean, cov, cross) of the aggregates of the latent field over groups of env.test_X (or `x`) given the
+        sampled dataset: the from-scratch branch of predict with utils.group_posterior in place of the moments.  Local on a
+        sharded agent: no collective."""
+        ind, y, var = self.get_sampled_dataset()
+        x = self.env.test_X if x is None else x
+        self._pool_key = None                                       # group_posterior reloads the pool
+        return group_posterior(self.gp, self.env.X[ind], y, x, group, var, test_var=test_var, weight=weight, n_groups=n_groups,
+                               return_cross=return_cross)
 
     def _predict_incremental(self, ind, y, var, return_var, return_cov, return_mi):
         """utils.predictive_distribution on the held-out set, with the factor kept across calls."""

@@ -3,7 +3,8 @@
 // factor of the train set and its updates), api_candidates.hip (candidate solve and posterior), api_greedy.hip (scoring,
 // picks, the sharded exchange), api_mi.hip (the MI criterion's state, on one GPU and over the ranks), api_vr.hip (the
 // variance-reduction criterion), api_paths.hip (best_path block scoring), api_paths_vr.hip (the variance-reduction utility of
-// whole paths), api_fit.hip (MLL gradient, one fit iteration), api_sample.hip (joint posterior draws).
+// whole paths), api_fit.hip (MLL gradient, one fit iteration), api_sample.hip (joint posterior draws),
+// api_group.hip (the joint posterior of group aggregates).
 // Every file defines its members of Impl<T> and instantiates Impl<float> / Impl<double> for them.
 #pragma once
 #include <limits.h>
@@ -114,6 +115,9 @@ struct Impl {
     // joint draws of the latent field at the candidates by pathwise conditioning (api_sample.hip)
     static int sample_posterior(algp_ctx* c, int S, int F, const double* omega, const double* phase, const double* weights,
                                 const double* prior, const double* eps, void* out);
+    // the joint posterior of sums over groups of candidate rows (api_group.hip)
+    static int group_posterior(algp_ctx* c, const int32_t* group, const double* weight, int64_t Q, void* mean_out, void* cov_out,
+                               void* cross_out);
     static int build_set_matrix(algp_ctx* c, const int64_t* idx, int64_t m, const void* var, int64_t* mpad_out, T* dst = nullptr);
     static int set_entropy(algp_ctx* c, const int64_t* idx, int64_t m, const void* var, double* H);
     static int inverse_diag_resident(algp_ctx* c, int64_t m, int64_t mpad, void* diag_out);

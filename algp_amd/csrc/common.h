@@ -440,6 +440,7 @@ struct algp_ctx {
     // scratch for auxiliary factorizations (entropy_from_cov, set entropies, MI terms, posterior cov)
     algp::DevBuf auxA, auxInv, auxW, auxIdx, auxVar, auxD, hostStage;
     algp::DevBuf smp;                    // algp_sample_posterior's scratch, one allocation carved up per call (api_sample.hip)
+    algp::DevBuf grp;                    // algp_group_posterior's scratch, likewise (api_group.hip)
 
     // profiling
     bool prof_on = false;

@@ -1,6 +1,7 @@
-// launchers defined in vecops.hip.  A launcher whose kernel evaluates the pool covariance takes the source as a KmatSrc
-// (make_src(c) at the call site) and hands its kernel the typed device view (cov_src -> CovSrc, common.h); every entry C(pa, pb)
-// is pool_cov (common.h), whatever the kernel holds the two sites' coordinates in.
+// launchers defined in vecops.hip (the sums over groups of candidate rows at the end: group.hip).  A launcher whose kernel
+// evaluates the pool covariance takes the source as a KmatSrc (make_src(c) at the call site) and hands its kernel the typed
+// device view (cov_src -> CovSrc, common.h); every entry C(pa, pb) is pool_cov (common.h), whatever the kernel holds the two
+// sites' coordinates in.
 #pragma once
 #include "common.h"
 namespace algp {
@@ -139,6 +140,36 @@ int mi_assemble_launch(algp_ctx* c, int64_t m, int g, int first, const char* gat
 template <typename T>
 int kgemv_launch(algp_ctx* c, int64_t M, const int64_t* qidx, const KmatSrc& s, int64_t N, const int64_t* aidx, const T* alpha, T ybar,
                  T* mu);
+// ---- sums over groups of candidate rows (group.hip; algp_group_posterior, api_group.hip) ----
+// The labelled rows sorted by group on the host (a stable counting sort): slot m of the sorted list holds candidate row perm[m]
+// of group gid[m] with coefficient coef[m]; group q owns the slots [off[q], off[q + 1]).  All on the device.
+template <typename T>
+struct GroupSegs {
+    const int* perm;
+    const int* gid;
+    const T* coef;
+    const int64_t* off;
+    int64_t Lm;          // labelled rows
+    int Q;
+};
+// members per chunk of the sorted list: a launch's workgroups each walk one chunk; the pieces of a group that spans chunks go to
+// a buffer of two slots per chunk (part) and are added in chunk order.  span / nspan: the groups that span chunks of that size
+constexpr int GROUP_CHUNK = 1024;      // group_ksum_launch
+constexpr int GROUP_ROWCHUNK = 256;    // group_rowsum_launch
+// U[q][j] = sum_{l in q} coef_l (k(x_j, x_l) + [j = l] extra_j) for j < M, 0 for M <= j < Mpad (leading dimension Mpad), K never
+// stored; the rows of U of groups without members are not written; part: 2 ceil(Lm / GROUP_CHUNK) x Mpad
+template <typename T>
+int group_ksum_launch(algp_ctx* c, const KmatSrc& s, const int64_t* cidx, int64_t M, int64_t Mpad, const T* extra, const GroupSegs<T>& g,
+                      const int* span, int nspan, T* U, T* part);
+// dst[q][c] = sum_{l in q} coef_l V[perm_l][c] for c < ncols; part: 2 ceil(Lm / GROUP_ROWCHUNK) x ld_part.  16-byte loads where
+// ncols and the leading dimensions allow, else a column per thread (the mean: V = mu, one column)
+template <typename T>
+int group_rowsum_launch(algp_ctx* c, const T* V, int64_t ldv, int64_t ncols, const GroupSegs<T>& g, const int* span, int nspan, T* dst,
+                        int64_t ld_dst, T* part, int64_t ld_part);
+// cov[p][q] = cov[q][p] = sum_{l in q} coef_l X[p][perm_l] (- sub[p][q], sub or null) for q <= p < Q; cov: Q x Q, packed
+template <typename T>
+int group_colsum_launch(algp_ctx* c, const T* X, int64_t ldx, const GroupSegs<T>& g, const T* sub, int64_t lds, T* cov);
+
 template <typename T>
 int pad_identity_launch(algp_ctx* c, T* A, int64_t n, int64_t npad, int64_t ld);
 template <typename T>

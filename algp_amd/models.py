@@ -259,5 +259,12 @@ class GPR(object):
         return posterior_samples(self, self._train_x, self._train_y, x, self._train_var, n_samples=n_samples,
                                  n_features=n_features, rng=rng)
 
+    def group_posterior(self, x, group, test_var=None, weight=None, n_groups=None, return_cross=False):
+        """(mean, cov) or (mean, cov, cross) of the aggregates of the latent field f over groups of the sites `x`, conditioned
+        on the stored training data: utils.group_posterior."""
+        from .utils import group_posterior
+        return group_posterior(self, self._train_x, self._train_y, x, group, self._train_var, test_var=test_var, weight=weight,
+                               n_groups=n_groups, return_cross=return_cross)
+
     def get_embeddings(self, x):
         return np.asarray(x)                                                     # identity latent (models.py:199-203)

@@ -123,6 +123,28 @@ def posterior_samples(gp, train_x, train_y, test_x, train_var=None, n_samples=1,
     return c.sample_posterior(eps, weights=weights, omega=omega, phase=phase)
 
 
+def group_posterior(gp, train_x, train_y, test_x, group, train_var=None, test_var=None, weight=None, n_groups=None,
+                    return_cross=False):
+    """(mean, cov) or (mean, cov, cross): the joint posterior of the aggregates g_q = sum_{j in q} a_j f(test_x_j) of the
+    latent field over groups of test sites -- a genotype's plots, a field row -- on the device (algp_group_posterior): pool,
+    train set and candidates exactly as predictive_distribution sets them (prior_includes_noise=False, extra_var=test_var).
+    group, weight, n_groups: see Context.group_posterior; cov = A Sigma A^T for the Sigma predictive_distribution returns
+    with return_cov, without that matrix being formed; cross = A Sigma."""
+    c = gp.ctx
+    gp.sync_hypers()
+    train_x = np.asarray(train_x, dtype=np.float64)
+    train_x = train_x.reshape(len(train_x), -1)
+    test_x = np.asarray(test_x, dtype=np.float64)
+    test_x = test_x.reshape(len(test_x), -1)
+    N, M = len(train_x), len(test_x)
+    c.set_pool(np.vstack([train_x, test_x]))
+    c.set_train(np.arange(N), train_y, train_var)
+    c.set_candidates(np.arange(N, N + M), prior_includes_noise=False, extra_var=test_var)
+    c.fit_and_solve()
+    mean, cov, cross = c.group_posterior(group, weight=weight, n_groups=n_groups, want_cov=True, want_cross=return_cross)
+    return (mean, cov, cross) if return_cross else (mean, cov)
+
+
 def compute_mae(true, pred):
     return np.mean(np.abs(true - pred))                        # utils.py:227-228
 

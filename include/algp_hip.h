@@ -218,6 +218,34 @@ int algp_posterior_mean(algp_ctx* ctx, const int64_t* idx, int64_t M, void* mu_o
 int algp_sample_posterior(algp_ctx* ctx, int S, int F, const double* omega, const double* phase, const double* weights,
                           const double* prior, const double* eps, void* out);
 
+/* ---- the joint posterior of group aggregates: genotype, row and plot means (no reference counterpart) -----------------------
+ * algp_group_posterior: Q linear functionals g_q = sum_{j in q} a_j f(x_j) of the LATENT field f over groups of candidate rows
+ * (no observation noise is added), from the resident candidate solve.  group[M]: one label per candidate row, in candidate
+ * order: a label in [0, Q) puts the row into that group, -1 into none.  weight[M] (host doubles, finite, any sign) are the
+ * coefficients as given, a_j = weight[j] (a labelled row may carry 0); weight == NULL: the plain group mean, a_j = 1 / n_q.
+ * With A the Q x M matrix of coefficients, in the context's dtype, host memory, row-major, each may be NULL (which of them are
+ * non-NULL decides what is computed):
+ *   mean_out[Q]      = A mu, mu what algp_get_posterior reports
+ *   cov_out[Q * Q]   = A Sigma A^T, Sigma = K_xx + diag(extra_var) - V^T V exactly the matrix algp_get_posterior_cov defines
+ *                      (no sigma_n^2; extra_var per row; two rows of one site share K(x, x)); both triangles, identical bits
+ *   cross_out[Q * M] = A Sigma: cross[q * M + j] = cov(g_q, f_j)
+ * No M x M matrix exists anywhere: the kernel values are summed by group as they are formed (Q x M), the rows of V^T are summed
+ * by group (Q x N), and cross = A K - (A V^T) V is one product; without cross_out that product is not launched
+ * (cov = A K A^T - (A V^T)(A V^T)^T), and mean_out alone needs neither.  M N + M L kernel evaluations and flop for L labelled
+ * rows, plus 2 Q M N for cross.
+ * weight == NULL and a group without members: ALGP_ERR_BAD_ARG (the message names the group); with explicit weights an empty
+ * group is the zero functional: mean 0, its row and column of cov 0.  Q < 1, group NULL with M > 0, a label outside [-1, Q)
+ * (the message names the row), a non-finite weight: ALGP_ERR_BAD_ARG, before anything is launched.
+ * Preconditions, those of algp_get_posterior_cov for its reasons: a candidate solve is resident, no pick committed since, no
+ * candidate solved as a unit row (the message names it) -- ALGP_ERR_STATE; a coordinate pool (an explicit covariance:
+ * ALGP_ERR_BAD_ARG).  algp_set_candidate_alive masks are ignored.  The call reads the resident state and writes none of it (V^T,
+ * z, the variances, the lazy-greedy bounds, the criteria's state).  Every sum has one fixed order (no floating-point atomics):
+ * the results carry the same bits in every run.  The scratch belongs to the context (counted by algp_device_bytes, freed by
+ * algp_destroy); if it does not fit: ALGP_ERR_OOM with the byte count, before anything is allocated.
+ * Profiling: the kernel sums under ALGP_PROF_KMAT, the grouped sums under ALGP_PROF_ROWS, the products under ALGP_PROF_GEMM_OTHER. */
+int algp_group_posterior(algp_ctx* ctx, const int32_t* group, const double* weight, int64_t Q, void* mean_out, void* cov_out,
+                         void* cross_out);
+
 /* ---- a7: Agent.greedy (agent.py:295-356) ---------------------------------------------------
  * algp_scores: utilities of every candidate under the current state
  *   entropy: CONST + 1/2 log(pv_j + ss) (unsampled) | 1/2 log(1 + delta s_jj) (mobile-sampled)
