@@ -1,10 +1,17 @@
 """GPU parity of the greedy / scoring path (reference agent.py:295-403) through the C-ABI,
 against the golden vectors captured from the reference and against the fp64 oracle."""
+import os
+import sys
+
 import numpy as np
 import pytest
 
-from algp_amd import _hip
-from oracle import gp_oracle as O
+if os.path.dirname(os.path.abspath(__file__)) not in sys.path:
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import mi_forms as MIF                               # noqa: E402
+from algp_amd import _hip                            # noqa: E402
+from oracle import gp_oracle as O                    # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -405,6 +412,9 @@ def test_mi_criterion_rank1_updates_follow_the_oracle_pick_by_pick(dtname):
     forced = [free[0], int(mob_only[3]), free[1], int(mob_only[77]), int(cand[5]), int(mob_only[100])]
     assert len(set(forced)) == 6
     picks, ut = O.greedy_fast(Cm, static, mobile, 0.1, 1.0, 6, 'mutual_information', forced_picks=forced)
+    ut_f, H = MIF.reference(Cm, static, mobile, 0.1, 1.0, forced)
+    assert np.array_equal(ut_f, ut)
+    unit = mobile[cand]
     c = _hip.Context(dt)
     c.set_hypers(hyp.log_lengthscale, hyp.log_outputscale, hyp.log_noise)
     c.set_pool(X)
@@ -421,6 +431,11 @@ def test_mi_criterion_rank1_updates_follow_the_oracle_pick_by_pick(dtname):
         assert np.array_equal(np.isfinite(gut[k]), live), k
         scale = np.max(np.abs(want[live]))
         assert np.max(np.abs(gut[k][live] - want[live])) <= rel * scale, (k, np.max(np.abs(gut[k][live] - want[live])), scale)
+        # that bar is relative to the whole pool's entropy, which every candidate shares; the offset and each candidate's
+        # own part are bounded apart by tests/mi_forms.py
+        m = MIF.measure(gut[k], want, unit, H[k])
+        print('MI n2000 %s pick %d: offset %.2e of sum|H| %.1f, per-candidate %.2e of spread %.3f' % (dtname, k + 1, abs(m.off), m.hsum, m.per, m.spread))
+        MIF.compare(gut[k], want, unit, dt, H[k], 'pick %d' % (k + 1))
     # a second run in the same context rebuilds the inverses after the solve and gives the same bits
     c.solve_candidates()
     got2, gut2 = c.greedy(_hip.CRIT_MUTUAL_INFORMATION, 0.1, 1.0, 6, forced_picks=forced, want_utilities=True)
@@ -433,11 +448,13 @@ def test_mi_criterion_rank1_updates_follow_the_oracle_pick_by_pick(dtname):
     want = ut[2][cand]
     live = np.isfinite(want)
     assert np.max(np.abs(s2[live] - want[live])) <= rel * np.max(np.abs(want[live]))
+    MIF.compare(s2, want, unit, dt, H[2], 'built with two picks')
     c.commit_pick(forced[2], 0.1, 1.0)
     s3 = c.scores(_hip.CRIT_MUTUAL_INFORMATION, 0.1, 1.0)
     want = ut[3][cand]
     live = np.isfinite(want)
     assert np.max(np.abs(s3[live] - want[live])) <= rel * np.max(np.abs(want[live]))
+    MIF.compare(s3, want, unit, dt, H[3], 'built with two picks, one folded')
     c.close()
 
 

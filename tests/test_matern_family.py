@@ -40,6 +40,7 @@ if os.path.join(REPO, 'tests') not in sys.path:
     sys.path.insert(0, os.path.join(REPO, 'tests'))
 
 import matern_forms as MF                            # noqa: E402
+import mi_forms as MIF                               # noqa: E402
 import test_rhs_fused as RF                          # noqa: E402
 import test_variance_reduction as VR                 # noqa: E402
 from algp_amd import _hip                            # noqa: E402
@@ -275,6 +276,8 @@ def test_pool_mi_picks(kid, dt):
     p = pool_problem(kid)
     picks_o, ut_o = _memo(p, 'mi', lambda: O.greedy_fast(p.C, p.static, p.mobile, S_STD, M_STD, 3, 'mutual_information'))
     cand = np.where(~p.static)[0]
+    ut_f, H = _memo(p, 'mi_H', lambda: MIF.reference(p.C, p.static, p.mobile, S_STD, M_STD, picks_o))
+    assert np.array_equal(ut_f, ut_o)
     rel = tol(dt, 1e-7, 3e-3)
     for explicit in (False, True):
         c = _pool_ctx(p, dt, explicit, cand=cand)
@@ -288,6 +291,11 @@ def test_pool_mi_picks(kid, dt):
             err = float(np.max(np.abs(ut[k][live] - want[live])))
             print('MI %s pick %d: %.2e of %.3f' % ('explicit' if explicit else 'coordinates', k, err, scale))
             assert err <= rel * scale
+            # the offset all candidates share and each candidate's own part, bounded apart (tests/mi_forms.py)
+            m = MIF.measure(ut[k], want, p.mobile[cand], H[k])
+            print('MI %s pick %d: offset %.2e of sum|H| %.1f, per-candidate %.2e of spread %.3f' % (
+                'explicit' if explicit else 'coordinates', k, abs(m.off), m.hsum, m.per, m.spread))
+            MIF.compare(ut[k], want, p.mobile[cand], dt, H[k], 'pick %d' % k)
         if np.dtype(dt) == np.float64:
             assert _top_gap(ut_o) > 2 * rel * scale, 'the inputs no longer separate the picks'
             c.solve_candidates()
