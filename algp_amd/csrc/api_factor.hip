@@ -217,6 +217,7 @@ int Impl<T>::exchange_new_rows(algp_ctx* c, int64_t Nb, int64_t p0, int* placed,
     memcpy(&mine[3], &h, sizeof(h));
     std::vector<double> all;
     ALGP_TRY(comm_agree(c, mine, all));
+    // (not comm_first_failure: this word's rule is the LARGEST status, 1 being the soft "solve the rows yourselves", 0..64)
     int worst = 0, bad_rank = -1;
     bool same = true;
     for (int r = 0; r < nr; ++r) {

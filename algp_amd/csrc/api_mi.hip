@@ -12,15 +12,14 @@
 // and factors the group's matrix (replicated, no communication), computes only its own 128-row blocks of X (blocks member,
 // member + g, ...: mi_trinv_rows, mi_shard.hip) and releases the factor.  The diagonals, the rank-1 lists U / W, their signs
 // and the three entropies stay WHOLE on every rank, so scoring is mi_score_launch on each rank's own candidates.
-// Collectives, all of them all-gathers through comm_agree / comm_exchange (comm.hip) (RCCL or the caller's host transport):
+// Collectives, all of them all-gathers through comm_agree_checked / comm_exchange (RCCL or the caller's host transport):
 //   first pick of an algp_greedy_sharded call: a 32-byte agreement word (status, whether a build is needed, picks so far);
 //     then, when any rank needs it, the build and ONE gather of every rank's diagonal pieces and entropies;
 //   every pick folded: a gather of the owners' rows at the pick ([header | row of X_bar | row of X_all] per rank), then a
 //     gather of every rank's entries of the pick's columns with the earlier terms removed; every rank puts the whole columns
 //     together and folds them into its copy of both diagonals (mi_rank1_kernel, as on one GPU).
-// Every gather carries each rank's status word in its 32-byte header: a rank that fails (memory, a factor that is not
-// positive definite, a HIP error, an injected failure) still takes part in every collective of the step, and every rank
-// returns the first failing rank's code from the same call.
+// Every one of them carries each rank's status word, so that a rank that fails keeps its peers company and every rank returns
+// its code from the same call: the protocol is described once, above comm_first_failure in comm.hip.
 #include "api_impl.h"
 
 using namespace algp;
@@ -216,11 +215,8 @@ static void mi_payloads(const algp_ctx* c, int64_t mb, int64_t mbpad, int64_t np
     *cbytes = 32 + es * (size_t)NB * (size_t)(Gb.maxloc + Ga.maxloc);
 }
 
-// an agreed failure (comm_agreed_fail, comm.hip) drops the state: the next call rebuilds it
-static int mi_agreed_fail(algp_ctx* c, int code, int bad, const std::string& local_err, const char* what) {
-    c->mi.valid = false;
-    return comm_agreed_fail(c, code, bad, local_err, what, "the mutual-information state");
-}
+// an agreed failure of a checked collective (comm.hip) drops the state: the next call rebuilds it
+static const CommState MI_STATE = {"the mutual-information state", [](algp_ctx* c) { c->mi.valid = false; }};
 
 // host side of a build: the sets, the payload sizes, and this rank's memory check -- nothing allocated yet
 template <typename T>
@@ -304,14 +300,7 @@ int Impl<T>::mi_shard_fold(algp_ctx* c, int st) {
     size_t rbytes, cbytes;
     mi_payloads(c, mb, mbpad, npad, es, &rbytes, &cbytes);
     const int64_t q = mi.npicks;
-    if (st == ALGP_OK && !mi.holds(1))
-        st = fail(c, ALGP_ERR_STATE, "greedy_sharded: the sharded mutual-information state is not built");
-    if (st == ALGP_OK && q >= (int64_t)c->picks.size())
-        st = fail(c, ALGP_ERR_STATE, "greedy_sharded: this rank has no committed pick left to fold");
-    if (st == ALGP_OK && c->debug_fail_next_mi) {
-        st = fail(c, c->debug_fail_next_mi, "mutual_information: failure injected by algp_debug_fail_at in the fold of a pick");
-        c->debug_fail_next_mi = 0;
-    }
+    st = comm_fold_status(c, st, mi.holds(1), "the sharded mutual-information state", q, "mutual_information", &c->debug_fail_next_mi);
     PickRec pk;
     pk.pool_idx = 0;
     pk.in_train = 1;
@@ -335,11 +324,7 @@ int Impl<T>::mi_shard_fold(algp_ctx* c, int st) {
         if (hipMemcpyAsync(own + 32 + es * mbpad, p(mi.Xall) + lr * npad, es * npad, hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
             st = fail(c, ALGP_ERR_HIP, "greedy_sharded: copying this rank's row of the pool's inverse failed");
     }
-    std::string local_err = st != ALGP_OK ? c->err : std::string();
-    std::vector<double> hdr;
-    int code = 0, bad = -1;
-    ALGP_TRY(comm_exchange(c, rbytes, st, nullptr, hdr, code, bad));
-    if (code) return mi_agreed_fail(c, code, bad, local_err, "the row exchange of a pick");
+    ALGP_TRY(comm_exchange(c, MI_STATE, "the row exchange of a pick", rbytes, st));
     // 2. this rank's entries of the pick's columns, the earlier picks' terms removed
     const char* rows = own + rbytes;
     const int r = (int)(q - mi.base);
@@ -359,9 +344,7 @@ int Impl<T>::mi_shard_fold(algp_ctx* c, int st) {
             st = mi_cols_local_launch<T>(c, Ga.nloc * NB, Ga.g, Ga.member, n, p(mi.Col) + mbpad, p(mi.W), npad,
                                          Hs + 3 + MAX_APPEND, r, pk.pool_idx, (T*)(own + 32 + es * NB * (size_t)Gb.maxloc));
     }
-    local_err = st != ALGP_OK ? c->err : std::string();
-    ALGP_TRY(comm_exchange(c, cbytes, st, nullptr, hdr, code, bad));
-    if (code) return mi_agreed_fail(c, code, bad, local_err, "the column exchange of a pick");
+    ALGP_TRY(comm_exchange(c, MI_STATE, "the column exchange of a pick", cbytes, st));
     // 3. on every rank: the whole columns, folded into both diagonals (mi_rank1_kernel at the next slot of each list)
     const char* pcs = own + cbytes;
     const LazyPick* lp = (const LazyPick*)c->lazypicks.p + q;
@@ -392,24 +375,13 @@ int Impl<T>::mi_shard_step(algp_ctx* c, double ss, double sm, int st, bool first
         // every rank plans and checks its memory, whether or not it needs the build: any rank's need is everybody's
         if (st == ALGP_OK) st = mi_shard_plan(c, ss, sm, pl);
         if (st == ALGP_OK) st = comm_rows_reserve(c, std::max(pl.rbytes, pl.cbytes));   // the exchange's staging (MB)
-        const std::string local_err = st != ALGP_OK ? c->err : std::string();
         // field 1: whether this rank needs a build, and its layout (2 n_complement + need): a rank attached with another
         // split would gather other byte counts, so the layouts are compared before any payload travels
         const double mine[4] = {(double)st, 2.0 * c->mi.ncomp + (need ? 1.0 : 0.0), (double)c->picks.size(), (double)c->mi.npicks};
         std::vector<double> all;
-        ALGP_TRY(comm_agree(c, mine, all));
-        int code = 0, bad = -1;
-        bool any_need = false, same = true, same_layout = true;
-        for (int r = 0; r < c->comm_nranks; ++r) {
-            const double s = all[(size_t)r * 4];
-            if (s != 0.0 && bad < 0) { bad = r; code = s == s ? (int)s : ALGP_ERR_HIP; }
-            const int64_t f = (int64_t)all[(size_t)r * 4 + 1];
-            any_need = any_need || (f & 1) != 0;
-            same_layout = same_layout && (f >> 1) == (int64_t)c->mi.ncomp;
-        }
-        for (int r = 0; r < c->comm_nranks; ++r)    // picks so far, and (without a build) picks folded so far: equal everywhere
-            same = same && all[(size_t)r * 4 + 2] == all[2] && (any_need || all[(size_t)r * 4 + 3] == all[3]);
-        if (code) return mi_agreed_fail(c, code, bad, local_err, "the plan");
+        ALGP_TRY(comm_agree_checked(c, MI_STATE, "the plan", mine, all));
+        bool any_need = false, same_layout = true;
+        for (int r = 0; r < c->comm_nranks; ++r) same_layout = same_layout && ((int64_t)all[(size_t)r * 4 + 1] >> 1) == (int64_t)c->mi.ncomp;
         if (!same_layout) {
             c->mi.valid = false;
             std::string got;
@@ -417,18 +389,12 @@ int Impl<T>::mi_shard_step(algp_ctx* c, double ss, double sm, int st, bool first
             return fail(c, ALGP_ERR_BAD_ARG, "greedy_sharded: the ranks attached different MI layouts (n_complement_ranks per rank: " +
                                                  got + "); call algp_comm_set_mi_groups with the same value on every rank");
         }
-        if (!same) {
-            c->mi.valid = false;
-            return fail(c, ALGP_ERR_STATE, "greedy_sharded: the ranks hold different numbers of committed picks (a commit failed on "
-                                           "one of them); re-solve the candidates on every rank");
-        }
+        ALGP_TRY(comm_picks_agree(c, MI_STATE, "greedy_sharded", all, 4, 1, &any_need));
         if (any_need) {
             double H3[3] = {0.0, 0.0, 0.0};
-            int bst = mi_shard_build(c, pl, H3);
-            const std::string berr = bst != ALGP_OK ? c->err : std::string();
+            const int bst = mi_shard_build(c, pl, H3);
             std::vector<double> hdr;
-            ALGP_TRY(comm_exchange(c, pl.cbytes, bst, H3, hdr, code, bad));
-            if (code) return mi_agreed_fail(c, code, bad, berr, "the build");
+            ALGP_TRY(comm_exchange(c, MI_STATE, "the build", pl.cbytes, bst, H3, &hdr));
             // whole diagonals from the pieces, the entropies from the first rank of each group
             const MiGroup Gb = mi_group(c, 0, pl.mb, pl.mbpad), Ga = mi_group(c, 1, c->n_pool, pl.npad);
             const char* pcs = (const char*)c->rowx.p + pl.cbytes;
@@ -440,8 +406,7 @@ int Impl<T>::mi_shard_step(algp_ctx* c, double ss, double sm, int st, bool first
         }
         rounds = (int64_t)c->picks.size() - c->mi.npicks;    // the same on every rank (agreed above)
     }
-    for (int64_t i = 0; i < rounds; ++i) ALGP_TRY(mi_shard_fold(c, i == 0 ? st : ALGP_OK));
-    return ALGP_OK;
+    return comm_catch_up(c, rounds, st, &Impl<T>::mi_shard_fold);
 }
 
 template struct Impl<float>;

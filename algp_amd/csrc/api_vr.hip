@@ -16,7 +16,7 @@
 // Over the ranks of a communicator (algp_comm_set_vr_exchange): the targets are the ordinary rows of
 // EVERY rank's shard (the shards disjoint), and a rank keeps w for its own rows only.  The targets of the other ranks enter
 // through their rows of V^T and their pool indices -- the pool and the target weights are replicated:
-//   agreement (first scoring of a call; comm_agree, ten doubles): status, rows, picks committed and folded, whether this rank
+//   agreement (first scoring of a call; comm_agree_checked, ten doubles): status, rows, picks committed and folded, whether this rank
 //     needs a build and whether it builds at every scoring, the layout's rows per round, the weights' hash, Npad, n_pool;
 //   build (vr_shard_build): a second four-double word (allocations), then R = ceil(largest shard / B) rounds -- pack rows
 //     [tB, (t+1)B) behind their pool indices (vr_pack_rows_kernel), comm_exchange, ONE rectangular product of the rank's whole V^T
@@ -24,9 +24,8 @@
 //     last 32-byte exchange with the outcome of the disjointness check (vr_overlap_kernel);
 //   fold (vr_shard_fold): ONE exchange per pick of every rank's partial t = V_T^T rt, partial sum_T omega r^2 and (pool index,
 //     rt) pairs; the partials are summed in rank order, the kernel-GEMV runs over the gathered pairs for the rank's own rows.
-// Every exchange carries each rank's status: a rank that fails still takes part, every rank returns its code from the same
-// call, and the state is dropped and rebuilt by the next call.  The gather and the product of a round run one after the
-// other on the context's stream.
+// Every one of them carries each rank's status word (the protocol: above comm_first_failure in comm.hip).  The gather and
+// the product of a round run one after the other on the context's stream.
 #include "api_impl.h"
 
 using namespace algp;
@@ -155,10 +154,8 @@ static void vr_fold_layout(const algp_ctx* c, int64_t cap, int64_t* off_t, int64
     *bytes = (size_t)round_up(*off_val + (int64_t)c->es * cap, 16);
 }
 
-static int vr_agreed_fail(algp_ctx* c, int code, int bad, const std::string& local_err, const char* what) {
-    c->vr.drop();
-    return comm_agreed_fail(c, code, bad, local_err, what, "the variance-reduction state");
-}
+// an agreed failure of a checked collective (comm.hip) drops the state: the next call rebuilds it
+static const CommState VR_STATE = {"the variance-reduction state", [](algp_ctx* c) { c->vr.drop(); }};
 
 // The build over the ranks: w of this rank's rows against the targets of every rank, all committed picks included.  Every
 // rank has agreed to build (vr_shard_step); max_rows: the largest shard; st: this rank's status so far.
@@ -197,15 +194,10 @@ int Impl<T>::vr_shard_build(algp_ctx* c, int64_t max_rows, int st) {
                       std::make_pair(&vr.Tidx, sizeof(int64_t) * (size_t)nr * (size_t)std::max<int64_t>(max_rows, 1)),
                       std::make_pair(&vr.Trt, es * (size_t)nr * (size_t)std::max<int64_t>(max_rows, 1))})
         if (bst == ALGP_OK) bst = ensure(c, *need.first, need.second);
-    std::string local_err = bst != ALGP_OK ? c->err : std::string();
     {
         const double mine[4] = {(double)bst, 0.0, 0.0, 0.0};
         std::vector<double> all;
-        ALGP_TRY(comm_agree(c, mine, all));
-        for (int r = 0; r < nr; ++r)
-            if (all[(size_t)r * 4] != 0.0)
-                return vr_agreed_fail(c, all[(size_t)r * 4] == all[(size_t)r * 4] ? (int)all[(size_t)r * 4] : ALGP_ERR_HIP, r, local_err,
-                                      "the allocations of the build");
+        ALGP_TRY(comm_agree_checked(c, VR_STATE, "the allocations of the build", mine, all));
     }
     int lst = ALGP_OK;                                          // what a launch of this rank failed with: its status in the next exchange
     if (M > 0) lst = vr_zero_picks_block(c, q);
@@ -213,15 +205,11 @@ int Impl<T>::vr_shard_build(algp_ctx* c, int64_t max_rows, int st) {
     char* own = (char*)c->rowx.p;
     const char* all = own + slice;
     const KmatSrc s = make_src(c);
-    std::vector<double> hdr;
-    int code = 0, bad = -1;
     for (int64_t t = 0; t < R; ++t) {
         if (lst == ALGP_OK)
             lst = vr_pack_rows_launch<T>(c, M, t * B, B, (const int*)c->ckind.p, (const int64_t*)c->Cidx.p, p(c->Vt), ldv, K, Npad + q,
                                          (int64_t*)(own + 32), (T*)(own + 32 + 8 * B));
-        local_err = lst != ALGP_OK ? c->err : std::string();
-        ALGP_TRY(comm_exchange(c, slice, lst, nullptr, hdr, code, bad));
-        if (code) return vr_agreed_fail(c, code, bad, local_err, "a round of the build");
+        ALGP_TRY(comm_exchange(c, VR_STATE, "a round of the build", slice, lst));
         lst = vr_overlap_launch(c, all + 32, (int64_t)slice, nr, c->comm_rank, B, c->n_pool, (int*)vr.Mark.p);
         if (lst == ALGP_OK && M > 0)
             lst = gemm_nt_launch_vrx<T>(c, ALGP_PROF_GEMM_OTHER, Mpad, B, K, p(c->Vt), ldv, (const T*)(all + 32 + 8 * B), K,
@@ -237,9 +225,7 @@ int Impl<T>::vr_shard_build(algp_ctx* c, int64_t max_rows, int st) {
     if (lst == ALGP_OK && hit)
         lst = fail(c, ALGP_ERR_STATE, "variance_reduction: a pool site of this rank's candidate set is listed by another rank too; the "
                                       "shards must be disjoint");
-    local_err = lst != ALGP_OK ? c->err : std::string();
-    ALGP_TRY(comm_exchange(c, 32, lst, nullptr, hdr, code, bad));
-    if (code) return vr_agreed_fail(c, code, bad, local_err, "the build");
+    ALGP_TRY(comm_exchange(c, VR_STATE, "the build", 32, lst));
     vr.npicks = q;
     vr.max_rows = max_rows;
     vr.over_ranks = true;
@@ -257,14 +243,8 @@ int Impl<T>::vr_shard_fold(algp_ctx* c, int st) {
     int64_t off_t, off_idx, off_val;
     size_t bytes;
     vr_fold_layout(c, cap, &off_t, &off_idx, &off_val, &bytes);
-    if (st == ALGP_OK && !(vr.valid && vr.over_ranks))
-        st = fail(c, ALGP_ERR_STATE, "greedy_sharded: the variance-reduction state over the ranks is not built");
-    if (st == ALGP_OK && q >= (int64_t)c->picks.size())
-        st = fail(c, ALGP_ERR_STATE, "greedy_sharded: this rank has no committed pick left to fold");
-    if (st == ALGP_OK && c->debug_fail_next_vr) {
-        st = fail(c, c->debug_fail_next_vr, "variance_reduction: failure injected by algp_debug_fail_at in the fold of a pick");
-        c->debug_fail_next_vr = 0;
-    }
+    st = comm_fold_status(c, st, vr.valid && vr.over_ranks, "the variance-reduction state over the ranks", q, "variance_reduction",
+                          &c->debug_fail_next_vr);
     if (c->rowx.cap < bytes * (size_t)(nr + 1) || (c->host_gather && c->rowx_host_cap < bytes * (size_t)(nr + 1))) {
         // the build and vr_shard_step reserve the staging before a word that carries their failure, so this is a rank that never
         // built: its refusal (set above) or the reservation's travels in the status word like any other -- unless no buffer is
@@ -285,11 +265,7 @@ int Impl<T>::vr_shard_fold(algp_ctx* c, int st) {
     if (st == ALGP_OK)
         st = vr_pairs_launch<T>(c, M, cap, (const int*)c->ckind.p, (const int64_t*)c->Cidx.p, M > 0 ? p(vr.R) + Mpad : (const T*)nullptr,
                                 (int64_t*)(own + off_idx), (T*)(own + off_val));
-    const std::string local_err = st != ALGP_OK ? c->err : std::string();
-    std::vector<double> hdr;
-    int code = 0, bad = -1;
-    ALGP_TRY(comm_exchange(c, bytes, st, nullptr, hdr, code, bad));
-    if (code) return vr_agreed_fail(c, code, bad, local_err, "the fold of a pick");
+    ALGP_TRY(comm_exchange(c, VR_STATE, "the fold of a pick", bytes, st));
     // 2. the sums in rank order, the kernel-GEMV over every rank's pairs for this rank's rows, the update of w
     const int rc = [&]() {
         ALGP_TRY(vr_fold_gathered_launch<T>(c, own + bytes, (int64_t)bytes, nr, col, cap, 32, off_t, off_idx, off_val, p(vr.Tv), p(vr.Nrm),
@@ -333,29 +309,22 @@ int Impl<T>::vr_shard_step(algp_ctx* c, int st, bool first_of_call) {
             vr_fold_layout(c, std::max<int64_t>(vr.max_rows, 1), &off_t, &off_idx, &off_val, &fbytes);
             st = comm_rows_reserve(c, fbytes);
         }
-        const std::string local_err = st != ALGP_OK ? c->err : std::string();
         const uint64_t h = c->has_tw ? (c->tw_hash & (((uint64_t)1 << 52) - 1)) | 1 : 0;    // exact as a double; 0: no weights
         const double mine[10] = {(double)st, (double)c->M, (double)q, have ? (double)vr.npicks : 0.0, (need ? 1.0 : 0.0) + (rank1 ? 0.0 : 2.0),
                                  (double)vr.xrows, (double)h, (double)c->Npad, (double)c->n_pool, 0.0};
         std::vector<double> all;
-        ALGP_TRY(comm_agree(c, mine, all, 10));
-        int code = 0, bad = -1;
-        bool any_need = false, same_picks = true, same_layout = true, same_tw = true, same_sizes = true;
+        ALGP_TRY(comm_agree_checked(c, VR_STATE, "the plan", mine, all, 10));
+        bool any_need = false, same_layout = true, same_tw = true, same_sizes = true;
         int64_t max_rows = 0;
-        vr.every_time = false;
+        vr.every_time = false;                                  // read only by the later picks of a call that got past this word
         for (int r = 0; r < nr; ++r) {
             const double* a = &all[(size_t)r * 10];
-            if (a[0] != 0.0 && bad < 0) { bad = r; code = a[0] == a[0] ? (int)a[0] : ALGP_ERR_HIP; }
-            any_need = any_need || ((int)a[4] & 1) != 0;
             vr.every_time = vr.every_time || ((int)a[4] & 2) != 0;
             same_layout = same_layout && a[5] == mine[5];
             same_tw = same_tw && a[6] == mine[6];
             same_sizes = same_sizes && a[7] == mine[7] && a[8] == mine[8];
             max_rows = std::max(max_rows, (int64_t)a[1]);
         }
-        for (int r = 0; r < nr; ++r)        // picks so far, and (without a build) picks folded so far: equal everywhere
-            same_picks = same_picks && all[(size_t)r * 10 + 2] == all[2] && (any_need || all[(size_t)r * 10 + 3] == all[3]);
-        if (code) return vr_agreed_fail(c, code, bad, local_err, "the plan");
         if (!same_layout) {
             vr.drop();
             std::string got;
@@ -372,19 +341,14 @@ int Impl<T>::vr_shard_step(algp_ctx* c, int st, bool first_of_call) {
             vr.drop();
             return fail(c, ALGP_ERR_STATE, "variance_reduction: the ranks hold different pools or train sets");
         }
-        if (!same_picks) {
-            vr.drop();
-            return fail(c, ALGP_ERR_STATE, "variance_reduction: the ranks hold different numbers of committed picks (a commit failed on "
-                                           "one of them); re-solve the candidates on every rank");
-        }
+        ALGP_TRY(comm_picks_agree(c, VR_STATE, "variance_reduction", all, 10, 4, &any_need));
         if (any_need) ALGP_TRY(vr_shard_build(c, max_rows));
         rounds = q - vr.npicks;                                // the same on every rank (agreed above)
     } else if (vr.every_time) {
         ALGP_TRY(vr_shard_build(c, vr.max_rows, st));
         rounds = 0;
     }
-    for (int64_t i = 0; i < rounds; ++i) ALGP_TRY(vr_shard_fold(c, i == 0 ? st : ALGP_OK));
-    return ALGP_OK;
+    return comm_catch_up(c, rounds, st, &Impl<T>::vr_shard_fold);
 }
 
 // the pool's target weights (host doubles, checked by the caller; null: detach) to the device in the context's dtype

@@ -7,10 +7,9 @@
 // statistic and row of V^T (comm_payload_bytes: 32 B + one row, ~80 KB at N = 10 000 fp64) to
 // ONE all-gather on the context's stream; a one-thread kernel takes the first maximum in rank order (= np.argmax over
 // the concatenated scores, agent.py:349, shards being contiguous in rank order) and the worst status, and the 40-byte
-// result is the pick's ONLY read-back.  The status word is what keeps the ranks together: a rank that cannot score
-// (no solve, an allocation that failed, ...) still takes part in the gather and reports its error code there, so every
-// rank returns that error instead of waiting for a peer that left.  Every rank then commits the same winner to its shard
-// (a rank that does not own it copies the owner's row out of the gather buffer: no second collective, no rebuild).
+// result is the pick's ONLY read-back.  The status word is what keeps the ranks together, here as in every other collective
+// of this file (the protocol: above comm_first_failure; the pick's own word: first_max_reduce).  Every rank then commits the
+// same winner to its shard (a rank that does not own it copies the owner's row out of the gather buffer: no rebuild).
 // Transports: RCCL (algp_comm_init; opened with dlopen, so the library loads and every single-GPU entry point works
 // without it), a caller-supplied host all-gather (algp_comm_init_host: MPI, gloo, ... -- also what lets two ranks share
 // ONE card in the tests, which RCCL refuses), or none (one rank: the same kernels without the gather).
@@ -36,8 +35,8 @@ struct RcclApi {
 };
 
 // ONE copy of RCCL per process: a second one (PyTorch ships its own librccl.so next to the ROCm one) corrupts the heap
-// at exit.  So: the copy that is already mapped (a process that imported torch first), else $ALGP_RCCL_PATH, else the
-// system's.  (A process that opens the system's copy here and imports torch afterwards ends up with two.)
+// at exit.  So: $ALGP_RCCL_PATH alone when it is set, else the copy that is already mapped (a process that imported torch
+// first), else the system's.  (A process that opens the system's copy here and imports torch afterwards ends up with two.)
 static int find_loaded_rccl(struct dl_phdr_info* info, size_t, void* data) {
     if (info->dlpi_name && strstr(info->dlpi_name, "librccl")) {
         *(std::string*)data = info->dlpi_name;
@@ -255,6 +254,30 @@ void comm_destroy(algp_ctx* c) {
     c->comm_rank = 0;
 }
 
+// The one all-gather of this file: `bytes` per rank, in rank order, over whichever transport is attached.  RCCL: dev_send ->
+// dev_recv, stream-ordered on c->stream.  The caller's host transport: host_send -> host_recv, blocking; a dev_send is staged
+// down to host_send first (one copy, one synchronisation).  who: the caller's prefix in the messages.  A failure here is a
+// failure of the transport itself: no status word can report it, the caller returns it at once.
+static int all_gather(algp_ctx* c, const char* who, size_t bytes, const void* dev_send, void* dev_recv, void* host_send, void* host_recv) {
+    if (c->comm) {
+        RcclApi* api = rccl_api(nullptr);
+        if (!api) return fail(c, ALGP_ERR_STATE, std::string(who) + ": the RCCL communicator has no library behind it");
+        const ncclResult_t r = api->AllGather(dev_send, dev_recv, bytes, ncclChar, (ncclComm_t)c->comm, c->stream);
+        if (r != ncclSuccess)
+            return fail(c, ALGP_ERR_HIP, std::string("ncclAllGather: ") + (api->GetErrorString ? api->GetErrorString(r) : "failed"));
+        return ALGP_OK;
+    }
+    if (!c->host_gather) return fail(c, ALGP_ERR_STATE, std::string(who) + ": no communicator");
+    if (dev_send) {
+        ALGP_HIP(hipMemcpyAsync(host_send, dev_send, bytes, hipMemcpyDeviceToHost, c->stream));
+        ALGP_HIP(hipStreamSynchronize(c->stream));
+        c->n_syncs++;
+    }
+    const int rc = c->host_gather(c->host_gather_user, host_send, host_recv, (int64_t)bytes);
+    if (rc != 0) return fail(c, ALGP_ERR_HIP, std::string(who) + ": the caller's all-gather returned " + std::to_string(rc));
+    return ALGP_OK;
+}
+
 // The exchange of one pick.  (val_dev, pos_dev): the local argmax as the kernels before left it on the device (null: this
 // rank has no candidate to offer); status: 0 or the ALGP_ERR_* code this rank failed with while preparing it.  Everything
 // is stream-ordered; the single synchronisation (RCCL transport: the read-back of the record; host transport: the payload's
@@ -303,20 +326,12 @@ static int pick_exchange(algp_ctx* c, const double* val_dev, const int64_t* pos_
     }
     const char* gathered = all;
     if (c->comm) {
-        RcclApi* api = rccl_api(nullptr);
-        if (!api) return fail(c, ALGP_ERR_STATE, "greedy_sharded: the RCCL communicator has no library behind it");
-        const ncclResult_t r = api->AllGather(own, all, pb, ncclChar, (ncclComm_t)c->comm, c->stream);
-        if (r != ncclSuccess)
-            return fail(c, ALGP_ERR_HIP, std::string("ncclAllGather: ") + (api->GetErrorString ? api->GetErrorString(r) : "failed"));
+        ALGP_TRY(all_gather(c, "greedy_sharded", pb, own, all, nullptr, nullptr));
     } else if (c->host_gather) {
         // the caller's transport works on host memory: the payload goes down, the gathered payloads come back up
         char* hs = (char*)c->comm_host;
         char* hr = hs + pb;
-        ALGP_HIP(hipMemcpyAsync(hs, own, pb, hipMemcpyDeviceToHost, c->stream));
-        ALGP_HIP(hipStreamSynchronize(c->stream));
-        c->n_syncs++;
-        const int rc = c->host_gather(c->host_gather_user, hs, hr, (int64_t)pb);
-        if (rc != 0) return fail(c, ALGP_ERR_HIP, "greedy_sharded: the caller's all-gather returned " + std::to_string(rc));
+        ALGP_TRY(all_gather(c, "greedy_sharded", pb, own, nullptr, hs, hr));
         // the payloads are in host memory: the reduction of first_max_kernel runs here, and only the winner's payload (its
         // statistic and its row of V^T, what commit_enqueue reads) goes back up -- one row instead of one per rank, no
         // read-back of the record, one synchronisation less per pick
@@ -358,21 +373,14 @@ int comm_agree(algp_ctx* c, const double* mine, std::vector<double>& all, int nd
     const int nr = c->comm_nranks;
     const size_t wb = sizeof(double) * (size_t)nd;               // 32 bytes, or a wider word (the variance-reduction criterion's: 80)
     all.assign((size_t)nr * nd, 0.0);
-    if (c->host_gather) {
+    if (!c->comm) {                                              // the caller's transport takes host memory as it is
         std::vector<double> send(mine, mine + nd);
-        const int rc = c->host_gather(c->host_gather_user, send.data(), all.data(), (int64_t)wb);
-        if (rc != 0) return fail(c, ALGP_ERR_HIP, "factorize_update: the caller's all-gather returned " + std::to_string(rc));
-        return ALGP_OK;
+        return all_gather(c, "factorize_update", wb, nullptr, nullptr, send.data(), all.data());
     }
-    if (!c->comm) return fail(c, ALGP_ERR_STATE, "factorize_update: no communicator");
-    RcclApi* api = rccl_api(nullptr);
-    if (!api) return fail(c, ALGP_ERR_STATE, "factorize_update: the RCCL communicator has no library behind it");
     ALGP_TRY(ensure(c, c->commbuf, std::max<size_t>(c->commbuf.cap, wb * (size_t)(nr + 1))));
     char* own = (char*)c->commbuf.p;
     ALGP_HIP(hipMemcpyAsync(own, mine, wb, hipMemcpyHostToDevice, c->stream));
-    const ncclResult_t r = api->AllGather(own, own + wb, wb, ncclChar, (ncclComm_t)c->comm, c->stream);
-    if (r != ncclSuccess)
-        return fail(c, ALGP_ERR_HIP, std::string("ncclAllGather: ") + (api->GetErrorString ? api->GetErrorString(r) : "failed"));
+    ALGP_TRY(all_gather(c, "factorize_update", wb, own, own + wb, nullptr, nullptr));
     ALGP_HIP(hipMemcpyAsync(all.data(), own + wb, wb * (size_t)nr, hipMemcpyDeviceToHost, c->stream));
     ALGP_HIP(hipStreamSynchronize(c->stream));
     c->n_syncs++;
@@ -403,22 +411,10 @@ int comm_rows_gather(algp_ctx* c, size_t bytes_per_rank, const size_t* used_byte
     const int nr = c->comm_nranks;
     char* own = (char*)c->rowx.p;
     char* all = own + bytes_per_rank;
-    if (c->comm) {
-        RcclApi* api = rccl_api(nullptr);
-        if (!api) return fail(c, ALGP_ERR_STATE, "factorize_update: the RCCL communicator has no library behind it");
-        const ncclResult_t r = api->AllGather(own, all, bytes_per_rank, ncclChar, (ncclComm_t)c->comm, c->stream);
-        if (r != ncclSuccess)
-            return fail(c, ALGP_ERR_HIP, std::string("ncclAllGather: ") + (api->GetErrorString ? api->GetErrorString(r) : "failed"));
-        return ALGP_OK;
-    }
-    if (!c->host_gather) return fail(c, ALGP_ERR_STATE, "factorize_update: no communicator");
-    char* hs = (char*)c->rowx_host;
-    char* hr = hs + bytes_per_rank;
-    ALGP_HIP(hipMemcpyAsync(hs, own, bytes_per_rank, hipMemcpyDeviceToHost, c->stream));
-    ALGP_HIP(hipStreamSynchronize(c->stream));
-    c->n_syncs++;
-    const int rc = c->host_gather(c->host_gather_user, hs, hr, (int64_t)bytes_per_rank);
-    if (rc != 0) return fail(c, ALGP_ERR_HIP, "factorize_update: the caller's all-gather returned " + std::to_string(rc));
+    char* hs = (char*)c->rowx_host;                              // null under RCCL, which gathers on the device and is done
+    char* hr = hs ? hs + bytes_per_rank : nullptr;
+    ALGP_TRY(all_gather(c, "factorize_update", bytes_per_rank, own, all, hs, hr));
+    if (c->comm) return ALGP_OK;
     if (!used_bytes) {
         ALGP_HIP(hipMemcpyAsync(all, hr, bytes_per_rank * (size_t)nr, hipMemcpyHostToDevice, c->stream));
         return ALGP_OK;
@@ -432,36 +428,92 @@ int comm_rows_gather(algp_ctx* c, size_t bytes_per_rank, const size_t* used_byte
     return ALGP_OK;
 }
 
-// ---- the gathers of a criterion's state dealt over the ranks (api_mi.hip, api_vr.hip) -------------------------------------
-// Every such gather carries each rank's status word in a 32-byte header in front of its payload: a rank that failed still
-// takes part, and every rank returns the first failing rank's code from the same call.
-int comm_exchange(algp_ctx* c, size_t bytes, int st, const double* v3, std::vector<double>& hdr, int& code, int& bad) {
+// ---- the status-word protocol of a criterion's state kept over the ranks (api_mi.hip, api_vr.hip) -------------------------
+// Described here, once.  Every collective of such a state is an all-gather whose first double per rank is that rank's status:
+// 0, or the ALGP_ERR_* code it failed with while preparing its share (memory, a factor that is not positive definite, a HIP
+// error, an injected failure).  Nothing rank-local returns before a collective the peers enter: the failing rank takes part
+// and says so there.  Every rank then finds the same first failing rank and returns its code from the same call -- that rank
+// with its own message, the others naming it -- and drops the state, which the next call rebuilds.  Only a failure of the
+// transport itself returns at once, from whichever rank meets it and with the state kept: no exchange is left to report it.
+// The word travels in comm_agree_checked (a few doubles of host memory: what a step agrees on before any payload travels) and
+// in comm_exchange (a 32-byte header in front of each rank's payload at rowx).  The step that brings a state up to the
+// committed picks shares the word's view of the picks (comm_picks_agree), its folds' refusals (comm_fold_status) and their
+// loop (comm_catch_up); the word's other fields, the layout checks and the build are each criterion's own.
+
+// the first rank whose status (the first of its `stride` doubles) is non-zero, and its code; -1, 0: none
+int comm_first_failure(const double* words, int stride, int nranks, int* code) {
+    *code = 0;
+    for (int r = 0; r < nranks; ++r) {
+        const double s = words[(size_t)r * stride];
+        if (s == 0.0) continue;
+        *code = s == s ? (int)s : ALGP_ERR_HIP;                  // a NaN status counts as a failure too
+        return r;
+    }
+    return -1;
+}
+// local_err: this rank's message, captured before the collective overwrote it
+static int agreed_fail(algp_ctx* c, const CommState& s, const char* what, int code, int bad, const std::string& local_err) {
+    s.drop(c);
+    if (bad == c->comm_rank && !local_err.empty()) return fail(c, code, local_err);
+    return fail(c, code, "greedy_sharded: rank " + std::to_string(bad) + " failed with error " + std::to_string(code) + " in " + what +
+                             " of " + s.name + "; every rank returns it");
+}
+// comm_agree of a word whose first double is this rank's status
+int comm_agree_checked(algp_ctx* c, const CommState& s, const char* what, const double* mine, std::vector<double>& all, int nd) {
+    const std::string local_err = mine[0] != 0.0 ? c->err : std::string();
+    ALGP_TRY(comm_agree(c, mine, all, nd));
+    int code;
+    const int bad = comm_first_failure(all.data(), nd, c->comm_nranks, &code);
+    return bad < 0 ? ALGP_OK : agreed_fail(c, s, what, code, bad, local_err);
+}
+// this rank's header (status st, three values v3 or zeros) in front of its payload at rowx, comm_rows_gather of `bytes` per
+// rank, every header back to the host (hdr, where the caller reads the values: 4 doubles per rank)
+int comm_exchange(algp_ctx* c, const CommState& s, const char* what, size_t bytes, int st, const double* v3, std::vector<double>* hdr) {
+    const std::string local_err = st != ALGP_OK ? c->err : std::string();
     const int nr = c->comm_nranks;
     c->xhdr[0] = (double)st;
     for (int i = 0; i < 3; ++i) c->xhdr[1 + i] = v3 ? v3[i] : 0.0;
     char* own = (char*)c->rowx.p;
     ALGP_HIP(hipMemcpyAsync(own, c->xhdr, 32, hipMemcpyHostToDevice, c->stream));
     ALGP_TRY(comm_rows_gather(c, bytes));
-    hdr.assign((size_t)nr * 4, 0.0);
-    ALGP_HIP(hipMemcpy2DAsync(hdr.data(), 32, own + bytes, bytes, 32, (size_t)nr, hipMemcpyDeviceToHost, c->stream));
+    std::vector<double> unread;
+    std::vector<double>& h = hdr ? *hdr : unread;
+    h.assign((size_t)nr * 4, 0.0);
+    ALGP_HIP(hipMemcpy2DAsync(h.data(), 32, own + bytes, bytes, 32, (size_t)nr, hipMemcpyDeviceToHost, c->stream));
     ALGP_HIP(hipStreamSynchronize(c->stream));
     c->n_syncs++;
-    code = 0;
-    bad = -1;
-    for (int r = 0; r < nr && bad < 0; ++r)
-        if (hdr[(size_t)r * 4] != 0.0) {
-            bad = r;
-            code = hdr[(size_t)r * 4] == hdr[(size_t)r * 4] ? (int)hdr[(size_t)r * 4] : ALGP_ERR_HIP;
-        }
-    return ALGP_OK;
+    int code;
+    const int bad = comm_first_failure(h.data(), 4, nr, &code);
+    return bad < 0 ? ALGP_OK : agreed_fail(c, s, what, code, bad, local_err);
 }
-
-// an agreed failure: the failing rank keeps its own message, the others name it; the caller drops the state, which the next
-// call rebuilds
-int comm_agreed_fail(algp_ctx* c, int code, int bad, const std::string& local_err, const char* what, const char* state) {
-    if (bad == c->comm_rank && !local_err.empty()) return fail(c, code, local_err);
-    return fail(c, code, "greedy_sharded: rank " + std::to_string(bad) + " failed with error " + std::to_string(code) + " in " + what +
-                             " of " + state + "; every rank returns it");
+// An agreement word's doubles 2 and 3 are the picks committed and folded, bit 0 of double `need_at` that the rank needs a build:
+// *any_need, and that the picks committed -- without a build, the picks folded too -- are equal everywhere.  who: the prefix.
+int comm_picks_agree(algp_ctx* c, const CommState& s, const char* who, const std::vector<double>& all, int nd, int need_at, bool* any_need) {
+    bool need = false, same = true;
+    for (int r = 0; r < c->comm_nranks; ++r) need = need || ((int64_t)all[(size_t)r * nd + need_at] & 1) != 0;
+    for (int r = 0; r < c->comm_nranks; ++r) same = same && all[(size_t)r * nd + 2] == all[2] && (need || all[(size_t)r * nd + 3] == all[3]);
+    *any_need = need;
+    if (same) return ALGP_OK;
+    s.drop(c);
+    return fail(c, ALGP_ERR_STATE, std::string(who) + ": the ranks hold different numbers of committed picks (a commit failed on "
+                                   "one of them); re-solve the candidates on every rank");
+}
+// this rank's status for the fold of pick q: st, else what every fold refuses -- `state` not built, no committed pick left, the
+// failure injected through *inject (algp_debug_fail_at), under the criterion's prefix `crit`
+int comm_fold_status(algp_ctx* c, int st, bool built, const char* state, int64_t q, const char* crit, int* inject) {
+    if (st == ALGP_OK && !built) st = fail(c, ALGP_ERR_STATE, std::string("greedy_sharded: ") + state + " is not built");
+    if (st == ALGP_OK && q >= (int64_t)c->picks.size())
+        st = fail(c, ALGP_ERR_STATE, "greedy_sharded: this rank has no committed pick left to fold");
+    if (st == ALGP_OK && *inject) {
+        st = fail(c, *inject, std::string(crit) + ": failure injected by algp_debug_fail_at in the fold of a pick");
+        *inject = 0;
+    }
+    return st;
+}
+// the folds that catch up with the committed picks; the status so far travels in the first
+int comm_catch_up(algp_ctx* c, int64_t rounds, int st, int (*fold)(algp_ctx*, int)) {
+    for (int64_t i = 0; i < rounds; ++i) ALGP_TRY(fold(c, i == 0 ? st : ALGP_OK));
+    return ALGP_OK;
 }
 
 // test hook: first_max_kernel over a caller-made buffer of `nranks` triples (fabricated 8-rank cases on one GPU)

@@ -669,12 +669,19 @@ int comm_reserve(algp_ctx* c);
 int comm_agree(algp_ctx* c, const double* mine, std::vector<double>& all, int nd = 4);
 int comm_rows_reserve(algp_ctx* c, size_t bytes_per_rank);
 int comm_rows_gather(algp_ctx* c, size_t bytes_per_rank, const size_t* used_bytes = nullptr);
-// The gather of a sharded criterion's state (MI: api_mi.hip; variance reduction: api_vr.hip): this rank's 32-byte header
-// (status st, three values v3 or zeros) in front of its payload at rowx, comm_rows_gather of `bytes` per rank, every header
-// back to the host (hdr: 4 doubles per rank); code / bad: the first non-zero status in rank order and its rank (0 / -1: none).
-// comm_agreed_fail: the failing rank keeps its own message, the others name it (what: the step, state: whose state it is).
-int comm_exchange(algp_ctx* c, size_t bytes, int st, const double* v3, std::vector<double>& hdr, int& code, int& bad);
-int comm_agreed_fail(algp_ctx* c, int code, int bad, const std::string& local_err, const char* what, const char* state);
+// The status-word protocol of a criterion's state kept over the ranks (api_mi.hip, api_vr.hip): described with these functions
+// in comm.hip.  CommState: whose state a collective belongs to (an agreed failure names it and drops it); what: the step's name.
+struct CommState {
+    const char* name;
+    void (*drop)(algp_ctx*);
+};
+int comm_first_failure(const double* words, int stride, int nranks, int* code);
+int comm_agree_checked(algp_ctx* c, const CommState& s, const char* what, const double* mine, std::vector<double>& all, int nd = 4);
+int comm_exchange(algp_ctx* c, const CommState& s, const char* what, size_t bytes, int st, const double* v3 = nullptr,
+                  std::vector<double>* hdr = nullptr);
+int comm_picks_agree(algp_ctx* c, const CommState& s, const char* who, const std::vector<double>& all, int nd, int need_at, bool* any_need);
+int comm_fold_status(algp_ctx* c, int st, bool built, const char* state, int64_t q, const char* crit, int* inject);
+int comm_catch_up(algp_ctx* c, int64_t rounds, int st, int (*fold)(algp_ctx*, int));
 size_t comm_payload_bytes(const algp_ctx* c);
 int comm_debug_first_max(algp_ctx* c, const double* triples, int nranks, double* out5);
 void dag_release(algp_ctx* c);   // frees the cached task lists of the dependency-driven Cholesky
