@@ -34,7 +34,8 @@ int Impl<T>::set_candidates(algp_ctx* c, const int64_t* idx, int64_t M, int prio
 // The candidate solve's route (SolvePlan), decided once per call.  The only reader of the solve's switches, per plan (tests
 // flip them): $ALGP_TAIL_COLS=0 (the 128-column blocks, the full last tile), $ALGP_SOLVE_DAG=0 (the sweep for mid-sized
 // solves), $ALGP_ROW_STATS=0 (the sweep without its row statistics), $ALGP_FOLD=0 (fit_and_solve as its two phases),
-// $ALGP_RHS_FUSED=0 (the scheduled sweep with B^T written to V^T first).
+// $ALGP_RHS_FUSED=0 (the scheduled sweep with B^T written to V^T first), $ALGP_SPLIT_PANELS (fit_and_solve's sweep with its last
+// tile rows in the factorisation's launch: 0 = never, n = n tile rows).
 template <typename T>
 void Impl<T>::plan_route(algp_ctx* c, int incremental, bool allow_fold, typename Impl<T>::SolvePlan& pl) {
     const bool tail_on = env_switch("ALGP_TAIL_COLS", true), solve_dag_on = env_switch("ALGP_SOLVE_DAG", true),
@@ -117,33 +118,57 @@ void Impl<T>::plan_route(algp_ctx* c, int incremental, bool allow_fold, typename
     if (fold_on && M > 0 && panel_fits(Npad, Mpad)) pl.route = SolveRoute::Folded;
     else if (solve_dag_on && keep == 0 && Mpad / NB > 32 && panel_fits(Npad, Mpad) && c->cur == c->stream) pl.route = SolveRoute::TaskList;
     else pl.route = SolveRoute::Sweep;
+    // The split (fit_and_solve beyond the folded route's 400 tile rows): the scheduled sweep deals a product's tiles to 2 x CUs
+    // slots, four column tiles per row panel, so slots / 4 row panels make a whole round and the p = (Mpad / 128) mod (slots / 4)
+    // leftover panels are cut along k and summed by a finish launch, in every update product.  Those p tile rows -- the last
+    // ones, the tile with the padding row that carries y - ybar among them -- ride the factorisation's launch as its panel
+    // instead (the folded route's mechanism), whose last milliseconds leave most of the machine idle; the sweep then runs in
+    // whole rounds and the forward substitution for z falls away.  Only where the remaining rows run as scheduled launches.
+    // A set that still fits the folded route (up to 400 tile rows) stays there unless the switch forces the split: a rank's share
+    // on 2 GPUs, 391 = 384 + 7 tile rows, was measured 86.6 ms folded whole against 79.7 ms split (profiles/split_solve_ab.txt), but
+    // tests/test_full_size.py pins that size to the one launch.
+    // $ALGP_SPLIT_PANELS: unset = this rule for up to SPLIT_P_MAX panels, 0 = off, n = n tile rows wherever the conditions hold.
+    int64_t split = 0;
+    if (fold_on && pl.route != SolveRoute::TaskList && keep == 0 && M > 0 && M < Mpad && c->cur == c->stream && c->cu_count >= 2) {
+        const int forced = env_int("ALGP_SPLIT_PANELS", -1);
+        const int64_t per_round = 2 * c->cu_count / 4, left = (Mpad / NB) % per_round;
+        if (forced >= 0) split = forced;
+        else if (pl.route == SolveRoute::Sweep && left <= SPLIT_P_MAX) split = left;
+        if (!(split >= 1 && split < Mpad / NB && panel_fits(Npad, NB * split) && trsm_sched_wanted(c, Mpad - NB * split, Npad, keep)))
+            split = 0;
+        if (split) pl.route = SolveRoute::Sweep;
+    }
     // A train set that ends a few columns into its last 128-column tile (N = 10 000: 16 of 128) pays a full tile's price for
     // them: 79 K-steps of the task list per tile row, 2 M 128 N flop of the sweep (2.1 % of config 4's solve).  Up to 64 such
     // columns are instead what an append would add to a factor of N - r rows: the route solves the full tiles, the tail
-    // kernel (tail.hip, HBM-bound: one pass over V^T) the rest.  On the task-list and folded routes the tile row that
-    // carries y - ybar (a last tile with padding rows, fit_and_solve) keeps every column, so both do the same arithmetic.
+    // kernel (tail.hip, HBM-bound: one pass over V^T) the rest.  On the task-list and folded routes, and in the split's folded
+    // tile rows, the tile row that carries y - ybar (a last tile with padding rows, fit_and_solve) keeps every column, so all do
+    // the same arithmetic.
     const int64_t r = N % NB, N1 = Npad - NB;
     const bool narrow = r > 0 && r <= 64 && N1 >= 2048 && Mpad >= 2048 && tail_on &&
                         (pl.route != SolveRoute::Sweep || (keep == 0 && c->cur == c->stream && Mpad / NB > SWEEP_PUSH_TILES));
     if (narrow) {
         pl.narrow_r = (int)r;
-        pl.short_rows = pl.route == SolveRoute::Sweep ? Mpad : M < Mpad ? Mpad - NB : Mpad;
+        pl.short_rows = pl.route == SolveRoute::Sweep && !split ? Mpad : M < Mpad ? Mpad - NB : Mpad;
     }
+    pl.sweep_end = pl.narrow_r ? Npad - NB : Npad;
+    pl.split_tiles = (int)split;
+    pl.sweep_rows = Mpad - NB * split;
     pl.row_stats = pl.route == SolveRoute::Sweep && stats_on && keep == 0 && !pl.carried_sums;
     // Fused right-hand sides: where the sweep will run as scheduled launches with 512-block inverses (trsm_sched_wanted:
     // trsm_blocked's own predicate; a buffer it then cannot get sends it back to the materialised form), B^T is not written and
     // read back -- the update products generate their C tiles.  Two scaled coordinates per site only (rhs_gen_supported): wider
     // coordinates and an explicit pool covariance keep the kernel-matrix launch.
-    pl.sweep_end = pl.narrow_r ? Npad - NB : Npad;
     pl.rhs_fused = pl.route == SolveRoute::Sweep && keep == 0 && M > 0 && env_switch("ALGP_RHS_FUSED", true) &&
-                   trsm_sched_wanted(c, Mpad, pl.sweep_end, keep) && rhs_gen_supported(c->hyp.DP, c->pool_is_cov);
+                   trsm_sched_wanted(c, pl.sweep_rows, pl.sweep_end, keep) && rhs_gen_supported(c->hyp.DP, c->pool_is_cov);
 }
 
 template <typename T>
 int Impl<T>::rhs_window(algp_ctx* c, int64_t c0, int64_t w, void* out, int64_t ldo) {
     const int64_t live = std::max<int64_t>(0, std::min<int64_t>(c->N - c0, w));
+    const int64_t rows = c->rhs_rows;            // the sweep's rows: all of them, or those in front of the split's folded tile rows
     KmatSrc s = make_src(c);
-    return kmat_launch<T>(c, s, (const int64_t*)c->Cidx.p, c->M, c->Mpad, (const int64_t*)c->Aidx.p + c0, live, w, nullptr, 0,
+    return kmat_launch<T>(c, s, (const int64_t*)c->Cidx.p, std::min<int64_t>(c->M, rows), rows, (const int64_t*)c->Aidx.p + c0, live, w, nullptr, 0,
                           c->prior_noise ? (const int*)c->ckind.p : nullptr, 0, (T*)out, ldo, 0, c0);
 }
 
@@ -198,10 +223,12 @@ int Impl<T>::solve_prepare(algp_ctx* c, int incremental, typename Impl<T>::Solve
         // B^T stays a generator: the coordinates of its rows and columns gathered once, and only the columns that no launch of
         // the sweep writes -- a narrow last tile's (the tail kernel's) and the padding up to ldv -- go to V^T now
         const int DP = c->hyp.DP;
-        ALGP_TRY(ensure(c, c->rhs_rx, sizeof(T) * (size_t)Mpad * DP));
+        const int64_t Ms = pl.sweep_rows;                             // the generator serves the sweep's rows
+        c->rhs_rows = Ms;
+        ALGP_TRY(ensure(c, c->rhs_rx, sizeof(T) * (size_t)Ms * DP));
         ALGP_TRY(ensure(c, c->rhs_cx, sizeof(T) * (size_t)Npad * DP));
-        ALGP_TRY(ensure(c, c->rhs_rk, sizeof(int) * (size_t)Mpad));
-        ALGP_TRY(rhs_gather_launch<T>(c, (const T*)c->Xs.p, DP, (const int64_t*)c->Cidx.p, M, Mpad,
+        ALGP_TRY(ensure(c, c->rhs_rk, sizeof(int) * (size_t)Ms));
+        ALGP_TRY(rhs_gather_launch<T>(c, (const T*)c->Xs.p, DP, (const int64_t*)c->Cidx.p, std::min<int64_t>(M, Ms), Ms,
                                       c->prior_noise ? (const int*)c->ckind.p : nullptr, (const int64_t*)c->Aidx.p, N, Npad,
                                       p(c->rhs_rx), p(c->rhs_cx), (int*)c->rhs_rk.p));
         pl.gen.rx = c->rhs_rx.p;
@@ -212,7 +239,12 @@ int Impl<T>::solve_prepare(algp_ctx* c, int incremental, typename Impl<T>::Solve
         pl.gen.kernel = s.kernel;
         pl.gen.outputscale = s.outputscale;
         pl.gen.window = &Impl<T>::rhs_window;
-        return rhs_window(c, pl.sweep_end, ldv - pl.sweep_end, p(c->Vt) + pl.sweep_end, ldc);
+        ALGP_TRY(rhs_window(c, pl.sweep_end, ldv - pl.sweep_end, p(c->Vt) + pl.sweep_end, ldc));
+        // the split's folded tile rows are read by the factorisation's launch: their B^T, every column, is written
+        if (pl.split_tiles)
+            return kmat_launch<T>(c, s, (const int64_t*)c->Cidx.p + Ms, M - Ms, Mpad - Ms, (const int64_t*)c->Aidx.p, N, ldv, nullptr, 0,
+                                  c->prior_noise ? (const int*)c->ckind.p + Ms : nullptr, 0, p(c->Vt) + Ms * ldc, ldc, 0, 0);
+        return ALGP_OK;
     }
     // B^T: row j = C[cand_j, A] (ordinary) or e_pos (train-site candidate); zero padding.
     // Only columns >= keep are (re)generated and solved.
@@ -226,8 +258,9 @@ int Impl<T>::solve_prepare(algp_ctx* c, int incremental, typename Impl<T>::Solve
 template <typename T>
 int Impl<T>::solve_run(algp_ctx* c, typename Impl<T>::SolvePlan& pl) {
     const int64_t Npad = c->Npad, Mpad = c->Mpad, ldc = c->ldv, keep = pl.keep;
-    prof_span_begin(c, ALGP_PROF_TRSM, (double)(Npad - keep) * (double)(Npad + keep) * (double)Mpad,
-                    sizeof(T) * (double)Mpad * (double)Npad);
+    const int64_t booked = pl.route == SolveRoute::Sweep ? pl.sweep_rows : Mpad;      // the split's folded rows are booked by the task list
+    prof_span_begin(c, ALGP_PROF_TRSM, (double)(Npad - keep) * (double)(Npad + keep) * (double)booked,
+                    sizeof(T) * (double)booked * (double)Npad);
     int trc = ALGP_OK;
     if (pl.route == SolveRoute::Segments && pl.seg_window) {
         // the inverse of a 128 x 128 window of L that contains the range (inv(D)[S, S] = inv(D[S, S]) for any diagonal range S of
@@ -248,11 +281,13 @@ int Impl<T>::solve_run(algp_ctx* c, typename Impl<T>::SolvePlan& pl) {
     } else if (pl.route == SolveRoute::Sweep) {
         // a from-scratch solve of more than SWEEP_PUSH_TILES tile rows: its launches leave the rows' sums of v^2 and v z per
         // column tile (utils.py:301-304 needs nothing else of V^T), the 8 GB pass over V^T at config 4 falls away
+        // (the split: the rows in front of the folded tile rows, which the factorisation's launch has solved already)
+        const int64_t rows = pl.sweep_rows;
         T* stat = nullptr;
-        if (pl.row_stats && ensure(c, c->rowstat, sizeof(T) * 2 * (size_t)(Npad / NB) * (size_t)Mpad) == ALGP_OK)
+        if (pl.row_stats && ensure(c, c->rowstat, sizeof(T) * 2 * (size_t)(Npad / NB) * (size_t)rows) == ALGP_OK)
             stat = p(c->rowstat);
-        trc = trsm_blocked<T>(c, ALGP_PROF_GEMM_TRSM, p(c->Vt), Mpad, ldc, p(c->L), pl.sweep_end, c->Lld, p(c->invD),
-                              keep, p(c->z), stat, Mpad, &pl.rowstat_done, pl.rhs_fused ? &pl.gen : nullptr);
+        trc = trsm_blocked<T>(c, ALGP_PROF_GEMM_TRSM, p(c->Vt), rows, ldc, p(c->L), pl.sweep_end, c->Lld, p(c->invD),
+                              keep, p(c->z), stat, rows, &pl.rowstat_done, pl.rhs_fused ? &pl.gen : nullptr);
     } else {
         trc = fail(c, ALGP_ERR_STATE, "internal: the folded route is solved by the factorisation's launch (fit_and_solve)");
     }
@@ -267,13 +302,13 @@ int Impl<T>::solve_run(algp_ctx* c, typename Impl<T>::SolvePlan& pl) {
 template <typename T>
 int Impl<T>::solve_narrow_tile(algp_ctx* c, const typename Impl<T>::SolvePlan& pl) {
     if (pl.narrow_r == 0) return ALGP_OK;
-    const int64_t Mpad = c->Mpad, ldc = c->ldv, N1 = c->Npad - NB;
+    const int64_t rows = pl.sweep_rows, ldc = c->ldv, N1 = c->Npad - NB;   // rows: those whose statistics the sweep left
     ALGP_TRY(tail_cols_launch<T>(c, ALGP_PROF_TAIL_COLS, p(c->Vt), pl.short_rows, ldc, p(c->L), c->Lld, c->Npad,
                                  p(c->invD) + (N1 / NB) * NB * NB, N1, (int)round_up(pl.narrow_r, 16)));
     if (!pl.rowstat_done) return ALGP_OK;
     T* stat = p(c->rowstat);
-    return rows_reduce_launch<T>(c, p(c->Vt) + N1, Mpad, ldc, NB, p(c->z) + N1, stat + 2 * (N1 / NB) * Mpad,
-                                 stat + (2 * (N1 / NB) + 1) * Mpad);
+    return rows_reduce_launch<T>(c, p(c->Vt) + N1, rows, ldc, NB, p(c->z) + N1, stat + 2 * (N1 / NB) * rows,
+                                 stat + (2 * (N1 / NB) + 1) * rows);
 }
 
 
@@ -311,8 +346,14 @@ int Impl<T>::solve_finish(algp_ctx* c, int incremental, const unsigned char* ali
         c->uw_stable = N;
     } else {
         c->acc_cols = 0;
-        if (pl.rowstat_done) ALGP_TRY(rowstat_combine_launch<T>(c, p(c->rowstat), Mpad, (int)(Npad / NB), M, ss, dot));
-        else ALGP_TRY(rows_reduce_launch<T>(c, p(c->Vt), M, ldc, Npad, p(c->z), ss, dot));
+        if (pl.rowstat_done) {
+            // the sweep's rows from the sums its launches left; the split's folded rows, which no such launch wrote, in one pass
+            const int64_t Ms = pl.sweep_rows;
+            ALGP_TRY(rowstat_combine_launch<T>(c, p(c->rowstat), Ms, (int)(Npad / NB), std::min<int64_t>(M, Ms), ss, dot));
+            if (M > Ms) ALGP_TRY(rows_reduce_launch<T>(c, p(c->Vt) + Ms * ldc, M - Ms, ldc, Npad, p(c->z), ss + Ms, dot + Ms));
+        } else {
+            ALGP_TRY(rows_reduce_launch<T>(c, p(c->Vt), M, ldc, Npad, p(c->z), ss, dot));
+        }
     }
     const T prior = (T)(c->hyp.outputscale + (c->prior_noise ? c->hyp.noise : 0.0));
     ALGP_TRY(cand_finalize_launch<T>(c, M, (const int*)c->ckind.p, (const int64_t*)c->Cidx.p,
@@ -355,12 +396,29 @@ int Impl<T>::solve_candidates(algp_ctx* c, int incremental, const unsigned char*
 // list (TRSM / UPD tasks without a diagonal), so V^T = B^T L^-T comes out of the launch that factors S -- the candidates'
 // tile products fill the machine while the diagonal chain alone would leave it idle, and the 140 short launches of a
 // separate mid-sized solve disappear.  Larger candidate sets keep the two phases: the factorisation, then the
-// three-stream sweep of potrf.hip, which wins from ~55 000 rows on.  (Overlapping the two as separate launch sequences on
-// streams was measured in round 1 -- 207 vs 193 ms/step -- and removed.)
+// sweep of potrf.hip, which wins from ~55 000 rows on.  Where that sweep would be left with a few row panels over its whole
+// rounds, those last tile rows and z still go into the factorisation's launch and only the rest is swept (the split,
+// plan_route).  (Overlapping the two as separate launch
+// sequences on streams was measured in round 1 -- 207 vs 193 ms/step -- and removed.)
 template <typename T>
 int Impl<T>::fit_and_solve(algp_ctx* c) {
     SolvePlan pl;
     plan_route(c, 0, true, pl);
+    if (pl.split_tiles) {
+        // the split (plan_route): the last split_tiles tile rows are the factorisation's panel -- z rides in their padding row M,
+        // every other tile row of theirs leaves a narrow last column tile out -- and the sweep, in whole rounds, takes the rows in
+        // front of them; one tail launch then serves both parts' narrow tile (solve_run), no substitution launch for z
+        const int64_t Ms = pl.sweep_rows;
+        c->factored = false;
+        ALGP_TRY(solve_prepare(c, 0, pl));
+        Panel pn{p(c->Vt) + Ms * c->ldv, c->ldv, c->Mpad - Ms, 1};
+        pn.z_row = c->M - Ms;
+        ALGP_HIP(hipMemcpyAsync(p(c->Vt) + c->M * c->ldv, c->y0.p, sizeof(T) * c->Npad, hipMemcpyDeviceToDevice, c->stream));
+        pn.short_rows = pl.narrow_r ? pl.short_rows - Ms : 0;
+        ALGP_TRY(factorize(c, 0, &pn));
+        ALGP_TRY(solve_run(c, pl));
+        return solve_finish(c, 0, nullptr, pl);
+    }
     if (pl.route != SolveRoute::Folded) {
         ALGP_TRY(factorize(c, 0));
         ALGP_TRY(solve_prepare(c, 0, pl));

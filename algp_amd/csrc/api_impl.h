@@ -95,8 +95,15 @@ struct Impl {
         bool rowstat_done = false;           // solve_run's launches left the rows' sums per column tile in c->rowstat
         bool rhs_fused = false;              // Sweep: B^T is not written to V^T; the scheduled sweep's update products generate it (gen)
         int64_t sweep_end = 0;               // Sweep: the columns [0, sweep_end) are the sweep's, the rest the narrow tile's and padding
+        int split_tiles = 0;                 // Sweep, fit_and_solve: the last split_tiles tile rows (the one that carries z among them) ride
+        int64_t sweep_rows = 0;              // the factorisation's launch as its panel; the sweep solves rows [0, sweep_rows) only
         RhsGen gen;
     };
+    // The split is taken for up to this many leftover row panels of the sweep: the largest measured p that still pays.  Measured
+    // on an MI355X at N = 10 000, fp64, from today's routes for the two halves (profiles/split_solve_parts.txt, medians of 5):
+    // predicted gain per step +0.06 / +1.35 / +1.02 / -0.60 / -2.01 ms for p = 8 / 14 / 16 / 24 / 32 folded tile rows against
+    // the 1.2 ms asked of it (three times the headline's run-to-run spread); the step itself, p = 14: -1.3 ms of 153.3.
+    static constexpr int SPLIT_P_MAX = 14;
     // columns [c0, c0 + w) of the candidates' B^T by the kernel-matrix build, to out (leading dimension ldo): RhsGen::window
     static int rhs_window(algp_ctx* c, int64_t c0, int64_t w, void* out, int64_t ldo);
     // a sweep of more than this many tile rows runs left-looking in row chunks; only there does a narrow last tile go to

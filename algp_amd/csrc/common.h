@@ -369,6 +369,7 @@ struct algp_ctx {
     algp::DevBuf gemm_part;              // scheduled GEMM: partial sums of the k slices of a launch's leftover tiles (2 x CUs tiles)
     algp::DevBuf inv512, inv512_scr, trsm_tmp;   // candidate solve: explicit inverses of the factor's 512-column blocks, their scratch, mpad x 512
     algp::DevBuf rhs_rx, rhs_cx, rhs_rk;         // fused right-hand sides (RhsGen): gathered coordinates of the candidate rows, of the train columns; row kinds
+    int64_t rhs_rows = 0;                        // the leading candidate rows (a multiple of 128) that RhsGen::window writes: the sweep's
     std::vector<algp::DagCache> dag_cache;   // task lists of the dependency-driven Cholesky, per matrix size
     algp::DevBuf dag_state;              // its per-launch tile versions / control words / per-block log-determinants
     algp::DevBuf trsv_ctrl;              // ticket + per-block flags of the one-launch forward substitution (potrf.hip)
@@ -475,6 +476,8 @@ void prof_span_end2(algp_ctx* c);
 //   ALGP_TRSM_SCHED=0 (the big solve as row chunks on three streams instead of scheduled launches on one; read per call),
 //   ALGP_RHS_FUSED=0 (the scheduled sweep reads the candidates' right-hand sides B^T from V^T, where a kernel-matrix launch has
 //   put them, instead of forming them in its update products' epilogues; read per call),
+//   ALGP_SPLIT_PANELS=n (fit_and_solve's sweep with its last n tile rows in the factorisation's launch; unset: the rule of
+//   plan_route, 0: never; read per call),
 //   ALGP_FACTOR_FROM_VT=0 (new rows of an updated factor solved, not gathered), ALGP_LAZY_GREEDY=0 (every row scored before
 //   every pick), ALGP_TRSM_CHUNKS=n (row-chunk streams of the big solve; bench.py's one-stream leg sets it by the ABI).
 // Cross-check routes: ALGP_CHOL_DAG=0 (launch-sequence factorisation), ALGP_GATHER_ROWS=0 (remote commits rebuild the row),
