@@ -147,7 +147,7 @@ void prof_collect(algp_ctx* c) {
 }
 
 
-hipEvent_t sync_event_api(algp_ctx* c, size_t i) {
+hipEvent_t sync_event(algp_ctx* c, size_t i) {
     while (c->sync_events.size() <= i) {
         hipEvent_t e;
         hipEventCreateWithFlags(&e, hipEventDisableTiming);
@@ -461,7 +461,7 @@ int Impl<T>::trsm_host(algp_ctx* c, const void* L, int64_t n, const void* B, int
     if (rc == ALGP_OK) rc = ensure(c, inv, sizeof(T) * np * NB);
     for (int64_t kb = 0; rc == ALGP_OK && kb < np / NB; ++kb)
         rc = trinv_diag_launch<T>(c, (const T*)l.p + kb * NB * np + kb * NB, np, (T*)inv.p + kb * NB * NB);
-    if (rc == ALGP_OK) rc = trsm_blocked<T>(c, ALGP_PROF_GEMM_OTHER, (T*)b.p, mp, np, (const T*)l.p, np, np, (const T*)inv.p);
+    if (rc == ALGP_OK) rc = trsm_blocked<T>(c, {.klass = ALGP_PROF_GEMM_OTHER, .X = (T*)b.p, .mpad = mp, .ldx = np, .L = (const T*)l.p, .npad = np, .ldl = np, .invD = (const T*)inv.p});
     if (rc == ALGP_OK) {
         hipError_t e = hipMemcpy2DAsync(X, sizeof(T) * n, b.p, sizeof(T) * np, sizeof(T) * n, m,
                                         hipMemcpyDeviceToHost, c->stream);

@@ -134,7 +134,7 @@ void Impl<T>::plan_route(algp_ctx* c, int incremental, bool allow_fold, typename
         const int64_t per_round = 2 * c->cu_count / 4, left = (Mpad / NB) % per_round;
         if (forced >= 0) split = forced;
         else if (pl.route == SolveRoute::Sweep && left <= SPLIT_P_MAX) split = left;
-        if (!(split >= 1 && split < Mpad / NB && panel_fits(Npad, NB * split) && trsm_sched_wanted(c, Mpad - NB * split, Npad, keep)))
+        if (!(split >= 1 && split < Mpad / NB && panel_fits(Npad, NB * split) && trsm_plan(c, Mpad - NB * split, Npad, keep, {}).sched))
             split = 0;
         if (split) pl.route = SolveRoute::Sweep;
     }
@@ -144,9 +144,11 @@ void Impl<T>::plan_route(algp_ctx* c, int incremental, bool allow_fold, typename
     // kernel (tail.hip, HBM-bound: one pass over V^T) the rest.  On the task-list and folded routes, and in the split's folded
     // tile rows, the tile row that carries y - ybar (a last tile with padding rows, fit_and_solve) keeps every column, so all do
     // the same arithmetic.
+    // (the sweep: only where its rows run left-looking from column 0 on the context's own stream: there the row statistics ride along)
     const int64_t r = N % NB, N1 = Npad - NB;
+    const TrsmPlan whole = trsm_plan(c, Mpad, Npad, keep, {});
     const bool narrow = r > 0 && r <= 64 && N1 >= 2048 && Mpad >= 2048 && tail_on &&
-                        (pl.route != SolveRoute::Sweep || (keep == 0 && c->cur == c->stream && Mpad / NB > SWEEP_PUSH_TILES));
+                        (pl.route != SolveRoute::Sweep || (keep == 0 && whole.main_stream && whole.order == TrsmOrder::LeftLooking));
     if (narrow) {
         pl.narrow_r = (int)r;
         pl.short_rows = pl.route == SolveRoute::Sweep && !split ? Mpad : M < Mpad ? Mpad - NB : Mpad;
@@ -155,12 +157,12 @@ void Impl<T>::plan_route(algp_ctx* c, int incremental, bool allow_fold, typename
     pl.split_tiles = (int)split;
     pl.sweep_rows = Mpad - NB * split;
     pl.row_stats = pl.route == SolveRoute::Sweep && stats_on && keep == 0 && !pl.carried_sums;
-    // Fused right-hand sides: where the sweep will run as scheduled launches with 512-block inverses (trsm_sched_wanted:
-    // trsm_blocked's own predicate; a buffer it then cannot get sends it back to the materialised form), B^T is not written and
+    // Fused right-hand sides: where the sweep will run as scheduled launches with 512-block inverses (trsm_plan: trsm_blocked's
+    // own plan; a buffer it then cannot get sends it back to the materialised form), B^T is not written and
     // read back -- the update products generate their C tiles.  Two scaled coordinates per site only (rhs_gen_supported): wider
     // coordinates and an explicit pool covariance keep the kernel-matrix launch.
     pl.rhs_fused = pl.route == SolveRoute::Sweep && keep == 0 && M > 0 && env_switch("ALGP_RHS_FUSED", true) &&
-                   trsm_sched_wanted(c, pl.sweep_rows, pl.sweep_end, keep) && rhs_gen_supported(c->hyp.DP, c->pool_is_cov);
+                   trsm_plan(c, pl.sweep_rows, pl.sweep_end, keep, {.gen = true}).gen && rhs_gen_supported(c->hyp.DP, c->pool_is_cov);
 }
 
 template <typename T>
@@ -279,15 +281,18 @@ int Impl<T>::solve_run(algp_ctx* c, typename Impl<T>::SolvePlan& pl) {
         trc = solve_dag_panel<T>(c, p(c->L), Npad, c->Lld, p(c->invD), (int*)((double*)c->scal.p + SC_STALL), p(c->Vt), ldc, Mpad, 1,
                                  (int)(pl.short_rows / NB));
     } else if (pl.route == SolveRoute::Sweep) {
-        // a from-scratch solve of more than SWEEP_PUSH_TILES tile rows: its launches leave the rows' sums of v^2 and v z per
+        // a from-scratch solve of more than TRSM_PUSH_TILES tile rows: its launches leave the rows' sums of v^2 and v z per
         // column tile (utils.py:301-304 needs nothing else of V^T), the 8 GB pass over V^T at config 4 falls away
         // (the split: the rows in front of the folded tile rows, which the factorisation's launch has solved already)
         const int64_t rows = pl.sweep_rows;
         T* stat = nullptr;
         if (pl.row_stats && ensure(c, c->rowstat, sizeof(T) * 2 * (size_t)(Npad / NB) * (size_t)rows) == ALGP_OK)
             stat = p(c->rowstat);
-        trc = trsm_blocked<T>(c, ALGP_PROF_GEMM_TRSM, p(c->Vt), rows, ldc, p(c->L), pl.sweep_end, c->Lld, p(c->invD),
-                              keep, p(c->z), stat, rows, &pl.rowstat_done, pl.rhs_fused ? &pl.gen : nullptr);
+        TrsmPlan ran;
+        trc = trsm_blocked<T>(c, {.klass = ALGP_PROF_GEMM_TRSM, .X = p(c->Vt), .mpad = rows, .ldx = ldc, .L = p(c->L), .npad = pl.sweep_end,
+                                  .ldl = c->Lld, .invD = p(c->invD)},
+                              {.col_start = keep, .stats = {p(c->z), stat, rows}, .gen = pl.rhs_fused ? &pl.gen : nullptr}, &ran);
+        pl.rowstat_done = ran.stats;
     } else {
         trc = fail(c, ALGP_ERR_STATE, "internal: the folded route is solved by the factorisation's launch (fit_and_solve)");
     }

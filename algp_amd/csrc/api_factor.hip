@@ -26,7 +26,7 @@ int Impl<T>::factor_resident(algp_ctx* c, T* A, int64_t n, int64_t npad, T* invD
         ALGP_TRY(cholesky_dag_panel<T>(c, A, npad, ld, invD, sc + slot_logdet, (int*)(sc + slot_info), panel->P, panel->ldp,
                                        panel->mpad, panel->mode, (int)(panel->short_rows / NB)));
         if (panel->mode == 2 && panel->inv_out && c->stream2 && c->cur == c->stream) {
-            hipEvent_t ready = sync_event_api(c, 20), done = sync_event_api(c, 21);
+            hipEvent_t ready = sync_event(c, EV_INV_READY), done = sync_event(c, EV_INV_DONE);
             ALGP_HIP(hipEventRecord(ready, c->stream));
             ALGP_HIP(hipStreamWaitEvent(c->stream2, ready, 0));
             c->cur = c->stream2;
@@ -364,7 +364,7 @@ int Impl<T>::factorize(algp_ctx* c, int incremental, typename Impl<T>::Panel* pa
                                  (const T*)c->varA.p + Nb, c->pool_is_cov ? 0 : 1, nullptr, 1, rows, ld, Nb);
             // X = S[R, 0:Nb] L11^-T  (in place, against the kept blocks only)
             if (frc == ALGP_OK)
-                frc = trsm_blocked<T>(c, ALGP_PROF_GEMM_CHOL, rows, R, ld, p(c->L), Nb, ld, p(c->invD));
+                frc = trsm_blocked<T>(c, {.klass = ALGP_PROF_GEMM_CHOL, .X = rows, .mpad = R, .ldx = ld, .L = p(c->L), .npad = Nb, .ldl = ld, .invD = p(c->invD)});
         }
         // S_RR -= X X^T
         if (frc == ALGP_OK)

@@ -22,7 +22,6 @@ namespace algp {
 void release(algp_ctx* c, DevBuf& b);
 void release(algp_ctx* c, MiState& mi);   // every MI buffer (api_mi.hip)
 void release(algp_ctx* c, VrState& vr);   // every buffer of the variance-reduction criterion (api_vr.hip)
-hipEvent_t sync_event_api(algp_ctx* c, size_t i);
 KmatSrc make_src(algp_ctx* c);
 int sync(algp_ctx* c);
 int sync_checked(algp_ctx* c, const char* what);
@@ -106,9 +105,6 @@ struct Impl {
     static constexpr int SPLIT_P_MAX = 14;
     // columns [c0, c0 + w) of the candidates' B^T by the kernel-matrix build, to out (leading dimension ldo): RhsGen::window
     static int rhs_window(algp_ctx* c, int64_t c0, int64_t w, void* out, int64_t ldo);
-    // a sweep of more than this many tile rows runs left-looking in row chunks; only there does a narrow last tile go to
-    // the tail kernel (and only there do the row statistics ride along).  Mirrors TRSM_PUSH_TILES in potrf.hip.
-    static constexpr int64_t SWEEP_PUSH_TILES = 320;
     static void plan_route(algp_ctx* c, int incremental, bool allow_fold, SolvePlan& pl);
     static int solve_prepare(algp_ctx* c, int incremental, SolvePlan& pl);
     static int solve_run(algp_ctx* c, SolvePlan& pl);

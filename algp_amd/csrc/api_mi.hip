@@ -281,7 +281,8 @@ int Impl<T>::mi_shard_build(algp_ctx* c, MiPlan& pl, double* H3) {
         ALGP_TRY(factor_resident(c, p(c->mi.Full), G.m, G.mpad, p(c->auxInv), SC_AUXLOGDET, SC_AUXINFO, &ld));
         H3[1 + which] = (double)G.m * ENT_CONST + 0.5 * ld;
         T* X = p(which ? c->mi.Xall : c->mi.Xbar);
-        ALGP_TRY(mi_trinv_rows<T>(c, ALGP_PROF_GEMM_OTHER, X, G.mpad, G.nloc, G.g, G.member, p(c->mi.Full), G.mpad, G.mpad, p(c->auxInv)));
+        ALGP_TRY(mi_trinv_rows<T>(c, {.klass = ALGP_PROF_GEMM_OTHER, .X = X, .ldx = G.mpad, .L = p(c->mi.Full), .npad = G.mpad, .ldl = G.mpad, .invD = p(c->auxInv)},
+                                  G.nloc, G.g, G.member));
         T* dst = (T*)(own + 32 + (which ? es * NB * (size_t)Gb.maxloc : 0));
         if (G.nloc > 0) ALGP_TRY(rows_reduce_launch<T>(c, X, G.nloc * NB, G.mpad, G.mpad, (const T*)nullptr, dst, (T*)nullptr, 0));
     }

@@ -93,7 +93,7 @@ int Impl<T>::sample_posterior(algp_ctx* c, int S, int F, const double* omega, co
             ALGP_HIP(hipMemcpyAsync(stB, eps + s0 * N, sizeof(double) * (size_t)sl * N, hipMemcpyHostToDevice, c->stream));
             ALGP_TRY(sample_convert_launch<T>(c, stB, sl, N, E, SAMPLE_TILE, Npad, Npad, 0));
             ALGP_TRY(draw((const int64_t*)c->Aidx.p, {R, Npad, N, sl, (T)0, (const T*)c->y0.p, (const T*)c->varA.p, E, (T)c->hyp.noise}));
-            ALGP_TRY(trsm_blocked<T>(c, ALGP_PROF_GEMM_TRSM, R, SAMPLE_TILE, Npad, p(c->L), Npad, c->Lld, p(c->invD)));
+            ALGP_TRY(trsm_blocked<T>(c, {.klass = ALGP_PROF_GEMM_TRSM, .X = R, .mpad = SAMPLE_TILE, .ldx = Npad, .L = p(c->L), .npad = Npad, .ldl = c->Lld, .invD = p(c->invD)}));
         }
         ALGP_TRY(draw((const int64_t*)c->Cidx.p, {O, Mpad, M, sl, (T)c->ybar, nullptr, nullptr, nullptr, (T)0}));
         if (N > 0) {

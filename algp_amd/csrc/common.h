@@ -3,6 +3,7 @@
 #include <stdlib.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <functional>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -705,18 +706,58 @@ int cholesky_dag_panel(algp_ctx* c, T* A, int64_t npad, int64_t ld, T* invD, dou
 template <typename T>
 int solve_dag_panel(algp_ctx* c, const T* L, int64_t npad, int64_t ld, const T* invD, int* info, T* P, int64_t ldp, int64_t mpad,
                     int mode, int pshort = 0);
-// X (mpad x npad, ld ldx) <- X * L^-T, in place
+// ---- the blocked triangular solve X <- X L^-T on the GEMM (potrf.hip) ------------------------------------------------------
+constexpr int WB = 512;                     // its column block (two-level blocking: potrf.hip)
+constexpr int64_t TRSM_PUSH_TILES = 320;    // candidate solves of up to 320 x 128 rows run right-looking (trsm_push)
 template <typename T>
-// stat_out (with stat_w; or null): where every row takes the left-looking order from column 0 (more than 320 tile rows), the
-// launch that writes a column tile for the last time leaves the tile's row sums of x^2 and x * stat_w[column] at
-// stat_out[(2 tile + 0 / 1) * stat_ld + row]; *stats_done says whether that happened (else: take them in a pass over X)
-int trsm_blocked(algp_ctx* c, int klass, T* X, int64_t mpad, int64_t ldx, const T* L, int64_t npad,
-                 int64_t ldl, const T* invD, int64_t col_start = 0, const T* stat_w = nullptr, T* stat_out = nullptr,
-                 int64_t stat_ld = 0, bool* stats_done = nullptr, const RhsGen* gen = nullptr);
-// whether trsm_blocked would run this solve as scheduled launches with 512-block inverses, buffers permitting (potrf.hip)
-bool trsm_sched_wanted(const algp_ctx* c, int64_t mpad, int64_t npad, int64_t col_start);
-// (gen: X does not hold the right-hand sides of columns [0, npad) yet.  The scheduled sweep generates them; where it is not
-// taken after all, gen->window writes them into X first)
+struct TrsmOp {                  // the operands
+    int klass = 0;               // ALGP_PROF_* class the launches are booked under
+    T* X = nullptr;              // mpad x npad, leading dimension ldx: the right-hand sides, solved in place
+    int64_t mpad = 0, ldx = 0;
+    const T* L = nullptr;        // the factor: npad x npad, leading dimension ldl
+    int64_t npad = 0, ldl = 0;
+    const T* invD = nullptr;     // the explicit inverses of its 128 x 128 diagonal blocks
+};
+template <typename T>
+struct TrsmStats {               // row statistics (with w and out; out null: none).  Where every row takes the left-looking order
+    const T* w = nullptr;        // from column 0 (more than 320 tile rows), the launch that writes a column tile of X for the last
+    T* out = nullptr;            // time also leaves the tile's row sums of x^2 and x * w[column] at out[(2 tile + 0 / 1) * ld + row];
+    int64_t ld = 0;              // TrsmPlan::stats says whether that happened (else: take them in a pass over X)
+};
+template <typename T>
+struct TrsmOpt {                 // what is optional
+    int64_t col_start = 0;       // (multiple of 128): columns [0, col_start) of X already hold the solution
+    TrsmStats<T> stats;
+    const RhsGen* gen = nullptr; // X does not hold the right-hand sides of columns [0, npad) yet.  The scheduled sweep generates
+                                 // them; where it is not taken after all, gen->window writes them into X first
+};
+// How a solve of this shape runs: decided once, by trsm_plan (allocates nothing, launches nothing; the switches are read per call,
+// tests flip them), for trsm_blocked and for the candidate solve's plan (plan_route).
+enum class TrsmOrder { Short, Push, LeftLooking };      // trsm_short / trsm_push / trsm_left (potrf.hip)
+struct TrsmWants { bool stats = false, gen = false; };  // the caller has row statistics to take / a generator instead of a matrix
+struct TrsmPlan {
+    TrsmOrder order = TrsmOrder::Short;
+    bool main_stream = false;    // enqueued on the context's own stream: helper streams may run beside it
+    bool inv512 = false;         // LeftLooking: a full 512-column block is one product with its explicit inverse
+    bool sched = false;          // ... and every product a scheduled launch, one after the other on the caller's stream
+    bool stats = false;          // the launches leave the row statistics
+    bool gen = false;            // the update products generate the right-hand sides (sched only)
+    int chunks = 1;              // LeftLooking, not scheduled: row chunks on streams of their own
+};
+TrsmPlan trsm_plan(const algp_ctx* c, int64_t mpad, int64_t npad, int64_t col_start, TrsmWants wants);
+template <typename T>
+int trsm_blocked(algp_ctx* c, const TrsmOp<T>& op, const TrsmOpt<T>& opt = {}, TrsmPlan* ran = nullptr);   // *ran: its plan, less what no buffer was had for
+// The right-looking step inside a column block [j0, j1), 128 columns at a time: the product with the diagonal inverse over the first
+// rows_of(k0) rows (0: the column is skipped), then the push into the block's columns behind.  The short order's, and the L^-T sweeps'.
+template <typename T>
+int block_solve_right(algp_ctx* c, const TrsmOp<T>& op, int64_t j0, int64_t j1, const std::function<int64_t(int64_t)>& rows_of);
+// Slots of algp_ctx::sync_events (sync_event, api.hip).  0 .. 16 are the blocked solve's, 20 and up the API layer's.
+enum SyncSlot : size_t {
+    EV_CHUNK = 0,                // + k, k < 4: row chunk k of the left-looking order is done (slot 0 first marks their common start)
+    EV_PUSH_A = 8, EV_PUSH_B = 9, EV_PUSH_DONE = 16,   // the push order's rings a[J], b[J] (+ 2 (J & 3)); its helper stream has finished
+    EV_INV_READY = 20, EV_INV_DONE = 21,   // factor_resident's S^-1 on the helper stream (api_factor.hip; api_fit.hip waits)
+};
+hipEvent_t sync_event(algp_ctx* c, size_t slot);
 // columns [c0, c0 + w) of X <- the solution's new columns after rows c0.. were appended to L (tail.hip): c0 a multiple of 16,
 // w <= 64, inside one 128-column block whose explicit inverse is invD_blk; lrows = rows of L that exist
 template <typename T>

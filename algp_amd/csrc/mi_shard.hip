@@ -8,8 +8,6 @@
 
 namespace algp {
 
-constexpr int64_t MI_PANEL = 512;      // column block of the right-looking sweep (trinv_upper's WB)
-
 // local row tile t <-> global row block t g + member (the deal of rows over the g ranks of a group)
 __host__ __device__ inline int64_t mi_local_block(int64_t t, int g, int member) { return t * g + member; }
 
@@ -31,32 +29,23 @@ static int64_t mi_tiles_upto(int64_t kb, int64_t nloc, int g, int member) {
 // global block, so column tile k0 involves only the local tiles whose block is <= k0 / 128 -- a prefix of the local rows --
 // and the push of a finished column block into the trailing columns only the tiles left of its end: trinv_upper's sweep with
 // `rows = k0 + 128` replaced by that prefix.  Cost: sum over the rank's blocks b of 128 (n - 128 b)^2 multiply-adds
-// (~ n^3 / (3 g) flop); the tiles that would only ever see zeros are never launched.
+// (~ n^3 / (3 g) flop); the tiles that would only ever see zeros are never launched.  op: X the rank's nloc x 128 rows (mpad unused).
 template <typename T>
-int mi_trinv_rows(algp_ctx* c, int klass, T* X, int64_t ldx, int64_t nloc, int g, int member, const T* L, int64_t ldl,
-                  int64_t npad, const T* invD) {
+int mi_trinv_rows(algp_ctx* c, const TrsmOp<T>& op, int64_t nloc, int g, int member) {
+    const auto& [klass, X, mpad, ldx, L, npad, ldl, invD] = op;
     if (nloc <= 0) return ALGP_OK;
     if (nloc > 65535) return fail(c, ALGP_ERR_BAD_ARG, "mi_trinv_rows: too many row blocks");
     if (mi_local_block(nloc - 1, g, member) * NB >= npad) return fail(c, ALGP_ERR_BAD_ARG, "mi_trinv_rows: a row block outside the matrix");
     ALGP_HIP(hipMemsetAsync(X, 0, sizeof(T) * (size_t)nloc * NB * ldx, c->cur));
     hipLaunchKernelGGL(mi_rows_ident_kernel<T>, dim3((unsigned)nloc), dim3(NB), 0, c->cur, X, ldx, g, member);
     ALGP_HIP(hipGetLastError());
-    for (int64_t j0 = 0; j0 < npad; j0 += MI_PANEL) {
-        const int64_t w = std::min(MI_PANEL, npad - j0), j1 = j0 + w;
-        for (int64_t k0 = j0; k0 < j1; k0 += NB) {
-            const int64_t rows = mi_tiles_upto(k0 / NB, nloc, g, member) * NB;
-            if (rows == 0) continue;
-            T* Xk = X + k0;
-            ALGP_TRY(gemm_nt_launch<T>(c, klass, rows, NB, NB, (T)1, Xk, ldx, invD + (k0 / NB) * NB * NB, NB, (T)0, nullptr, 0, Xk, ldx, 0));
-            if (k0 + NB < j1)
-                ALGP_TRY(gemm_nt_launch<T>(c, klass, rows, j1 - (k0 + NB), NB, (T)-1, Xk, ldx, L + (k0 + NB) * ldl + k0, ldl, (T)1,
-                                           Xk + NB, ldx, Xk + NB, ldx, 0));
-        }
+    for (int64_t j0 = 0; j0 < npad; j0 += WB) {
+        const int64_t w = std::min<int64_t>(WB, npad - j0), j1 = j0 + w;
+        ALGP_TRY(block_solve_right<T>(c, op, j0, j1, [&](int64_t k0) { return mi_tiles_upto(k0 / NB, nloc, g, member) * NB; }));
         if (j1 >= npad) break;
         const int64_t rows = mi_tiles_upto(j1 / NB - 1, nloc, g, member) * NB;
         if (rows > 0)
-            ALGP_TRY(gemm_nt_launch<T>(c, klass, rows, npad - j1, w, (T)-1, X + j0, ldx, L + j1 * ldl + j0, ldl, (T)1, X + j1, ldx,
-                                       X + j1, ldx, 0));
+            ALGP_TRY(gemm_nt_launch<T>(c, klass, rows, npad - j1, w, (T)-1, X + j0, ldx, L + j1 * ldl + j0, ldl, (T)1, X + j1, ldx, X + j1, ldx, 0));
     }
     return ALGP_OK;
 }

@@ -74,10 +74,6 @@ ALGP_INSTANTIATE(trinv_diag_launch);
 // updated once per block with K = 512 (Cholesky) / produced by one n = 512 GEMM whose four column
 // tiles share each A row-panel through the XCD's L2 (TRSM).
 // ---------------------------------------------------------------------------------------------
-constexpr int WB = 512;
-constexpr int64_t TRSM_PUSH_TILES = 320;   // candidate solves of up to 320 x 128 rows run right-looking (trsm_rows_blocked)
-
-static hipEvent_t sync_event(algp_ctx* c, size_t i);
 template <typename T>
 int gemm_splitk_sub(algp_ctx* c, int klass, int64_t m, int64_t n, int64_t k, const T* A, int64_t lda, const T* B,
                     int64_t ldb, T* C, int64_t ldc, DevBuf& scratch);
@@ -217,132 +213,138 @@ static size_t inv512_scratch_elems(int64_t npad) {
     return nb <= 0 ? 0 : (size_t)nb * (4 * NB * NB + NB * NB + 2 * 256 * 256);
 }
 
-// X <- X L^-T, left-looking over 512-wide column blocks:
-//   X_J <- X_J - X_{0:J} L_{J,0:J}^T            (one GEMM, n = 512)
-//   inside J, 128 columns at a time: X_k <- (X_k - X_{J0:k} L_{k,J0:k}^T) inv(L_kk)^T
+// ---- X <- X L^-T: the two steps inside a column block, one function per order, the plan, trsm_blocked ------------------------
+// The left-looking step inside a column block [j0, j1), for its columns from first_col on, 128 at a time:
+//   X_k <- (X_k - X_{j0:k} L_{k,j0:k}^T) inv(L_kk)^T         (stats.out: a column tile's last write leaves its row statistics)
 template <typename T>
-static int trsm_rows_blocked(algp_ctx* c, int klass, T* X, int64_t mpad, int64_t ldx, const T* L, int64_t npad,
-                     int64_t ldl, const T* invD, int64_t col_start, bool whole_solve, const T* stat_w = nullptr,
-                     T* stat_out = nullptr, int64_t stat_ld = 0, const T* inv512 = nullptr, T* tmp512 = nullptr,
-                     const RhsGen* gen = nullptr) {
-    // gen (the scheduled sweep only: left-looking order, col_start == 0, inv512 / tmp512 given): X does not hold the right-hand
-    // sides; every update product generates its C tile (gemm_nt_launch_gen) -- the ragged last block's too, which then leaves
-    // D = X for the 128-column steps inside it.
-    // inv512 / tmp512 (left-looking order, col_start == 0): the explicit inverses of the full 512-column blocks
-    // (build_inv512) and mpad x 512 scratch, holding X_0 on entry: block J is then two launches -- T = X_J - X_{0:J} L_{J,0:J}^T
-    // into the scratch, X_J = T inv(L_JJ)^T -- instead of eight.
-    // stat_out (left-looking order only, col_start == 0: trsm_blocked decides): the launch that writes a column tile of X for
-    // the last time also leaves the tile's row sums of x^2 and x * stat_w[column] at stat_out[(2 tile + 0 / 1) * stat_ld + row]
-    // col_start (multiple of 128): columns [0, col_start) of X already hold the solution
-    if (mpad <= 32 * NB) {
-        // A short X (a few test points): the left-looking order below would walk K up to npad inside
-        // one or two workgroups (launch-latency bound).  Right-looking instead: solve one 128-column
-        // block, then update ALL remaining columns with K = 128 -- (npad-k)/128 column tiles in parallel.
-        // It re-reads/re-writes the trailing columns each step, which is negligible for so few rows.
-        if (col_start > 0)      // columns >= col_start still need the contributions of the kept ones
-            ALGP_TRY(gemm_splitk_sub<T>(c, klass, mpad, npad - col_start, col_start, X, ldx, L + col_start * ldl, ldl,
-                                        X + col_start, ldx, c->splitk));
-        for (int64_t k0 = col_start; k0 < npad; k0 += NB) {
-            T* Xk = X + k0;
-            ALGP_TRY(gemm_nt_launch<T>(c, klass, mpad, NB, NB, (T)1, Xk, ldx, invD + (k0 / NB) * NB * NB, NB, (T)0,
-                                       nullptr, 0, Xk, ldx, 0));
-            const int64_t nrem = npad - (k0 + NB);
-            if (nrem > 0)
-                ALGP_TRY(gemm_nt_launch<T>(c, klass, mpad, nrem, NB, (T)-1, Xk, ldx, L + (k0 + NB) * ldl + k0, ldl, (T)1,
-                                           Xk + NB, ldx, Xk + NB, ldx, 0));
-        }
-        return ALGP_OK;
+static int block_solve_left(algp_ctx* c, const TrsmOp<T>& op, int64_t j0, int64_t j1, int64_t first_col, const TrsmStats<T>& stats) {
+    const auto& [klass, X, mpad, ldx, L, npad, ldl, invD] = op;
+    for (int64_t k0 = std::max(j0, first_col); k0 < j1; k0 += NB) {
+        T* Xk = X + k0;
+        const T* inv = invD + (k0 / NB) * NB * NB;
+        if (k0 > j0) ALGP_TRY(gemm_nt_launch<T>(c, klass, mpad, NB, k0 - j0, (T)-1, X + j0, ldx, L + k0 * ldl + j0, ldl, (T)1, Xk, ldx, Xk, ldx, 0));
+        if (stats.out)
+            ALGP_TRY(gemm_nt_launch_stats<T>(c, klass, mpad, NB, (T)1, Xk, ldx, inv, NB, Xk, ldx, stats.w + k0, stats.out + 2 * (k0 / NB) * stats.ld, stats.ld));
+        else
+            ALGP_TRY(gemm_nt_launch<T>(c, klass, mpad, NB, NB, (T)1, Xk, ldx, inv, NB, (T)0, nullptr, 0, Xk, ldx, 0));
     }
-    if (whole_solve && col_start == 0 && mpad <= TRSM_PUSH_TILES * NB) {     // (never a row chunk of a larger solve)
-        // A mid-sized X (a few thousand to ~40 000 rows: a rank's share of the candidates on 4-8 GPUs, a held-out set):
-        // the left-looking order below launches (rows/128) x 4 tiles per block column, each walking a K of up to npad --
-        // 132 tiles on 512 slots per row chunk at 12 500 rows (41 TFLOP/s fp64).  RIGHT-looking over 512-column
-        // blocks instead: solve a block (inside it left-looking, as below), then push it into ALL columns to its right
-        // with one K = 512 GEMM of (rows/128) x (columns left/128) tiles -- the machine is full until the last few
-        // blocks, at the price of one read + write of the trailing columns per block (rows x npad^2 / 512 elements in
-        // all: 20 GB at 12 500 x 10 000 fp64, 64 flop per byte).  Measured at N = 10 000, fp64 (left-looking -> this):
-        // 5 000 rows 18.1 -> 13.2 ms, 12 500 rows 30.6 -> 23.4 ms (41 -> 53 TFLOP/s), 25 000 rows 45.9 -> 42.7 ms; equal at
-        // 50 000 rows, where the three row-chunk streams of the left-looking order fill the machine as well.
-        // Two streams: the short launches that solve block J+1 (and the push of block J into block J+1 alone, which they
-        // wait for) run on the caller's stream BESIDE the big push of block J into the columns beyond, on a helper stream.
-        //   main:   I(J) . record a[J] . wait b[J-1] . Q(J) . I(J+1) ...      I = solve inside the block, Q = push into the next block
-        //   helper: wait a[J] . P(J) . record b[J]                            P = push into everything beyond the next block
-        // Every column block receives its pushes in ascending J (P(J-1) before Q(J), both before I(J+1)).
-        constexpr int64_t PW = WB;                                  // (1024-wide pushes: 25.2 ms at 12 500 rows, 41.9 at 25 000)
-        hipStream_t sa = c->cur, sb = (c->cur == c->stream && c->stream2) ? c->stream2 : nullptr;
-        int rc = ALGP_OK;
-        int64_t jb = 0;
-        for (int64_t j0 = 0; j0 < npad && rc == ALGP_OK; j0 += PW, ++jb) {
-            const int64_t w = (npad - j0 < PW) ? npad - j0 : PW, j1 = j0 + w;
-            T* Xj = X + j0;
-            for (int64_t k0 = j0; k0 < j1 && rc == ALGP_OK; k0 += NB) {
-                T* Xk = X + k0;
-                if (k0 > j0)
-                    rc = gemm_nt_launch<T>(c, klass, mpad, NB, k0 - j0, (T)-1, Xj, ldx, L + k0 * ldl + j0, ldl, (T)1, Xk, ldx, Xk,
-                                           ldx, 0);
-                if (rc == ALGP_OK)
-                    rc = gemm_nt_launch<T>(c, klass, mpad, NB, NB, (T)1, Xk, ldx, invD + (k0 / NB) * NB * NB, NB, (T)0, nullptr, 0,
-                                           Xk, ldx, 0);
-            }
-            if (j1 >= npad || rc != ALGP_OK) break;
-            const int64_t wq = (npad - j1 < PW) ? npad - j1 : PW;           // width of the next block
-            if (sb) {
-                hipEvent_t ea = sync_event(c, 8 + 2 * (size_t)(jb & 3)), eb = sync_event(c, 9 + 2 * (size_t)(jb & 3));
-                hipEventRecord(ea, sa);
-                if (jb > 0) hipStreamWaitEvent(sa, sync_event(c, 9 + 2 * (size_t)((jb - 1) & 3)), 0);
-                rc = gemm_nt_launch<T>(c, klass, mpad, wq, w, (T)-1, Xj, ldx, L + j1 * ldl + j0, ldl, (T)1, X + j1, ldx, X + j1, ldx, 0);
-                if (rc == ALGP_OK && j1 + wq < npad) {
-                    hipStreamWaitEvent(sb, ea, 0);
-                    c->cur = sb;
-                    rc = gemm_nt_launch<T>(c, klass, mpad, npad - (j1 + wq), w, (T)-1, Xj, ldx, L + (j1 + wq) * ldl + j0, ldl, (T)1,
-                                           X + j1 + wq, ldx, X + j1 + wq, ldx, 0);
-                    c->cur = sa;
-                }
-                hipEventRecord(eb, sb);
-            } else {
-                rc = gemm_nt_launch<T>(c, klass, mpad, npad - j1, w, (T)-1, Xj, ldx, L + j1 * ldl + j0, ldl, (T)1, X + j1, ldx,
-                                       X + j1, ldx, 0);
-            }
-        }
-        if (sb) {                                                   // the caller's stream continues after the last push
-            hipEvent_t done = sync_event(c, 16);
-            hipEventRecord(done, sb);
-            hipStreamWaitEvent(sa, done, 0);
-        }
-        return rc;
+    return ALGP_OK;
+}
+template <typename T>
+int block_solve_right(algp_ctx* c, const TrsmOp<T>& op, int64_t j0, int64_t j1, const std::function<int64_t(int64_t)>& rows_of) {
+    const auto& [klass, X, mpad, ldx, L, npad, ldl, invD] = op;     // (mpad: rows_of says how many rows take part)
+    for (int64_t k0 = j0; k0 < j1; k0 += NB) {
+        const int64_t rows = rows_of(k0);
+        if (rows == 0) continue;
+        T* Xk = X + k0;
+        ALGP_TRY(gemm_nt_launch<T>(c, klass, rows, NB, NB, (T)1, Xk, ldx, invD + (k0 / NB) * NB * NB, NB, (T)0, nullptr, 0, Xk, ldx, 0));
+        if (k0 + NB < j1)
+            ALGP_TRY(gemm_nt_launch<T>(c, klass, rows, j1 - (k0 + NB), NB, (T)-1, Xk, ldx, L + (k0 + NB) * ldl + k0, ldl, (T)1, Xk + NB, ldx, Xk + NB, ldx, 0));
     }
-    const int64_t TWB = WB;                                     // outer block width
-    for (int64_t j0 = 0; j0 < npad; j0 += TWB) {
-        const int64_t w = (npad - j0 < TWB) ? npad - j0 : TWB;
+    return ALGP_OK;
+}
+ALGP_INSTANTIATE(block_solve_right);
+
+// A short X (a few test points, up to 32 tile rows): the left-looking order would walk K up to npad inside
+// one or two workgroups (launch-latency bound).  Right-looking instead: solve one 128-column
+// block, then update ALL remaining columns with K = 128 -- (npad-k)/128 column tiles in parallel.
+// It re-reads/re-writes the trailing columns each step, which is negligible for so few rows.
+template <typename T>
+static int trsm_short(algp_ctx* c, const TrsmOp<T>& op, int64_t col_start) {
+    if (col_start > 0)      // columns >= col_start still need the contributions of the kept ones
+        ALGP_TRY(gemm_splitk_sub<T>(c, op.klass, op.mpad, op.npad - col_start, col_start, op.X, op.ldx, op.L + col_start * op.ldl, op.ldl,
+                                    op.X + col_start, op.ldx, c->splitk));
+    return block_solve_right<T>(c, op, col_start, op.npad, [&](int64_t) { return op.mpad; });
+}
+
+// A mid-sized X from column 0 (a few thousand to ~40 000 rows: a rank's share of the candidates on 4-8 GPUs, a held-out set):
+// the left-looking order below launches (rows/128) x 4 tiles per block column, each walking a K of up to npad --
+// 132 tiles on 512 slots per row chunk at 12 500 rows (41 TFLOP/s fp64).  RIGHT-looking over 512-column
+// blocks instead: solve a block (inside it left-looking), then push it into ALL columns to its right
+// with one K = 512 GEMM of (rows/128) x (columns left/128) tiles -- the machine is full until the last few
+// blocks, at the price of one read + write of the trailing columns per block (rows x npad^2 / 512 elements in
+// all: 20 GB at 12 500 x 10 000 fp64, 64 flop per byte).  Measured at N = 10 000, fp64 (left-looking -> this):
+// 5 000 rows 18.1 -> 13.2 ms, 12 500 rows 30.6 -> 23.4 ms (41 -> 53 TFLOP/s), 25 000 rows 45.9 -> 42.7 ms; equal at
+// 50 000 rows, where the three row-chunk streams of the left-looking order fill the machine as well.
+// Two streams (helper: the solve is on the context's own stream): the short launches that solve block J+1 (and the push of block
+// J into block J+1 alone, which they wait for) run on the caller's stream BESIDE the big push of block J into the columns beyond.
+//   main:   I(J) . record a[J] . wait b[J-1] . Q(J) . I(J+1) ...      I = solve inside the block, Q = push into the next block
+//   helper: wait a[J] . P(J) . record b[J]                            P = push into everything beyond the next block
+// Every column block receives its pushes in ascending J (P(J-1) before Q(J), both before I(J+1)).
+template <typename T>
+static int trsm_push(algp_ctx* c, const TrsmOp<T>& op, bool helper) {
+    constexpr int64_t PW = WB;                                  // (1024-wide pushes: 25.2 ms at 12 500 rows, 41.9 at 25 000)
+    const auto& [klass, X, mpad, ldx, L, npad, ldl, invD] = op;
+    hipStream_t sa = c->cur, sb = (helper && c->stream2) ? c->stream2 : nullptr;
+    int rc = ALGP_OK;
+    int64_t jb = 0;
+    for (int64_t j0 = 0; j0 < npad && rc == ALGP_OK; j0 += PW, ++jb) {
+        const int64_t w = (npad - j0 < PW) ? npad - j0 : PW, j1 = j0 + w;
+        T* Xj = X + j0;
+        rc = block_solve_left<T>(c, op, j0, j1, j0, {});
+        if (j1 >= npad || rc != ALGP_OK) break;
+        const int64_t wq = (npad - j1 < PW) ? npad - j1 : PW;           // width of the next block
+        if (sb) {
+            hipEvent_t ea = sync_event(c, EV_PUSH_A + 2 * (size_t)(jb & 3)), eb = sync_event(c, EV_PUSH_B + 2 * (size_t)(jb & 3));
+            hipEventRecord(ea, sa);
+            if (jb > 0) hipStreamWaitEvent(sa, sync_event(c, EV_PUSH_B + 2 * (size_t)((jb - 1) & 3)), 0);
+            rc = gemm_nt_launch<T>(c, klass, mpad, wq, w, (T)-1, Xj, ldx, L + j1 * ldl + j0, ldl, (T)1, X + j1, ldx, X + j1, ldx, 0);
+            if (rc == ALGP_OK && j1 + wq < npad) {
+                hipStreamWaitEvent(sb, ea, 0);
+                c->cur = sb;
+                rc = gemm_nt_launch<T>(c, klass, mpad, npad - (j1 + wq), w, (T)-1, Xj, ldx, L + (j1 + wq) * ldl + j0, ldl, (T)1,
+                                       X + j1 + wq, ldx, X + j1 + wq, ldx, 0);
+                c->cur = sa;
+            }
+            hipEventRecord(eb, sb);
+        } else {
+            rc = gemm_nt_launch<T>(c, klass, mpad, npad - j1, w, (T)-1, Xj, ldx, L + j1 * ldl + j0, ldl, (T)1, X + j1, ldx,
+                                   X + j1, ldx, 0);
+        }
+    }
+    if (sb) {                                                   // the caller's stream continues after the last push
+        hipEvent_t done = sync_event(c, EV_PUSH_DONE);
+        hipEventRecord(done, sb);
+        hipStreamWaitEvent(sa, done, 0);
+    }
+    return rc;
+}
+
+// What only a left-looking solve from column 0 can have (TrsmPlan::inv512): the explicit inverses of the full 512-column blocks
+// (build_inv512) and mpad x 512 scratch, holding X_0 on entry: block J is then two launches -- T = X_J - X_{0:J} L_{J,0:J}^T
+// into the scratch, X_J = T inv(L_JJ)^T -- instead of eight.  gen (the scheduled sweep only, or null): X does not hold the
+// right-hand sides; every update product generates its C tile (gemm_nt_launch_gen) -- the ragged last block's too, which then
+// leaves D = X for the 128-column steps inside it.
+template <typename T>
+struct TrsmInv512 { const T* inv; T* tmp; const RhsGen* gen; };
+// Left-looking over 512-wide column blocks:
+//   X_J <- X_J - X_{0:J} L_{J,0:J}^T            (one GEMM, n = 512)
+//   inside J: one product with the block's inverse (blk, full blocks; col_start is 0 there), else block_solve_left
+// (A divide-and-conquer order of this sweep was measured in round 1: same time, 339 GB instead of 200 GB of HBM
+// traffic per solve at N = 10 000, M = 100 000 -- the big off-diagonal blocks of L fall out of the 4 MB L2s -- and removed.)
+template <typename T>
+static int trsm_left(algp_ctx* c, const TrsmOp<T>& op, int64_t col_start, const TrsmStats<T>& stats, const TrsmInv512<T>* blk) {
+    const auto& [klass, X, mpad, ldx, L, npad, ldl, invD] = op;
+    const RhsGen* gen = blk ? blk->gen : nullptr;
+    for (int64_t j0 = 0; j0 < npad; j0 += WB) {
+        const int64_t w = (npad - j0 < WB) ? npad - j0 : WB;
         if (j0 + w <= col_start) continue;
         const int64_t cs = j0 > col_start ? j0 : col_start;         // first column of this block to solve
         T* Xj = X + j0;
-        if (inv512 && tmp512 && w == TWB && col_start == 0) {
+        if (blk && w == WB) {
             // (block 0 has nothing to its left: the caller has copied its right-hand sides into the scratch)
-            if (j0 > 0 && gen) ALGP_TRY(gemm_nt_launch_gen<T>(c, klass, mpad, TWB, j0, (T)-1, X, ldx, L + j0 * ldl, ldl, (T)1, *gen, j0, tmp512, TWB));
-            else if (j0 > 0) ALGP_TRY(gemm_nt_launch<T>(c, klass, mpad, TWB, j0, (T)-1, X, ldx, L + j0 * ldl, ldl, (T)1, Xj, ldx, tmp512, TWB, 0));
-            ALGP_TRY(gemm_nt_launch_tri<T>(c, klass, mpad, TWB, tmp512, TWB, inv512 + (j0 / TWB) * TWB * TWB, TWB, Xj, ldx,
-                                           stat_w ? stat_w + j0 : nullptr, stat_out ? stat_out + 2 * (j0 / NB) * stat_ld : nullptr, stat_ld));
+            if (j0 > 0 && gen) ALGP_TRY(gemm_nt_launch_gen<T>(c, klass, mpad, WB, j0, (T)-1, X, ldx, L + j0 * ldl, ldl, (T)1, *gen, j0, blk->tmp, WB));
+            else if (j0 > 0) ALGP_TRY(gemm_nt_launch<T>(c, klass, mpad, WB, j0, (T)-1, X, ldx, L + j0 * ldl, ldl, (T)1, Xj, ldx, blk->tmp, WB, 0));
+            ALGP_TRY(gemm_nt_launch_tri<T>(c, klass, mpad, WB, blk->tmp, WB, blk->inv + (j0 / WB) * WB * WB, WB, Xj, ldx,
+                                           stats.w ? stats.w + j0 : nullptr, stats.out ? stats.out + 2 * (j0 / NB) * stats.ld : nullptr, stats.ld));
             continue;
         }
-        if (gen && (j0 == 0 || cs != j0)) return fail(c, ALGP_ERR_STATE, "internal: generated right-hand sides outside the scheduled sweep");
-        if (j0 > 0 && gen)
+        if (j0 > 0 && gen)       // (the ragged last block: block 0 is a full one where the inverses are taken)
             ALGP_TRY(gemm_nt_launch_gen<T>(c, klass, mpad, w, j0, (T)-1, X, ldx, L + j0 * ldl, ldl, (T)1, *gen, j0, Xj, ldx));
         else if (j0 > 0)
             ALGP_TRY(gemm_nt_launch<T>(c, klass, mpad, j0 + w - cs, j0, (T)-1, X, ldx, L + cs * ldl, ldl, (T)1, X + cs,
                                        ldx, X + cs, ldx, 0));
-        for (int64_t k0 = cs; k0 < j0 + w; k0 += NB) {
-            T* Xk = X + k0;
-            if (k0 > j0)
-                ALGP_TRY(gemm_nt_launch<T>(c, klass, mpad, NB, k0 - j0, (T)-1, Xj, ldx, L + k0 * ldl + j0, ldl, (T)1,
-                                           Xk, ldx, Xk, ldx, 0));
-            if (stat_out)
-                ALGP_TRY(gemm_nt_launch_stats<T>(c, klass, mpad, NB, (T)1, Xk, ldx, invD + (k0 / NB) * NB * NB, NB, Xk, ldx,
-                                                 stat_w + k0, stat_out + 2 * (k0 / NB) * stat_ld, stat_ld));
-            else
-                ALGP_TRY(gemm_nt_launch<T>(c, klass, mpad, NB, NB, (T)1, Xk, ldx, invD + (k0 / NB) * NB * NB, NB, (T)0,
-                                           nullptr, 0, Xk, ldx, 0));
-        }
+        ALGP_TRY(block_solve_left<T>(c, op, j0, j0 + w, col_start, stats));
     }
     return ALGP_OK;
 }
@@ -355,17 +357,10 @@ static int trsm_rows_blocked(algp_ctx* c, int klass, T* X, int64_t mpad, int64_t
 // gives (j0+w)/128 x (npad-j0-w)/128 tiles with K = 512, the shape of the Cholesky's trailing update.
 template <typename T>
 int trinv_upper(algp_ctx* c, int klass, T* X, int64_t npad, int64_t ldx, const T* L, int64_t ldl, const T* invD) {
+    const TrsmOp<T> op = {.klass = klass, .X = X, .ldx = ldx, .L = L, .npad = npad, .ldl = ldl, .invD = invD};
     for (int64_t j0 = 0; j0 < npad; j0 += WB) {
         const int64_t w = (npad - j0 < WB) ? npad - j0 : WB, j1 = j0 + w;
-        for (int64_t k0 = j0; k0 < j1; k0 += NB) {
-            T* Xk = X + k0;
-            const int64_t rows = k0 + NB;                         // rows below are zero in this column block
-            ALGP_TRY(gemm_nt_launch<T>(c, klass, rows, NB, NB, (T)1, Xk, ldx, invD + (k0 / NB) * NB * NB, NB, (T)0,
-                                       nullptr, 0, Xk, ldx, 0));
-            if (k0 + NB < j1)
-                ALGP_TRY(gemm_nt_launch<T>(c, klass, rows, j1 - (k0 + NB), NB, (T)-1, Xk, ldx, L + (k0 + NB) * ldl + k0,
-                                           ldl, (T)1, Xk + NB, ldx, Xk + NB, ldx, 0));
-        }
+        ALGP_TRY(block_solve_right<T>(c, op, j0, j1, [](int64_t k0) { return k0 + NB; }));     // rows below are zero in this column
         if (j1 < npad)
             ALGP_TRY(gemm_nt_launch<T>(c, klass, j1, npad - j1, w, (T)-1, X + j0, ldx, L + j1 * ldl + j0, ldl, (T)1,
                                        X + j1, ldx, X + j1, ldx, 0));
@@ -398,16 +393,10 @@ int trinv_upper_inplace(algp_ctx* c, int klass, T* XL, int64_t npad, int64_t ld,
     if (nt > 65535) return fail(c, ALGP_ERR_BAD_ARG, "trinv_upper_inplace: matrix too large");
     hipLaunchKernelGGL(tri_prep_kernel<T>, dim3(nt, nt), dim3(256), 0, c->cur, XL, ld);
     ALGP_HIP(hipGetLastError());
+    const TrsmOp<T> op = {.klass = klass, .X = XL, .ldx = ld, .L = XL, .npad = npad, .ldl = ld, .invD = invD};
     for (int64_t j0 = 0; j0 < npad; j0 += WB) {
         const int64_t w = (npad - j0 < WB) ? npad - j0 : WB, j1 = j0 + w;
-        for (int64_t k0 = j0; k0 < j1; k0 += NB) {
-            T* Xk = XL + k0;
-            const int64_t rows = k0 + NB;
-            ALGP_TRY(gemm_nt_launch<T>(c, klass, rows, NB, NB, (T)1, Xk, ld, invD + (k0 / NB) * NB * NB, NB, (T)0, nullptr, 0, Xk, ld, 0));
-            if (k0 + NB < j1)
-                ALGP_TRY(gemm_nt_launch<T>(c, klass, rows, j1 - (k0 + NB), NB, (T)-1, Xk, ld, XL + (k0 + NB) * ld + k0, ld, (T)1,
-                                           Xk + NB, ld, Xk + NB, ld, 0));
-        }
+        ALGP_TRY(block_solve_right<T>(c, op, j0, j1, [](int64_t k0) { return k0 + NB; }));
         if (j1 >= npad) break;
         // rows above the block: dense in X; rows inside it: from their own diagonal tile on
         if (j0 > 0)
@@ -431,111 +420,90 @@ int syrk_upper(algp_ctx* c, int klass, const T* X, int64_t npad, int64_t ldx, T*
 ALGP_INSTANTIATE(syrk_upper);
 ALGP_INSTANTIATE(trinv_upper);
 
-// (A divide-and-conquer order of this sweep was measured in round 1: same time, 339 GB instead of 200 GB of HBM
-// traffic per solve at N = 10 000, M = 100 000 -- the big off-diagonal blocks of L fall out of the 4 MB L2s -- and removed.)
-template <typename T>
-static int trsm_rows(algp_ctx* c, int klass, T* X, int64_t mpad, int64_t ldx, const T* L, int64_t npad,
-                     int64_t ldl, const T* invD, int64_t col_start, bool whole_solve, const T* stat_w = nullptr,
-                     T* stat_out = nullptr, int64_t stat_ld = 0, const T* inv512 = nullptr, T* tmp512 = nullptr,
-                     const RhsGen* gen = nullptr) {
-    return trsm_rows_blocked<T>(c, klass, X, mpad, ldx, L, npad, ldl, invD, col_start, whole_solve, stat_w, stat_out, stat_ld, inv512,
-                                tmp512, gen);
-}
-
-static hipEvent_t sync_event(algp_ctx* c, size_t i) {
-    while (c->sync_events.size() <= i) {
-        hipEvent_t e;
-        hipEventCreateWithFlags(&e, hipEventDisableTiming);
-        c->sync_events.push_back(e);
-    }
-    return c->sync_events[i];
-}
-
-// The rows of X (candidates) are independent, so a tall X is solved as row chunks on streams of their own (three by
+// How a solve of this shape runs (TrsmPlan, common.h): the only reader of $ALGP_TRSM_INV512, $ALGP_TRSM_SCHED, the context's
+// chunk count and of whether the solve is on the context's own stream.  The order goes by the tile rows; the rest belongs to
+// the left-looking order, and all of it but the chunks to one where every row goes through it from its first column.
+// chunks: the rows of X (candidates) are independent, so a tall X is solved as row chunks on streams of their own (three by
 // default, algp_debug_set_trsm_chunks / $ALGP_TRSM_CHUNKS): the tail of every big GEMM of one chunk (1044 workgroups
 // over 512 resident slots: the last round is 4 % full) and its short HBM-bound in-block launches run beside the other
 // chunks' MFMA-bound GEMMs -- 84 % of the fp64 matrix peak against 78.5 % with the launches back to back on one stream.
-// What trsm_blocked asks before it takes the 512-block inverses, and the scheduled launches on top of them -- everything but
-// the buffers, which it can only try to get.  The candidate solve's plan asks the same function (fused right-hand sides).
-static bool trsm_inv512_wanted(const algp_ctx* c, int64_t mpad, int64_t npad, int64_t col_start) {
-    return env_switch("ALGP_TRSM_INV512", true) && col_start == 0 && mpad / NB > TRSM_PUSH_TILES && npad / WB >= 1 && c->cur == c->stream;
-}
-bool trsm_sched_wanted(const algp_ctx* c, int64_t mpad, int64_t npad, int64_t col_start) {
-    return trsm_inv512_wanted(c, mpad, npad, col_start) && !c->trsm_chunks_explicit && c->cu_count > 0 && env_switch("ALGP_TRSM_SCHED", true);
+// sched, the scheduled sweep (default): the same launches, one after the other on the caller's stream, each as a grid of 2 x CUs
+// workgroups that walk a balanced work list (gemm.hip, SCHED; gemm_sched.h) -- no partial last round, the next tile's first
+// k-tiles under the current tile's epilogue.  An explicit chunk count ($ALGP_TRSM_CHUNKS, algp_debug_set_trsm_chunks) or
+// $ALGP_TRSM_SCHED=0 keeps the row chunks; $ALGP_TRSM_INV512=0 the 128-column steps inside a block, as in rounds 1-3.
+TrsmPlan trsm_plan(const algp_ctx* c, int64_t mpad, int64_t npad, int64_t col_start, TrsmWants wants) {
+    const int64_t tiles = mpad / NB;
+    TrsmPlan p;
+    p.main_stream = c->cur == c->stream;
+    p.order = tiles <= 32 ? TrsmOrder::Short : (col_start == 0 && tiles <= TRSM_PUSH_TILES) ? TrsmOrder::Push : TrsmOrder::LeftLooking;
+    const bool from_zero = p.order == TrsmOrder::LeftLooking && col_start == 0;
+    p.stats = wants.stats && from_zero;
+    p.inv512 = from_zero && npad / WB >= 1 && p.main_stream && env_switch("ALGP_TRSM_INV512", true);
+    p.sched = p.inv512 && !c->trsm_chunks_explicit && c->cu_count > 0 && env_switch("ALGP_TRSM_SCHED", true);
+    p.gen = wants.gen && p.sched;
+    if (p.order == TrsmOrder::LeftLooking && p.main_stream) {
+        const hipStream_t streams[4] = {c->stream, c->stream2, c->stream3, c->stream4};
+        p.chunks = c->trsm_chunks < 1 ? 1 : (c->trsm_chunks > 4 ? 4 : c->trsm_chunks);
+        while (p.chunks > 1 && (!streams[p.chunks - 1] || tiles < 32 * p.chunks)) --p.chunks;
+    }
+    return p;
 }
 
 template <typename T>
-int trsm_blocked(algp_ctx* c, int klass, T* X, int64_t mpad, int64_t ldx, const T* L, int64_t npad,
-                 int64_t ldl, const T* invD, int64_t col_start, const T* stat_w, T* stat_out, int64_t stat_ld, bool* stats_done,
-                 const RhsGen* gen) {
-    const int64_t tiles = mpad / NB;
-    // row statistics ride along where every row goes through the left-looking order from its first column
-    const bool stats = stat_out && stat_w && col_start == 0 && tiles > TRSM_PUSH_TILES;
-    if (stats_done) *stats_done = stats;
-    if (!stats) stat_out = nullptr;
-    // the left-looking order from column 0 (the same condition): 512-block inverses, one scratch of mpad x 512 for all chunks
-    // ($ALGP_TRSM_INV512=0: the 128-column steps inside a block, as in rounds 1-3)
-    const T* inv512 = nullptr;
-    T* tmp512 = nullptr;
-    {
-        if (trsm_inv512_wanted(c, mpad, npad, col_start) &&                                         // (switches read per call: tests flip them)
-            ensure(c, c->inv512, sizeof(T) * (size_t)(npad / WB) * WB * WB) == ALGP_OK &&
-            ensure(c, c->inv512_scr, sizeof(T) * inv512_scratch_elems<T>(npad)) == ALGP_OK &&
-            ensure(c, c->trsm_tmp, sizeof(T) * (size_t)mpad * WB) == ALGP_OK) {
-            ALGP_TRY(build_inv512<T>(c, klass, L, ldl, invD, npad, (T*)c->inv512.p, (T*)c->inv512_scr.p));
-            inv512 = (const T*)c->inv512.p;
-            tmp512 = (T*)c->trsm_tmp.p;
-        }
-    }
-    // The scheduled sweep (default): the same launches, one after the other on the caller's stream, each as a grid of 2 x CUs
-    // workgroups that walk a balanced work list (gemm.hip, SCHED; gemm_sched.h) -- no partial last round, the next tile's first
-    // k-tiles under the current tile's epilogue.  An explicit chunk count ($ALGP_TRSM_CHUNKS, algp_debug_set_trsm_chunks) or
-    // $ALGP_TRSM_SCHED=0 (read per call: tests flip it) keeps the row chunks below.  The partials scratch of the cut leftover
-    // tiles is provided here: nothing is allocated inside the sweep.
-    const bool sched = inv512 && trsm_sched_wanted(c, mpad, npad, col_start) &&
-                       ensure(c, c->gemm_part, sizeof(T) * 128 * 128 * 2 * (size_t)c->cu_count) == ALGP_OK;
-    // Right-hand sides that were to be generated (gen): the scheduled sweep takes them as they are; every other order reads
-    // them from X, so they are written there first, all of them, and the solve proceeds as it always has.
-    if (gen && !sched) {
-        ALGP_TRY(gen->window(c, 0, npad, X, ldx));
-        gen = nullptr;
-    }
-    if (inv512) {
+int trsm_blocked(algp_ctx* c, const TrsmOp<T>& op, const TrsmOpt<T>& opt, TrsmPlan* ran) {
+    const int64_t mpad = op.mpad, npad = op.npad, tiles = mpad / NB;
+    TrsmPlan pl = trsm_plan(c, mpad, npad, opt.col_start, {.stats = opt.stats.out && opt.stats.w, .gen = opt.gen != nullptr});
+    // The one downgrade: a buffer could not be had.  Without the partials scratch of the cut leftover tiles (provided here:
+    // nothing is allocated inside the sweep) the launches are not scheduled; without the 512-block inverses, their scratch or
+    // the one scratch of mpad x 512 for all chunks, neither is taken.  Right-hand sides that were to be generated: the scheduled
+    // sweep takes them as they are; every other order reads them from X, so they are written there first, all of them, and
+    // the solve proceeds as it always has.
+    pl.inv512 = pl.inv512 && ensure(c, c->inv512, sizeof(T) * (size_t)(npad / WB) * WB * WB) == ALGP_OK &&
+                ensure(c, c->inv512_scr, sizeof(T) * inv512_scratch_elems<T>(npad)) == ALGP_OK &&
+                ensure(c, c->trsm_tmp, sizeof(T) * (size_t)mpad * WB) == ALGP_OK;
+    pl.sched = pl.sched && pl.inv512 && ensure(c, c->gemm_part, sizeof(T) * 128 * 128 * 2 * (size_t)c->cu_count) == ALGP_OK;
+    pl.gen = pl.gen && pl.sched;
+    if (ran) *ran = pl;
+    const TrsmInv512<T> blk = {(const T*)c->inv512.p, (T*)c->trsm_tmp.p, pl.gen ? opt.gen : nullptr}, *inv512 = pl.inv512 ? &blk : nullptr;
+    if (pl.inv512) ALGP_TRY(build_inv512<T>(c, op.klass, op.L, op.ldl, op.invD, npad, (T*)c->inv512.p, (T*)c->inv512_scr.p));
+    if (opt.gen && !pl.gen) ALGP_TRY(opt.gen->window(c, 0, npad, op.X, op.ldx));
+    if (pl.inv512) {
         // block 0's right-hand sides into the scratch: its product with inv(L_00)^T cannot run in place (a workgroup of column
         // tile c reads the tiles left of it in the same rows).  Generated: a 512-column window of the kernel-matrix build writes
         // them there; else a strided copy out of X.
-        if (gen) ALGP_TRY(gen->window(c, 0, WB, tmp512, WB));
-        else ALGP_HIP(hipMemcpy2DAsync(tmp512, sizeof(T) * WB, X, sizeof(T) * ldx, sizeof(T) * WB, (size_t)mpad, hipMemcpyDeviceToDevice, c->cur));
+        if (pl.gen) ALGP_TRY(opt.gen->window(c, 0, WB, blk.tmp, WB));
+        else ALGP_HIP(hipMemcpy2DAsync(blk.tmp, sizeof(T) * WB, op.X, sizeof(T) * op.ldx, sizeof(T) * WB, (size_t)mpad, hipMemcpyDeviceToDevice, c->cur));
     }
-    if (sched) {
-        c->gemm_sched = true;
-        const int rc = trsm_rows<T>(c, klass, X, mpad, ldx, L, npad, ldl, invD, col_start, true, stat_w, stat_out, stat_ld, inv512, tmp512, gen);
+    const TrsmStats<T> stats = {opt.stats.w, pl.stats ? opt.stats.out : nullptr, opt.stats.ld};
+    if (pl.order == TrsmOrder::Short) return trsm_short<T>(c, op, opt.col_start);
+    if (pl.order == TrsmOrder::Push) return trsm_push<T>(c, op, pl.main_stream);
+    if (pl.sched || pl.chunks == 1) {
+        c->gemm_sched = pl.sched;
+        const int rc = trsm_left<T>(c, op, opt.col_start, stats, inv512);
         c->gemm_sched = false;
         return rc;
     }
     hipStream_t streams[4] = {c->stream, c->stream2, c->stream3, c->stream4};
-    int nch = c->trsm_chunks < 1 ? 1 : (c->trsm_chunks > 4 ? 4 : c->trsm_chunks);
-    while (nch > 1 && (!streams[nch - 1] || tiles < 32 * nch)) --nch;
-    if (col_start == 0 && tiles <= TRSM_PUSH_TILES) nch = 1;    // the right-looking order fills the machine by itself
-    if (nch == 1 || c->cur != c->stream)
-        return trsm_rows<T>(c, klass, X, mpad, ldx, L, npad, ldl, invD, col_start, true, stat_w, stat_out, stat_ld, inv512, tmp512);
-    ALGP_HIP(hipEventRecord(sync_event(c, 0), streams[0]));
+    ALGP_HIP(hipEventRecord(sync_event(c, EV_CHUNK), streams[0]));
     int rc = ALGP_OK;
     int64_t r0 = 0;
-    for (int k = nch - 1; k >= 0; --k) {                       // helper streams first, the main stream last
-        const int64_t rows = (k == 0) ? mpad - r0 : (tiles / nch) * NB;
-        if (k > 0) ALGP_HIP(hipStreamWaitEvent(streams[k], sync_event(c, 0), 0));
+    for (int k = pl.chunks - 1; k >= 0; --k) {                       // helper streams first, the main stream last
+        TrsmOp<T> rows = op;                                   // this chunk's rows of X, of the statistics, of the scratch
+        rows.X = op.X + r0 * op.ldx;
+        rows.mpad = (k == 0) ? mpad - r0 : (tiles / pl.chunks) * NB;
+        const TrsmStats<T> rstats = {stats.w, stats.out ? stats.out + r0 : nullptr, stats.ld};
+        const TrsmInv512<T> rblk = {blk.inv, inv512 ? blk.tmp + r0 * WB : nullptr, nullptr};
+        if (k > 0) ALGP_HIP(hipStreamWaitEvent(streams[k], sync_event(c, EV_CHUNK), 0));
         c->cur = streams[k];
-        if (rc == ALGP_OK)
-            rc = trsm_rows<T>(c, klass, X + r0 * ldx, rows, ldx, L, npad, ldl, invD, col_start, false, stat_w,
-                              stat_out ? stat_out + r0 : nullptr, stat_ld, inv512, tmp512 ? tmp512 + r0 * WB : nullptr);
-        r0 += rows;
+        if (rc == ALGP_OK)           // (a chunk of exactly 32 tile rows is a short X, as it always was: with kept columns only)
+            rc = rows.mpad <= 32 * NB ? trsm_short<T>(c, rows, opt.col_start) : trsm_left<T>(c, rows, opt.col_start, rstats, inv512 ? &rblk : nullptr);
+        r0 += rows.mpad;
     }
     c->cur = streams[0];
     // the main stream continues only after every chunk is done (also on the error path)
-    for (int k = 1; k < nch; ++k) {
-        hipEventRecord(sync_event(c, (size_t)k), streams[k]);
-        hipStreamWaitEvent(streams[0], sync_event(c, (size_t)k), 0);
+    for (int k = 1; k < pl.chunks; ++k) {
+        hipEventRecord(sync_event(c, EV_CHUNK + (size_t)k), streams[k]);
+        hipStreamWaitEvent(streams[0], sync_event(c, EV_CHUNK + (size_t)k), 0);
     }
     return rc;
 }

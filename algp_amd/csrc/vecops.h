@@ -128,8 +128,7 @@ int mi_score_launch(algp_ctx* c, int64_t M, const int* ckind, const int64_t* cid
 // MI criterion dealt over ranks (mi_shard.hip): a rank's row blocks t g + member of X = L^-T (nloc of them, X zeroed here),
 // its pieces of a pick's column with the earlier picks' terms removed, and a whole vector put together from gathered pieces
 template <typename T>
-int mi_trinv_rows(algp_ctx* c, int klass, T* X, int64_t ldx, int64_t nloc, int g, int member, const T* L, int64_t ldl,
-                  int64_t npad, const T* invD);
+int mi_trinv_rows(algp_ctx* c, const TrsmOp<T>& op, int64_t nloc, int g, int member);
 template <typename T>
 int mi_cols_local_launch(algp_ctx* c, int64_t rows, int g, int member, int64_t m, const T* raw, const T* U, int64_t ldu,
                          const double* sgn, int q, int64_t cpos, T* out);
