@@ -41,6 +41,8 @@ SIGNATURES = {
     'algp_last_jitter': (C.c_double, [_c_ctx]),
     'algp_dtype': (C.c_int, [_c_ctx]),
     'algp_set_hypers': (C.c_int, [_c_ctx, C.c_int, C.c_int, _dblp, C.c_double, C.c_double]),
+    'algp_set_hypers_additive': (C.c_int, [_c_ctx, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, _dblp,
+                                           C.c_double]),
     'algp_kernel_matrix': (C.c_int, [_c_ctx, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int,
                                      C.c_void_p]),
     'algp_set_pool': (C.c_int, [_c_ctx, C.c_void_p, C.c_int64]),
@@ -65,6 +67,7 @@ SIGNATURES = {
     'algp_get_posterior': (C.c_int, [_c_ctx, C.c_void_p, C.c_void_p]),
     'algp_get_posterior_cov': (C.c_int, [_c_ctx, C.c_void_p, _dblp]),
     'algp_posterior_mean': (C.c_int, [_c_ctx, _i64p, C.c_int64, C.c_void_p]),
+    'algp_posterior_mean_component': (C.c_int, [_c_ctx, C.c_int, _i64p, C.c_int64, C.c_void_p]),
     'algp_sample_posterior': (C.c_int, [_c_ctx, C.c_int, C.c_int, _dblp, _dblp, _dblp, _dblp, _dblp, C.c_void_p]),
     'algp_group_posterior': (C.c_int, [_c_ctx, C.POINTER(C.c_int32), _dblp, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     'algp_scores': (C.c_int, [_c_ctx, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_int]),
@@ -207,6 +210,23 @@ class Context(object):
         self.D = len(ls)
         self._check(self.lib.algp_set_hypers(self.h, int(kernel), len(ls), ls.ctypes.data_as(_dblp),
                                              float(log_outputscale), float(log_noise)))
+        self.additive = False
+
+    def set_hypers_additive(self, log_lengthscale, split, log_outputscale_a, log_outputscale_b, log_noise,
+                            kernel_a=KERNEL_RBF, kernel_b=KERNEL_RBF):
+        """The additive kernel os_a kappa_a(r_a) + os_b kappa_b(r_b): r_a over the first `split` coordinates, r_b over the
+        others; log_lengthscale has one entry per coordinate (algp_set_hypers_additive).  A refusal (ValueError) leaves the
+        hyper-parameters in force untouched."""
+        ls = np.ascontiguousarray(np.atleast_1d(log_lengthscale), dtype=np.float64)
+        self._check(self.lib.algp_set_hypers_additive(self.h, len(ls), int(kernel_a), int(split), float(log_outputscale_a),
+                                                      int(kernel_b), float(log_outputscale_b), ls.ctypes.data_as(_dblp),
+                                                      float(log_noise)))
+        self.D = len(ls)
+        self.additive = True
+
+    def _n_grad(self):
+        # D + 2 for a single kernel, D + 3 under the additive one (two outputscales)
+        return self.D + (3 if getattr(self, 'additive', False) else 2)
 
     def _check_width(self, x, what):
         """The C side reads n * D values: a wrong-width array would be over-read or silently reinterpreted."""
@@ -300,8 +320,9 @@ class Context(object):
         return self._get_double(self.lib.algp_get_mll)
 
     def mll_grad(self):
-        """d MLL / d (log_lengthscale[D], log_outputscale, log_noise); not divided by N."""
-        g = np.empty(self.D + 2, dtype=np.float64)
+        """d MLL / d (log_lengthscale[D], log_outputscale, log_noise); not divided by N.  Under the additive kernel:
+        (log_lengthscale[D], log_outputscale_a, log_outputscale_b, log_noise)."""
+        g = np.empty(self._n_grad(), dtype=np.float64)
         self._check(self.lib.algp_get_mll_grad(self.h, g.ctypes.data_as(_dblp)))
         return g
 
@@ -309,7 +330,7 @@ class Context(object):
         """(mll, grad): factorisation, marginal log likelihood and its gradient for the current hyper-parameters in one
         call -- the device work of one iteration of GPR.fit (algp_fit_step).  want_mll=False / want_grad=False pass NULL
         for that output (the ABI then skips its work) and return None in its place."""
-        g = np.empty(self.D + 2, dtype=np.float64) if want_grad else None
+        g = np.empty(self._n_grad(), dtype=np.float64) if want_grad else None
         v = C.c_double()
         self._check(self.lib.algp_fit_step(self.h, C.byref(v) if want_mll else None,
                                            g.ctypes.data_as(_dblp) if want_grad else None))
@@ -370,6 +391,14 @@ class Context(object):
         idx = self._idx(idx)
         mu = np.empty(len(idx), dtype=self.dtype)
         self._check(self.lib.algp_posterior_mean(self.h, _i64(idx), len(idx), _ptr(mu)))
+        return mu
+
+    def posterior_mean_component(self, component, idx):
+        """One part's share of the posterior mean under the additive kernel (0: the first coordinates' part, 1: the other),
+        without the constant mean: component 0 + component 1 + mean(train y) = posterior_mean (algp_posterior_mean_component)."""
+        idx = self._idx(idx)
+        mu = np.empty(len(idx), dtype=self.dtype)
+        self._check(self.lib.algp_posterior_mean_component(self.h, int(component), _i64(idx), len(idx), _ptr(mu)))
         return mu
 
     def sample_posterior(self, eps, weights=None, omega=None, phase=None, prior=None):

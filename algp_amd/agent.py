@@ -80,8 +80,14 @@ class Agent(object):
 
     # ---- model plumbing (agent.py:34-45) --------------------------------------------------------
     def _init_model(self, args):
+        nu = getattr(args, 'matern_nu', 1.5)
+        kernel_params = {'type': args.kernel, 'nu': nu}
+        if args.kernel == 'additive':
+            kernel_params = {'type': 'additive', 'split': getattr(args, 'kernel_split', 2),
+                             'parts': ({'type': getattr(args, 'kernel_a', 'matern'), 'nu': nu},
+                                       {'type': getattr(args, 'kernel_b', 'rbf'), 'nu': nu})}
         self.gp = GPR(latent=args.latent, lr=args.lr, max_iterations=args.max_iterations,
-                      kernel_params={'type': args.kernel, 'nu': getattr(args, 'matern_nu', 1.5)}, learn_likelihood_noise=self.learn_likelihood_noise,
+                      kernel_params=kernel_params, learn_likelihood_noise=self.learn_likelihood_noise,
                       dtype=getattr(args, 'dtype', np.float64), device=getattr(args, 'device', 0))
 
     def load_model(self, parent_agent):
@@ -317,7 +323,7 @@ class Agent(object):
             self._pctx = _hip.Context(self.gp.dtype, self.gp.device)
         c = self._pctx
         if key != self._pctx_key:
-            c.set_hypers(hkey[0], hkey[1], hkey[2], hkey[3])
+            self.gp.push_hypers(c)
             c.set_pool(np.vstack([np.asarray(self.env.X, np.float64).reshape(n, -1),
                                   np.asarray(self.env.test_X, np.float64).reshape(m, -1)]))
             self._pctx_key = key
@@ -771,7 +777,7 @@ class Agent(object):
         hk = self.gp.hypers()
         c = _hip.Context(self.gp.dtype, self.gp.device)
         try:
-            c.set_hypers(hk[0], hk[1], hk[2], hk[3])
+            self.gp.push_hypers(c)
             c.set_pool(np.vstack([x_rows, test_x]))                 # every collected sample is a pool entry of its own
             test_idx = np.arange(len(x_rows), len(x_rows) + len(test_x))
             for r in range(1, num_runs + 1):

@@ -166,6 +166,11 @@ KmatSrc make_src(algp_ctx* c) {
     s.kernel = c->hyp.kernel;
     s.outputscale = c->hyp.outputscale;
     s.noise = c->hyp.noise;
+    if (c->hyp.additive) {
+        s.kernel_b = c->hyp.kernel_b;
+        s.da = c->hyp.Da;
+        s.outputscale_b = c->hyp.outputscale_b;
+    }
     return s;
 }
 
@@ -570,10 +575,41 @@ int algp_set_hypers(algp_ctx* c, int kernel, int D, const double* log_ls, double
         c->pos_in_train.clear();
     }
     c->hyp.kernel = kernel;
+    c->hyp.additive = false;
     c->hyp.D = D;
     c->hyp.DP = D <= 2 ? 2 : (D <= 4 ? 4 : 8);
     for (int d = 0; d < MAXD; ++d) c->hyp.inv_ls[d] = d < D ? exp(-log_ls[d]) : 0.0;
     c->hyp.outputscale = exp(log_os);
+    c->hyp.noise = exp(log_noise);
+    c->hyp.set = true;
+    c->hyp_stamp++;
+    c->factored = false;
+    c->solved = false;
+    FINISH(c, DISPATCH(c, rescale_pool(c)));
+}
+
+int algp_set_hypers_additive(algp_ctx* c, int D, int kernel_a, int Da, double log_os_a, int kernel_b, double log_os_b,
+                             const double* log_ls, double log_noise) {
+    CHECK_CTX(c);
+    if (D < 2 || D > MAXD || !log_ls) return fail(c, ALGP_ERR_BAD_ARG, "set_hypers_additive: 2 <= D <= 8 required");
+    if (Da < 1 || Da > D - 1) return fail(c, ALGP_ERR_BAD_ARG, "set_hypers_additive: 1 <= Da <= D - 1 required");
+    if (kernel_a < ALGP_KERNEL_RBF || kernel_a > ALGP_KERNEL_MATERN25 || kernel_b < ALGP_KERNEL_RBF || kernel_b > ALGP_KERNEL_MATERN25)
+        return fail(c, ALGP_ERR_BAD_ARG, "set_hypers_additive: unknown kernel");
+    // everything from here on as algp_set_hypers does it
+    if (c->hyp.set && c->hyp.D != D && c->n_pool > 0 && !c->pool_is_cov) {
+        c->n_pool = 0;
+        c->N = 0;
+        c->pos_in_train.clear();
+    }
+    c->hyp.kernel = kernel_a;
+    c->hyp.additive = true;
+    c->hyp.kernel_b = kernel_b;
+    c->hyp.Da = Da;
+    c->hyp.D = D;
+    c->hyp.DP = D <= 2 ? 2 : (D <= 4 ? 4 : 8);
+    for (int d = 0; d < MAXD; ++d) c->hyp.inv_ls[d] = d < D ? exp(-log_ls[d]) : 0.0;
+    c->hyp.outputscale = exp(log_os_a);
+    c->hyp.outputscale_b = exp(log_os_b);
     c->hyp.noise = exp(log_noise);
     c->hyp.set = true;
     c->hyp_stamp++;

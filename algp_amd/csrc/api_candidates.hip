@@ -162,7 +162,7 @@ void Impl<T>::plan_route(algp_ctx* c, int incremental, bool allow_fold, typename
     // read back -- the update products generate their C tiles.  Two scaled coordinates per site only (rhs_gen_supported): wider
     // coordinates and an explicit pool covariance keep the kernel-matrix launch.
     pl.rhs_fused = pl.route == SolveRoute::Sweep && keep == 0 && M > 0 && env_switch("ALGP_RHS_FUSED", true) &&
-                   trsm_plan(c, pl.sweep_rows, pl.sweep_end, keep, {.gen = true}).gen && rhs_gen_supported(c->hyp.DP, c->pool_is_cov);
+                   trsm_plan(c, pl.sweep_rows, pl.sweep_end, keep, {.gen = true}).gen && rhs_gen_supported(c->hyp.DP, c->pool_is_cov, c->hyp.additive);
 }
 
 template <typename T>
@@ -360,7 +360,7 @@ int Impl<T>::solve_finish(algp_ctx* c, int incremental, const unsigned char* ali
             ALGP_TRY(rows_reduce_launch<T>(c, p(c->Vt), M, ldc, Npad, p(c->z), ss, dot));
         }
     }
-    const T prior = (T)(c->hyp.outputscale + (c->prior_noise ? c->hyp.noise : 0.0));
+    const T prior = (T)(c->hyp.prior_var() + (c->prior_noise ? c->hyp.noise : 0.0));
     ALGP_TRY(cand_finalize_launch<T>(c, M, (const int*)c->ckind.p, (const int64_t*)c->Cidx.p,
                                      c->pool_is_cov ? (const T*)c->Cp.p : nullptr, c->n_pool, prior,
                                      c->cextra.p ? (const T*)c->cextra.p : nullptr, ss, dot, (T)c->ybar, p(c->dstat),
@@ -498,7 +498,7 @@ int Impl<T>::get_posterior_cov(algp_ctx* c, void* cov_out, double* mi_out) {
     // visible divergence in a regime where the reference's own number carries no information.
     const double eps = sizeof(T) == 8 ? 2.220446049250313e-16 : 1.1920928955078125e-07;
     for (int attempt = 0;; ++attempt) {
-        const double jitter = attempt == 0 ? 0.0 : 64.0 * eps * c->hyp.outputscale * pow(100.0, attempt - 1);
+        const double jitter = attempt == 0 ? 0.0 : 64.0 * eps * c->hyp.prior_var() * pow(100.0, attempt - 1);
         // cov_xx = K_xx + diag(test_var)   (utils.py:297; no likelihood noise)
         ALGP_TRY(kmat_launch<T>(c, s, (const int64_t*)c->Cidx.p, M, Mpad, (const int64_t*)c->Cidx.p, M, Mpad, extra, 0,
                                 nullptr, 1, p(c->auxA), Mpad));
@@ -530,7 +530,7 @@ int Impl<T>::get_posterior_cov(algp_ctx* c, void* cov_out, double* mi_out) {
 
 
 template <typename T>
-int Impl<T>::posterior_mean(algp_ctx* c, const int64_t* idx, int64_t M, void* mu_out) {
+int Impl<T>::posterior_mean(algp_ctx* c, const int64_t* idx, int64_t M, void* mu_out, int parts) {
     if (!c->factored || c->train_dirty) return fail(c, ALGP_ERR_STATE, "posterior_mean: call algp_factorize first");
     if (c->pool_is_cov) return fail(c, ALGP_ERR_BAD_ARG, "posterior_mean needs a coordinate pool");
     if (M == 0) return ALGP_OK;
@@ -538,8 +538,11 @@ int Impl<T>::posterior_mean(algp_ctx* c, const int64_t* idx, int64_t M, void* mu
     ALGP_TRY(ensure(c, c->auxD, sizeof(T) * M));
     ALGP_HIP(hipMemcpyAsync(c->auxIdx.p, idx, sizeof(int64_t) * M, hipMemcpyHostToDevice, c->stream));
     ALGP_TRY(need_alpha(c));
-    ALGP_TRY(kgemv_launch<T>(c, M, (const int64_t*)c->auxIdx.p, make_src(c), c->N, (const int64_t*)c->Aidx.p,
-                             (const T*)c->alpha.p, (T)c->ybar, p(c->auxD)));
+    // parts != 3 (algp_posterior_mean_component): one part of the additive kernel switched off, and no constant mean
+    KmatSrc s = make_src(c);
+    s.parts = parts;
+    ALGP_TRY(kgemv_launch<T>(c, M, (const int64_t*)c->auxIdx.p, s, c->N, (const int64_t*)c->Aidx.p,
+                             (const T*)c->alpha.p, parts == 3 ? (T)c->ybar : (T)0, p(c->auxD)));
     ALGP_HIP(hipMemcpyAsync(mu_out, c->auxD.p, sizeof(T) * M, hipMemcpyDeviceToHost, c->stream));
     const int rc = sync_checked(c, "posterior_mean");
     if (rc != ALGP_OK) c->alpha_valid = false;
@@ -601,6 +604,18 @@ int algp_posterior_mean(algp_ctx* c, const int64_t* idx, int64_t M, void* mu) {
     for (int64_t i = 0; i < M; ++i)
         if (idx[i] < 0 || idx[i] >= c->n_pool) return fail(c, ALGP_ERR_BAD_ARG, "posterior_mean: index outside the pool");
     FINISH(c, DISPATCH(c, posterior_mean(c, idx, M, mu)));
+}
+
+int algp_posterior_mean_component(algp_ctx* c, int component, const int64_t* idx, int64_t M, void* mu) {
+    CHECK_CTX(c);
+    if (component < 0 || component > 1) return fail(c, ALGP_ERR_BAD_ARG, "posterior_mean_component: component must be 0 or 1");
+    if (M < 0 || (M > 0 && (!idx || !mu))) return fail(c, ALGP_ERR_BAD_ARG, "posterior_mean_component: bad arguments");
+    if (c->pool_is_cov) return fail(c, ALGP_ERR_BAD_ARG, "posterior_mean_component needs a coordinate pool");
+    if (!c->hyp.set || !c->hyp.additive)
+        return fail(c, ALGP_ERR_STATE, "posterior_mean_component: a single kernel is in force (algp_set_hypers_additive)");
+    for (int64_t i = 0; i < M; ++i)
+        if (idx[i] < 0 || idx[i] >= c->n_pool) return fail(c, ALGP_ERR_BAD_ARG, "posterior_mean_component: index outside the pool");
+    FINISH(c, DISPATCH(c, posterior_mean(c, idx, M, mu, 1 << component)));
 }
 
 }  // extern "C"

@@ -30,16 +30,29 @@ int Impl<T>::mll_grad(algp_ctx* c, double* grad_out, bool have_X, bool inv_enque
     }
     if (inv_enqueued) ALGP_HIP(hipStreamWaitEvent(c->stream, sync_event(c, EV_INV_DONE), 0));
     else ALGP_TRY(syrk_upper<T>(c, ALGP_PROF_GEMM_OTHER, p(c->auxW), Npad, Npad, p(c->auxA), Npad));
-    double* sc = (double*)c->scal.p + SC_GRAD;        // slots 16..27: os, trace, ls[0..8)
+    double* sc = (double*)c->scal.p + SC_GRAD;        // slots 16..27: os, trace, ls[0..8); additive: os_a, os_b, trace, ls[0..8)
     ALGP_HIP(hipMemsetAsync(sc, 0, sizeof(double) * 12, c->stream));
-    ALGP_TRY(mll_grad_launch<T>(c, p(c->auxA), Npad, N, (const T*)c->Xs.p, DP, (const int64_t*)c->Aidx.p,
-                                (const T*)c->alpha.p, c->hyp.kernel, (T)c->hyp.outputscale, sc,
-                                (double*)c->auxW.p /* X = L^-T is spent: room for the per-workgroup partials */));
+    const bool add = c->hyp.additive;
+    if (add)
+        ALGP_TRY(mll_grad_add_launch<T>(c, p(c->auxA), Npad, N, (const T*)c->Xs.p, DP, (const int64_t*)c->Aidx.p, (const T*)c->alpha.p,
+                                        c->hyp.kernel, (T)c->hyp.outputscale, c->hyp.kernel_b, (T)c->hyp.outputscale_b, c->hyp.Da, sc,
+                                        (double*)c->auxW.p));
+    else
+        ALGP_TRY(mll_grad_launch<T>(c, p(c->auxA), Npad, N, (const T*)c->Xs.p, DP, (const int64_t*)c->Aidx.p,
+                                    (const T*)c->alpha.p, c->hyp.kernel, (T)c->hyp.outputscale, sc,
+                                    (double*)c->auxW.p /* X = L^-T is spent: room for the per-workgroup partials */));
     double h[12];
     ALGP_HIP(hipMemcpyAsync(h, sc, sizeof(h), hipMemcpyDeviceToHost, c->stream));
     {
         const int rc = sync_checked(c, "get_mll_grad");
         if (rc != ALGP_OK) { c->alpha_valid = false; return rc; }
+    }
+    if (add) {                                        // D + 3: [log ls | log os_a, log os_b, log sigma_n^2]
+        for (int d = 0; d < D; ++d) grad_out[d] = 0.5 * h[3 + d];
+        grad_out[D] = 0.5 * h[0];
+        grad_out[D + 1] = 0.5 * h[1];
+        grad_out[D + 2] = 0.5 * c->hyp.noise * h[2];
+        return ALGP_OK;
     }
     for (int d = 0; d < D; ++d) grad_out[d] = 0.5 * h[2 + d];
     grad_out[D] = 0.5 * h[0];

@@ -114,7 +114,8 @@ struct Impl {
     static int fit_and_solve(algp_ctx* c);
     static int get_posterior(algp_ctx* c, void* mu, void* var);
     static int get_posterior_cov(algp_ctx* c, void* cov_out, double* mi_out);
-    static int posterior_mean(algp_ctx* c, const int64_t* idx, int64_t M, void* mu_out);
+    // parts: KmatSrc::parts -- 3: the posterior mean; 1, 2: one part's share of it under the additive kernel, without ybar
+    static int posterior_mean(algp_ctx* c, const int64_t* idx, int64_t M, void* mu_out, int parts = 3);
     // joint draws of the latent field at the candidates by pathwise conditioning (api_sample.hip)
     static int sample_posterior(algp_ctx* c, int S, int F, const double* omega, const double* phase, const double* weights,
                                 const double* prior, const double* eps, void* out);

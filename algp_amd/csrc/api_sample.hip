@@ -75,7 +75,7 @@ int Impl<T>::sample_posterior(algp_ctx* c, int S, int F, const double* omega, co
         ALGP_TRY(sample_convert_launch<T>(c, stC, F, D, om, Fpad, DP, DP, 0));
         ALGP_TRY(sample_convert_launch<T>(c, stC + (size_t)F * D, 1, F, ph, 1, Fpad, Fpad, 0));
     }
-    const T scale = F > 0 ? (T)sqrt(2.0 * c->hyp.outputscale / (double)F) : (T)1;
+    const T scale = F > 0 ? (T)sqrt(2.0 * c->hyp.prior_var() / (double)F) : (T)1;
     for (int64_t s0 = 0; s0 < S; s0 += SAMPLE_TILE) {
         const int sl = (int)std::min<int64_t>(SAMPLE_TILE, S - s0);
         if (F > 0) {

@@ -6,6 +6,7 @@
 #include <functional>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 #include "../../include/algp_hip.h"
 
@@ -53,6 +54,12 @@ struct Hypers {
     double inv_ls[MAXD] = {0};
     double outputscale = 1.0, noise = 1.0;
     bool set = false;
+    // the additive form (algp_set_hypers_additive): k = os kappa_kernel(r_a) + os_b kappa_kernel_b(r_b), r_a over the first Da
+    // coordinates and r_b over the others; kernel / outputscale above are part a's
+    bool additive = false;
+    int kernel_b = ALGP_KERNEL_RBF, Da = 0;
+    double outputscale_b = 0.0;
+    double prior_var() const { return additive ? outputscale + outputscale_b : outputscale; }   // K_jj
 };
 
 struct PickRec {           // one committed greedy pick, host side (the device keeps a LazyPick with the row's scale)
@@ -251,6 +258,39 @@ __device__ __forceinline__ T kmat_value(int kernel, T os, const T (&xr)[DP], con
     }
     return kval<T, FAM>(kernel, os, r2);
 }
+// The additive form, a third family (2) beside the two above: k = os_a kappa_a(r_a) + os_b kappa_b(r_b), r_a over the first da
+// scaled coordinates, r_b over the others (the zero padding adds nothing).  It is compiled as instantiations of its own (the
+// matrix build's FAM = 2, a source type of its own for pool_cov below, fit.hip's second gradient kernel), so that the code the
+// single forms run stays what it was.  ONE definition of the two squared distances and of the sum for every site: each
+// square rounded on its own and added in coordinate order (contraction off), so the matrix build, the criteria and the gradient
+// see the same r_a^2, r_b^2 and the same value for a pair of sites.
+template <int DP, typename C, typename XA, typename XB>
+__device__ __forceinline__ void split_r2(const XA* xa, const XB* xb, int da, C& ra, C& rb) {
+#pragma clang fp contract(off)
+    ra = (C)0;
+    rb = (C)0;
+#pragma unroll
+    for (int d = 0; d < DP; ++d) {
+        const C df = (C)xa[d] - (C)xb[d];
+        const C q = df * df;
+        ra += d < da ? q : (C)0;
+        rb += d < da ? (C)0 : q;
+    }
+}
+// parts: bit 0 = part a, bit 1 = part b (3: the kernel; one bit: a component of the posterior mean)
+template <typename T>
+__device__ __forceinline__ T kval_add(int ka, T osa, T ra, int kb, T osb, T rb, int parts = 3) {
+#pragma clang fp contract(off)
+    const T va = (parts & 1) ? kval<T>(ka, osa, ra) : (T)0;
+    const T vb = (parts & 2) ? kval<T>(kb, osb, rb) : (T)0;
+    return va + vb;
+}
+template <typename T, int DP>
+__device__ __forceinline__ T kmat_value_add(int ka, T osa, int kb, T osb, int da, const T (&xr)[DP], const T (&xc)[DP]) {
+    T ra, rb;
+    split_r2<DP>(&xr[0], &xc[0], da, ra, rb);
+    return kval_add<T>(ka, osa, ra, kb, osb, rb);
+}
 // Entry (row, global column gcol) of the candidates' right-hand side B^T = K(candidates, train) as the matrix build writes it:
 // kind -1: an ordinary row, k(x_row, x_col) in the columns of the train set (gcol < ncols), 0 in the padding behind them;
 // kind >= 0: the unit row e_kind (a candidate that is a train site under prior_includes_noise); kind -2: a padding row, 0.
@@ -282,9 +322,29 @@ struct CovSrc {
 // xa, xb: the two sites' coordinates wherever the kernel holds them (registers, LDS, memory), in any type; computed in the type
 // of s.os.  S: a CovSrc, or any argument struct with its fields (the GEMM's VrGemmArgs, read in place: a CovSrc made from it in
 // the epilogue moved the address arithmetic around it).
+// The additive form's source: CovSrc (kernel, os: part a) and part b, the split and the parts that count.  A source type of its
+// own, so that a kernel instantiated for it is another kernel than the single forms' (never made for an explicit covariance)
+template <typename T, typename C = T>
+struct CovSrcAdd : CovSrc<T, C> {
+    int kernel_b, da, parts;
+    C os_b;
+};
+// S carries the additive fields (CovSrcAdd, or the GEMM's argument structs with the same fields appended)
+template <typename S, typename = void>
+struct is_additive : std::false_type {};
+template <typename S>
+struct is_additive<S, std::void_t<decltype(std::declval<S>().kernel_b)>> : std::true_type {};
+
 template <int DP, bool NOISE = true, typename S, typename XA, typename XB>
 __device__ __forceinline__ auto pool_cov(const S& s, int64_t pa, int64_t pb, const XA* xa, const XB* xb) {
-    using C = decltype(s.os);
+    using C = std::remove_cv_t<decltype(s.os)>;
+    if constexpr (is_additive<S>::value) {
+        C ra, rb;
+        split_r2<DP>(xa, xb, s.da, ra, rb);
+        C v = kval_add<C>(s.kernel, s.os, ra, s.kernel_b, s.os_b, rb, s.parts);
+        if (NOISE && pa == pb) v += s.noise;
+        return v;
+    }
     if (s.Cp) return (C)s.Cp[pa * s.n_pool + pb];
     C r2 = (C)0;
 #pragma unroll
@@ -521,12 +581,30 @@ struct KmatSrc {
     int kernel;
     double outputscale;
     double noise;        // sigma_n^2 added when pool indices coincide (coords mode only)
+    // the additive form (kernel_b >= 0; kernel / outputscale are then part a's): part b, the first da coordinates are part a's,
+    // parts: bit 0 = a, bit 1 = b counts (3 everywhere but in algp_posterior_mean_component)
+    int kernel_b = -1, da = 0, parts = 3;
+    double outputscale_b = 0;
+    bool additive() const { return kernel_b >= 0 && !Cp; }
 };
 // the device-side view of a source (CovSrc above).  The one place that says what `noise` means per pool kind: an explicit
 // covariance carries sigma_n^2 on its diagonal already, so nothing is added to it anywhere
 template <typename T, typename C = T>
 inline CovSrc<T, C> cov_src(const KmatSrc& s) {
     return {(const T*)s.Xs, (const T*)s.Cp, s.n_pool, s.kernel, (C)s.outputscale, (C)(s.Cp ? 0.0 : s.noise)};
+}
+// f(the typed source): a CovSrc, or a CovSrcAdd under the additive form -- the kernel's source type is a template argument, so
+// the additive form runs instantiations of its own
+template <typename T, typename C = T, typename F>
+inline void with_src(const KmatSrc& s, F&& f) {
+    if (s.additive()) {
+        CovSrcAdd<T, C> a;
+        static_cast<CovSrc<T, C>&>(a) = cov_src<T, C>(s);
+        a.kernel_b = s.kernel_b; a.da = s.da; a.parts = s.parts; a.os_b = (C)s.outputscale_b;
+        f(a);
+    } else {
+        f(cov_src<T, C>(s));
+    }
 }
 // The padded coordinate width (2, 4 or 8) as a compile-time constant: f(std::integral_constant<int, DP>{}), one launch line
 // per kernel instead of three
@@ -564,8 +642,9 @@ int rhs_gather_launch(algp_ctx* c, const T* Xs, int DP, const int64_t* ridx, int
 template <typename T>
 int gemm_nt_launch_gen(algp_ctx* c, int klass, int64_t m, int64_t n, int64_t k, T alpha, const T* A, int64_t lda, const T* B,
                        int64_t ldb, T beta, const RhsGen& gen, int64_t col0, T* D, int64_t ldd);
-// whether gemm_nt_launch_gen has a kernel for this generator (DP = 2; wider coordinates take the materialised route)
-bool rhs_gen_supported(int DP, bool pool_is_cov);
+// whether gemm_nt_launch_gen has a kernel for this generator (DP = 2; wider coordinates and the additive form take the
+// materialised route)
+bool rhs_gen_supported(int DP, bool pool_is_cov, bool additive = false);
 
 // out[r][c] for r<rows_pad, c<cols_pad (ld = ldo):
 //   r<rows && c<cols : value(ridx[r], cidx[c])  [+ diag terms when the pool indices coincide]

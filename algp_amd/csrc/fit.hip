@@ -108,6 +108,97 @@ __global__ __launch_bounds__(256) void mll_grad_kernel(const T* Sinv, int64_t ld
             (s_red[0][threadIdx.x] + s_red[1][threadIdx.x]) + (s_red[2][threadIdx.x] + s_red[3][threadIdx.x]);
 }
 
+// The additive kernel (common.h: family 2), a kernel of its own beside the two copies above: S = os_a kappa_a(r_a) + os_b kappa_b(r_b)
+// + ..., so dS/dlog os_a = K_a, dS/dlog os_b = K_b, and dS/dlog ls_d = dk_c u_d^2 with c the part that owns coordinate d (d < da: a).
+// Two kdk values per pair, from the two squared distances of split_r2's rule (each square rounded on its own, added in
+// coordinate order).  Per workgroup: [0] = os_a, [1] = os_b, [2] = noise trace, [3..3+DP) = ls -- 11 sums at most.  The same
+// tiles, staging and fixed-order reduction as mll_grad_kernel.
+template <typename T, int DP>
+__global__ __launch_bounds__(256) void mll_grad_add_kernel(const T* Sinv, int64_t ld, int64_t N, const T* Xs, const int64_t* aidx,
+                                                           const T* alpha, int kernel_a, T os_a, int kernel_b, T os_b, int da,
+                                                           int repeats, double* partial) {
+#pragma clang fp contract(off)
+    int bi = (int)((sqrt(8.0 * (double)blockIdx.x + 1.0) - 1.0) * 0.5);
+    while ((int64_t)(bi + 1) * (bi + 2) / 2 <= (int64_t)blockIdx.x) ++bi;
+    while ((int64_t)bi * (bi + 1) / 2 > (int64_t)blockIdx.x) --bi;
+    const int bj = (int)(blockIdx.x - (int64_t)bi * (bi + 1) / 2);
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    __shared__ T s_x[64][DP];
+    __shared__ T s_a[64];
+    __shared__ int64_t s_p[64];
+    if (threadIdx.x < 64) {
+        const int64_t i = (int64_t)bi * 64 + threadIdx.x;
+        const bool ok = i < N;
+        const int64_t pi = ok ? aidx[i] : 0;
+#pragma unroll
+        for (int d = 0; d < DP; ++d) s_x[threadIdx.x][d] = ok ? Xs[pi * DP + d] : (T)0;
+        s_a[threadIdx.x] = ok ? alpha[i] : (T)0;
+        s_p[threadIdx.x] = ok ? pi : (int64_t)-1;
+    }
+    const int64_t j = (int64_t)bj * 64 + tx;
+    double g_osa = 0, g_osb = 0, g_tr = 0, g_ls[DP];
+#pragma unroll
+    for (int d = 0; d < DP; ++d) g_ls[d] = 0;
+    T xj[DP], aj = (T)0;
+    int64_t pj = -2;
+#pragma unroll
+    for (int d = 0; d < DP; ++d) xj[d] = (T)0;
+    if (j < N) {
+        pj = aidx[j];
+#pragma unroll
+        for (int d = 0; d < DP; ++d) xj[d] = Xs[pj * DP + d];
+        aj = alpha[j];
+    }
+    __syncthreads();
+    if (j < N) {
+        for (int rr = 0; rr < 16; ++rr) {
+            const int li = ty * 16 + rr;
+            const int64_t i = (int64_t)bi * 64 + li;
+            if (i >= N || j > i) continue;
+            T u2[DP], ra = (T)0, rb = (T)0;
+#pragma unroll
+            for (int d = 0; d < DP; ++d) {
+                const T df = s_x[li][d] - xj[d];
+                u2[d] = df * df;
+                ra += d < da ? u2[d] : (T)0;
+                rb += d < da ? (T)0 : u2[d];
+            }
+            const T w = s_a[li] * aj - Sinv[i * ld + j];
+            const double m = (i == j) ? 1.0 : 2.0;
+            T dka, dkb;
+            const T ka = kdk<T>(kernel_a, os_a, ra, dka);
+            const T kb = kdk<T>(kernel_b, os_b, rb, dkb);
+            g_osa += m * (double)(w * ka);
+            g_osb += m * (double)(w * kb);
+            if (i == j) g_tr += (double)w;
+            else if (repeats && s_p[li] == pj) g_tr += 2.0 * (double)w;
+#pragma unroll
+            for (int d = 0; d < DP; ++d) g_ls[d] += m * (double)(w * (d < da ? dka : dkb) * u2[d]);
+        }
+    }
+    auto wsum = [](double v) {
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+        return v;
+    };
+    __shared__ double s_red[4][3 + DP];
+    g_osa = wsum(g_osa);
+    g_osb = wsum(g_osb);
+    g_tr = wsum(g_tr);
+#pragma unroll
+    for (int d = 0; d < DP; ++d) g_ls[d] = wsum(g_ls[d]);
+    if (tx == 0) {
+        s_red[ty][0] = g_osa;
+        s_red[ty][1] = g_osb;
+        s_red[ty][2] = g_tr;
+#pragma unroll
+        for (int d = 0; d < DP; ++d) s_red[ty][3 + d] = g_ls[d];
+    }
+    __syncthreads();
+    if (threadIdx.x < 3 + DP)
+        partial[(int64_t)blockIdx.x * (3 + DP) + threadIdx.x] =
+            (s_red[0][threadIdx.x] + s_red[1][threadIdx.x]) + (s_red[2][threadIdx.x] + s_red[3][threadIdx.x]);
+}
+
 // out[q] += sum over blocks of partial[b][q], q < nq: one workgroup, thread-strided then shuffle tree
 __global__ __launch_bounds__(256) void mll_grad_reduce_kernel(const double* partial, int64_t nblocks, int nq, double* out) {
     __shared__ double part[4];
@@ -145,5 +236,25 @@ int mll_grad_launch(algp_ctx* c, const T* Sinv, int64_t ld, int64_t N, const T* 
     return ALGP_OK;
 }
 ALGP_INSTANTIATE(mll_grad_launch);
+
+// the additive kernel's: out_dev[0] = os_a, [1] = os_b, [2] = noise trace, [3..3+DP) = ls
+template <typename T>
+int mll_grad_add_launch(algp_ctx* c, const T* Sinv, int64_t ld, int64_t N, const T* Xs, int DP, const int64_t* aidx, const T* alpha,
+                        int kernel_a, T os_a, int kernel_b, T os_b, int da, double* out_dev, double* partial) {
+    if (N <= 0) return ALGP_OK;
+    const int rp = c->train_has_repeats ? 1 : 0;
+    const unsigned nb = (unsigned)((N + 63) / 64);
+    ProfScope ps(c, ALGP_PROF_KMAT, 0.5 * (double)N * N * (3.0 * DP + 16.0), sizeof(T) * 0.5 * (double)N * N);
+    dim3 grid(nb * (nb + 1) / 2), blk(256);
+    with_dp(DP, [&](auto dp) {
+        hipLaunchKernelGGL((mll_grad_add_kernel<T, decltype(dp)::value>), grid, blk, 0, c->cur, Sinv, ld, N, Xs, aidx, alpha, kernel_a, os_a,
+                           kernel_b, os_b, da, rp, partial);
+    });
+    ALGP_HIP(hipGetLastError());
+    hipLaunchKernelGGL(mll_grad_reduce_kernel, dim3(1), dim3(256), 0, c->cur, partial, (int64_t)grid.x, 3 + DP, out_dev);
+    ALGP_HIP(hipGetLastError());
+    return ALGP_OK;
+}
+ALGP_INSTANTIATE(mll_grad_add_launch);
 
 }  // namespace algp

@@ -154,16 +154,25 @@ struct VrxGemmArgs : VrGemmArgs<T> {};
 template <typename T>
 struct VrxWGemmArgs : VrxGemmArgs<T> {};
 
+// The additive form of any of the argument structs above (and of PvrGemmArgs below): part b's fields appended, which is what
+// makes pool_cov take its additive branch (is_additive, common.h) and the launch a kernel of its own -- the single forms'
+// kernels, their arguments and their instructions stay what they were.
+template <typename T, typename Base>
+struct AddGemmArgs : Base {
+    int kernel_b, da, parts;
+    T os_b;
+};
+
 // C(prow, pcol) for the two epilogues below: pool_cov (common.h) over the launch's own source fields, the coordinates of the
 // row in registers and of the column staged in LDS, both at width MAXD
-template <typename T>
-__device__ __forceinline__ T vr_pool_cov(const VrGemmArgs<T>& g, int64_t prow, int64_t pcol, const T (&xrow)[MAXD], const T* xcol) {
+template <typename T, typename G>
+__device__ __forceinline__ T vr_pool_cov(const G& g, int64_t prow, int64_t pcol, const T (&xrow)[MAXD], const T* xcol) {
     return pool_cov<MAXD>(g, prow, pcol, &xrow[0], xcol);
 }
 
 // RECT: the columns are described by cpool (this slice's 128 x tiles_n pool indices) instead of cidx / ckind / M
-template <typename T, bool WEIGHTED, bool RECT, typename ACC>
-__device__ __forceinline__ void vr_epilogue(const VrGemmArgs<T>& g, char* smem, const ACC (&acc)[4][4], int64_t m0, int64_t n0, int bn,
+template <typename T, bool WEIGHTED, bool RECT, typename G, typename ACC>
+__device__ __forceinline__ void vr_epilogue(const G& g, char* smem, const ACC (&acc)[4][4], int64_t m0, int64_t n0, int bn,
                                             int wr, int wc, int lane, int tid, const int64_t* cpool = nullptr) {
     using F = MF<T>;
     const int fr = lane & 15;
@@ -273,8 +282,8 @@ struct PvrGemmArgs : VrGemmArgs<T> {
     int64_t lde;
 };
 
-template <typename T, typename ACC>
-__device__ __forceinline__ void pvr_epilogue(const PvrGemmArgs<T>& g, char* smem, const ACC (&acc)[4][4], int64_t m0, int64_t n0, int wr,
+template <typename T, typename G, typename ACC>
+__device__ __forceinline__ void pvr_epilogue(const G& g, char* smem, const ACC (&acc)[4][4], int64_t m0, int64_t n0, int wr,
                                              int wc, int lane, int tid) {
     using F = MF<T>;
     const int fr = lane & 15;
@@ -322,6 +331,9 @@ __device__ __forceinline__ void pvr_epilogue(const PvrGemmArgs<T>& g, char* smem
                 const T cv = vr_pool_cov<T>(g, prow, pcol, xrow, xc + col * MAXD);
                 const T sw = wcol[col];
                 Er[col] = (rowon && sw != (T)0) ? sw * (cv - acc[i][j][r]) : (T)0;
+                // the additive form evaluates two kernels per entry: one column after the other, or the scheduler overlaps the
+                // four and the fp64 kernel no longer fits its registers beside the accumulators (the single forms: as before)
+                if constexpr (is_additive<G>::value) __builtin_amdgcn_sched_barrier(0);
             }
         }
 }
@@ -557,11 +569,11 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel_dma4(Args g) {
         }
     }
 
-    if constexpr (std::is_same<Args, PvrGemmArgs<T>>::value) {
+    if constexpr (std::is_base_of<PvrGemmArgs<T>, Args>::value) {
         pvr_epilogue<T>(g, smem, acc, m0, n0, wr, wc, lane, tid);
         return;
     } else if constexpr (VR) {
-        constexpr bool WEIGHTED = std::is_same<Args, VrWGemmArgs<T>>::value || std::is_same<Args, VrxWGemmArgs<T>>::value;
+        constexpr bool WEIGHTED = std::is_base_of<VrWGemmArgs<T>, Args>::value || std::is_base_of<VrxWGemmArgs<T>, Args>::value;
         if constexpr (std::is_base_of<VrxGemmArgs<T>, Args>::value)
             vr_epilogue<T, WEIGHTED, true>(g, smem, acc, m0, n0, (int)bz * g.tiles_n + cur_bn, wr, wc, lane, tid,
                                            reinterpret_cast<const int64_t*>(reinterpret_cast<const char*>(g.cpool) +
@@ -961,7 +973,7 @@ int gemm_nt(algp_ctx* c, const GemmNt<T>& p) {
                     dim3((unsigned)gx, (unsigned)p.batch), g);
 }
 
-bool rhs_gen_supported(int DP, bool pool_is_cov) { return DP == 2 && !pool_is_cov; }
+bool rhs_gen_supported(int DP, bool pool_is_cov, bool additive) { return DP == 2 && !pool_is_cov && !additive; }
 
 // The scheduled update product with its C tile generated (GEN above): booked like the loading form -- the same flop; the C
 // tile's bytes are not read.
@@ -997,6 +1009,17 @@ static void vr_fill(VrGemmArgs<T>& g, const KmatSrc& s, const int64_t* cidx, con
     g.os = (T)s.outputscale; g.noise = (T)s.noise;
 }
 
+// the launch of one of the three forms below: the tile kernel for the argument struct as it is, or under the additive kernel for
+// its additive form (AddGemmArgs) -- instantiations of their own
+template <typename T, typename G>
+static int vr_dispatch(algp_ctx* c, int klass, const Booking& bk, dim3 grid, const G& g, const KmatSrc& s) {
+    if (!s.additive()) return dispatch(c, klass, bk.flops, bk.bytes, gemm_nt_kernel_dma4<T, false, G>, grid, g);
+    AddGemmArgs<T, G> a;
+    static_cast<G&>(a) = g;
+    a.kernel_b = s.kernel_b; a.da = s.da; a.parts = 3; a.os_b = (T)s.outputscale_b;
+    return dispatch(c, klass, bk.flops, bk.bytes, gemm_nt_kernel_dma4<T, false, AddGemmArgs<T, G>>, grid, a);
+}
+
 // The variance-reduction column sums of rows [0, mpad) of V^T against its rows [ncol0, ncol0 + n): per row and column
 // tile bn of the launch, part[bn * part_ld + row] = sum over the tile's target columns j of (kappa_row C(row, j) - V_row . V_j)^2,
 // the dot products over the first k columns, every column weighted by tw[its pool site] where tw is given.  Nothing else is
@@ -1014,10 +1037,10 @@ int gemm_nt_launch_vr(algp_ctx* c, int klass, int64_t mpad, int64_t n, int64_t k
     gemm_fill(g, p);
     vr_fill(g, s, cidx, ckind, M, ncol0, tw);
     const Booking bk = gemm_book(p, tiles, 128.0);
-    if (!tw) return dispatch(c, klass, bk.flops, bk.bytes, gemm_nt_kernel_dma4<T, false, VrGemmArgs<T>>, dim3((unsigned)tiles), g);
+    if (!tw) return vr_dispatch<T>(c, klass, bk, dim3((unsigned)tiles), g, s);
     VrWGemmArgs<T> gw;
     static_cast<VrGemmArgs<T>&>(gw) = g;
-    return dispatch(c, klass, bk.flops, bk.bytes, gemm_nt_kernel_dma4<T, false, VrWGemmArgs<T>>, dim3((unsigned)tiles), gw);
+    return vr_dispatch<T>(c, klass, bk, dim3((unsigned)tiles), gw, s);
 }
 ALGP_INSTANTIATE(gemm_nt_launch_vr);
 
@@ -1043,10 +1066,10 @@ int gemm_nt_launch_vrx(algp_ctx* c, int klass, int64_t mpad, int64_t n, int64_t 
     g.cpool = cpool;
     const Booking bk = gemm_book(p, tiles, 128.0);
     const dim3 grid((unsigned)tiles, (unsigned)nslices);
-    if (!tw) return dispatch(c, klass, bk.flops, bk.bytes, gemm_nt_kernel_dma4<T, false, VrxGemmArgs<T>>, grid, g);
+    if (!tw) return vr_dispatch<T>(c, klass, bk, grid, g, s);
     VrxWGemmArgs<T> gw;
     static_cast<VrGemmArgs<T>&>(gw) = g;
-    return dispatch(c, klass, bk.flops, bk.bytes, gemm_nt_kernel_dma4<T, false, VrxWGemmArgs<T>>, grid, gw);
+    return vr_dispatch<T>(c, klass, bk, grid, gw, s);
 }
 ALGP_INSTANTIATE(gemm_nt_launch_vrx);
 
@@ -1068,7 +1091,7 @@ int gemm_nt_launch_pvr(algp_ctx* c, int klass, int64_t upad, int64_t n, int64_t 
     vr_fill(g, s, cidx, ckind, M, ncol0, tw);
     g.uidx = uidx; g.U = U; g.E = E; g.lde = lde;
     const Booking bk = gemm_book(p, tiles, 128.0 * 128.0);
-    return dispatch(c, klass, bk.flops, bk.bytes, gemm_nt_kernel_dma4<T, false, PvrGemmArgs<T>>, dim3((unsigned)tiles), g);
+    return vr_dispatch<T>(c, klass, bk, dim3((unsigned)tiles), g, s);
 }
 ALGP_INSTANTIATE(gemm_nt_launch_pvr);
 

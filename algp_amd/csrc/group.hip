@@ -33,6 +33,16 @@ struct GroupCovSrc {
     int64_t n_pool;
     T os, noise;
 };
+// KERNEL = -1: the additive form -- the two forms, the split and part b's outputscale at run time (pool_cov's additive branch)
+template <typename T>
+struct GroupCovSrc<T, -1> {
+    static constexpr const T* Cp = nullptr;
+    const T* Xs;
+    int64_t n_pool;
+    T os, noise;
+    int kernel, kernel_b, da, parts;
+    T os_b;
+};
 template <typename F>
 inline void with_kernel(int kernel, F&& f) {
     if (kernel == ALGP_KERNEL_RBF) f(std::integral_constant<int, ALGP_KERNEL_RBF>{});
@@ -154,7 +164,12 @@ int group_ksum_launch(algp_ctx* c, const KmatSrc& s, const int64_t* cidx, int64_
         ProfScope ps(c, ALGP_PROF_KMAT, evals * (3.0 * s.DP + 2.0), sizeof(T) * (double)Mpad * (double)(g.Q + 2 * nspan));
         const CovSrc<T> cs = cov_src<T>(s);
         const dim3 grid((unsigned)((Mpad + GROUP_KROWS - 1) / GROUP_KROWS), (unsigned)nch);
-        with_kernel(s.kernel, [&](auto kn) {
+        if (s.additive()) {
+            GroupKsumArgs<T, -1> a = {{cs.Xs, cs.n_pool, cs.os, cs.noise, s.kernel, s.kernel_b, s.da, 3, (T)s.outputscale_b}, cidx, M, Mpad, g, U, part};
+            with_dp(s.DP, [&](auto dp) {
+                hipLaunchKernelGGL((group_ksum_kernel<T, decltype(dp)::value, -1>), grid, dim3(256), 0, c->cur, a);
+            });
+        } else with_kernel(s.kernel, [&](auto kn) {
             constexpr int KERNEL = decltype(kn)::value;
             GroupKsumArgs<T, KERNEL> a = {{cs.Xs, cs.n_pool, cs.os, cs.noise}, cidx, M, Mpad, g, U, part};
             with_dp(s.DP, [&](auto dp) {

@@ -51,6 +51,10 @@ struct KmatArgs {
     T outputscale;
     T* out;
     int64_t ldo;
+    // the additive form (FAM = 2; kernel_b < 0: a single form): part b, and the coordinates [0, da) that are part a's.  Behind
+    // everything else: the single forms' kernels read their arguments where they always were
+    int kernel_b, da;
+    T outputscale_b;
 };
 
 // (the kernel value itself: kval / kmat_value in common.h, shared with the product epilogue that generates B^T, gemm.hip)
@@ -58,7 +62,8 @@ struct KmatArgs {
 // EQ: entries whose row and column address the same pool site receive a diagonal term (the symmetric builds); without it
 // (the candidates' B^T, cross matrices) the index comparisons are not even compiled in -- they and the other per-element
 // bookkeeping were half of the kernel's VALU instructions, and the kernel is VALU-issue bound (profiles/r04_valu_by_kernel.json).
-// FAM: the family of a.kernel (kernel_family, common.h): one copy of the kernel per family, the form selected inside it
+// FAM: the family of a.kernel (kernel_family, common.h): one copy of the kernel per family, the form selected inside it; 2: the
+// additive form (kmat_value_add), any two of the four forms
 template <typename T, int DP, bool EQ, int FAM>
 __global__ __launch_bounds__(256) void kmat_kernel(KmatArgs<T> a) {
     constexpr int VEC = Vec16<T>::N;
@@ -129,7 +134,9 @@ __global__ __launch_bounds__(256) void kmat_kernel(KmatArgs<T> a) {
                 for (int d = 0; d < DP; ++d) xr[d] = s_x[rr][d];
 #pragma unroll
                 for (int v = 0; v < VEC; ++v) {
-                    const T val = kmat_value<T, DP, FAM>(a.kernel, a.outputscale, xr, xc[v]);
+                    T val;
+                    if constexpr (FAM == 2) val = kmat_value_add<T, DP>(a.kernel, a.outputscale, a.kernel_b, a.outputscale_b, a.da, xr, xc[v]);
+                    else val = kmat_value<T, DP, FAM>(a.kernel, a.outputscale, xr, xc[v]);
                     o[v] = live[v] ? val : (T)0;
                 }
             }
@@ -185,7 +192,8 @@ static int kmat_dispatch(algp_ctx* c, const KmatArgs<T>& a, int DP) {
                 else hipLaunchKernelGGL((kmat_kernel<T, decltype(dp)::value, false, FAM>), grid, dim3(256), 0, c->cur, b);
             });
         };
-        if (kernel_family(a.kernel)) launch(std::integral_constant<int, 1>{});
+        if (a.kernel_b >= 0 && !a.Cp) launch(std::integral_constant<int, 2>{});
+        else if (kernel_family(a.kernel)) launch(std::integral_constant<int, 1>{});
         else launch(std::integral_constant<int, 0>{});
     }
     ALGP_HIP(hipGetLastError());
@@ -213,6 +221,7 @@ int kmat_launch(algp_ctx* c, const KmatSrc& s, const int64_t* ridx, int64_t rows
     a.col_shift = col_shift;
     a.kernel = s.kernel;
     a.outputscale = (T)s.outputscale;
+    a.kernel_b = s.kernel_b; a.da = s.da; a.outputscale_b = (T)s.outputscale_b;
     a.out = out;
     a.ldo = ldo;
     return kmat_dispatch<T>(c, a, s.DP);
@@ -239,6 +248,7 @@ int kmat_xy_launch(algp_ctx* c, const T* xs1, int64_t n1, const T* xs2, int64_t 
     a.col_shift = 0;
     a.kernel = c->hyp.kernel;
     a.outputscale = (T)c->hyp.outputscale;
+    a.kernel_b = c->hyp.additive ? c->hyp.kernel_b : -1; a.da = c->hyp.Da; a.outputscale_b = (T)c->hyp.outputscale_b;
     a.out = out;
     a.ldo = ldo;
     return kmat_dispatch<T>(c, a, c->hyp.DP);

@@ -185,4 +185,8 @@ int trinv_diag_launch(algp_ctx* c, const T* A, int64_t lda, T* inv_out);
 template <typename T>
 int mll_grad_launch(algp_ctx* c, const T* Sinv, int64_t ld, int64_t N, const T* Xs, int DP, const int64_t* aidx,
                     const T* alpha, int kernel, T os, double* out_dev, double* partial);
+// under the additive kernel: out_dev[0] = os_a, [1] = os_b, [2] = noise trace, [3..3+DP) = ls (fit.hip)
+template <typename T>
+int mll_grad_add_launch(algp_ctx* c, const T* Sinv, int64_t ld, int64_t N, const T* Xs, int DP, const int64_t* aidx, const T* alpha,
+                        int kernel_a, T os_a, int kernel_b, T os_b, int da, double* out_dev, double* partial);
 }  // namespace algp

@@ -726,8 +726,8 @@ int argmax_launch(algp_ctx* c, const double* s, int64_t M, double* out_val, int6
 // V^T[j][ncols] = r_j.   b'_j = C(pick, j) when the pick is a new site and row j is ordinary.
 // ---------------------------------------------------------------------------------------------
 // b'_j = C(pick, j) when the pick is a new site and row j is ordinary, else 0
-template <typename T, int DP>
-__device__ __forceinline__ T pick_bprime(bool unit, int64_t pj, const CovSrc<T>& src, int64_t pick_pool, int pick_in_train) {
+template <typename T, int DP, typename S>
+__device__ __forceinline__ T pick_bprime(bool unit, int64_t pj, const S& src, int64_t pick_pool, int pick_in_train) {
     return (!pick_in_train && !unit) ? pool_cov<DP>(src, pick_pool, pj) : (T)0;
 }
 
@@ -811,11 +811,12 @@ ALGP_INSTANTIATE(gather_rows_launch);
 // pos_dev != null: the row is the one an argmax kernel has just left on the device (*pos_dev; < 0 = no row, nothing to
 // do), so that argmax -> refresh -> refresh -> argmax is one stream-ordered chain without a host round trip.
 // ---------------------------------------------------------------------------------------------
-template <typename T, int DP, bool COOP>
+// S: the source's type -- CovSrc<T>, or CovSrcAdd<T> (the additive form's own instantiations; with_src, common.h)
+template <typename T, int DP, bool COOP, typename S>
 __global__ __launch_bounds__(COOP ? 1024 : 256) void lazy_refresh_kernel(int64_t M, int mode, int64_t pos, const int64_t* pos_dev,
                                                            const LazyPick* picks,
                                                            int npicks, const int* ckind, const int64_t* cidx,
-                                                           CovSrc<T> src, const T* prevrows, int64_t ldv, T* Vt, T* dstat,
+                                                           S src, const T* prevrows, int64_t ldv, T* Vt, T* dstat,
                                                            int* fresh, const unsigned char* alive, double* scores,
                                                            double ss, double delta) {
     const int lane = threadIdx.x & 63;
@@ -895,13 +896,15 @@ int lazy_refresh_launch(algp_ctx* c, int64_t M, int mode, int64_t pos, const Laz
     if (g > 65536) g = 65536;
     ProfScope ps(c, ALGP_PROF_ROWS, 0.0, 13.0 * M);
     dim3 grid((unsigned)g), blk(coop ? 1024 : 256);
-    auto launch = [&](auto dp, auto co) {
-        hipLaunchKernelGGL((lazy_refresh_kernel<T, decltype(dp)::value, decltype(co)::value>), grid, blk, 0, c->cur, M, mode, pos, pos_dev,
-                           picks, npicks, ckind, cidx, cov_src<T>(s), prevrows, ldv, Vt, dstat, fresh, alive, scores, ss, delta);
-    };
-    with_dp(s.DP, [&](auto dp) {
-        if (coop) launch(dp, std::true_type{});
-        else launch(dp, std::false_type{});
+    with_src<T>(s, [&](auto src) {
+        auto launch = [&](auto dp, auto co) {
+            hipLaunchKernelGGL((lazy_refresh_kernel<T, decltype(dp)::value, decltype(co)::value, decltype(src)>), grid, blk, 0, c->cur, M, mode,
+                               pos, pos_dev, picks, npicks, ckind, cidx, src, prevrows, ldv, Vt, dstat, fresh, alive, scores, ss, delta);
+        };
+        with_dp(s.DP, [&](auto dp) {
+            if (coop) launch(dp, std::true_type{});
+            else launch(dp, std::false_type{});
+        });
     });
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
@@ -1052,10 +1055,10 @@ int fresh_at_launch(algp_ctx* c, const int* fresh, const int64_t* idx, double* o
 // so V_j = L[lpos, :]^T - d_lpos u with u = the candidate's unit row.  Accumulation in fp64 for either dtype.
 // ---------------------------------------------------------------------------------------------
 constexpr int PATH_SITES = 64;
-template <typename T, int DP>
+template <typename T, int DP, typename S>
 __global__ __launch_bounds__(256) void path_score_kernel(const int64_t* cpos, const int64_t* lpos, int maxlen, const int64_t* cidx,
                                                          const T* Vt, int64_t ldv, int64_t ncols, const T* L, int64_t ldl,
-                                                         const T* varA, CovSrc<T, double> src, double sm, double* out) {
+                                                         const T* varA, S src, double sm, double* out) {
     __shared__ double G[PATH_SITES][PATH_SITES + 1];
     __shared__ double R[PATH_SITES][33];
     __shared__ int64_t s_c[PATH_SITES], s_l[PATH_SITES];
@@ -1148,9 +1151,11 @@ int path_score_launch(algp_ctx* c, const int64_t* cpos, const int64_t* lpos, int
                       const T* Vt, int64_t ldv, int64_t ncols, const T* L, int64_t ldl, const T* varA, const KmatSrc& s, double sm,
                       double* out) {
     if (npaths <= 0) return ALGP_OK;
-    with_dp(s.DP, [&](auto dp) {
-        hipLaunchKernelGGL((path_score_kernel<T, decltype(dp)::value>), dim3((unsigned)npaths), dim3(256), 0, c->cur, cpos, lpos, maxlen,
-                           cidx, Vt, ldv, ncols, L, ldl, varA, cov_src<T, double>(s), sm, out);
+    with_src<T, double>(s, [&](auto src) {
+        with_dp(s.DP, [&](auto dp) {
+            hipLaunchKernelGGL((path_score_kernel<T, decltype(dp)::value, decltype(src)>), dim3((unsigned)npaths), dim3(256), 0, c->cur, cpos,
+                               lpos, maxlen, cidx, Vt, ldv, ncols, L, ldl, varA, src, sm, out);
+        });
     });
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
@@ -1162,8 +1167,8 @@ ALGP_INSTANTIATE(path_score_launch);
 // second-reading transform included), the Gram matrices of a batch of paths are ONE batched MFMA product (gemm.hip), this
 // kernel turns each into G = C_PP + sigma_m^2 I - Gram (identity on the padding) in place, and the blocks are factored
 // as 2 x 2 tiles of 128 by the diagonal-block kernel + two batched tile products (api.hip: score_paths_big).
-template <typename T, int DP>
-__global__ __launch_bounds__(256) void path_assemble_kernel(const int64_t* cpos, int ppad, const int64_t* cidx, CovSrc<T, double> src,
+template <typename T, int DP, typename S>
+__global__ __launch_bounds__(256) void path_assemble_kernel(const int64_t* cpos, int ppad, const int64_t* cidx, S src,
                                                             double sm, T* G) {
     __shared__ int64_t s_p[256];
     __shared__ int s_n;
@@ -1193,9 +1198,11 @@ __global__ __launch_bounds__(256) void path_assemble_kernel(const int64_t* cpos,
 template <typename T>
 int path_assemble_launch(algp_ctx* c, const int64_t* cpos, int batch, int ppad, const int64_t* cidx, const KmatSrc& s, double sm, T* G) {
     if (batch <= 0) return ALGP_OK;
-    with_dp(s.DP, [&](auto dp) {
-        hipLaunchKernelGGL((path_assemble_kernel<T, decltype(dp)::value>), dim3((unsigned)batch), dim3(256), 0, c->cur, cpos, ppad, cidx,
-                           cov_src<T, double>(s), sm, G);
+    with_src<T, double>(s, [&](auto src) {
+        with_dp(s.DP, [&](auto dp) {
+            hipLaunchKernelGGL((path_assemble_kernel<T, decltype(dp)::value, decltype(src)>), dim3((unsigned)batch), dim3(256), 0, c->cur, cpos,
+                               ppad, cidx, src, sm, G);
+        });
     });
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
@@ -1225,8 +1232,8 @@ int path_finish_launch(algp_ctx* c, const int64_t* cpos, int ppad, int batch, co
 // caller's output it writes (pid).  Only the lower tiles of Gamma and Phi are valid: every read goes to [max][min].
 // ---------------------------------------------------------------------------------------------
 // Gamma = C(U, U) - Gram in place, on and below the diagonal (one workgroup per row; sm is added per path)
-template <typename T, int DP>
-__global__ __launch_bounds__(256) void pvr_assemble_kernel(const int64_t* uidx, int64_t U, int64_t ld, CovSrc<T, double> src, T* G) {
+template <typename T, int DP, typename S>
+__global__ __launch_bounds__(256) void pvr_assemble_kernel(const int64_t* uidx, int64_t U, int64_t ld, S src, T* G) {
     const int64_t a = blockIdx.x;
     const int64_t pa = uidx[a];
     double xa[DP];
@@ -1237,9 +1244,11 @@ __global__ __launch_bounds__(256) void pvr_assemble_kernel(const int64_t* uidx, 
 template <typename T>
 int pvr_assemble_launch(algp_ctx* c, const int64_t* uidx, int64_t U, int64_t ld, const KmatSrc& s, T* G) {
     if (U <= 0) return ALGP_OK;
-    with_dp(s.DP, [&](auto dp) {
-        hipLaunchKernelGGL((pvr_assemble_kernel<T, decltype(dp)::value>), dim3((unsigned)U), dim3(256), 0, c->cur, uidx, U, ld,
-                           cov_src<T, double>(s), G);
+    with_src<T, double>(s, [&](auto src) {
+        with_dp(s.DP, [&](auto dp) {
+            hipLaunchKernelGGL((pvr_assemble_kernel<T, decltype(dp)::value, decltype(src)>), dim3((unsigned)U), dim3(256), 0, c->cur, uidx, U,
+                               ld, src, G);
+        });
     });
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;
@@ -1437,8 +1446,8 @@ ALGP_INSTANTIATE(pvr_trace_launch);
 // materialised (utils.py:301; for an explicit covariance a gather of its entries).
 // One wave per output; lanes stride over the train set (coordinates and alpha are L2 resident).
 // ---------------------------------------------------------------------------------------------
-template <typename T, int DP>
-__global__ __launch_bounds__(256) void kgemv_kernel(int64_t M, const int64_t* qidx, CovSrc<T> src, int64_t N, const int64_t* aidx,
+template <typename T, int DP, typename S>
+__global__ __launch_bounds__(256) void kgemv_kernel(int64_t M, const int64_t* qidx, S src, int64_t N, const int64_t* aidx,
                                                     const T* alpha, T ybar, T* mu) {
     const int lane = threadIdx.x & 63;
     const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -1463,9 +1472,11 @@ int kgemv_launch(algp_ctx* c, int64_t M, const int64_t* qidx, const KmatSrc& s, 
     if (g > 8192) g = 8192;
     ProfScope ps(c, ALGP_PROF_KMAT, (double)M * N * (s.Cp ? 2.0 : 3.0 * s.DP + 4.0),
                  sizeof(T) * (s.Cp ? (double)M * N : (double)(M + N) * (s.DP + 1)));
-    with_dp(s.DP, [&](auto dp) {
-        hipLaunchKernelGGL((kgemv_kernel<T, decltype(dp)::value>), dim3((unsigned)g), dim3(256), 0, c->cur, M, qidx, cov_src<T>(s), N, aidx,
-                           alpha, ybar, mu);
+    with_src<T>(s, [&](auto src) {
+        with_dp(s.DP, [&](auto dp) {
+            hipLaunchKernelGGL((kgemv_kernel<T, decltype(dp)::value, decltype(src)>), dim3((unsigned)g), dim3(256), 0, c->cur, M, qidx, src, N,
+                               aidx, alpha, ybar, mu);
+        });
     });
     ALGP_HIP(hipGetLastError());
     return ALGP_OK;

@@ -17,6 +17,10 @@ What differs, deliberately:
     rbf (north_star scope; the reference also has linear / non_linear latents and a spectral
     mixture kernel, models.py:23-44, 221-223): anything else, another nu included, raises
     NotImplementedError like models.py:227, 248;
+  * kernel_params = {'type': 'additive', 'split': Da, 'parts': ({'type': 'matern', 'nu': 1.5}, {'type': 'rbf'})} is the sum of
+    two such kernels, the first over coordinates [0, Da), the second over the others (genotype effect + spatial trend), with
+    gpytorch's AdditiveKernel parameter names: kernel_covar_module.kernels.{0,1}.log_outputscale and
+    kernel_covar_module.kernels.{0,1}.base_kernel.log_lengthscale; GPR.predict_components splits the posterior mean;
   * `fit` uses the analytic MLL gradient computed on the device with the reference's own optimiser
     objects (torch.optim.Adam + ReduceLROnPlateau(patience=50), models.py:121-124).
 """
@@ -54,6 +58,27 @@ class _ScaleKernel(nn.Module):
         self.log_outputscale = nn.Parameter(torch.zeros(1, dtype=torch.float64))
 
 
+class _AdditiveKernel(nn.Module):
+    """Two ScaleKernels, the first on the leading `split` coordinates, the second on the others (gpytorch's AdditiveKernel)."""
+
+    def __init__(self, split, ard_num_dims):
+        super(_AdditiveKernel, self).__init__()
+        self.kernels = nn.ModuleList([_ScaleKernel(split), _ScaleKernel(ard_num_dims - split)])
+
+
+def _kernel_id(params):
+    """The library's id of a single form: {'type': 'rbf' | 'matern'[, 'nu': 0.5 | 1.5 | 2.5]} (None: rbf)."""
+    kernel = params['type'] if params is not None else 'rbf'
+    if kernel not in _KERNELS:
+        raise NotImplementedError(kernel)
+    if kernel == 'matern' and 'nu' in params:
+        nu = params['nu']
+        if nu not in _MATERN_NU:
+            raise NotImplementedError('matern nu=%r: nu is one of 0.5, 1.5, 2.5' % (nu,))
+        return _MATERN_NU[nu]
+    return _KERNELS[kernel]
+
+
 class _GaussianLikelihood(nn.Module):
     def __init__(self):
         super(_GaussianLikelihood, self).__init__()
@@ -71,6 +96,20 @@ class ExactGPModel(nn.Module):
             raise NotImplementedError('latent function %r is outside the MI355X hot path (identity only)' % (latent,))
         self.latent_func = IdentityLatentFunction()
         kernel = kernel_params['type'] if kernel_params is not None else 'rbf'
+        self.split = None
+        if kernel == 'additive':
+            D = int(np.shape(train_x)[-1])
+            parts = kernel_params.get('parts')
+            split = kernel_params.get('split')
+            if parts is None or len(parts) != 2:
+                raise ValueError("additive kernel: 'parts' must hold two kernel descriptions")
+            if split is None or not 1 <= int(split) <= D - 1:
+                raise ValueError("additive kernel: 'split' must be in [1, D - 1] (D = %d)" % D)
+            self.split = int(split)
+            self.kernel_type = ('additive', self.split, _kernel_id(parts[0]), _kernel_id(parts[1]))
+            self.kernel_covar_module = _AdditiveKernel(self.split, D)
+            self.likelihood = likelihood
+            return
         if kernel not in _KERNELS:
             raise NotImplementedError(kernel)
         self.kernel_type = _KERNELS[kernel]
@@ -113,8 +152,14 @@ class GPR(object):
         return self._ctx
 
     def hypers(self):
-        """(log_lengthscale[D], log_outputscale, log_noise, kernel id) as plain floats."""
+        """(log_lengthscale[D], log_outputscale, log_noise, kernel id) as plain floats.  Under the additive kernel the
+        lengthscales of the two parts in coordinate order, log_outputscale a pair and the id ('additive', split, id_a, id_b)."""
         m = self.model
+        if m.split is not None:
+            ks = m.kernel_covar_module.kernels
+            ls = np.concatenate([k.base_kernel.log_lengthscale.detach().double().reshape(-1).numpy() for k in ks])
+            return (ls, tuple(float(k.log_outputscale.item()) for k in ks), float(self.likelihood.log_noise.item()),
+                    m.kernel_type)
         return (m.kernel_covar_module.base_kernel.log_lengthscale.detach().double().reshape(-1).numpy().copy(),
                 float(m.kernel_covar_module.log_outputscale.item()), float(self.likelihood.log_noise.item()),
                 m.kernel_type)
@@ -124,10 +169,18 @@ class GPR(object):
         ls, los, ln, kt = self.hypers()
         key = (tuple(ls), los, ln, kt)
         if key != self._hyp_key:
-            self.ctx.set_hypers(ls, los, ln, kt)
+            self.push_hypers(self.ctx)
             self._hyp_key = key
             return True
         return False
+
+    def push_hypers(self, ctx):
+        """Set the current hyper-parameters on `ctx` (this model's own context, or another one that is to compute with them)."""
+        ls, los, ln, kt = self.hypers()
+        if isinstance(kt, tuple):
+            ctx.set_hypers_additive(ls, kt[1], los[0], los[1], ln, kt[2], kt[3])
+        else:
+            ctx.set_hypers(ls, los, ln, kt)
 
     # ---- models.py:103-115 ------------------------------------------------------------------
     @property
@@ -185,18 +238,35 @@ class GPR(object):
         self.reset(x, y, var)
         self._load_train_on_device()
         named = dict(self.model.named_parameters())
-        p_ls = named['kernel_covar_module.base_kernel.log_lengthscale']
-        p_os = named['kernel_covar_module.log_outputscale']
         p_n = named['likelihood.log_noise']
-        D = p_ls.numel()
+        if self.model.split is not None:
+            # the D + 3 gradient: [log ls in coordinate order | log os_a, log os_b | log noise]
+            route = []
+            at = 0
+            for k in (0, 1):
+                p = named['kernel_covar_module.kernels.%d.base_kernel.log_lengthscale' % k]
+                route.append((p, at, at + p.numel()))
+                at += p.numel()
+            for k in (0, 1):
+                route.append((named['kernel_covar_module.kernels.%d.log_outputscale' % k], at + k, at + k + 1))
+            route.append((p_n, at + 2, at + 3))
+        else:
+            p_ls = named['kernel_covar_module.base_kernel.log_lengthscale']
+            p_os = named['kernel_covar_module.log_outputscale']
+            D = p_ls.numel()
+            route = None
         initial_ll = final_ll = None
         losses = []
         for i in range(self.max_iter):
             self.optimizer.zero_grad()
             loss, g = self.neg_mll_and_grad()
-            p_ls.grad = torch.from_numpy(g[:D].copy()).reshape(p_ls.shape)
-            p_os.grad = torch.tensor([g[D]], dtype=torch.float64)
-            p_n.grad = torch.tensor([g[D + 1]], dtype=torch.float64)
+            if route is not None:
+                for p, a, b in route:
+                    p.grad = torch.from_numpy(g[a:b].copy()).reshape(p.shape)
+            else:
+                p_ls.grad = torch.from_numpy(g[:D].copy()).reshape(p_ls.shape)
+                p_os.grad = torch.tensor([g[D]], dtype=torch.float64)
+                p_n.grad = torch.tensor([g[D + 1]], dtype=torch.float64)
             self.optimizer.step()
             self.lr_scheduler.step(loss)
             if disp:
@@ -251,6 +321,23 @@ class GPR(object):
             return mu, var + self.dtype.type(noise)
         cov, _ = c.posterior_cov()
         return mu, cov + self.dtype.type(noise) * np.eye(M, dtype=self.dtype)
+
+    def predict_components(self, x):
+        """(mean_a, mean_b): the two parts' shares of the posterior mean of the latent field at `x` under the additive kernel
+        -- with the genotype coordinates first, mean_a is the genotype effect adjusted for spatial trend.  The constant mean
+        belongs to neither: mean_a + mean_b + mean(train y) = predict(x)."""
+        if self.model is None or self.model.split is None:
+            raise ValueError("predict_components needs kernel_params['type'] = 'additive'")
+        c = self.ctx
+        self.sync_hypers()
+        x = np.asarray(x, dtype=np.float64)
+        x = x.reshape(len(x), -1)
+        N, M = len(self._train_x), len(x)
+        c.set_pool(np.vstack([self._train_x, x]))
+        c.set_train(np.arange(N), self._train_y, self._train_var)
+        c.factorize()
+        idx = np.arange(N, N + M)
+        return c.posterior_mean_component(0, idx), c.posterior_mean_component(1, idx)
 
     def sample_posterior(self, x, n_samples=1, n_features=2048, rng=None):
         """(n_samples, len(x)) joint draws of the latent field f at `x` (no observation noise), conditioned on the stored

@@ -86,9 +86,28 @@ def spectral_draws(kernel_id, D, n_features, rng):
     (n_features, D) float64, and phases ~ U[0, 2 pi), (n_features,) float64, so that with x scaled by 1 / lengthscale
     E[2 os cos(omega . x + phase) cos(omega . x' + phase)] = k(x, x').  RBF: omega ~ N(0, I); Matern-nu: a multivariate
     Student-t with 2 nu degrees of freedom, omega = z sqrt(2 nu / c), z ~ N(0, I), c ~ chi^2(2 nu), one c per feature.
-    Drawn from `rng` (a RandomState or a seed) in this order: z, c (Matern only), phase."""
+    Drawn from `rng` (a RandomState or a seed) in this order: z, c (Matern only), phase.
+    The additive kernel: kernel_id = ('additive', split, id_a, id_b, os_a, os_b).  The normalised spectral density of a sum
+    of kernels is the mixture of the parts' densities with weights os_c / (os_a + os_b), so every feature belongs to one
+    part, chosen with that probability: its frequencies are that part's draw in the part's own coordinates and ZERO in the
+    other's, and the amplitude is sqrt(2 (os_a + os_b) / F) (algp_sample_posterior).  Order: the parts' uniform draws (F),
+    part a's z and c, part b's z and c, phase."""
     rng = _rng(rng)
     D, F = int(D), int(n_features)
+    if isinstance(kernel_id, tuple):
+        _, split, id_a, id_b, os_a, os_b = kernel_id
+        split = int(split)
+        in_a = rng.uniform(size=F) < os_a / (os_a + os_b)
+        omega = np.zeros((F, D))
+        for ident, lo, hi, mine in ((id_a, 0, split, in_a), (id_b, split, D, ~in_a)):
+            w = rng.standard_normal((F, hi - lo))
+            if ident != _hip.KERNEL_RBF:
+                if ident not in _MATERN_NU:
+                    raise NotImplementedError('spectral_draws: kernel id %r' % (ident,))
+                w = w * np.sqrt(2.0 * _MATERN_NU[ident] / rng.chisquare(2.0 * _MATERN_NU[ident], size=F))[:, None]
+            omega[mine, lo:hi] = w[mine]
+        phase = rng.uniform(0.0, 2.0 * np.pi, size=F)
+        return np.ascontiguousarray(omega, dtype=np.float64), np.ascontiguousarray(phase, dtype=np.float64)
     omega = rng.standard_normal((F, D))
     if kernel_id != _hip.KERNEL_RBF:
         if kernel_id not in _MATERN_NU:
@@ -117,7 +136,9 @@ def posterior_samples(gp, train_x, train_y, test_x, train_var=None, n_samples=1,
     c.set_train(np.arange(N), train_y, train_var)
     c.set_candidates(np.arange(N, N + M), prior_includes_noise=False)
     c.fit_and_solve()
-    omega, phase = spectral_draws(gp.hypers()[3], train_x.shape[1], n_features, rng)
+    hyp = gp.hypers()
+    kid = hyp[3] + tuple(np.exp(hyp[1])) if isinstance(hyp[3], tuple) else hyp[3]      # additive: with the two outputscales
+    omega, phase = spectral_draws(kid, train_x.shape[1], n_features, rng)
     weights = rng.standard_normal((int(n_samples), int(n_features)))
     eps = rng.standard_normal((int(n_samples), N))
     return c.sample_posterior(eps, weights=weights, omega=omega, phase=phase)

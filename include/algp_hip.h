@@ -90,6 +90,18 @@ int algp_dtype(const algp_ctx* ctx);
  * sigma_n^2 = exp(log_noise) (models.py:180).                                                  */
 int algp_set_hypers(algp_ctx* ctx, int kernel, int D, const double* log_lengthscale,
                     double log_outputscale, double log_noise);
+/* The additive kernel over two coordinate groups (gpytorch's AdditiveKernel of two ScaleKernels, each on its active dims):
+ *   k(x, x') = os_a kappa_a(r_a) + os_b kappa_b(r_b),
+ * r_a over the first Da coordinates, r_b over the other D - Da, each with its own form (kernel_a, kernel_b: any of the four ids
+ * above, kappa the form at outputscale 1), its own outputscale and the ARD lengthscales of its coordinates (log_lengthscale: D
+ * entries in coordinate order) -- phenotype = genotype effect + spatial trend + noise.  The prior variance of a site is
+ * os_a + os_b.  2 <= D <= 8 and 1 <= Da <= D - 1; anything else is ALGP_ERR_BAD_ARG and the context keeps the hyper-parameters
+ * it had.  Replaces the hyper-parameters exactly as algp_set_hypers does (factor and candidate solve invalidated, the pool
+ * rescaled, a pool of another width dropped); a later algp_set_hypers returns the context to a single kernel.  Every entry
+ * point then works on the additive kernel; algp_get_mll_grad / algp_fit_step return D + 3 entries (below), and
+ * algp_posterior_mean_component splits the posterior mean.                                       */
+int algp_set_hypers_additive(algp_ctx* ctx, int D, int kernel_a, int Da, double log_outputscale_a, int kernel_b,
+                             double log_outputscale_b, const double* log_lengthscale, double log_noise);
 
 /* ---- a1: GPR.cov_mat (models.py:161-181) -------------------------------------------------
  * out[n1*n2] (host) = K(x1,x2) ; x2 == NULL -> symmetric K(x1,x1) (models.py:169-170);
@@ -146,7 +158,10 @@ int algp_get_mll(algp_ctx* ctx, double* mll);                /* -1/2 y0'alpha - 
 /* ---- f2: gradient of the MLL for GPR.fit (models.py:137-159; the loss there is -MLL/N) ------
  * grad_out[D+2] = d MLL / d (log_lengthscale[0..D), log_outputscale, log_noise), NOT divided by N.
  * Needs a coordinate pool and a current factorisation.  With a site in more than one train row the
- * cross entries of its rows hold sigma_n^2 (algp_set_train) and count in the log_noise entry.       */
+ * cross entries of its rows hold sigma_n^2 (algp_set_train) and count in the log_noise entry.
+ * Under an additive kernel (algp_set_hypers_additive) grad_out has D+3 entries: (log_lengthscale[0..D), log_outputscale_a,
+ * log_outputscale_b, log_noise); lengthscale entry d belongs to the part that owns coordinate d.  The same holds for
+ * algp_fit_step.  Every sum is a fixed-order sum of per-workgroup partials: the same bits in every run.       */
 int algp_get_mll_grad(algp_ctx* ctx, double* grad_out);
 /* The device work of ONE iteration of GPR.fit (models.py:145-158: output = model(train_x); loss = -mll(output, train_y);
  * loss.backward()) in one call, for the current hyper-parameters and train set: = algp_factorize + algp_get_mll +
@@ -187,6 +202,13 @@ int algp_get_posterior(algp_ctx* ctx, void* mu_out, void* var_out);      /* eith
 int algp_get_posterior_cov(algp_ctx* ctx, void* cov_out, double* mi_out);
 /* mean only, mu = ybar + K_xa alpha with K never materialised (utils.py:301)                   */
 int algp_posterior_mean(algp_ctx* ctx, const int64_t* idx, int64_t M, void* mu_out);
+/* One part's share of the posterior mean under an additive kernel (component 0 = a, 1 = b):
+ *   mu_c(j) = sum_i os_c kappa_c(r_c(x_j, x_A_i)) alpha_i,
+ * the same kernel-GEMV with the other part switched off.  The constant mean belongs to neither part: component 0 + component 1
+ * + ybar is algp_posterior_mean to rounding.  (With a = genotype coordinates: the genotype effect adjusted for spatial trend.)
+ * A single kernel in force: ALGP_ERR_STATE.  An explicit-covariance pool, a component other than 0 / 1: ALGP_ERR_BAD_ARG.
+ * Component variances are not computed.                                                          */
+int algp_posterior_mean_component(algp_ctx* ctx, int component, const int64_t* idx, int64_t M, void* mu_out);
 
 /* ---- joint posterior draws at the candidates: pathwise conditioning (no reference counterpart) ------------------------------
  * algp_sample_posterior: out[s * M + j] = draw s of the LATENT field f at candidate j (candidate order, the context's dtype; no
@@ -201,6 +223,11 @@ int algp_posterior_mean(algp_ctx* ctx, const int64_t* idx, int64_t M, void* mu_o
  *     for Matern-nu), phase (F) ~ U[0, 2 pi), weights W (S x F) standard normal; Xs = x / lengthscale is the resident pool.
  *     prior must be NULL.  Needs a coordinate pool (an explicit covariance: ALGP_ERR_BAD_ARG).  The product runs on the matrix
  *     cores with its cosines generated in registers; phase and cosine are computed in the context's dtype.
+ *     Under an additive kernel the amplitude is sqrt(2 (os_a + os_b) / F) and every row of omega is drawn for ONE part: from that
+ *     part's spectral density in its own coordinates, ZERO in the other part's.  The caller picks the part of each feature with
+ *     probability os_c / (os_a + os_b).  That is unbiased because the normalised spectral density of a sum of kernels is the
+ *     mixture of the parts' normalised densities with exactly those weights: E[2 (os_a + os_b) cos(w.x + p) cos(w.x' + p)]
+ *     = (os_a + os_b) sum_c os_c / (os_a + os_b) kappa_c = k(x, x').
  *   F == 0, values mode: G = prior (S x n_pool values of a prior draw at EVERY pool site, e.g. chol(K_pool) xi on a small
  *     pool); omega, phase, weights must be NULL.  Both pool kinds.
  * Any other combination of NULL / non-NULL, S < 1, F < 0, eps NULL with N > 0, out NULL with M > 0: ALGP_ERR_BAD_ARG.

@@ -16,7 +16,9 @@ from algp_amd.utils import compute_mae
 
 def run_demo(args):
     np.random.seed(args.seed)
-    env = SyntheticField(args.rows, args.cols, num_test=args.num_test)
+    # an additive kernel whose first part is the whole position (row, col) needs a coordinate for its second: genotype ids
+    genotypes = 12 if args.kernel == 'additive' and args.kernel_split == 2 else 0
+    env = SyntheticField(args.rows, args.cols, num_test=args.num_test, num_genotypes=genotypes)
     agent = Agent(env, args, static_std=args.static_std, mobile_std=10 * args.static_std)
     agent.reset()
     agent._setup_ipp(args.criterion, args.update)
