@@ -43,6 +43,9 @@ SIGNATURES = {
     'algp_set_hypers': (C.c_int, [_c_ctx, C.c_int, C.c_int, _dblp, C.c_double, C.c_double]),
     'algp_set_hypers_additive': (C.c_int, [_c_ctx, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, _dblp,
                                            C.c_double]),
+    'algp_set_hypers_relationship': (C.c_int, [_c_ctx, C.c_int, C.c_int, C.c_double, _dblp, C.c_double, _dblp, C.c_int64,
+                                               C.c_double]),
+    'algp_genotype_posterior': (C.c_int, [_c_ctx, C.c_void_p, C.c_void_p, C.c_void_p]),
     'algp_kernel_matrix': (C.c_int, [_c_ctx, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int,
                                      C.c_void_p]),
     'algp_set_pool': (C.c_int, [_c_ctx, C.c_void_p, C.c_int64]),
@@ -211,6 +214,7 @@ class Context(object):
         self._check(self.lib.algp_set_hypers(self.h, int(kernel), len(ls), ls.ctypes.data_as(_dblp),
                                              float(log_outputscale), float(log_noise)))
         self.additive = False
+        self.relationship = False
 
     def set_hypers_additive(self, log_lengthscale, split, log_outputscale_a, log_outputscale_b, log_noise,
                             kernel_a=KERNEL_RBF, kernel_b=KERNEL_RBF):
@@ -223,9 +227,50 @@ class Context(object):
                                                       float(log_noise)))
         self.D = len(ls)
         self.additive = True
+        self.relationship = False
+
+    def set_hypers_relationship(self, log_lengthscale, log_outputscale_a, log_outputscale_g, log_noise, kernel_a=KERNEL_RBF,
+                                G=None, n_genotypes=None):
+        """The relationship kernel os_a kappa_a(r_a) + os_g G[g, g'] (algp_set_hypers_relationship): log_lengthscale has one
+        entry per SPATIAL coordinate (D - 1 of them); the last coordinate of every site is its integer genotype id in
+        [0, Q).  G: a (Q, Q) symmetric relationship matrix, or None for the identity with Q = n_genotypes.  A refusal
+        (ValueError) leaves the hyper-parameters, the table and the pool in force untouched."""
+        ls = np.ascontiguousarray(np.atleast_1d(log_lengthscale), dtype=np.float64)
+        gp = None
+        if G is not None:
+            G = np.ascontiguousarray(G, dtype=np.float64)
+            if G.ndim != 2 or G.shape[0] != G.shape[1]:
+                raise ValueError('G must be a square matrix, got shape %s' % (G.shape,))
+            if n_genotypes is not None and int(n_genotypes) != G.shape[0]:
+                raise ValueError('n_genotypes = %d does not match G of shape %s' % (int(n_genotypes), G.shape))
+            Q = G.shape[0]
+            gp = G.ctypes.data_as(_dblp)
+        elif n_genotypes is None:
+            raise ValueError('pass G or n_genotypes (the identity relationship of that many genotypes)')
+        else:
+            Q = int(n_genotypes)
+        self._check(self.lib.algp_set_hypers_relationship(self.h, len(ls) + 1, int(kernel_a), float(log_outputscale_a),
+                                                          ls.ctypes.data_as(_dblp), float(log_outputscale_g), gp, Q,
+                                                          float(log_noise)))
+        self.D = len(ls) + 1
+        self.additive = False
+        self.relationship = True
+        self.Q = Q
+
+    def genotype_posterior(self, want_var=True, want_cov=False):
+        """(mean, var or None, cov or None) of the Q genotype effects under the relationship kernel, in the context's dtype
+        (algp_genotype_posterior): BLUPs, prediction-error variances, joint covariance.  Needs a current factorisation."""
+        if not getattr(self, 'relationship', False):
+            raise ValueError('genotype_posterior: no relationship kernel is in force (set_hypers_relationship)')
+        mean = np.empty(self.Q, dtype=self.dtype)
+        var = np.empty(self.Q, dtype=self.dtype) if want_var else None
+        cov = np.empty((self.Q, self.Q), dtype=self.dtype) if want_cov else None
+        self._check(self.lib.algp_genotype_posterior(self.h, _ptr(mean), _ptr(var), _ptr(cov)))
+        return mean, var, cov
 
     def _n_grad(self):
-        # D + 2 for a single kernel, D + 3 under the additive one (two outputscales)
+        # D + 2 for a single kernel, D + 3 under the additive one (two outputscales); the relationship kernel: D - 1
+        # lengthscales, two outputscales and the noise, D + 2
         return self.D + (3 if getattr(self, 'additive', False) else 2)
 
     def _check_width(self, x, what):
@@ -259,10 +304,10 @@ class Context(object):
         x = self._arr(x)
         x = x.reshape(len(x), -1)
         self._check_width(x, 'set_pool')
-        self.n_pool = x.shape[0]
         self.pool_generation += 1
         self._pool_owner = None
         self._check(self.lib.algp_set_pool(self.h, _ptr(x), x.shape[0]))
+        self.n_pool = x.shape[0]             # (after the call: a pool refused for its genotype ids leaves the one there was)
 
     def set_pool_cov(self, cov):
         cov = self._arr(cov)

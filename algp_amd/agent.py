@@ -86,6 +86,13 @@ class Agent(object):
             kernel_params = {'type': 'additive', 'split': getattr(args, 'kernel_split', 2),
                              'parts': ({'type': getattr(args, 'kernel_a', 'matern'), 'nu': nu},
                                        {'type': getattr(args, 'kernel_b', 'rbf'), 'nu': nu})}
+        if args.kernel == 'genotype':
+            # part a's form over the position, a table-valued genotype part over the ids in the last coordinate
+            path = getattr(args, 'relationship', None)
+            G = None if path is None else np.load(path)
+            kernel_params = {'type': 'genotype', 'spatial': {'type': getattr(args, 'kernel_a', 'matern'), 'nu': nu},
+                             'relationship': G,
+                             'n_genotypes': None if G is not None else int(getattr(self.env, 'num_genotypes', 0))}
         self.gp = GPR(latent=args.latent, lr=args.lr, max_iterations=args.max_iterations,
                       kernel_params=kernel_params, learn_likelihood_noise=self.learn_likelihood_noise,
                       dtype=getattr(args, 'dtype', np.float64), device=getattr(args, 'device', 0))

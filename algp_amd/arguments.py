@@ -1,7 +1,9 @@
 """Command-line flags of the reference (reference arguments.py:7-52), same names and defaults.
-Differences: `--kernel` accepts {rbf, matern, additive} only, and `--matern_nu` {0.5, 1.5, 2.5} picks the Matern form
+Differences: `--kernel` accepts {rbf, matern, additive, genotype} only, and `--matern_nu` {0.5, 1.5, 2.5} picks the Matern form
 (the reference fixes nu in its source, models.py:219-222); `--kernel additive` is the sum of `--kernel_a` over the first
-`--kernel_split` coordinates and `--kernel_b` over the others (`--matern_nu` applies to its Matern parts); `--dtype`/`--device` select the GPU precision
+`--kernel_split` coordinates and `--kernel_b` over the others (`--matern_nu` applies to its Matern parts); `--kernel genotype` is
+`--kernel_a` (with `--matern_nu`) over the position plus a genotype effect per id in the last coordinate, with the relationship
+matrix of `--relationship PATH` (a .npy file) or independent genotypes without it; `--dtype`/`--device` select the GPU precision
 and card; no results directory is created and nothing prompts (the reference's interactive
 `input()` at arguments.py:41-49 blocks unattended runs)."""
 import argparse
@@ -15,11 +17,12 @@ def get_parser():
     p.add_argument('--max_iterations', default=200, type=int)
     p.add_argument('--data_file', default=None)
     p.add_argument('--phenotype', default='plant_height')
-    p.add_argument('--kernel', default='matern', choices=['rbf', 'matern', 'additive'])
+    p.add_argument('--kernel', default='matern', choices=['rbf', 'matern', 'additive', 'genotype'])
     p.add_argument('--matern_nu', default=1.5, type=float, choices=[0.5, 1.5, 2.5])
     p.add_argument('--kernel_split', default=2, type=int, help='additive kernel: coordinates [0, split) belong to part a')
     p.add_argument('--kernel_a', default='matern', choices=['rbf', 'matern'], help='additive kernel: form of part a')
     p.add_argument('--kernel_b', default='rbf', choices=['rbf', 'matern'], help='additive kernel: form of part b')
+    p.add_argument('--relationship', default=None, help='genotype kernel: .npy file with the Q x Q relationship matrix (default: identity)')
     p.add_argument('--latent', default=None)
     p.add_argument('--num_sims', default=10, type=int)
     p.add_argument('--num_runs', default=6, type=int)

@@ -3,6 +3,8 @@
 // per-candidate quantity comes from the HIP kernels in this directory; what the host computes is bookkeeping
 // (index maps, the mean of the targets) and O(1) scalar combinations of values the kernels returned.
 // (Split by concern in round 6: see api_impl.h.)
+#include <cmath>
+
 #include "api_impl.h"
 
 using namespace algp;
@@ -171,8 +173,42 @@ KmatSrc make_src(algp_ctx* c) {
         s.da = c->hyp.Da;
         s.outputscale_b = c->hyp.outputscale_b;
     }
+    if (c->hyp.rel) {
+        s.da = c->hyp.Da;
+        s.G = c->hyp.has_table ? c->Gtab.p : nullptr;
+        s.Q = c->hyp.Q;
+        s.outputscale_g = c->hyp.outputscale_g;
+    }
     return s;
 }
+
+// the single and the additive setters return the context to their forms: the relationship table goes
+void leave_relationship(algp_ctx* c) {
+    c->hyp.rel = false;
+    c->hyp.has_table = false;
+    c->hyp.Q = 0;
+    c->hyp.Ghash = 0;
+    c->hyp.gdiag_max = 1.0;
+    if (c->Gtab.p) {
+        hipStreamSynchronize(c->stream);
+        release(c, c->Gtab);
+    }
+}
+
+// The relationship form's check of the id coordinate (the last of D) of n sites, on the host before any launch: an integer in
+// [0, Q).  what: the entry point and the operand, for the message, which names the row.
+template <typename T>
+int rel_check_ids(algp_ctx* c, const T* x, int64_t n, int D, int64_t Q, const char* what) {
+    for (int64_t i = 0; i < n; ++i) {
+        const double g = (double)x[i * D + D - 1];
+        if (!(g >= 0.0 && g < (double)Q && g == floor(g)))
+            return fail(c, ALGP_ERR_BAD_ARG, std::string(what) + ": row " + std::to_string(i) + " carries the genotype id " + std::to_string(g) +
+                                                 ", not an integer in [0, " + std::to_string(Q) + ")");
+    }
+    return ALGP_OK;
+}
+template int rel_check_ids<float>(algp_ctx*, const float*, int64_t, int, int64_t, const char*);
+template int rel_check_ids<double>(algp_ctx*, const double*, int64_t, int, int64_t, const char*);
 
 int sync(algp_ctx* c) {
     ALGP_HIP(hipStreamSynchronize(c->stream));
@@ -211,6 +247,25 @@ int Impl<T>::rescale_pool(algp_ctx* c) {
     if (c->pool_is_cov || c->n_pool == 0 || !c->hyp.set) return ALGP_OK;
     ALGP_TRY(ensure(c, c->Xs, sizeof(T) * c->n_pool * c->hyp.DP));
     return scale_coords_launch<T>(c, (const T*)c->Xraw.p, c->n_pool, p(c->Xs));
+}
+
+// the relationship form: the ids of the resident coordinate pool (read back from the raw coordinates) checked against Q
+template <typename T>
+int Impl<T>::rel_check_pool(algp_ctx* c, int D, int64_t Q) {
+    std::vector<T> x((size_t)c->n_pool * D);
+    ALGP_HIP(hipMemcpyAsync(x.data(), c->Xraw.p, sizeof(T) * x.size(), hipMemcpyDeviceToHost, c->stream));
+    ALGP_TRY(sync(c));
+    return rel_check_ids<T>(c, x.data(), c->n_pool, D, Q, "set_hypers_relationship: the resident pool");
+}
+
+// the table in the context's dtype into a buffer of its own (the caller swaps it in once nothing can fail any more)
+template <typename T>
+int Impl<T>::rel_upload_table(algp_ctx* c, const double* G, int64_t Q, DevBuf& dst) {
+    std::vector<T> g((size_t)Q * Q);
+    for (size_t i = 0; i < g.size(); ++i) g[i] = (T)G[i];
+    ALGP_TRY(ensure(c, dst, sizeof(T) * g.size()));
+    ALGP_HIP(hipMemcpy(dst.p, g.data(), sizeof(T) * g.size(), hipMemcpyHostToDevice));
+    return ALGP_OK;
 }
 
 
@@ -540,7 +595,7 @@ void algp_destroy(algp_ctx* c) {
     DevBuf* bufs[] = {&c->Xs, &c->Xraw, &c->Cp, &c->Aidx, &c->yA, &c->varA, &c->y0, &c->L, &c->invD, &c->z, &c->alpha,
                       &c->scal, &c->Cidx, &c->ckind, &c->cextra, &c->Vt, &c->dstat, &c->mu, &c->alive, &c->scores,
                       &c->lrow, &c->remote, &c->commbuf, &c->tvec, &c->amax, &c->prevrows, &c->fresh, &c->lazypicks, &c->yraw, &c->uvec, &c->wvec, &c->acc3, &c->rowstat, &c->inv512, &c->inv512_scr, &c->trsm_tmp, &c->gemm_part, &c->rhs_rx, &c->rhs_cx, &c->rhs_rk, &c->splitk, &c->dag_state, &c->dag_stats, &c->trsv_ctrl, &c->auxA, &c->auxInv, &c->auxW, &c->auxIdx,
-                      &c->auxVar, &c->auxD, &c->hostStage, &c->rowx, &c->tailE, &c->tailPart, &c->ldpart, &c->tw, &c->smp, &c->grp};
+                      &c->auxVar, &c->auxD, &c->hostStage, &c->rowx, &c->tailE, &c->tailPart, &c->ldpart, &c->tw, &c->smp, &c->grp, &c->Gtab, &c->Gprior, &c->gen};
     for (DevBuf* b : bufs) release(c, *b);
     release(c, c->mi);
     release(c, c->vr);
@@ -576,6 +631,7 @@ int algp_set_hypers(algp_ctx* c, int kernel, int D, const double* log_ls, double
     }
     c->hyp.kernel = kernel;
     c->hyp.additive = false;
+    leave_relationship(c);
     c->hyp.D = D;
     c->hyp.DP = D <= 2 ? 2 : (D <= 4 ? 4 : 8);
     for (int d = 0; d < MAXD; ++d) c->hyp.inv_ls[d] = d < D ? exp(-log_ls[d]) : 0.0;
@@ -603,6 +659,7 @@ int algp_set_hypers_additive(algp_ctx* c, int D, int kernel_a, int Da, double lo
     }
     c->hyp.kernel = kernel_a;
     c->hyp.additive = true;
+    leave_relationship(c);
     c->hyp.kernel_b = kernel_b;
     c->hyp.Da = Da;
     c->hyp.D = D;
@@ -618,11 +675,86 @@ int algp_set_hypers_additive(algp_ctx* c, int D, int kernel_a, int Da, double lo
     FINISH(c, DISPATCH(c, rescale_pool(c)));
 }
 
+int algp_set_hypers_relationship(algp_ctx* c, int D, int kernel_a, double log_os_a, const double* log_ls, double log_os_g,
+                                 const double* G, int64_t Q, double log_noise) {
+    CHECK_CTX(c);
+    if (D < 2 || D > MAXD || !log_ls) return fail(c, ALGP_ERR_BAD_ARG, "set_hypers_relationship: 2 <= D <= 8 required");
+    if (kernel_a < ALGP_KERNEL_RBF || kernel_a > ALGP_KERNEL_MATERN25) return fail(c, ALGP_ERR_BAD_ARG, "set_hypers_relationship: unknown kernel");
+    if (Q < 1) return fail(c, ALGP_ERR_BAD_ARG, "set_hypers_relationship: Q >= 1 required");
+    if (c->dtype == ALGP_F32 && Q > ((int64_t)1 << 24))
+        return fail(c, ALGP_ERR_BAD_ARG, "set_hypers_relationship: an fp32 context holds the ids exactly up to Q = 2^24 only");
+    if (G && Q > 46340) return fail(c, ALGP_ERR_BAD_ARG, "set_hypers_relationship: a table of more than 46340 genotypes is not supported");
+    double gmax = 1.0;
+    uint64_t gh = 0;
+    if (G) {
+        for (int64_t p = 0; p < Q; ++p)
+            for (int64_t q = 0; q <= p; ++q) {
+                const double a = G[p * Q + q], b = G[q * Q + p];
+                if (!std::isfinite(a) || !std::isfinite(b))
+                    return fail(c, ALGP_ERR_BAD_ARG, "set_hypers_relationship: G[" + std::to_string(p) + ", " + std::to_string(q) + "] is not finite");
+                if (memcmp(&a, &b, sizeof(double)) != 0)
+                    return fail(c, ALGP_ERR_BAD_ARG, "set_hypers_relationship: G[" + std::to_string(p) + ", " + std::to_string(q) +
+                                                         "] and its mirror entry differ (G must be bitwise symmetric)");
+            }
+        gmax = G[0];
+        for (int64_t q = 1; q < Q; ++q) gmax = std::max(gmax, G[q * Q + q]);
+        gh = 1469598103934665603ull;
+        const unsigned char* bytes = (const unsigned char*)G;
+        for (size_t b = 0; b < sizeof(double) * (size_t)Q * (size_t)Q; ++b) gh = (gh ^ bytes[b]) * 1099511628211ull;
+        if (gh == 0) gh = 1;
+    }
+    // the resident coordinate pool stays only with the same width: its ids must fit the new Q.  A refusal changes nothing.
+    const bool pool_stays = c->n_pool > 0 && !c->pool_is_cov && c->hyp.set && c->hyp.D == D;
+    if (pool_stays) ALGP_TRY(DISPATCH(c, rel_check_pool(c, D, Q)));
+    algp::DevBuf tab;
+    if (G) {
+        const int rc = DISPATCH(c, rel_upload_table(c, G, Q, tab));
+        if (rc != ALGP_OK) { release(c, tab); return rc; }
+    }
+    // everything from here on as algp_set_hypers does it
+    if (c->hyp.set && c->hyp.D != D && c->n_pool > 0 && !c->pool_is_cov) {
+        c->n_pool = 0;
+        c->N = 0;
+        c->pos_in_train.clear();
+    }
+    leave_relationship(c);
+    c->Gtab = tab;
+    c->hyp.kernel = kernel_a;
+    c->hyp.additive = false;
+    c->hyp.rel = true;
+    c->hyp.has_table = G != nullptr;
+    c->hyp.Q = Q;
+    c->hyp.Ghash = gh;
+    c->hyp.gdiag_max = gmax;
+    c->hyp.Da = D - 1;
+    c->hyp.D = D;
+    c->hyp.DP = D <= 2 ? 2 : (D <= 4 ? 4 : 8);
+    for (int d = 0; d < MAXD; ++d) c->hyp.inv_ls[d] = d < D - 1 ? exp(-log_ls[d]) : 0.0;
+    c->hyp.inv_ls[D - 1] = 1.0;                              // the id is never scaled: the scaled pool holds it exactly
+    c->hyp.outputscale = exp(log_os_a);
+    c->hyp.outputscale_g = exp(log_os_g);
+    c->hyp.noise = exp(log_noise);
+    c->hyp.set = true;
+    c->hyp_stamp++;
+    c->factored = false;
+    c->solved = false;
+    FINISH(c, DISPATCH(c, rescale_pool(c)));
+}
+
 int algp_kernel_matrix(algp_ctx* c, const void* x1, int64_t n1, const void* x2, int64_t n2, const void* diag_add,
                        int add_lik, void* out) {
     CHECK_CTX(c);
     NEED_HYPERS(c);
     if (!x1 || n1 < 0 || n2 < 0 || !out) return fail(c, ALGP_ERR_BAD_ARG, "kernel_matrix: bad arguments");
+    if (c->hyp.rel) {
+        if (c->dtype == ALGP_F64) {
+            ALGP_TRY(rel_check_ids<double>(c, (const double*)x1, n1, c->hyp.D, c->hyp.Q, "kernel_matrix: x1"));
+            if (x2) ALGP_TRY(rel_check_ids<double>(c, (const double*)x2, n2, c->hyp.D, c->hyp.Q, "kernel_matrix: x2"));
+        } else {
+            ALGP_TRY(rel_check_ids<float>(c, (const float*)x1, n1, c->hyp.D, c->hyp.Q, "kernel_matrix: x1"));
+            if (x2) ALGP_TRY(rel_check_ids<float>(c, (const float*)x2, n2, c->hyp.D, c->hyp.Q, "kernel_matrix: x2"));
+        }
+    }
     FINISH(c, DISPATCH(c, kernel_matrix(c, x1, n1, x2, n2, diag_add, add_lik, out)));
 }
 
@@ -630,6 +762,9 @@ int algp_set_pool(algp_ctx* c, const void* x, int64_t n) {
     CHECK_CTX(c);
     NEED_HYPERS(c);
     if (!x || n <= 0) return fail(c, ALGP_ERR_BAD_ARG, "set_pool: bad arguments");
+    if (c->hyp.rel)                                          // before anything changes: a refused pool leaves the one there was
+        ALGP_TRY(c->dtype == ALGP_F64 ? rel_check_ids<double>(c, (const double*)x, n, c->hyp.D, c->hyp.Q, "set_pool")
+                                      : rel_check_ids<float>(c, (const float*)x, n, c->hyp.D, c->hyp.Q, "set_pool"));
     c->factored = c->solved = false;
     c->hyp_stamp++;
     c->pos_in_train.clear();

@@ -162,7 +162,7 @@ void Impl<T>::plan_route(algp_ctx* c, int incremental, bool allow_fold, typename
     // read back -- the update products generate their C tiles.  Two scaled coordinates per site only (rhs_gen_supported): wider
     // coordinates and an explicit pool covariance keep the kernel-matrix launch.
     pl.rhs_fused = pl.route == SolveRoute::Sweep && keep == 0 && M > 0 && env_switch("ALGP_RHS_FUSED", true) &&
-                   trsm_plan(c, pl.sweep_rows, pl.sweep_end, keep, {.gen = true}).gen && rhs_gen_supported(c->hyp.DP, c->pool_is_cov, c->hyp.additive);
+                   trsm_plan(c, pl.sweep_rows, pl.sweep_end, keep, {.gen = true}).gen && rhs_gen_supported(c->hyp.DP, c->pool_is_cov, c->hyp.additive || c->hyp.rel);
 }
 
 template <typename T>
@@ -317,6 +317,27 @@ int Impl<T>::solve_narrow_tile(algp_ctx* c, const typename Impl<T>::SolvePlan& p
 }
 
 
+// The prior variance K_jj (+ sigma_n^2 under prior_includes_noise) of candidate j as cand_finalize_launch takes it: entry
+// p * stride + p of a table for pool site p, or one scalar where there is no table.  An explicit covariance: its diagonal
+// (stride n_pool).  The relationship form: os_a + os_g G[g_p, g_p] differs from site to site, so the priors of all pool sites
+// are kept in a vector (stride 0), rebuilt when the hyper-parameters, the pool or prior_includes_noise changed.
+template <typename T>
+int Impl<T>::site_prior(algp_ctx* c, SitePrior& pr) {
+    const double noise = c->prior_noise ? c->hyp.noise : 0.0;
+    pr = {c->pool_is_cov ? (const T*)c->Cp.p : nullptr, c->n_pool, (T)(c->hyp.prior_var() + noise)};
+    if (c->pool_is_cov || !c->hyp.rel) return ALGP_OK;
+    if (c->gprior_stamp != c->hyp_stamp || c->gprior_noise != c->prior_noise || !c->Gprior.p) {
+        ALGP_TRY(ensure(c, c->Gprior, sizeof(T) * c->n_pool));
+        ALGP_TRY(rel_prior_launch<T>(c, c->hyp.has_table ? (const T*)c->Gtab.p : nullptr, c->hyp.Q, (T)(c->hyp.outputscale + noise),
+                                     (T)c->hyp.outputscale_g, (const T*)c->Xs.p, c->hyp.DP, c->hyp.Da, c->n_pool, p(c->Gprior)));
+        c->gprior_stamp = c->hyp_stamp;
+        c->gprior_noise = c->prior_noise;
+    }
+    pr.tab = (const T*)c->Gprior.p;
+    pr.stride = 0;
+    return ALGP_OK;
+}
+
 template <typename T>
 int Impl<T>::solve_finish(algp_ctx* c, int incremental, const unsigned char* alive_host, const typename Impl<T>::SolvePlan& pl) {
     const int64_t N = c->N, Npad = c->Npad, M = c->M, Mpad = c->Mpad, ldc = c->ldv, keep = pl.keep;
@@ -360,9 +381,9 @@ int Impl<T>::solve_finish(algp_ctx* c, int incremental, const unsigned char* ali
             ALGP_TRY(rows_reduce_launch<T>(c, p(c->Vt), M, ldc, Npad, p(c->z), ss, dot));
         }
     }
-    const T prior = (T)(c->hyp.prior_var() + (c->prior_noise ? c->hyp.noise : 0.0));
-    ALGP_TRY(cand_finalize_launch<T>(c, M, (const int*)c->ckind.p, (const int64_t*)c->Cidx.p,
-                                     c->pool_is_cov ? (const T*)c->Cp.p : nullptr, c->n_pool, prior,
+    SitePrior pr;
+    ALGP_TRY(site_prior(c, pr));
+    ALGP_TRY(cand_finalize_launch<T>(c, M, (const int*)c->ckind.p, (const int64_t*)c->Cidx.p, pr.tab, pr.stride, pr.scalar,
                                      c->cextra.p ? (const T*)c->cextra.p : nullptr, ss, dot, (T)c->ybar, p(c->dstat),
                                      p(c->mu), (unsigned char*)c->alive.p));
     if (alive_host) ALGP_HIP(hipMemcpyAsync(c->alive.p, alive_host, M, hipMemcpyHostToDevice, c->stream));
@@ -611,7 +632,7 @@ int algp_posterior_mean_component(algp_ctx* c, int component, const int64_t* idx
     if (component < 0 || component > 1) return fail(c, ALGP_ERR_BAD_ARG, "posterior_mean_component: component must be 0 or 1");
     if (M < 0 || (M > 0 && (!idx || !mu))) return fail(c, ALGP_ERR_BAD_ARG, "posterior_mean_component: bad arguments");
     if (c->pool_is_cov) return fail(c, ALGP_ERR_BAD_ARG, "posterior_mean_component needs a coordinate pool");
-    if (!c->hyp.set || !c->hyp.additive)
+    if (!c->hyp.set || !(c->hyp.additive || c->hyp.rel))
         return fail(c, ALGP_ERR_STATE, "posterior_mean_component: a single kernel is in force (algp_set_hypers_additive)");
     for (int64_t i = 0; i < M; ++i)
         if (idx[i] < 0 || idx[i] >= c->n_pool) return fail(c, ALGP_ERR_BAD_ARG, "posterior_mean_component: index outside the pool");

@@ -32,8 +32,12 @@ int Impl<T>::mll_grad(algp_ctx* c, double* grad_out, bool have_X, bool inv_enque
     else ALGP_TRY(syrk_upper<T>(c, ALGP_PROF_GEMM_OTHER, p(c->auxW), Npad, Npad, p(c->auxA), Npad));
     double* sc = (double*)c->scal.p + SC_GRAD;        // slots 16..27: os, trace, ls[0..8); additive: os_a, os_b, trace, ls[0..8)
     ALGP_HIP(hipMemsetAsync(sc, 0, sizeof(double) * 12, c->stream));
-    const bool add = c->hyp.additive;
-    if (add)
+    const bool add = c->hyp.additive || c->hyp.rel;    // three leading sums: the second outputscale (os_b, or os_g under the relationship form)
+    if (c->hyp.rel)
+        ALGP_TRY(mll_grad_rel_launch<T>(c, p(c->auxA), Npad, N, (const T*)c->Xs.p, DP, (const int64_t*)c->Aidx.p, (const T*)c->alpha.p,
+                                        c->hyp.kernel, (T)c->hyp.outputscale, c->hyp.has_table ? (const T*)c->Gtab.p : nullptr, c->hyp.Q,
+                                        (T)c->hyp.outputscale_g, c->hyp.Da, sc, (double*)c->auxW.p));
+    else if (add)
         ALGP_TRY(mll_grad_add_launch<T>(c, p(c->auxA), Npad, N, (const T*)c->Xs.p, DP, (const int64_t*)c->Aidx.p, (const T*)c->alpha.p,
                                         c->hyp.kernel, (T)c->hyp.outputscale, c->hyp.kernel_b, (T)c->hyp.outputscale_b, c->hyp.Da, sc,
                                         (double*)c->auxW.p));
@@ -47,11 +51,12 @@ int Impl<T>::mll_grad(algp_ctx* c, double* grad_out, bool have_X, bool inv_enque
         const int rc = sync_checked(c, "get_mll_grad");
         if (rc != ALGP_OK) { c->alpha_valid = false; return rc; }
     }
-    if (add) {                                        // D + 3: [log ls | log os_a, log os_b, log sigma_n^2]
-        for (int d = 0; d < D; ++d) grad_out[d] = 0.5 * h[3 + d];
-        grad_out[D] = 0.5 * h[0];
-        grad_out[D + 1] = 0.5 * h[1];
-        grad_out[D + 2] = 0.5 * c->hyp.noise * h[2];
+    if (add) {                                        // D + 3: [log ls | log os_a, log os_b, log sigma_n^2]; relationship: D + 2, the id has no lengthscale
+        const int nl = c->hyp.rel ? D - 1 : D;
+        for (int d = 0; d < nl; ++d) grad_out[d] = 0.5 * h[3 + d];
+        grad_out[nl] = 0.5 * h[0];
+        grad_out[nl + 1] = 0.5 * h[1];
+        grad_out[nl + 2] = 0.5 * c->hyp.noise * h[2];
         return ALGP_OK;
     }
     for (int d = 0; d < D; ++d) grad_out[d] = 0.5 * h[2 + d];

@@ -98,8 +98,9 @@ int Impl<T>::remote_row(algp_ctx* c, int64_t pool_idx, int in_train) {
     ALGP_TRY(kmat_launch<T>(c, s, r.cidx, 1, 1, (const int64_t*)c->Aidx.p, N, Npad, nullptr, 0, r.ckind, 0, l, ldv));
     ALGP_TRY(trsv_forward<T>(c, p(c->L), Npad, c->Lld, p(c->invD), l));
     ALGP_TRY(rows_reduce_launch<T>(c, l, 1, ldv, Npad, (const T*)nullptr, r.ss, (T*)nullptr));
-    const T prior = (T)(c->hyp.prior_var() + (c->prior_noise ? c->hyp.noise : 0.0));
-    ALGP_TRY(cand_finalize_launch<T>(c, 1, r.ckind, r.cidx, c->pool_is_cov ? (const T*)c->Cp.p : nullptr, c->n_pool, prior,
+    SitePrior pr;
+    ALGP_TRY(site_prior(c, pr));
+    ALGP_TRY(cand_finalize_launch<T>(c, 1, r.ckind, r.cidx, pr.tab, pr.stride, pr.scalar,
                                      (const T*)nullptr, r.ss, r.dot, (T)0, r.dstat, r.mu, r.alive));
     if (!c->picks.empty())
         ALGP_TRY(lazy_refresh_launch<T>(c, 1, 2, 0, (const LazyPick*)c->lazypicks.p, (int)c->picks.size(), r.ckind, r.cidx,

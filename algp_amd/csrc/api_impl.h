@@ -4,7 +4,7 @@
 // picks, the sharded exchange), api_mi.hip (the MI criterion's state, on one GPU and over the ranks), api_vr.hip (the
 // variance-reduction criterion), api_paths.hip (best_path block scoring), api_paths_vr.hip (the variance-reduction utility of
 // whole paths), api_fit.hip (MLL gradient, one fit iteration), api_sample.hip (joint posterior draws),
-// api_group.hip (the joint posterior of group aggregates).
+// api_group.hip (the joint posterior of group aggregates), api_genotype.hip (the genotype effects under the relationship form).
 // Every file defines its members of Impl<T> and instantiates Impl<float> / Impl<double> for them.
 #pragma once
 #include <limits.h>
@@ -23,6 +23,9 @@ void release(algp_ctx* c, DevBuf& b);
 void release(algp_ctx* c, MiState& mi);   // every MI buffer (api_mi.hip)
 void release(algp_ctx* c, VrState& vr);   // every buffer of the variance-reduction criterion (api_vr.hip)
 KmatSrc make_src(algp_ctx* c);
+void leave_relationship(algp_ctx* c);     // the relationship form's table goes (api.hip)
+template <typename T>
+int rel_check_ids(algp_ctx* c, const T* x, int64_t n, int D, int64_t Q, const char* what);
 int sync(algp_ctx* c);
 int sync_checked(algp_ctx* c, const char* what);
 // the variance-reduction criterion is scored over the ranks of the communicator: a layout is attached (algp_comm_set_vr_exchange)
@@ -40,6 +43,13 @@ struct Impl {
     static int kernel_matrix(algp_ctx* c, const void* x1, int64_t n1, const void* x2, int64_t n2, const void* diag_add,
                              int add_lik, void* out);
     static int set_pool(algp_ctx* c, const void* x, int64_t n);
+    // the relationship form (api.hip): the resident pool's ids against Q; the table to the device; (api_candidates.hip) the prior
+    // variance of the candidates as cand_finalize_launch takes it; (api_genotype.hip) the genotype effects' posterior
+    static int rel_check_pool(algp_ctx* c, int D, int64_t Q);
+    static int rel_upload_table(algp_ctx* c, const double* G, int64_t Q, DevBuf& dst);
+    struct SitePrior { const T* tab; int64_t stride; T scalar; };
+    static int site_prior(algp_ctx* c, SitePrior& pr);
+    static int genotype_posterior(algp_ctx* c, void* mean_out, void* var_out, void* cov_out);
     static uint64_t train_sites_hash(const algp_ctx* c, const std::vector<int64_t>& idx);
     static int set_pool_cov(algp_ctx* c, const void* cov, int64_t n);
     static int set_train(algp_ctx* c, const int64_t* idx, int64_t N, const void* y, const void* var);

@@ -59,7 +59,19 @@ struct Hypers {
     bool additive = false;
     int kernel_b = ALGP_KERNEL_RBF, Da = 0;
     double outputscale_b = 0.0;
-    double prior_var() const { return additive ? outputscale + outputscale_b : outputscale; }   // K_jj
+    // the relationship form (algp_set_hypers_relationship): k = os kappa_kernel(r_a) + os_g G[g, g'], r_a over the first D - 1
+    // coordinates (Da), g the integer id in coordinate D - 1 (inverse lengthscale exactly 1); kernel / outputscale are part a's.
+    // The table lives in algp_ctx::Gtab in the context's dtype (has_table; else G = I); Ghash: the FNV-1a fingerprint of the
+    // caller's Q x Q doubles (0 for the identity), what algp_factorize_from compares as it compares the sites' coordinates by
+    // theirs; gdiag_max = max_q G_qq (1 for the identity)
+    bool rel = false;
+    bool has_table = false;
+    int64_t Q = 0;
+    double outputscale_g = 0.0, gdiag_max = 1.0;
+    uint64_t Ghash = 0;
+    // K_jj where it is one scalar (the single and additive forms); under the relationship form the LARGEST prior variance (the
+    // jitter's scale) -- the per-site prior goes through algp_ctx::Gprior
+    double prior_var() const { return rel ? outputscale + outputscale_g * gdiag_max : additive ? outputscale + outputscale_b : outputscale; }
 };
 
 struct PickRec {           // one committed greedy pick, host side (the device keeps a LazyPick with the row's scale)
@@ -291,6 +303,48 @@ __device__ __forceinline__ T kmat_value_add(int ka, T osa, int kb, T osb, int da
     split_r2<DP>(&xr[0], &xc[0], da, ra, rb);
     return kval_add<T>(ka, osa, ra, kb, osb, rb);
 }
+// The relationship form, a fourth family (3): k = os_a kappa_a(r_a) + os_g G[ia Q + ib], r_a over the first da scaled coordinates
+// and ia, ib the two sites' integer ids, held exactly in coordinate da (its inverse lengthscale is 1; validated on the host to be
+// integers in [0, Q) before any launch, and the zero padding reads id 0).  G null: the identity, the part's value os_g (ia == ib).
+// Compiled as instantiations of its own like the additive form.  ONE definition for every site: r_a^2 as split_r2 sums it (each
+// square rounded on its own, coordinate order, contraction off), the table index in 64 bits, one rounded product os_g G and one
+// rounded sum of the two terms.
+template <int DP, typename C, typename XA, typename XB>
+__device__ __forceinline__ void rel_r2(const XA* xa, const XB* xb, int da, C& ra, int64_t& ia, int64_t& ib) {
+#pragma clang fp contract(off)
+    ra = (C)0;
+    C ga = (C)0, gb = (C)0;
+#pragma unroll
+    for (int d = 0; d < DP; ++d) {
+        const C va = (C)xa[d], vb = (C)xb[d];
+        const C df = va - vb;
+        const C q = df * df;
+        ra += d < da ? q : (C)0;
+        ga = d == da ? va : ga;
+        gb = d == da ? vb : gb;
+    }
+    ia = (int64_t)ga;
+    ib = (int64_t)gb;
+}
+// parts: bit 0 = the spatial part, bit 1 = the genotype part (as kval_add)
+template <typename C, typename T>
+__device__ __forceinline__ C kval_rel(int ka, C osa, C ra, const T* G, int64_t Q, C osg, int64_t ia, int64_t ib, int parts = 3) {
+#pragma clang fp contract(off)
+    const C va = (parts & 1) ? kval<C>(ka, osa, ra) : (C)0;
+    C vg = (C)0;
+    if (parts & 2) {
+        const C g = G ? (C)G[ia * Q + ib] : (ia == ib ? (C)1 : (C)0);
+        vg = osg * g;
+    }
+    return va + vg;
+}
+template <typename T, int DP>
+__device__ __forceinline__ T kmat_value_rel(int ka, T osa, const T* G, int64_t Q, T osg, int da, const T (&xr)[DP], const T (&xc)[DP]) {
+    T ra;
+    int64_t ia, ib;
+    rel_r2<DP>(&xr[0], &xc[0], da, ra, ia, ib);
+    return kval_rel<T, T>(ka, osa, ra, G, Q, osg, ia, ib);
+}
 // Entry (row, global column gcol) of the candidates' right-hand side B^T = K(candidates, train) as the matrix build writes it:
 // kind -1: an ordinary row, k(x_row, x_col) in the columns of the train set (gcol < ncols), 0 in the padding behind them;
 // kind >= 0: the unit row e_kind (a candidate that is a train site under prior_includes_noise); kind -2: a padding row, 0.
@@ -335,10 +389,33 @@ struct is_additive : std::false_type {};
 template <typename S>
 struct is_additive<S, std::void_t<decltype(std::declval<S>().kernel_b)>> : std::true_type {};
 
+// The relationship form's source: CovSrc (kernel, os: the spatial part), the table (null: the identity) in the storage type, its
+// order, the genotype part's outputscale, the coordinate that holds the id (da = D - 1) and the parts that count.  A source type
+// of its own for the reason CovSrcAdd is one.
+template <typename T, typename C = T>
+struct CovSrcRel : CovSrc<T, C> {
+    const T* G;
+    int64_t Q;
+    int da, parts;
+    C os_g;
+};
+// S carries the relationship fields (CovSrcRel, or the GEMM's argument structs with the same fields appended)
+template <typename S, typename = void>
+struct is_rel : std::false_type {};
+template <typename S>
+struct is_rel<S, std::void_t<decltype(std::declval<S>().os_g)>> : std::true_type {};
+
 template <int DP, bool NOISE = true, typename S, typename XA, typename XB>
 __device__ __forceinline__ auto pool_cov(const S& s, int64_t pa, int64_t pb, const XA* xa, const XB* xb) {
     using C = std::remove_cv_t<decltype(s.os)>;
-    if constexpr (is_additive<S>::value) {
+    if constexpr (is_rel<S>::value) {
+        C ra;
+        int64_t ia, ib;
+        rel_r2<DP>(xa, xb, s.da, ra, ia, ib);
+        C v = kval_rel<C>(s.kernel, s.os, ra, s.G, s.Q, s.os_g, ia, ib, s.parts);
+        if (NOISE && pa == pb) v += s.noise;
+        return v;
+    } else if constexpr (is_additive<S>::value) {
         C ra, rb;
         split_r2<DP>(xa, xb, s.da, ra, rb);
         C v = kval_add<C>(s.kernel, s.os, ra, s.kernel_b, s.os_b, rb, s.parts);
@@ -503,6 +580,12 @@ struct algp_ctx {
     algp::DevBuf auxA, auxInv, auxW, auxIdx, auxVar, auxD, hostStage;
     algp::DevBuf smp;                    // algp_sample_posterior's scratch, one allocation carved up per call (api_sample.hip)
     algp::DevBuf grp;                    // algp_group_posterior's scratch, likewise (api_group.hip)
+    // the relationship form (Hypers::rel): the Q x Q table in the context's dtype (while hyp.has_table), the prior variance
+    // os_a + os_g G[g_j, g_j] of every pool site (the per-site prior of cand_finalize_launch, rebuilt with the scaled pool), and
+    // algp_genotype_posterior's scratch, one allocation carved up per call (api_genotype.hip)
+    algp::DevBuf Gtab, Gprior, gen;
+    uint64_t gprior_stamp = 0;           // Gprior holds the priors for this hyp_stamp and gprior_noise (prior_includes_noise)
+    int gprior_noise = -1;
 
     // profiling
     bool prof_on = false;
@@ -586,6 +669,12 @@ struct KmatSrc {
     int kernel_b = -1, da = 0, parts = 3;
     double outputscale_b = 0;
     bool additive() const { return kernel_b >= 0 && !Cp; }
+    // the relationship form (Q > 0; kernel / outputscale are then the spatial part's, da = D - 1 the id's coordinate, kernel_b
+    // stays -1): the table in the context's dtype or null for the identity, its order, the genotype part's outputscale
+    const void* G = nullptr;
+    int64_t Q = 0;
+    double outputscale_g = 0;
+    bool rel() const { return Q > 0 && !Cp; }
 };
 // the device-side view of a source (CovSrc above).  The one place that says what `noise` means per pool kind: an explicit
 // covariance carries sigma_n^2 on its diagonal already, so nothing is added to it anywhere
@@ -593,11 +682,16 @@ template <typename T, typename C = T>
 inline CovSrc<T, C> cov_src(const KmatSrc& s) {
     return {(const T*)s.Xs, (const T*)s.Cp, s.n_pool, s.kernel, (C)s.outputscale, (C)(s.Cp ? 0.0 : s.noise)};
 }
-// f(the typed source): a CovSrc, or a CovSrcAdd under the additive form -- the kernel's source type is a template argument, so
-// the additive form runs instantiations of its own
+// f(the typed source): a CovSrc, a CovSrcAdd under the additive form or a CovSrcRel under the relationship form -- the kernel's
+// source type is a template argument, so those two forms run instantiations of their own
 template <typename T, typename C = T, typename F>
 inline void with_src(const KmatSrc& s, F&& f) {
-    if (s.additive()) {
+    if (s.rel()) {
+        CovSrcRel<T, C> a;
+        static_cast<CovSrc<T, C>&>(a) = cov_src<T, C>(s);
+        a.G = (const T*)s.G; a.Q = s.Q; a.da = s.da; a.parts = s.parts; a.os_g = (C)s.outputscale_g;
+        f(a);
+    } else if (s.additive()) {
         CovSrcAdd<T, C> a;
         static_cast<CovSrc<T, C>&>(a) = cov_src<T, C>(s);
         a.kernel_b = s.kernel_b; a.da = s.da; a.parts = s.parts; a.os_b = (C)s.outputscale_b;
@@ -642,8 +736,8 @@ int rhs_gather_launch(algp_ctx* c, const T* Xs, int DP, const int64_t* ridx, int
 template <typename T>
 int gemm_nt_launch_gen(algp_ctx* c, int klass, int64_t m, int64_t n, int64_t k, T alpha, const T* A, int64_t lda, const T* B,
                        int64_t ldb, T beta, const RhsGen& gen, int64_t col0, T* D, int64_t ldd);
-// whether gemm_nt_launch_gen has a kernel for this generator (DP = 2; wider coordinates and the additive form take the
-// materialised route)
+// whether gemm_nt_launch_gen has a kernel for this generator (DP = 2; wider coordinates, the additive and the relationship form
+// (additive = true for either) take the materialised route)
 bool rhs_gen_supported(int DP, bool pool_is_cov, bool additive = false);
 
 // out[r][c] for r<rows_pad, c<cols_pad (ld = ldo):

@@ -257,4 +257,212 @@ int mll_grad_add_launch(algp_ctx* c, const T* Sinv, int64_t ld, int64_t N, const
 }
 ALGP_INSTANTIATE(mll_grad_add_launch);
 
+// The relationship kernel (common.h: family 3), a third gradient kernel: S = os_a kappa_a(r_a) + os_g G[g_i, g_j] + ..., so
+// dS/dlog os_a = K_a, dS/dlog os_g = os_g G[g_i, g_j] (the part's value as kval_rel rounds it), and dS/dlog ls_d = dk_a u_d^2 for
+// the spatial coordinates d < da; the id's coordinate has no lengthscale (its sum stays 0 and is not returned).  r_a^2 by
+// rel_r2's rule.  Per workgroup: [0] = os_a, [1] = os_g, [2] = noise trace, [3..3+DP) = ls.  The same tiles, staging and
+// fixed-order reduction as mll_grad_kernel; the table entry is one gather per pair.
+template <typename T, int DP>
+__global__ __launch_bounds__(256) void mll_grad_rel_kernel(const T* Sinv, int64_t ld, int64_t N, const T* Xs, const int64_t* aidx,
+                                                           const T* alpha, int kernel_a, T os_a, const T* G, int64_t Q, T os_g, int da,
+                                                           int repeats, double* partial) {
+#pragma clang fp contract(off)
+    int bi = (int)((sqrt(8.0 * (double)blockIdx.x + 1.0) - 1.0) * 0.5);
+    while ((int64_t)(bi + 1) * (bi + 2) / 2 <= (int64_t)blockIdx.x) ++bi;
+    while ((int64_t)bi * (bi + 1) / 2 > (int64_t)blockIdx.x) --bi;
+    const int bj = (int)(blockIdx.x - (int64_t)bi * (bi + 1) / 2);
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    __shared__ T s_x[64][DP];
+    __shared__ T s_a[64];
+    __shared__ int64_t s_p[64];
+    if (threadIdx.x < 64) {
+        const int64_t i = (int64_t)bi * 64 + threadIdx.x;
+        const bool ok = i < N;
+        const int64_t pi = ok ? aidx[i] : 0;
+#pragma unroll
+        for (int d = 0; d < DP; ++d) s_x[threadIdx.x][d] = ok ? Xs[pi * DP + d] : (T)0;
+        s_a[threadIdx.x] = ok ? alpha[i] : (T)0;
+        s_p[threadIdx.x] = ok ? pi : (int64_t)-1;
+    }
+    const int64_t j = (int64_t)bj * 64 + tx;
+    double g_osa = 0, g_osg = 0, g_tr = 0, g_ls[DP];
+#pragma unroll
+    for (int d = 0; d < DP; ++d) g_ls[d] = 0;
+    T xj[DP], aj = (T)0;
+    int64_t pj = -2;
+#pragma unroll
+    for (int d = 0; d < DP; ++d) xj[d] = (T)0;
+    if (j < N) {
+        pj = aidx[j];
+#pragma unroll
+        for (int d = 0; d < DP; ++d) xj[d] = Xs[pj * DP + d];
+        aj = alpha[j];
+    }
+    __syncthreads();
+    if (j < N) {
+        for (int rr = 0; rr < 16; ++rr) {
+            const int li = ty * 16 + rr;
+            const int64_t i = (int64_t)bi * 64 + li;
+            if (i >= N || j > i) continue;
+            T u2[DP], ra = (T)0, gi = (T)0, gj = (T)0;
+#pragma unroll
+            for (int d = 0; d < DP; ++d) {
+                const T xi = s_x[li][d];
+                const T df = xi - xj[d];
+                u2[d] = df * df;
+                ra += d < da ? u2[d] : (T)0;
+                gi = d == da ? xi : gi;
+                gj = d == da ? xj[d] : gj;
+            }
+            const int64_t ia = (int64_t)gi, ib = (int64_t)gj;
+            const T w = s_a[li] * aj - Sinv[i * ld + j];
+            const double m = (i == j) ? 1.0 : 2.0;
+            T dka;
+            const T ka = kdk<T>(kernel_a, os_a, ra, dka);
+            const T kg = os_g * (G ? G[ia * Q + ib] : (ia == ib ? (T)1 : (T)0));
+            g_osa += m * (double)(w * ka);
+            g_osg += m * (double)(w * kg);
+            if (i == j) g_tr += (double)w;
+            else if (repeats && s_p[li] == pj) g_tr += 2.0 * (double)w;
+#pragma unroll
+            for (int d = 0; d < DP; ++d) g_ls[d] += d < da ? m * (double)(w * dka * u2[d]) : 0.0;
+        }
+    }
+    auto wsum = [](double v) {
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+        return v;
+    };
+    __shared__ double s_red[4][3 + DP];
+    g_osa = wsum(g_osa);
+    g_osg = wsum(g_osg);
+    g_tr = wsum(g_tr);
+#pragma unroll
+    for (int d = 0; d < DP; ++d) g_ls[d] = wsum(g_ls[d]);
+    if (tx == 0) {
+        s_red[ty][0] = g_osa;
+        s_red[ty][1] = g_osg;
+        s_red[ty][2] = g_tr;
+#pragma unroll
+        for (int d = 0; d < DP; ++d) s_red[ty][3 + d] = g_ls[d];
+    }
+    __syncthreads();
+    if (threadIdx.x < 3 + DP)
+        partial[(int64_t)blockIdx.x * (3 + DP) + threadIdx.x] =
+            (s_red[0][threadIdx.x] + s_red[1][threadIdx.x]) + (s_red[2][threadIdx.x] + s_red[3][threadIdx.x]);
+}
+
+// the relationship kernel's: out_dev[0] = os_a, [1] = os_g, [2] = noise trace, [3..3+DP) = ls (zero from the id's coordinate on)
+template <typename T>
+int mll_grad_rel_launch(algp_ctx* c, const T* Sinv, int64_t ld, int64_t N, const T* Xs, int DP, const int64_t* aidx, const T* alpha,
+                        int kernel_a, T os_a, const T* G, int64_t Q, T os_g, int da, double* out_dev, double* partial) {
+    if (N <= 0) return ALGP_OK;
+    const int rp = c->train_has_repeats ? 1 : 0;
+    const unsigned nb = (unsigned)((N + 63) / 64);
+    ProfScope ps(c, ALGP_PROF_KMAT, 0.5 * (double)N * N * (3.0 * DP + 10.0), sizeof(T) * (double)N * N);
+    dim3 grid(nb * (nb + 1) / 2), blk(256);
+    with_dp(DP, [&](auto dp) {
+        hipLaunchKernelGGL((mll_grad_rel_kernel<T, decltype(dp)::value>), grid, blk, 0, c->cur, Sinv, ld, N, Xs, aidx, alpha, kernel_a, os_a,
+                           G, Q, os_g, da, rp, partial);
+    });
+    ALGP_HIP(hipGetLastError());
+    hipLaunchKernelGGL(mll_grad_reduce_kernel, dim3(1), dim3(256), 0, c->cur, partial, (int64_t)grid.x, 3 + DP, out_dev);
+    ALGP_HIP(hipGetLastError());
+    return ALGP_OK;
+}
+ALGP_INSTANTIATE(mll_grad_rel_launch);
+
+// ---------------------------------------------------------------------------------------------
+// The relationship form's gathers from its table (algp_genotype_posterior's B, the per-site prior of the candidates).
+// ---------------------------------------------------------------------------------------------
+// B[q][i] = os_g G[q, g_i] for q < Q and train row i < N (g_i: the id in coordinate da of the row's pool site), zero in the
+// padding up to Qpad x Npad: the right-hand sides of the genotype posterior.  The product rounds as kval_rel's does.
+template <typename T>
+__global__ __launch_bounds__(256) void rel_gather_b_kernel(const T* G, int64_t Q, T os_g, const T* Xs, int DP, int da, const int64_t* aidx,
+                                                           int64_t N, int64_t Qpad, int64_t Npad, T* B) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t q = blockIdx.y;
+    if (i >= Npad) return;
+    T v = (T)0;
+    if (q < Q && i < N) {
+        const int64_t gi = (int64_t)Xs[aidx[i] * DP + da];
+        v = os_g * (G ? G[q * Q + gi] : (q == gi ? (T)1 : (T)0));
+    }
+    B[q * Npad + i] = v;
+}
+template <typename T>
+int rel_gather_b_launch(algp_ctx* c, const T* G, int64_t Q, T os_g, const T* Xs, int DP, int da, const int64_t* aidx, int64_t N,
+                        int64_t Qpad, int64_t Npad, T* B) {
+    if (Qpad <= 0 || Npad <= 0) return ALGP_OK;
+    if (Qpad > 65535) return fail(c, ALGP_ERR_BAD_ARG, "genotype_posterior: at most 65408 genotypes");
+    ProfScope ps(c, ALGP_PROF_ROWS, (double)Qpad * Npad, sizeof(T) * 2.0 * (double)Qpad * Npad);
+    hipLaunchKernelGGL(rel_gather_b_kernel<T>, dim3((unsigned)((Npad + 255) / 256), (unsigned)Qpad), dim3(256), 0, c->cur, G, Q, os_g, Xs, DP,
+                       da, aidx, N, Qpad, Npad, B);
+    ALGP_HIP(hipGetLastError());
+    return ALGP_OK;
+}
+ALGP_INSTANTIATE(rel_gather_b_launch);
+
+// prior[j] = os_a + os_g G[g_j, g_j] for every pool site j < n: K_jj under the relationship form, where the single forms have one
+// scalar.  The value the matrix build gives the diagonal: kappa_a(0) = 1 exactly in all four forms (os_a * 1), then kval_rel's
+// product and sum.
+template <typename T>
+__global__ __launch_bounds__(256) void rel_prior_kernel(const T* G, int64_t Q, T os_a, T os_g, const T* Xs, int DP, int da, int64_t n, T* prior) {
+#pragma clang fp contract(off)
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    const int64_t g = (int64_t)Xs[j * DP + da];
+    const T vg = os_g * (G ? G[g * Q + g] : (T)1);
+    prior[j] = os_a + vg;
+}
+template <typename T>
+int rel_prior_launch(algp_ctx* c, const T* G, int64_t Q, T os_a, T os_g, const T* Xs, int DP, int da, int64_t n, T* prior) {
+    if (n <= 0) return ALGP_OK;
+    hipLaunchKernelGGL(rel_prior_kernel<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->cur, G, Q, os_a, os_g, Xs, DP, da, n, prior);
+    ALGP_HIP(hipGetLastError());
+    return ALGP_OK;
+}
+ALGP_INSTANTIATE(rel_prior_launch);
+
+// cov[p][q] = cov[q][p] = os_g G[p, q] - WW[p][q] for q <= p < Q (WW: the lower tiles of W W^T, leading dimension ldw; null: no
+// train rows, nothing is subtracted): the genotype posterior's covariance, both triangles from the one value -- identical bits.
+// The product os_g G rounds as kval_rel's does.
+template <typename T>
+__global__ __launch_bounds__(256) void rel_cov_finish_kernel(const T* G, int64_t Q, T os_g, const T* WW, int64_t ldw, T* cov) {
+#pragma clang fp contract(off)
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t p = blockIdx.y;
+    if (q > p || p >= Q) return;
+    const T pr = os_g * (G ? G[p * Q + q] : (p == q ? (T)1 : (T)0));
+    const T v = WW ? pr - WW[p * ldw + q] : pr;
+    cov[p * Q + q] = v;
+    cov[q * Q + p] = v;
+}
+template <typename T>
+int rel_cov_finish_launch(algp_ctx* c, const T* G, int64_t Q, T os_g, const T* WW, int64_t ldw, T* cov) {
+    if (Q <= 0) return ALGP_OK;
+    if (Q > 65535) return fail(c, ALGP_ERR_BAD_ARG, "genotype_posterior: at most 65408 genotypes");
+    ProfScope ps(c, ALGP_PROF_ROWS, (double)Q * Q, sizeof(T) * 2.5 * (double)Q * Q);
+    hipLaunchKernelGGL(rel_cov_finish_kernel<T>, dim3((unsigned)((Q + 255) / 256), (unsigned)Q), dim3(256), 0, c->cur, G, Q, os_g, WW, ldw, cov);
+    ALGP_HIP(hipGetLastError());
+    return ALGP_OK;
+}
+ALGP_INSTANTIATE(rel_cov_finish_launch);
+// var[q] = os_g G[q, q] - ss[q], q < Q (ss: the squared row norms of W, or null)
+template <typename T>
+__global__ __launch_bounds__(256) void rel_var_finish_kernel(const T* G, int64_t Q, T os_g, const T* ss, T* var) {
+#pragma clang fp contract(off)
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= Q) return;
+    const T pr = os_g * (G ? G[q * Q + q] : (T)1);
+    var[q] = ss ? pr - ss[q] : pr;
+}
+template <typename T>
+int rel_var_finish_launch(algp_ctx* c, const T* G, int64_t Q, T os_g, const T* ss, T* var) {
+    if (Q <= 0) return ALGP_OK;
+    hipLaunchKernelGGL(rel_var_finish_kernel<T>, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, c->cur, G, Q, os_g, ss, var);
+    ALGP_HIP(hipGetLastError());
+    return ALGP_OK;
+}
+ALGP_INSTANTIATE(rel_var_finish_launch);
+
 }  // namespace algp

@@ -163,6 +163,15 @@ struct AddGemmArgs : Base {
     T os_b;
 };
 
+// The relationship form of the same structs: the table's fields appended (is_rel, common.h), kernels of their own likewise
+template <typename T, typename Base>
+struct RelGemmArgs : Base {
+    const T* G;
+    int64_t Q;
+    int da, parts;
+    T os_g;
+};
+
 // C(prow, pcol) for the two epilogues below: pool_cov (common.h) over the launch's own source fields, the coordinates of the
 // row in registers and of the column staged in LDS, both at width MAXD
 template <typename T, typename G>
@@ -333,7 +342,7 @@ __device__ __forceinline__ void pvr_epilogue(const G& g, char* smem, const ACC (
                 Er[col] = (rowon && sw != (T)0) ? sw * (cv - acc[i][j][r]) : (T)0;
                 // the additive form evaluates two kernels per entry: one column after the other, or the scheduler overlaps the
                 // four and the fp64 kernel no longer fits its registers beside the accumulators (the single forms: as before)
-                if constexpr (is_additive<G>::value) __builtin_amdgcn_sched_barrier(0);
+                if constexpr (is_additive<G>::value || is_rel<G>::value) __builtin_amdgcn_sched_barrier(0);
             }
         }
 }
@@ -1013,6 +1022,12 @@ static void vr_fill(VrGemmArgs<T>& g, const KmatSrc& s, const int64_t* cidx, con
 // its additive form (AddGemmArgs) -- instantiations of their own
 template <typename T, typename G>
 static int vr_dispatch(algp_ctx* c, int klass, const Booking& bk, dim3 grid, const G& g, const KmatSrc& s) {
+    if (s.rel()) {
+        RelGemmArgs<T, G> a;
+        static_cast<G&>(a) = g;
+        a.G = (const T*)s.G; a.Q = s.Q; a.da = s.da; a.parts = 3; a.os_g = (T)s.outputscale_g;
+        return dispatch(c, klass, bk.flops, bk.bytes, gemm_nt_kernel_dma4<T, false, RelGemmArgs<T, G>>, grid, a);
+    }
     if (!s.additive()) return dispatch(c, klass, bk.flops, bk.bytes, gemm_nt_kernel_dma4<T, false, G>, grid, g);
     AddGemmArgs<T, G> a;
     static_cast<G&>(a) = g;

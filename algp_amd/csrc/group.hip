@@ -43,6 +43,20 @@ struct GroupCovSrc<T, -1> {
     int kernel, kernel_b, da, parts;
     T os_b;
 };
+// KERNEL = -2: the relationship form -- the spatial form, the table and the genotype part's outputscale at run time (pool_cov's
+// relationship branch)
+template <typename T>
+struct GroupCovSrc<T, -2> {
+    static constexpr const T* Cp = nullptr;
+    const T* Xs;
+    int64_t n_pool;
+    T os, noise;
+    int kernel;
+    const T* G;
+    int64_t Q;
+    int da, parts;
+    T os_g;
+};
 template <typename F>
 inline void with_kernel(int kernel, F&& f) {
     if (kernel == ALGP_KERNEL_RBF) f(std::integral_constant<int, ALGP_KERNEL_RBF>{});
@@ -164,7 +178,12 @@ int group_ksum_launch(algp_ctx* c, const KmatSrc& s, const int64_t* cidx, int64_
         ProfScope ps(c, ALGP_PROF_KMAT, evals * (3.0 * s.DP + 2.0), sizeof(T) * (double)Mpad * (double)(g.Q + 2 * nspan));
         const CovSrc<T> cs = cov_src<T>(s);
         const dim3 grid((unsigned)((Mpad + GROUP_KROWS - 1) / GROUP_KROWS), (unsigned)nch);
-        if (s.additive()) {
+        if (s.rel()) {
+            GroupKsumArgs<T, -2> a = {{cs.Xs, cs.n_pool, cs.os, cs.noise, s.kernel, (const T*)s.G, s.Q, s.da, 3, (T)s.outputscale_g}, cidx, M, Mpad, g, U, part};
+            with_dp(s.DP, [&](auto dp) {
+                hipLaunchKernelGGL((group_ksum_kernel<T, decltype(dp)::value, -2>), grid, dim3(256), 0, c->cur, a);
+            });
+        } else if (s.additive()) {
             GroupKsumArgs<T, -1> a = {{cs.Xs, cs.n_pool, cs.os, cs.noise, s.kernel, s.kernel_b, s.da, 3, (T)s.outputscale_b}, cidx, M, Mpad, g, U, part};
             with_dp(s.DP, [&](auto dp) {
                 hipLaunchKernelGGL((group_ksum_kernel<T, decltype(dp)::value, -1>), grid, dim3(256), 0, c->cur, a);

@@ -189,4 +189,19 @@ int mll_grad_launch(algp_ctx* c, const T* Sinv, int64_t ld, int64_t N, const T* 
 template <typename T>
 int mll_grad_add_launch(algp_ctx* c, const T* Sinv, int64_t ld, int64_t N, const T* Xs, int DP, const int64_t* aidx, const T* alpha,
                         int kernel_a, T os_a, int kernel_b, T os_b, int da, double* out_dev, double* partial);
+// under the relationship kernel: out_dev[0] = os_a, [1] = os_g, [2] = noise trace, [3..3+DP) = ls (fit.hip)
+template <typename T>
+int mll_grad_rel_launch(algp_ctx* c, const T* Sinv, int64_t ld, int64_t N, const T* Xs, int DP, const int64_t* aidx, const T* alpha,
+                        int kernel_a, T os_a, const T* G, int64_t Q, T os_g, int da, double* out_dev, double* partial);
+// the relationship form's gathers from its table (fit.hip): B[q][i] = os_g G[q, g_i] (Qpad x Npad, zero padded), the prior
+// variance os_a + os_g G[g_j, g_j] of every pool site, and the two last steps of algp_genotype_posterior
+template <typename T>
+int rel_gather_b_launch(algp_ctx* c, const T* G, int64_t Q, T os_g, const T* Xs, int DP, int da, const int64_t* aidx, int64_t N,
+                        int64_t Qpad, int64_t Npad, T* B);
+template <typename T>
+int rel_prior_launch(algp_ctx* c, const T* G, int64_t Q, T os_a, T os_g, const T* Xs, int DP, int da, int64_t n, T* prior);
+template <typename T>
+int rel_cov_finish_launch(algp_ctx* c, const T* G, int64_t Q, T os_g, const T* WW, int64_t ldw, T* cov);
+template <typename T>
+int rel_var_finish_launch(algp_ctx* c, const T* G, int64_t Q, T os_g, const T* ss, T* var);
 }  // namespace algp

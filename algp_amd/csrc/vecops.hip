@@ -242,6 +242,8 @@ ALGP_INSTANTIATE(rowstat_combine_launch);
 
 // ---------------------------------------------------------------------------------------------
 // candidate finalize: dstat = prior - ss (ordinary) | ss (unit row: [S^-1]_jj); mu = ybar + dot
+// prior of pool site p: Cp[p * n_pool + p] where Cp is given (the diagonal of an explicit covariance; with n_pool = 0 a vector of
+// per-site priors, the relationship form's), else prior_const
 // ---------------------------------------------------------------------------------------------
 template <typename T>
 __global__ void cand_finalize_kernel(int64_t M, const int* ckind, const int64_t* cidx, const T* Cp, int64_t n_pool,

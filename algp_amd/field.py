@@ -12,15 +12,18 @@ class SyntheticField(object):
     def __init__(self, num_rows=20, num_cols=20, num_test=40, k=5, num_genotypes=0):
         """num_genotypes > 0: a genotype-id column behind (row, col) -- every plot gets one of that many genotypes at
         random, as a field trial scatters its replicates -- and the genotype's effect is added to the smooth field: the data an
-        additive kernel with split 2 (position | genotype) is meant for."""
+        additive kernel with split 2 (position | genotype) and the genotype kernel are meant for; genotype_effect keeps the simulated
+        effects."""
         self.num_rows, self.num_cols = num_rows, num_cols
         x, y = generate_gaussian_data(num_rows, num_cols, k=k)          # utils.py:90-108
         x = x.astype(np.float64)
+        self.num_genotypes, self.genotype_effect = int(num_genotypes), None
         if num_genotypes > 0:
             geno = np.random.randint(num_genotypes, size=len(x))
             effect = np.random.normal(0.0, 0.5 * np.std(y), size=num_genotypes)
             x = np.hstack([x, geno[:, None].astype(np.float64)])
             y = y + effect[geno]
+            self.genotype_effect = effect
         perm = np.random.permutation(len(x))                            # env.py:60-63
         test_ind, train_ind = perm[:num_test], perm[num_test:]
         self.X, self.Y = x[train_ind], y[train_ind]

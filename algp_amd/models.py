@@ -21,6 +21,12 @@ What differs, deliberately:
     two such kernels, the first over coordinates [0, Da), the second over the others (genotype effect + spatial trend), with
     gpytorch's AdditiveKernel parameter names: kernel_covar_module.kernels.{0,1}.log_outputscale and
     kernel_covar_module.kernels.{0,1}.base_kernel.log_lengthscale; GPR.predict_components splits the posterior mean;
+  * kernel_params = {'type': 'genotype', 'spatial': {'type': 'matern', 'nu': 1.5}, 'relationship': G_or_None, 'n_genotypes': Q}
+    is the relationship kernel os_a kappa_a(r_a) + os_g G[g, g'] (GBLUP with a spatial term): the LAST column of x holds the
+    integer genotype ids, the others are spatial; G is a (Q, Q) relationship matrix or None for the identity.  Parameter names
+    follow the additive layout: kernel_covar_module.kernels.0.base_kernel.log_lengthscale (1, 1, D - 1),
+    kernel_covar_module.kernels.0.log_outputscale, kernel_covar_module.kernels.1.log_outputscale (the table is data, not a
+    parameter); GPR.genotype_effects gives the BLUPs with their variances or joint covariance;
   * `fit` uses the analytic MLL gradient computed on the device with the reference's own optimiser
     objects (torch.optim.Adam + ReduceLROnPlateau(patience=50), models.py:121-124).
 """
@@ -66,6 +72,22 @@ class _AdditiveKernel(nn.Module):
         self.kernels = nn.ModuleList([_ScaleKernel(split), _ScaleKernel(ard_num_dims - split)])
 
 
+class _TableKernel(nn.Module):
+    """The genotype part os_g G[g, g']: its outputscale is the only parameter."""
+
+    def __init__(self):
+        super(_TableKernel, self).__init__()
+        self.log_outputscale = nn.Parameter(torch.zeros(1, dtype=torch.float64))
+
+
+class _GenotypeKernel(nn.Module):
+    """ScaleKernel over the D - 1 spatial coordinates plus the table-valued genotype part."""
+
+    def __init__(self, ard_num_dims):
+        super(_GenotypeKernel, self).__init__()
+        self.kernels = nn.ModuleList([_ScaleKernel(ard_num_dims - 1), _TableKernel()])
+
+
 def _kernel_id(params):
     """The library's id of a single form: {'type': 'rbf' | 'matern'[, 'nu': 0.5 | 1.5 | 2.5]} (None: rbf)."""
     kernel = params['type'] if params is not None else 'rbf'
@@ -97,6 +119,27 @@ class ExactGPModel(nn.Module):
         self.latent_func = IdentityLatentFunction()
         kernel = kernel_params['type'] if kernel_params is not None else 'rbf'
         self.split = None
+        self.relationship = None               # (G or None, Q) under the genotype kernel
+        if kernel == 'genotype':
+            D = int(np.shape(train_x)[-1])
+            if D < 2:
+                raise ValueError('genotype kernel: x needs a spatial coordinate and the genotype id column (D >= 2)')
+            G = kernel_params.get('relationship')
+            Q = kernel_params.get('n_genotypes')
+            if G is not None:
+                G = np.ascontiguousarray(G, dtype=np.float64)
+                if G.ndim != 2 or G.shape[0] != G.shape[1]:
+                    raise ValueError("genotype kernel: 'relationship' must be a square matrix")
+                if Q is not None and int(Q) != G.shape[0]:
+                    raise ValueError("genotype kernel: 'n_genotypes' does not match 'relationship'")
+                Q = G.shape[0]
+            elif Q is None:
+                raise ValueError("genotype kernel: pass 'relationship' or 'n_genotypes'")
+            self.relationship = (G, int(Q))
+            self.kernel_type = ('genotype', _kernel_id(kernel_params.get('spatial')))
+            self.kernel_covar_module = _GenotypeKernel(D)
+            self.likelihood = likelihood
+            return
         if kernel == 'additive':
             D = int(np.shape(train_x)[-1])
             parts = kernel_params.get('parts')
@@ -155,6 +198,11 @@ class GPR(object):
         """(log_lengthscale[D], log_outputscale, log_noise, kernel id) as plain floats.  Under the additive kernel the
         lengthscales of the two parts in coordinate order, log_outputscale a pair and the id ('additive', split, id_a, id_b)."""
         m = self.model
+        if m.relationship is not None:         # D - 1 spatial lengthscales, (log os_a, log os_g), ('genotype', id_a)
+            ks = m.kernel_covar_module.kernels
+            return (ks[0].base_kernel.log_lengthscale.detach().double().reshape(-1).numpy().copy(),
+                    (float(ks[0].log_outputscale.item()), float(ks[1].log_outputscale.item())),
+                    float(self.likelihood.log_noise.item()), m.kernel_type)
         if m.split is not None:
             ks = m.kernel_covar_module.kernels
             ls = np.concatenate([k.base_kernel.log_lengthscale.detach().double().reshape(-1).numpy() for k in ks])
@@ -177,7 +225,10 @@ class GPR(object):
     def push_hypers(self, ctx):
         """Set the current hyper-parameters on `ctx` (this model's own context, or another one that is to compute with them)."""
         ls, los, ln, kt = self.hypers()
-        if isinstance(kt, tuple):
+        if isinstance(kt, tuple) and kt[0] == 'genotype':
+            G, Q = self.model.relationship
+            ctx.set_hypers_relationship(ls, los[0], los[1], ln, kernel_a=kt[1], G=G, n_genotypes=Q)
+        elif isinstance(kt, tuple):
             ctx.set_hypers_additive(ls, kt[1], los[0], los[1], ln, kt[2], kt[3])
         else:
             ctx.set_hypers(ls, los, ln, kt)
@@ -239,7 +290,13 @@ class GPR(object):
         self._load_train_on_device()
         named = dict(self.model.named_parameters())
         p_n = named['likelihood.log_noise']
-        if self.model.split is not None:
+        if self.model.relationship is not None:
+            # the D + 2 gradient: [log ls of the D - 1 spatial coordinates | log os_a, log os_g | log noise]
+            p = named['kernel_covar_module.kernels.0.base_kernel.log_lengthscale']
+            at = p.numel()
+            route = [(p, 0, at), (named['kernel_covar_module.kernels.0.log_outputscale'], at, at + 1),
+                     (named['kernel_covar_module.kernels.1.log_outputscale'], at + 1, at + 2), (p_n, at + 2, at + 3)]
+        elif self.model.split is not None:
             # the D + 3 gradient: [log ls in coordinate order | log os_a, log os_b | log noise]
             route = []
             at = 0
@@ -326,8 +383,8 @@ class GPR(object):
         """(mean_a, mean_b): the two parts' shares of the posterior mean of the latent field at `x` under the additive kernel
         -- with the genotype coordinates first, mean_a is the genotype effect adjusted for spatial trend.  The constant mean
         belongs to neither: mean_a + mean_b + mean(train y) = predict(x)."""
-        if self.model is None or self.model.split is None:
-            raise ValueError("predict_components needs kernel_params['type'] = 'additive'")
+        if self.model is None or (self.model.split is None and self.model.relationship is None):
+            raise ValueError("predict_components needs kernel_params['type'] = 'additive' or 'genotype'")
         c = self.ctx
         self.sync_hypers()
         x = np.asarray(x, dtype=np.float64)
@@ -338,6 +395,20 @@ class GPR(object):
         c.factorize()
         idx = np.arange(N, N + M)
         return c.posterior_mean_component(0, idx), c.posterior_mean_component(1, idx)
+
+    def genotype_effects(self, return_cov=False):
+        """(mean, var), or (mean, cov) with return_cov: the posterior of the Q genotype effects under the genotype kernel,
+        conditioned on the stored training data -- BLUPs, prediction-error variances or the joint covariance for rankings and
+        contrasts, genotypes without a plot included (algp_genotype_posterior)."""
+        if self.model is None or self.model.relationship is None:
+            raise ValueError("genotype_effects needs kernel_params['type'] = 'genotype'")
+        c = self.ctx
+        self.sync_hypers()
+        c.set_pool(self._train_x)
+        c.set_train(np.arange(len(self._train_x)), self._train_y, self._train_var)
+        c.factorize()
+        mean, var, cov = c.genotype_posterior(want_var=not return_cov, want_cov=return_cov)
+        return (mean, cov) if return_cov else (mean, var)
 
     def sample_posterior(self, x, n_samples=1, n_features=2048, rng=None):
         """(n_samples, len(x)) joint draws of the latent field f at `x` (no observation noise), conditioned on the stored

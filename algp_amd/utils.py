@@ -118,12 +118,48 @@ def spectral_draws(kernel_id, D, n_features, rng):
     return np.ascontiguousarray(omega, dtype=np.float64), np.ascontiguousarray(phase, dtype=np.float64)
 
 
+def relationship_prior_draws(kernel_a, log_lengthscale, os_a, os_g, G, n_genotypes, x, n_samples, n_features, rng, chunk=4096):
+    """(n_samples, len(x)) float64 draws of the PRIOR of the relationship kernel os_a kappa_a(r_a) + os_g G[g, g'] at the sites
+    `x` (last column: the genotype ids), built on the host in NumPy -- the genotype part has no spectral density, so the device's
+    features mode cannot draw it, and the result goes to algp_sample_posterior in values mode.
+    Spatial part: n_features random Fourier features of kappa_a over the D - 1 spatial coordinates scaled by 1 / lengthscale,
+    amplitude sqrt(2 os_a / F), evaluated in chunks of `chunk` sites.  Genotype part: u = sqrt(os_g) chol(G + jitter I) xi with
+    jitter = 1e-10 max(diag G) (u = sqrt(os_g) xi for G None), gathered by id.  Drawn from `rng` in this order:
+    spectral_draws(kernel_a, D - 1, n_features, rng), the weights standard_normal((n_samples, n_features)), xi
+    standard_normal((n_samples, Q))."""
+    rng = _rng(rng)
+    x = np.asarray(x, dtype=np.float64)
+    x = x.reshape(len(x), -1)
+    S, F, Ds = int(n_samples), int(n_features), x.shape[1] - 1
+    ids = x[:, -1].astype(np.int64)
+    Q = int(n_genotypes) if G is None else int(np.shape(G)[0])
+    omega, phase = spectral_draws(kernel_a, Ds, F, rng)
+    weights = rng.standard_normal((S, F))
+    xi = rng.standard_normal((S, Q))
+    xs = x[:, :Ds] * np.exp(-np.asarray(log_lengthscale, dtype=np.float64).reshape(-1))
+    out = np.empty((S, len(x)))
+    amp = np.sqrt(2.0 * os_a / F)
+    for i0 in range(0, len(x), int(chunk)):
+        i1 = min(len(x), i0 + int(chunk))
+        out[:, i0:i1] = amp * (weights @ np.cos(xs[i0:i1] @ omega.T + phase).T)
+    if G is None:
+        u = np.sqrt(os_g) * xi
+    else:
+        G = np.asarray(G, dtype=np.float64)
+        Lg = np.linalg.cholesky(G + 1e-10 * np.max(np.diag(G)) * np.eye(Q))
+        u = np.sqrt(os_g) * (xi @ Lg.T)
+    out += u[:, ids]
+    return out
+
+
 def posterior_samples(gp, train_x, train_y, test_x, train_var=None, n_samples=1, n_features=2048, rng=None):
     """(n_samples, len(test_x)) joint draws of the latent field at `test_x` given the train data, by pathwise conditioning
     on the device (algp_sample_posterior): pool, train set and candidates exactly as predictive_distribution sets them
     (prior_includes_noise=False), the prior draw from `n_features` random Fourier features of the kernel.  Everything random
     comes from `rng` (a RandomState or a seed), in this order: spectral_draws(kernel, D, n_features, rng), the weights
-    standard_normal((n_samples, n_features)), the train-noise draws standard_normal((n_samples, N))."""
+    standard_normal((n_samples, n_features)), the train-noise draws standard_normal((n_samples, N)).
+    Under the genotype kernel the prior is drawn on the host at every pool site (relationship_prior_draws, whose draws come
+    first, in its own order) and passed in values mode; then the train-noise draws standard_normal((n_samples, N))."""
     c = gp.ctx
     gp.sync_hypers()
     rng = _rng(rng)
@@ -137,6 +173,12 @@ def posterior_samples(gp, train_x, train_y, test_x, train_var=None, n_samples=1,
     c.set_candidates(np.arange(N, N + M), prior_includes_noise=False)
     c.fit_and_solve()
     hyp = gp.hypers()
+    if isinstance(hyp[3], tuple) and hyp[3][0] == 'genotype':
+        G, Q = gp.model.relationship
+        prior = relationship_prior_draws(hyp[3][1], hyp[0], np.exp(hyp[1][0]), np.exp(hyp[1][1]), G, Q, np.vstack([train_x, test_x]),
+                                         n_samples, n_features, rng)
+        eps = rng.standard_normal((int(n_samples), N))
+        return c.sample_posterior(eps, prior=prior)
     kid = hyp[3] + tuple(np.exp(hyp[1])) if isinstance(hyp[3], tuple) else hyp[3]      # additive: with the two outputscales
     omega, phase = spectral_draws(kid, train_x.shape[1], n_features, rng)
     weights = rng.standard_normal((int(n_samples), int(n_features)))

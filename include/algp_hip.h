@@ -102,6 +102,32 @@ int algp_set_hypers(algp_ctx* ctx, int kernel, int D, const double* log_lengthsc
  * algp_posterior_mean_component splits the posterior mean.                                       */
 int algp_set_hypers_additive(algp_ctx* ctx, int D, int kernel_a, int Da, double log_outputscale_a, int kernel_b,
                              double log_outputscale_b, const double* log_lengthscale, double log_noise);
+/* The relationship kernel: a spatial part plus a genotype part given by a TABLE (GBLUP with a spatial term),
+ *   k((s, g), (s', g')) = os_a kappa_a(r(s, s')) + os_g G[g, g'].
+ * Pool layout: coordinates [0, D-1) are spatial, each with its own ARD lengthscale (log_lengthscale: D-1 entries), kernel_a any of
+ * the four ids above; coordinate D-1 is the genotype id, an integer in [0, Q).  The id is never scaled (its inverse lengthscale
+ * is exactly 1), so the resident scaled pool holds it exactly: an fp32 context requires Q <= 2^24.  2 <= D <= 8, Q >= 1.
+ * G: Q x Q row-major host doubles, symmetric positive semi-definite (genomic, pedigree based, ...), copied to the device in the
+ * context's dtype; NULL: the identity (independent genotype effects) -- no table is stored and the part's value is os_g (g == g').
+ * G must be finite and bitwise symmetric (G[p, q] and G[q, p] the same bits), else ALGP_ERR_BAD_ARG; it is NOT tested for
+ * definiteness: a matrix S that is not positive definite is reported by the factorisation, as always.  Its diagonal need not be
+ * constant: the prior variance of site j is os_a + os_g G[g_j, g_j], and every criterion, posterior and utility uses the
+ * site's own.  (The jitter of algp_get_posterior_cov is scaled by the largest prior variance.)
+ * Replaces the hyper-parameters exactly as algp_set_hypers_additive does (factor and candidate solve invalidated, the pool
+ * rescaled, a pool of another width dropped); a later algp_set_hypers or algp_set_hypers_additive returns the context to those
+ * forms and frees the table.  Those two keep refusing every kernel id outside 0..3: this form has no id, only this entry point.
+ * Ids are validated on the host, before any launch, wherever coordinates meet these hyper-parameters: algp_set_pool,
+ * algp_kernel_matrix (both operands) and this call itself when a coordinate pool of width D is resident.  An id that is no
+ * integer, below 0 or >= Q: ALGP_ERR_BAD_ARG, the message names the row.  A refused call changes nothing: the context keeps the
+ * pool and the hyper-parameters it had.
+ * Under this kernel: algp_get_mll_grad / algp_fit_step return D + 2 entries, (log_lengthscale[0..D-1), log_outputscale_a,
+ * log_outputscale_g, log_noise), with dS/dlog os_g = os_g G[g_i, g_j], from fixed-order sums (the same bits in every run);
+ * algp_posterior_mean_component splits the mean (0: spatial, 1: genotype); algp_genotype_posterior gives the genotype effects;
+ * algp_factorize_from takes two contexts' hyper-parameters as equal only if Q, os_g and the tables' contents (by a 64-bit
+ * fingerprint of the caller's doubles) agree; algp_sample_posterior works in values mode (F == 0) and refuses features mode with
+ * ALGP_ERR_BAD_ARG -- the genotype part has no spectral density.  The fused right-hand-side generation stays off.                */
+int algp_set_hypers_relationship(algp_ctx* ctx, int D, int kernel_a, double log_outputscale_a, const double* log_lengthscale,
+                                 double log_outputscale_g, const double* G, int64_t Q, double log_noise);
 
 /* ---- a1: GPR.cov_mat (models.py:161-181) -------------------------------------------------
  * out[n1*n2] (host) = K(x1,x2) ; x2 == NULL -> symmetric K(x1,x1) (models.py:169-170);
@@ -209,6 +235,21 @@ int algp_posterior_mean(algp_ctx* ctx, const int64_t* idx, int64_t M, void* mu_o
  * A single kernel in force: ALGP_ERR_STATE.  An explicit-covariance pool, a component other than 0 / 1: ALGP_ERR_BAD_ARG.
  * Component variances are not computed.                                                          */
 int algp_posterior_mean_component(algp_ctx* ctx, int component, const int64_t* idx, int64_t M, void* mu_out);
+/* (Under the relationship kernel, algp_set_hypers_relationship: component 0 = the spatial part, 1 = the genotype part, whose
+ * value at a site equals algp_genotype_posterior's mean of the site's id to rounding.)
+ * The posterior of the genotype effects u ~ N(0, os_g G) themselves under the relationship kernel -- BLUPs, their prediction-error
+ * variances and their joint covariance -- for all Q genotypes, those without an observed plot included (predicted through their
+ * relatives; under G = NULL such a genotype has mean exactly 0 and variance os_g).  With B = os_g G[:, g_A] (Q x N, gathered by
+ * the train rows' ids), L the resident factor of S, W = B L^-T and z = L^-1 (y - ybar):
+ *   mean_out[Q]    = W z                      (no constant mean: u has prior mean 0)
+ *   var_out[Q]     = os_g G_qq - |W_q|^2      (or NULL)
+ *   cov_out[Q * Q] = os_g G - W W^T           (or NULL; both triangles written, identical bits; var is its diagonal to rounding)
+ * host arrays in the context's dtype.  Needs a current factorisation and a coordinate pool under this kernel, else ALGP_ERR_STATE;
+ * picks committed since the factorisation: ALGP_ERR_STATE (the effects would not include them, as algp_get_posterior_cov).
+ * mean_out NULL, more than 65 408 genotypes: ALGP_ERR_BAD_ARG.  The scratch (Q_pad x N_pad, and Q_pad x Q_pad + Q x Q for cov) belongs to the context, is
+ * counted by algp_device_bytes and freed by algp_destroy; if it does not fit the call returns ALGP_ERR_OOM with the byte count
+ * before allocating.  Reads resident state and writes none of it; the same bits on every call.                                  */
+int algp_genotype_posterior(algp_ctx* ctx, void* mean_out, void* var_out, void* cov_out);
 
 /* ---- joint posterior draws at the candidates: pathwise conditioning (no reference counterpart) ------------------------------
  * algp_sample_posterior: out[s * M + j] = draw s of the LATENT field f at candidate j (candidate order, the context's dtype; no

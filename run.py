@@ -17,7 +17,8 @@ from algp_amd.utils import compute_mae
 def run_demo(args):
     np.random.seed(args.seed)
     # an additive kernel whose first part is the whole position (row, col) needs a coordinate for its second: genotype ids
-    genotypes = 12 if args.kernel == 'additive' and args.kernel_split == 2 else 0
+    # (the genotype kernel reads the ids from the same column)
+    genotypes = 12 if (args.kernel == 'additive' and args.kernel_split == 2) or args.kernel == 'genotype' else 0
     env = SyntheticField(args.rows, args.cols, num_test=args.num_test, num_genotypes=genotypes)
     agent = Agent(env, args, static_std=args.static_std, mobile_std=10 * args.static_std)
     agent.reset()
@@ -35,6 +36,13 @@ def run_demo(args):
         errors.append(err)
         print('Run {}/{}: picks {} test ERROR {:.4f} predictive variance max {:.3f} min {:.3f} mean {:.3f} ({:.3f}s)'
               .format(i + 1, args.num_runs, picks, err, var.max(), var.min(), var.mean(), time.time() - t0))
+    if args.kernel == 'genotype':
+        # the genotype effects themselves, beside the simulated ones (both centred: the constant mean absorbs their average)
+        mean, var = agent.gp.genotype_effects()
+        sim = env.genotype_effect - env.genotype_effect.mean()
+        print('genotype   fitted effect  (sd)     simulated')
+        for q in range(len(mean)):
+            print('{:8d}   {:+.4f}  ({:.4f})   {:+.4f}'.format(q, mean[q] - mean.mean(), np.sqrt(max(var[q], 0.0)), sim[q]))
     return errors
 
 
