@@ -182,17 +182,28 @@ KmatSrc make_src(algp_ctx* c) {
     return s;
 }
 
-// the single and the additive setters return the context to their forms: the relationship table goes
-void leave_relationship(algp_ctx* c) {
-    c->hyp.rel = false;
-    c->hyp.has_table = false;
-    c->hyp.Q = 0;
-    c->hyp.Ghash = 0;
-    c->hyp.gdiag_max = 1.0;
+// The one end of the three setters, once nothing can refuse the call any more: `next` (validated, every field of its form
+// filled, the others at their defaults) replaces the hyper-parameters whole, `table` (the relationship form's, already on the
+// device; else empty) replaces the previous table, and what was computed under the old ones goes.
+static int install_hypers(algp_ctx* c, Hypers next, DevBuf table = {}) {
+    if (c->hyp.set && c->hyp.D != next.D && c->n_pool > 0 && !c->pool_is_cov) {
+        // the resident coordinates have another width: drop the pool, the caller sets a new one
+        c->n_pool = 0;
+        c->N = 0;
+        c->pos_in_train.clear();
+    }
     if (c->Gtab.p) {
         hipStreamSynchronize(c->stream);
         release(c, c->Gtab);
     }
+    c->Gtab = table;
+    next.DP = next.D <= 2 ? 2 : (next.D <= 4 ? 4 : 8);
+    next.set = true;
+    c->hyp = next;
+    c->hyp_stamp++;
+    c->factored = false;
+    c->solved = false;
+    return DISPATCH(c, rescale_pool(c));
 }
 
 // The relationship form's check of the id coordinate (the last of D) of n sites, on the host before any launch: an integer in
@@ -623,25 +634,13 @@ int algp_set_hypers(algp_ctx* c, int kernel, int D, const double* log_ls, double
     CHECK_CTX(c);
     if (D < 1 || D > MAXD || !log_ls) return fail(c, ALGP_ERR_BAD_ARG, "set_hypers: 1 <= D <= 8 required");
     if (kernel < ALGP_KERNEL_RBF || kernel > ALGP_KERNEL_MATERN25) return fail(c, ALGP_ERR_BAD_ARG, "set_hypers: unknown kernel");
-    if (c->hyp.set && c->hyp.D != D && c->n_pool > 0 && !c->pool_is_cov) {
-        // the resident coordinates have another width: drop the pool, the caller sets a new one
-        c->n_pool = 0;
-        c->N = 0;
-        c->pos_in_train.clear();
-    }
-    c->hyp.kernel = kernel;
-    c->hyp.additive = false;
-    leave_relationship(c);
-    c->hyp.D = D;
-    c->hyp.DP = D <= 2 ? 2 : (D <= 4 ? 4 : 8);
-    for (int d = 0; d < MAXD; ++d) c->hyp.inv_ls[d] = d < D ? exp(-log_ls[d]) : 0.0;
-    c->hyp.outputscale = exp(log_os);
-    c->hyp.noise = exp(log_noise);
-    c->hyp.set = true;
-    c->hyp_stamp++;
-    c->factored = false;
-    c->solved = false;
-    FINISH(c, DISPATCH(c, rescale_pool(c)));
+    Hypers next;
+    next.kernel = kernel;
+    next.D = D;
+    for (int d = 0; d < D; ++d) next.inv_ls[d] = exp(-log_ls[d]);
+    next.outputscale = exp(log_os);
+    next.noise = exp(log_noise);
+    FINISH(c, install_hypers(c, next));
 }
 
 int algp_set_hypers_additive(algp_ctx* c, int D, int kernel_a, int Da, double log_os_a, int kernel_b, double log_os_b,
@@ -651,28 +650,17 @@ int algp_set_hypers_additive(algp_ctx* c, int D, int kernel_a, int Da, double lo
     if (Da < 1 || Da > D - 1) return fail(c, ALGP_ERR_BAD_ARG, "set_hypers_additive: 1 <= Da <= D - 1 required");
     if (kernel_a < ALGP_KERNEL_RBF || kernel_a > ALGP_KERNEL_MATERN25 || kernel_b < ALGP_KERNEL_RBF || kernel_b > ALGP_KERNEL_MATERN25)
         return fail(c, ALGP_ERR_BAD_ARG, "set_hypers_additive: unknown kernel");
-    // everything from here on as algp_set_hypers does it
-    if (c->hyp.set && c->hyp.D != D && c->n_pool > 0 && !c->pool_is_cov) {
-        c->n_pool = 0;
-        c->N = 0;
-        c->pos_in_train.clear();
-    }
-    c->hyp.kernel = kernel_a;
-    c->hyp.additive = true;
-    leave_relationship(c);
-    c->hyp.kernel_b = kernel_b;
-    c->hyp.Da = Da;
-    c->hyp.D = D;
-    c->hyp.DP = D <= 2 ? 2 : (D <= 4 ? 4 : 8);
-    for (int d = 0; d < MAXD; ++d) c->hyp.inv_ls[d] = d < D ? exp(-log_ls[d]) : 0.0;
-    c->hyp.outputscale = exp(log_os_a);
-    c->hyp.outputscale_b = exp(log_os_b);
-    c->hyp.noise = exp(log_noise);
-    c->hyp.set = true;
-    c->hyp_stamp++;
-    c->factored = false;
-    c->solved = false;
-    FINISH(c, DISPATCH(c, rescale_pool(c)));
+    Hypers next;
+    next.kernel = kernel_a;
+    next.additive = true;
+    next.kernel_b = kernel_b;
+    next.Da = Da;
+    next.D = D;
+    for (int d = 0; d < D; ++d) next.inv_ls[d] = exp(-log_ls[d]);
+    next.outputscale = exp(log_os_a);
+    next.outputscale_b = exp(log_os_b);
+    next.noise = exp(log_noise);
+    FINISH(c, install_hypers(c, next));
 }
 
 int algp_set_hypers_relationship(algp_ctx* c, int D, int kernel_a, double log_os_a, const double* log_ls, double log_os_g,
@@ -711,34 +699,21 @@ int algp_set_hypers_relationship(algp_ctx* c, int D, int kernel_a, double log_os
         const int rc = DISPATCH(c, rel_upload_table(c, G, Q, tab));
         if (rc != ALGP_OK) { release(c, tab); return rc; }
     }
-    // everything from here on as algp_set_hypers does it
-    if (c->hyp.set && c->hyp.D != D && c->n_pool > 0 && !c->pool_is_cov) {
-        c->n_pool = 0;
-        c->N = 0;
-        c->pos_in_train.clear();
-    }
-    leave_relationship(c);
-    c->Gtab = tab;
-    c->hyp.kernel = kernel_a;
-    c->hyp.additive = false;
-    c->hyp.rel = true;
-    c->hyp.has_table = G != nullptr;
-    c->hyp.Q = Q;
-    c->hyp.Ghash = gh;
-    c->hyp.gdiag_max = gmax;
-    c->hyp.Da = D - 1;
-    c->hyp.D = D;
-    c->hyp.DP = D <= 2 ? 2 : (D <= 4 ? 4 : 8);
-    for (int d = 0; d < MAXD; ++d) c->hyp.inv_ls[d] = d < D - 1 ? exp(-log_ls[d]) : 0.0;
-    c->hyp.inv_ls[D - 1] = 1.0;                              // the id is never scaled: the scaled pool holds it exactly
-    c->hyp.outputscale = exp(log_os_a);
-    c->hyp.outputscale_g = exp(log_os_g);
-    c->hyp.noise = exp(log_noise);
-    c->hyp.set = true;
-    c->hyp_stamp++;
-    c->factored = false;
-    c->solved = false;
-    FINISH(c, DISPATCH(c, rescale_pool(c)));
+    Hypers next;
+    next.kernel = kernel_a;
+    next.rel = true;
+    next.has_table = G != nullptr;
+    next.Q = Q;
+    next.Ghash = gh;
+    next.gdiag_max = gmax;
+    next.Da = D - 1;
+    next.D = D;
+    for (int d = 0; d < D - 1; ++d) next.inv_ls[d] = exp(-log_ls[d]);
+    next.inv_ls[D - 1] = 1.0;                                // the id is never scaled: the scaled pool holds it exactly
+    next.outputscale = exp(log_os_a);
+    next.outputscale_g = exp(log_os_g);
+    next.noise = exp(log_noise);
+    FINISH(c, install_hypers(c, next, tab));
 }
 
 int algp_kernel_matrix(algp_ctx* c, const void* x1, int64_t n1, const void* x2, int64_t n2, const void* diag_add,

@@ -459,12 +459,7 @@ int Impl<T>::factorize_from(algp_ctx* c, algp_ctx* src) {
     if (src->dtype != c->dtype || src->device != c->device)
         return fail(c, ALGP_ERR_BAD_ARG, "factorize_from: contexts differ in dtype or device");
     if (!src->factored || src->train_dirty) return fail(c, ALGP_ERR_STATE, "factorize_from: the source holds no factor");
-    const Hypers &a = c->hyp, &b = src->hyp;
-    bool same = a.D == b.D && a.kernel == b.kernel && a.outputscale == b.outputscale && a.noise == b.noise && a.additive == b.additive &&
-                (!a.additive || (a.kernel_b == b.kernel_b && a.Da == b.Da && a.outputscale_b == b.outputscale_b));
-    same = same && a.rel == b.rel && (!a.rel || (a.Q == b.Q && a.outputscale_g == b.outputscale_g && a.Ghash == b.Ghash));
-    for (int d = 0; same && d < a.D; ++d) same = a.inv_ls[d] == b.inv_ls[d];
-    if (!same) return fail(c, ALGP_ERR_STATE, "factorize_from: hyper-parameters differ");
+    if (!c->hyp.same_model(src->hyp)) return fail(c, ALGP_ERR_STATE, "factorize_from: hyper-parameters differ");
     if (src->N != N || src->fact_idx != c->train_idx || src->fact_var != c->train_var_host)
         return fail(c, ALGP_ERR_STATE, "factorize_from: the source factor belongs to a different train set");
     if (c->pool_is_cov || src->pool_is_cov)

@@ -13,7 +13,6 @@ int Impl<T>::mll_grad(algp_ctx* c, double* grad_out, bool have_X, bool inv_enque
     if (!c->factored || c->train_dirty) return fail(c, ALGP_ERR_STATE, "get_mll_grad: call algp_factorize first");
     if (c->pool_is_cov) return fail(c, ALGP_ERR_BAD_ARG, "get_mll_grad needs a coordinate pool");
     const int64_t N = c->N, Npad = c->Npad;
-    const int D = c->hyp.D, DP = c->hyp.DP;
     if (have_X && !c->alpha_valid) {
         // alpha = L^-T z = X z with the X the launch left in auxW: one pass over its upper triangle (0.4 GB at N = 10 000)
         // instead of the backward substitution's chain of 79 hand-offs
@@ -30,38 +29,23 @@ int Impl<T>::mll_grad(algp_ctx* c, double* grad_out, bool have_X, bool inv_enque
     }
     if (inv_enqueued) ALGP_HIP(hipStreamWaitEvent(c->stream, sync_event(c, EV_INV_DONE), 0));
     else ALGP_TRY(syrk_upper<T>(c, ALGP_PROF_GEMM_OTHER, p(c->auxW), Npad, Npad, p(c->auxA), Npad));
-    double* sc = (double*)c->scal.p + SC_GRAD;        // slots 16..27: os, trace, ls[0..8); additive: os_a, os_b, trace, ls[0..8)
+    // slots 16..27: [0, nos) the outputscale sums (two under the additive and the relationship form: os_a, then os_b or os_g),
+    // [nos] the noise trace, [nos + 1, nos + 1 + DP) the lengthscale sums
+    double* sc = (double*)c->scal.p + SC_GRAD;
     ALGP_HIP(hipMemsetAsync(sc, 0, sizeof(double) * 12, c->stream));
-    const bool add = c->hyp.additive || c->hyp.rel;    // three leading sums: the second outputscale (os_b, or os_g under the relationship form)
-    if (c->hyp.rel)
-        ALGP_TRY(mll_grad_rel_launch<T>(c, p(c->auxA), Npad, N, (const T*)c->Xs.p, DP, (const int64_t*)c->Aidx.p, (const T*)c->alpha.p,
-                                        c->hyp.kernel, (T)c->hyp.outputscale, c->hyp.has_table ? (const T*)c->Gtab.p : nullptr, c->hyp.Q,
-                                        (T)c->hyp.outputscale_g, c->hyp.Da, sc, (double*)c->auxW.p));
-    else if (add)
-        ALGP_TRY(mll_grad_add_launch<T>(c, p(c->auxA), Npad, N, (const T*)c->Xs.p, DP, (const int64_t*)c->Aidx.p, (const T*)c->alpha.p,
-                                        c->hyp.kernel, (T)c->hyp.outputscale, c->hyp.kernel_b, (T)c->hyp.outputscale_b, c->hyp.Da, sc,
-                                        (double*)c->auxW.p));
-    else
-        ALGP_TRY(mll_grad_launch<T>(c, p(c->auxA), Npad, N, (const T*)c->Xs.p, DP, (const int64_t*)c->Aidx.p,
-                                    (const T*)c->alpha.p, c->hyp.kernel, (T)c->hyp.outputscale, sc,
-                                    (double*)c->auxW.p /* X = L^-T is spent: room for the per-workgroup partials */));
+    ALGP_TRY(mll_grad_launch<T>(c, p(c->auxA), Npad, N, (const int64_t*)c->Aidx.p, (const T*)c->alpha.p, make_src(c), sc,
+                                (double*)c->auxW.p /* X = L^-T is spent: room for the per-workgroup partials */));
     double h[12];
     ALGP_HIP(hipMemcpyAsync(h, sc, sizeof(h), hipMemcpyDeviceToHost, c->stream));
     {
         const int rc = sync_checked(c, "get_mll_grad");
         if (rc != ALGP_OK) { c->alpha_valid = false; return rc; }
     }
-    if (add) {                                        // D + 3: [log ls | log os_a, log os_b, log sigma_n^2]; relationship: D + 2, the id has no lengthscale
-        const int nl = c->hyp.rel ? D - 1 : D;
-        for (int d = 0; d < nl; ++d) grad_out[d] = 0.5 * h[3 + d];
-        grad_out[nl] = 0.5 * h[0];
-        grad_out[nl + 1] = 0.5 * h[1];
-        grad_out[nl + 2] = 0.5 * c->hyp.noise * h[2];
-        return ALGP_OK;
-    }
-    for (int d = 0; d < D; ++d) grad_out[d] = 0.5 * h[2 + d];
-    grad_out[D] = 0.5 * h[0];
-    grad_out[D + 1] = 0.5 * c->hyp.noise * h[1];
+    // [log ls | the log outputscales | log sigma_n^2]; under the relationship form the id has no lengthscale
+    const int nos = (c->hyp.additive || c->hyp.rel) ? 2 : 1, nl = c->hyp.rel ? c->hyp.D - 1 : c->hyp.D;
+    for (int d = 0; d < nl; ++d) grad_out[d] = 0.5 * h[nos + 1 + d];
+    for (int q = 0; q < nos; ++q) grad_out[nl + q] = 0.5 * h[q];
+    grad_out[nl + nos] = 0.5 * c->hyp.noise * h[nos];
     return ALGP_OK;
 }
 

@@ -23,7 +23,6 @@ void release(algp_ctx* c, DevBuf& b);
 void release(algp_ctx* c, MiState& mi);   // every MI buffer (api_mi.hip)
 void release(algp_ctx* c, VrState& vr);   // every buffer of the variance-reduction criterion (api_vr.hip)
 KmatSrc make_src(algp_ctx* c);
-void leave_relationship(algp_ctx* c);     // the relationship form's table goes (api.hip)
 template <typename T>
 int rel_check_ids(algp_ctx* c, const T* x, int64_t n, int D, int64_t Q, const char* what);
 int sync(algp_ctx* c);

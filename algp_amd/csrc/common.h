@@ -72,6 +72,15 @@ struct Hypers {
     // K_jj where it is one scalar (the single and additive forms); under the relationship form the LARGEST prior variance (the
     // jitter's scale) -- the per-site prior goes through algp_ctx::Gprior
     double prior_var() const { return rel ? outputscale + outputscale_g * gdiag_max : additive ? outputscale + outputscale_b : outputscale; }
+    // the same covariance function of the sites' coordinates (algp_factorize_from): the form, and of each form the fields that
+    // count under it, the table by its fingerprint
+    bool same_model(const Hypers& b) const {
+        bool same = D == b.D && kernel == b.kernel && outputscale == b.outputscale && noise == b.noise && additive == b.additive &&
+                    (!additive || (kernel_b == b.kernel_b && Da == b.Da && outputscale_b == b.outputscale_b));
+        same = same && rel == b.rel && (!rel || (Q == b.Q && outputscale_g == b.outputscale_g && Ghash == b.Ghash));
+        for (int d = 0; same && d < D; ++d) same = inv_ls[d] == b.inv_ls[d];
+        return same;
+    }
 };
 
 struct PickRec {           // one committed greedy pick, host side (the device keeps a LazyPick with the row's scale)
@@ -272,7 +281,7 @@ __device__ __forceinline__ T kmat_value(int kernel, T os, const T (&xr)[DP], con
 }
 // The additive form, a third family (2) beside the two above: k = os_a kappa_a(r_a) + os_b kappa_b(r_b), r_a over the first da
 // scaled coordinates, r_b over the others (the zero padding adds nothing).  It is compiled as instantiations of its own (the
-// matrix build's FAM = 2, a source type of its own for pool_cov below, fit.hip's second gradient kernel), so that the code the
+// matrix build's FAM = 2, a source type of its own for pool_cov below, a form type of its own for fit.hip's gradient kernel), so that the code the
 // single forms run stays what it was.  ONE definition of the two squared distances and of the sum for every site: each
 // square rounded on its own and added in coordinate order (contraction off), so the matrix build, the criteria and the gradient
 // see the same r_a^2, r_b^2 and the same value for a pair of sites.
@@ -326,16 +335,21 @@ __device__ __forceinline__ void rel_r2(const XA* xa, const XB* xb, int da, C& ra
     ia = (int64_t)ga;
     ib = (int64_t)gb;
 }
+// the genotype part's value os_g G[ia, ib]: kval_rel's, and every other site's that takes an entry of the table (fit.hip: the
+// gradient, the genotype posterior's right-hand sides and prior, the per-site prior)
+template <typename C, typename T>
+__device__ __forceinline__ C rel_entry(const T* G, int64_t Q, C osg, int64_t ia, int64_t ib) {
+#pragma clang fp contract(off)
+    const C g = G ? (C)G[ia * Q + ib] : (ia == ib ? (C)1 : (C)0);
+    return osg * g;
+}
 // parts: bit 0 = the spatial part, bit 1 = the genotype part (as kval_add)
 template <typename C, typename T>
 __device__ __forceinline__ C kval_rel(int ka, C osa, C ra, const T* G, int64_t Q, C osg, int64_t ia, int64_t ib, int parts = 3) {
 #pragma clang fp contract(off)
     const C va = (parts & 1) ? kval<C>(ka, osa, ra) : (C)0;
     C vg = (C)0;
-    if (parts & 2) {
-        const C g = G ? (C)G[ia * Q + ib] : (ia == ib ? (C)1 : (C)0);
-        vg = osg * g;
-    }
+    if (parts & 2) vg = rel_entry<C>(G, Q, osg, ia, ib);
     return va + vg;
 }
 template <typename T, int DP>

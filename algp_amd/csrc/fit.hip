@@ -15,12 +15,122 @@
 
 namespace algp {
 
-// FAM: the family of `kernel` (kernel_family, common.h): one copy of the kernel per family
-template <typename T, int DP, int FAM>
-__global__ __launch_bounds__(256) void mll_grad_kernel(const T* Sinv, int64_t ld, int64_t N, const T* Xs,
-                                                       const int64_t* aidx, const T* alpha, int kernel, T os,
-                                                       int repeats /* a pool site occurs in more than one row */,
-                                                       double* partial /* per workgroup: [0]=os, [1]=noise trace, [2..2+DP) = ls */) {
+// ---------------------------------------------------------------------------------------------
+// What a kernel form says about one pair of rows (i, j); the tiling, staging, accumulation and reduction are mll_grad_kernel's.
+//   NOS              the number of outputscales, each with a sum of its own
+//   pair<DP>         from the row's coordinates and alpha_i (both in LDS), the column's (registers) and s = S^-1_ij: returns the
+//                    weight W_ij = alpha_i alpha_j - s and hands back the pair's terms, kv[q] = dS_ij/dlog os_q, dk[d] = the
+//                    lengthscale factor of the part that owns coordinate d (dS_ij/dlog ls_d = dk[d] u2[d]), u2[d] = u_d^2.
+//                    In this order: the squared distances, the weight, the kernel values.  alpha_i comes by reference so that
+//                    its read from LDS stands where the weight is formed: read ahead of the distances it cost the fp32 DP = 8
+//                    kernel two VGPRs and a wave, read behind the kernel values (which branch on the form) 1 % of the time at DP = 2
+//   SINV_UP_FRONT    a thread's 16 entries of S^-1 are loaded ahead of a fully unrolled row loop (else: read pair by pair in a
+//                    rolled one)
+//   PAIR_FLOPS, SINV_ELEMS   the profile's accounting: flops per pair beyond 3 DP, elements read per N^2
+// The rounding is part of each form and written out in it: the single forms are compiled with contraction on (the squared
+// distance a running fused sum, the weight one fused multiply-add), the two-part forms with contraction off (each square and
+// the weight's product rounded on their own, split_r2's and rel_r2's rule: the distances the matrix build sees).
+// ---------------------------------------------------------------------------------------------
+// One kernel of family FAM (kernel_family, common.h): one copy of the gradient kernel per family
+template <typename T, int FAM>
+struct GradSingle {
+    static constexpr int NOS = 1;
+    static constexpr bool SINV_UP_FRONT = true;
+    static constexpr double PAIR_FLOPS = 8.0, SINV_ELEMS = 0.5;
+    int kernel;
+    T os;
+    template <int DP>
+    __device__ __forceinline__ T pair(const T (&xi)[DP], const T (&xj)[DP], const T& ai, T aj, T s, T (&kv)[NOS], T (&dk)[DP], T (&u2)[DP]) const {
+        T r2 = (T)0;
+#pragma unroll
+        for (int d = 0; d < DP; ++d) {
+            const T df = xi[d] - xj[d];
+            u2[d] = df * df;
+            r2 += u2[d];
+        }
+        const T w = kfma(ai, aj, -s);                            // one fused multiply-add
+        T k1;                                                    // 0 at r = 0 for nu = 1/2
+        kv[0] = kdk<T, FAM>(kernel, os, r2, k1);
+#pragma unroll
+        for (int d = 0; d < DP; ++d) dk[d] = k1;
+        return w;
+    }
+};
+
+// The additive kernel (common.h: family 2): S = os_a kappa_a(r_a) + os_b kappa_b(r_b) + ..., so dS/dlog os_a = K_a, dS/dlog os_b
+// = K_b, and coordinate d belongs to part a where d < da.  Two kdk values per pair.
+template <typename T>
+struct GradAdd {
+    static constexpr int NOS = 2;
+    static constexpr bool SINV_UP_FRONT = false;
+    static constexpr double PAIR_FLOPS = 16.0, SINV_ELEMS = 0.5;
+    int kernel_a;
+    T os_a;
+    int kernel_b;
+    T os_b;
+    int da;
+    template <int DP>
+    __device__ __forceinline__ T pair(const T (&xi)[DP], const T (&xj)[DP], const T& ai, T aj, T s, T (&kv)[NOS], T (&dk)[DP], T (&u2)[DP]) const {
+#pragma clang fp contract(off)
+        T ra, rb, dka, dkb;
+        split_r2<DP>(&xi[0], &xj[0], da, ra, rb);
+#pragma unroll
+        for (int d = 0; d < DP; ++d) {
+            const T df = xi[d] - xj[d];
+            u2[d] = df * df;                                     // the squares split_r2 has just summed
+        }
+        const T aa = ai * aj;                                    // a rounded product, then the difference
+        const T w = aa - s;
+        kv[0] = kdk<T>(kernel_a, os_a, ra, dka);
+        kv[1] = kdk<T>(kernel_b, os_b, rb, dkb);
+#pragma unroll
+        for (int d = 0; d < DP; ++d) dk[d] = d < da ? dka : dkb;
+        return w;
+    }
+};
+
+// The relationship kernel (common.h: family 3): S = os_a kappa_a(r_a) + os_g G[g_i, g_j] + ..., so dS/dlog os_a = K_a, dS/dlog os_g
+// = os_g G[g_i, g_j] (rel_entry: one gather per pair), and only the spatial coordinates d < da have a lengthscale: the id's
+// coordinate and the padding get the factor 0, their sums stay 0 and are not returned.
+template <typename T>
+struct GradRel {
+    static constexpr int NOS = 2;
+    static constexpr bool SINV_UP_FRONT = false;
+    static constexpr double PAIR_FLOPS = 10.0, SINV_ELEMS = 1.0;
+    int kernel_a;
+    T os_a;
+    const T* G;
+    int64_t Q;
+    T os_g;
+    int da;
+    template <int DP>
+    __device__ __forceinline__ T pair(const T (&xi)[DP], const T (&xj)[DP], const T& ai, T aj, T s, T (&kv)[NOS], T (&dk)[DP], T (&u2)[DP]) const {
+#pragma clang fp contract(off)
+        T ra, dka;
+        int64_t ia, ib;
+        rel_r2<DP>(&xi[0], &xj[0], da, ra, ia, ib);
+#pragma unroll
+        for (int d = 0; d < DP; ++d) {
+            const T df = xi[d] - xj[d];
+            u2[d] = df * df;                                     // the squares rel_r2 has just summed
+        }
+        const T aa = ai * aj;                                    // a rounded product, then the difference
+        const T w = aa - s;
+        kv[0] = kdk<T>(kernel_a, os_a, ra, dka);
+        kv[1] = rel_entry<T>(G, Q, os_g, ia, ib);
+#pragma unroll
+        for (int d = 0; d < DP; ++d) dk[d] = d < da ? dka : (T)0;
+        return w;
+    }
+};
+
+// Per workgroup, and after the reduction: [0, NOS) = the outputscale sums, [NOS] = the noise trace, [NOS+1, NOS+1+DP) = the
+// lengthscale sums -- 11 at most.
+template <typename T, int DP, typename Form>
+__global__ __launch_bounds__(256) void mll_grad_kernel(const T* Sinv, int64_t ld, int64_t N, const T* Xs, const int64_t* aidx,
+                                                       const T* alpha, Form f,
+                                                       int repeats /* a pool site occurs in more than one row */, double* partial) {
+    constexpr int NOS = Form::NOS, NQ = NOS + 1 + DP;
     // one workgroup = a 64-row x 64-col tile of the lower triangle; the grid enumerates only those
     // (blockIdx.x -> (bi, bj <= bi)).  The 64 rows' coordinates and alpha are staged in LDS once.
     int bi = (int)((sqrt(8.0 * (double)blockIdx.x + 1.0) - 1.0) * 0.5);
@@ -41,7 +151,9 @@ __global__ __launch_bounds__(256) void mll_grad_kernel(const T* Sinv, int64_t ld
         s_p[threadIdx.x] = ok ? pi : (int64_t)-1;
     }
     const int64_t j = (int64_t)bj * 64 + tx;
-    double g_os = 0, g_tr = 0, g_ls[DP];
+    double g_os[NOS], g_tr = 0, g_ls[DP];
+#pragma unroll
+    for (int q = 0; q < NOS; ++q) g_os[q] = 0;
 #pragma unroll
     for (int d = 0; d < DP; ++d) g_ls[d] = 0;
     T xj[DP], aj = (T)0;
@@ -56,146 +168,61 @@ __global__ __launch_bounds__(256) void mll_grad_kernel(const T* Sinv, int64_t ld
     }
     __syncthreads();
     if (j < N) {
-        T sv[16];                                                // this thread's 16 entries of S^-1, loaded up front
+        // the rows li = ty * 16 + rr of this thread's column.  Their entries of S^-1 up front and the loop unrolled, or each read
+        // where its pair is formed in a rolled loop: by the form.  (One loop with the body written out and the sums in variables
+        // of their own: the body as a lambda called from two loops, or the sums as one array, gave the single forms' kernels 3 to
+        // 6 % more instructions at DP = 2 -- exec-mask regions and moves -- and as much more time.)
+        constexpr int UNROLL = Form::SINV_UP_FRONT ? 16 : 1;
+        T sv[UNROLL];
+        if constexpr (Form::SINV_UP_FRONT) {
 #pragma unroll
-        for (int rr = 0; rr < 16; ++rr) {
-            const int64_t i = (int64_t)bi * 64 + ty * 16 + rr;
-            sv[rr] = (i < N && j <= i) ? Sinv[i * ld + j] : (T)0;
+            for (int rr = 0; rr < 16; ++rr) {
+                const int64_t i = (int64_t)bi * 64 + ty * 16 + rr;
+                sv[rr] = (i < N && j <= i) ? Sinv[i * ld + j] : (T)0;
+            }
         }
-#pragma unroll
+#pragma unroll UNROLL
         for (int rr = 0; rr < 16; ++rr) {
             const int li = ty * 16 + rr;
             const int64_t i = (int64_t)bi * 64 + li;
             if (i >= N || j > i) continue;
-            T u2[DP], r2 = (T)0;
-#pragma unroll
-            for (int d = 0; d < DP; ++d) {
-                const T df = s_x[li][d] - xj[d];
-                u2[d] = df * df;
-                r2 += u2[d];
-            }
-            const T w = s_a[li] * aj - sv[rr];
+            T s;
+            if constexpr (Form::SINV_UP_FRONT) s = sv[rr];
+            else s = Sinv[i * ld + j];
+            T kv[NOS], dk[DP], u2[DP];
+            const T w = f.template pair<DP>(s_x[li], xj, s_a[li], aj, s, kv, dk, u2);
+            // m * x is exact (m = 1 or 2), so the sums are the same doubles with and without contraction
             const double m = (i == j) ? 1.0 : 2.0;               // symmetric: off-diagonal pairs count twice
-            T dk;                                                // dk * u_d^2 = dK/dlog ls_d (kdk, common.h; 0 at r = 0 for nu = 1/2)
-            const T kv = kdk<T, FAM>(kernel, os, r2, dk);
-            g_os += m * (double)(w * kv);
+#pragma unroll
+            for (int q = 0; q < NOS; ++q) g_os[q] += m * (double)(w * kv[q]);
             if (i == j) g_tr += (double)w;
             else if (repeats && s_p[li] == pj) g_tr += 2.0 * (double)w;   // a second row of the same site: S_ij holds sigma_n^2 too
 #pragma unroll
-            for (int d = 0; d < DP; ++d) g_ls[d] += m * (double)(w * dk * u2[d]);
+            for (int d = 0; d < DP; ++d) g_ls[d] += m * (double)((w * dk[d]) * u2[d]);
         }
     }
     // block reduction: wave shuffles, LDS across the 4 waves, then one partial per block and quantity (summed in fixed
     // order by mll_grad_reduce_kernel: the gradient, and with it a whole fit trajectory, is the same in every run)
+    __shared__ double s_red[4][NQ];
     auto wsum = [](double v) {
         for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
         return v;
     };
-    __shared__ double s_red[4][2 + DP];
-    g_os = wsum(g_os);
+#pragma unroll
+    for (int q = 0; q < NOS; ++q) g_os[q] = wsum(g_os[q]);
     g_tr = wsum(g_tr);
 #pragma unroll
     for (int d = 0; d < DP; ++d) g_ls[d] = wsum(g_ls[d]);
     if (tx == 0) {
-        s_red[ty][0] = g_os;
-        s_red[ty][1] = g_tr;
 #pragma unroll
-        for (int d = 0; d < DP; ++d) s_red[ty][2 + d] = g_ls[d];
+        for (int q = 0; q < NOS; ++q) s_red[ty][q] = g_os[q];
+        s_red[ty][NOS] = g_tr;
+#pragma unroll
+        for (int d = 0; d < DP; ++d) s_red[ty][NOS + 1 + d] = g_ls[d];
     }
     __syncthreads();
-    if (threadIdx.x < 2 + DP)
-        partial[(int64_t)blockIdx.x * (2 + DP) + threadIdx.x] =
-            (s_red[0][threadIdx.x] + s_red[1][threadIdx.x]) + (s_red[2][threadIdx.x] + s_red[3][threadIdx.x]);
-}
-
-// The additive kernel (common.h: family 2), a kernel of its own beside the two copies above: S = os_a kappa_a(r_a) + os_b kappa_b(r_b)
-// + ..., so dS/dlog os_a = K_a, dS/dlog os_b = K_b, and dS/dlog ls_d = dk_c u_d^2 with c the part that owns coordinate d (d < da: a).
-// Two kdk values per pair, from the two squared distances of split_r2's rule (each square rounded on its own, added in
-// coordinate order).  Per workgroup: [0] = os_a, [1] = os_b, [2] = noise trace, [3..3+DP) = ls -- 11 sums at most.  The same
-// tiles, staging and fixed-order reduction as mll_grad_kernel.
-template <typename T, int DP>
-__global__ __launch_bounds__(256) void mll_grad_add_kernel(const T* Sinv, int64_t ld, int64_t N, const T* Xs, const int64_t* aidx,
-                                                           const T* alpha, int kernel_a, T os_a, int kernel_b, T os_b, int da,
-                                                           int repeats, double* partial) {
-#pragma clang fp contract(off)
-    int bi = (int)((sqrt(8.0 * (double)blockIdx.x + 1.0) - 1.0) * 0.5);
-    while ((int64_t)(bi + 1) * (bi + 2) / 2 <= (int64_t)blockIdx.x) ++bi;
-    while ((int64_t)bi * (bi + 1) / 2 > (int64_t)blockIdx.x) --bi;
-    const int bj = (int)(blockIdx.x - (int64_t)bi * (bi + 1) / 2);
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    __shared__ T s_x[64][DP];
-    __shared__ T s_a[64];
-    __shared__ int64_t s_p[64];
-    if (threadIdx.x < 64) {
-        const int64_t i = (int64_t)bi * 64 + threadIdx.x;
-        const bool ok = i < N;
-        const int64_t pi = ok ? aidx[i] : 0;
-#pragma unroll
-        for (int d = 0; d < DP; ++d) s_x[threadIdx.x][d] = ok ? Xs[pi * DP + d] : (T)0;
-        s_a[threadIdx.x] = ok ? alpha[i] : (T)0;
-        s_p[threadIdx.x] = ok ? pi : (int64_t)-1;
-    }
-    const int64_t j = (int64_t)bj * 64 + tx;
-    double g_osa = 0, g_osb = 0, g_tr = 0, g_ls[DP];
-#pragma unroll
-    for (int d = 0; d < DP; ++d) g_ls[d] = 0;
-    T xj[DP], aj = (T)0;
-    int64_t pj = -2;
-#pragma unroll
-    for (int d = 0; d < DP; ++d) xj[d] = (T)0;
-    if (j < N) {
-        pj = aidx[j];
-#pragma unroll
-        for (int d = 0; d < DP; ++d) xj[d] = Xs[pj * DP + d];
-        aj = alpha[j];
-    }
-    __syncthreads();
-    if (j < N) {
-        for (int rr = 0; rr < 16; ++rr) {
-            const int li = ty * 16 + rr;
-            const int64_t i = (int64_t)bi * 64 + li;
-            if (i >= N || j > i) continue;
-            T u2[DP], ra = (T)0, rb = (T)0;
-#pragma unroll
-            for (int d = 0; d < DP; ++d) {
-                const T df = s_x[li][d] - xj[d];
-                u2[d] = df * df;
-                ra += d < da ? u2[d] : (T)0;
-                rb += d < da ? (T)0 : u2[d];
-            }
-            const T w = s_a[li] * aj - Sinv[i * ld + j];
-            const double m = (i == j) ? 1.0 : 2.0;
-            T dka, dkb;
-            const T ka = kdk<T>(kernel_a, os_a, ra, dka);
-            const T kb = kdk<T>(kernel_b, os_b, rb, dkb);
-            g_osa += m * (double)(w * ka);
-            g_osb += m * (double)(w * kb);
-            if (i == j) g_tr += (double)w;
-            else if (repeats && s_p[li] == pj) g_tr += 2.0 * (double)w;
-#pragma unroll
-            for (int d = 0; d < DP; ++d) g_ls[d] += m * (double)(w * (d < da ? dka : dkb) * u2[d]);
-        }
-    }
-    auto wsum = [](double v) {
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-        return v;
-    };
-    __shared__ double s_red[4][3 + DP];
-    g_osa = wsum(g_osa);
-    g_osb = wsum(g_osb);
-    g_tr = wsum(g_tr);
-#pragma unroll
-    for (int d = 0; d < DP; ++d) g_ls[d] = wsum(g_ls[d]);
-    if (tx == 0) {
-        s_red[ty][0] = g_osa;
-        s_red[ty][1] = g_osb;
-        s_red[ty][2] = g_tr;
-#pragma unroll
-        for (int d = 0; d < DP; ++d) s_red[ty][3 + d] = g_ls[d];
-    }
-    __syncthreads();
-    if (threadIdx.x < 3 + DP)
-        partial[(int64_t)blockIdx.x * (3 + DP) + threadIdx.x] =
+    if (threadIdx.x < NQ)
+        partial[(int64_t)blockIdx.x * NQ + threadIdx.x] =
             (s_red[0][threadIdx.x] + s_red[1][threadIdx.x]) + (s_red[2][threadIdx.x] + s_red[3][threadIdx.x]);
 }
 
@@ -213,169 +240,40 @@ __global__ __launch_bounds__(256) void mll_grad_reduce_kernel(const double* part
     }
 }
 
+// out_dev in the kernel's layout for the form of `s` (a coordinate pool's source, make_src): NOS + 1 + DP doubles
 template <typename T>
-int mll_grad_launch(algp_ctx* c, const T* Sinv, int64_t ld, int64_t N, const T* Xs, int DP, const int64_t* aidx,
-                    const T* alpha, int kernel, T os, double* out_dev, double* partial) {
+int mll_grad_launch(algp_ctx* c, const T* Sinv, int64_t ld, int64_t N, const int64_t* aidx, const T* alpha, const KmatSrc& s,
+                    double* out_dev, double* partial) {
     if (N <= 0) return ALGP_OK;
     const int rp = c->train_has_repeats ? 1 : 0;
     const unsigned nb = (unsigned)((N + 63) / 64);
-    ProfScope ps(c, ALGP_PROF_KMAT, 0.5 * (double)N * N * (3.0 * DP + 8.0), sizeof(T) * 0.5 * (double)N * N);
     dim3 grid(nb * (nb + 1) / 2), blk(256);
-    auto launch = [&](auto fam) {
-        constexpr int FAM = decltype(fam)::value;
-        with_dp(DP, [&](auto dp) {
-            hipLaunchKernelGGL((mll_grad_kernel<T, decltype(dp)::value, FAM>), grid, blk, 0, c->cur, Sinv, ld, N, Xs, aidx, alpha, kernel, os,
-                               rp, partial);
+    auto launch = [&](auto f) -> int {
+        using Form = decltype(f);
+        ProfScope ps(c, ALGP_PROF_KMAT, 0.5 * (double)N * N * (3.0 * s.DP + Form::PAIR_FLOPS), sizeof(T) * Form::SINV_ELEMS * (double)N * N);
+        with_dp(s.DP, [&](auto dp) {
+            hipLaunchKernelGGL((mll_grad_kernel<T, decltype(dp)::value, Form>), grid, blk, 0, c->cur, Sinv, ld, N, (const T*)s.Xs, aidx, alpha,
+                               f, rp, partial);
         });
+        ALGP_HIP(hipGetLastError());
+        hipLaunchKernelGGL(mll_grad_reduce_kernel, dim3(1), dim3(256), 0, c->cur, partial, (int64_t)grid.x, Form::NOS + 1 + s.DP, out_dev);
+        ALGP_HIP(hipGetLastError());
+        return ALGP_OK;
     };
-    if (kernel_family(kernel)) launch(std::integral_constant<int, 1>{});
-    else launch(std::integral_constant<int, 0>{});
-    ALGP_HIP(hipGetLastError());
-    hipLaunchKernelGGL(mll_grad_reduce_kernel, dim3(1), dim3(256), 0, c->cur, partial, (int64_t)grid.x, 2 + DP, out_dev);
-    ALGP_HIP(hipGetLastError());
-    return ALGP_OK;
+    const T os = (T)s.outputscale;
+    if (s.rel()) return launch(GradRel<T>{s.kernel, os, (const T*)s.G, s.Q, (T)s.outputscale_g, s.da});
+    if (s.additive()) return launch(GradAdd<T>{s.kernel, os, s.kernel_b, (T)s.outputscale_b, s.da});
+    if (kernel_family(s.kernel)) return launch(GradSingle<T, 1>{s.kernel, os});
+    return launch(GradSingle<T, 0>{s.kernel, os});
 }
 ALGP_INSTANTIATE(mll_grad_launch);
 
-// the additive kernel's: out_dev[0] = os_a, [1] = os_b, [2] = noise trace, [3..3+DP) = ls
-template <typename T>
-int mll_grad_add_launch(algp_ctx* c, const T* Sinv, int64_t ld, int64_t N, const T* Xs, int DP, const int64_t* aidx, const T* alpha,
-                        int kernel_a, T os_a, int kernel_b, T os_b, int da, double* out_dev, double* partial) {
-    if (N <= 0) return ALGP_OK;
-    const int rp = c->train_has_repeats ? 1 : 0;
-    const unsigned nb = (unsigned)((N + 63) / 64);
-    ProfScope ps(c, ALGP_PROF_KMAT, 0.5 * (double)N * N * (3.0 * DP + 16.0), sizeof(T) * 0.5 * (double)N * N);
-    dim3 grid(nb * (nb + 1) / 2), blk(256);
-    with_dp(DP, [&](auto dp) {
-        hipLaunchKernelGGL((mll_grad_add_kernel<T, decltype(dp)::value>), grid, blk, 0, c->cur, Sinv, ld, N, Xs, aidx, alpha, kernel_a, os_a,
-                           kernel_b, os_b, da, rp, partial);
-    });
-    ALGP_HIP(hipGetLastError());
-    hipLaunchKernelGGL(mll_grad_reduce_kernel, dim3(1), dim3(256), 0, c->cur, partial, (int64_t)grid.x, 3 + DP, out_dev);
-    ALGP_HIP(hipGetLastError());
-    return ALGP_OK;
-}
-ALGP_INSTANTIATE(mll_grad_add_launch);
-
-// The relationship kernel (common.h: family 3), a third gradient kernel: S = os_a kappa_a(r_a) + os_g G[g_i, g_j] + ..., so
-// dS/dlog os_a = K_a, dS/dlog os_g = os_g G[g_i, g_j] (the part's value as kval_rel rounds it), and dS/dlog ls_d = dk_a u_d^2 for
-// the spatial coordinates d < da; the id's coordinate has no lengthscale (its sum stays 0 and is not returned).  r_a^2 by
-// rel_r2's rule.  Per workgroup: [0] = os_a, [1] = os_g, [2] = noise trace, [3..3+DP) = ls.  The same tiles, staging and
-// fixed-order reduction as mll_grad_kernel; the table entry is one gather per pair.
-template <typename T, int DP>
-__global__ __launch_bounds__(256) void mll_grad_rel_kernel(const T* Sinv, int64_t ld, int64_t N, const T* Xs, const int64_t* aidx,
-                                                           const T* alpha, int kernel_a, T os_a, const T* G, int64_t Q, T os_g, int da,
-                                                           int repeats, double* partial) {
-#pragma clang fp contract(off)
-    int bi = (int)((sqrt(8.0 * (double)blockIdx.x + 1.0) - 1.0) * 0.5);
-    while ((int64_t)(bi + 1) * (bi + 2) / 2 <= (int64_t)blockIdx.x) ++bi;
-    while ((int64_t)bi * (bi + 1) / 2 > (int64_t)blockIdx.x) --bi;
-    const int bj = (int)(blockIdx.x - (int64_t)bi * (bi + 1) / 2);
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    __shared__ T s_x[64][DP];
-    __shared__ T s_a[64];
-    __shared__ int64_t s_p[64];
-    if (threadIdx.x < 64) {
-        const int64_t i = (int64_t)bi * 64 + threadIdx.x;
-        const bool ok = i < N;
-        const int64_t pi = ok ? aidx[i] : 0;
-#pragma unroll
-        for (int d = 0; d < DP; ++d) s_x[threadIdx.x][d] = ok ? Xs[pi * DP + d] : (T)0;
-        s_a[threadIdx.x] = ok ? alpha[i] : (T)0;
-        s_p[threadIdx.x] = ok ? pi : (int64_t)-1;
-    }
-    const int64_t j = (int64_t)bj * 64 + tx;
-    double g_osa = 0, g_osg = 0, g_tr = 0, g_ls[DP];
-#pragma unroll
-    for (int d = 0; d < DP; ++d) g_ls[d] = 0;
-    T xj[DP], aj = (T)0;
-    int64_t pj = -2;
-#pragma unroll
-    for (int d = 0; d < DP; ++d) xj[d] = (T)0;
-    if (j < N) {
-        pj = aidx[j];
-#pragma unroll
-        for (int d = 0; d < DP; ++d) xj[d] = Xs[pj * DP + d];
-        aj = alpha[j];
-    }
-    __syncthreads();
-    if (j < N) {
-        for (int rr = 0; rr < 16; ++rr) {
-            const int li = ty * 16 + rr;
-            const int64_t i = (int64_t)bi * 64 + li;
-            if (i >= N || j > i) continue;
-            T u2[DP], ra = (T)0, gi = (T)0, gj = (T)0;
-#pragma unroll
-            for (int d = 0; d < DP; ++d) {
-                const T xi = s_x[li][d];
-                const T df = xi - xj[d];
-                u2[d] = df * df;
-                ra += d < da ? u2[d] : (T)0;
-                gi = d == da ? xi : gi;
-                gj = d == da ? xj[d] : gj;
-            }
-            const int64_t ia = (int64_t)gi, ib = (int64_t)gj;
-            const T w = s_a[li] * aj - Sinv[i * ld + j];
-            const double m = (i == j) ? 1.0 : 2.0;
-            T dka;
-            const T ka = kdk<T>(kernel_a, os_a, ra, dka);
-            const T kg = os_g * (G ? G[ia * Q + ib] : (ia == ib ? (T)1 : (T)0));
-            g_osa += m * (double)(w * ka);
-            g_osg += m * (double)(w * kg);
-            if (i == j) g_tr += (double)w;
-            else if (repeats && s_p[li] == pj) g_tr += 2.0 * (double)w;
-#pragma unroll
-            for (int d = 0; d < DP; ++d) g_ls[d] += d < da ? m * (double)(w * dka * u2[d]) : 0.0;
-        }
-    }
-    auto wsum = [](double v) {
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-        return v;
-    };
-    __shared__ double s_red[4][3 + DP];
-    g_osa = wsum(g_osa);
-    g_osg = wsum(g_osg);
-    g_tr = wsum(g_tr);
-#pragma unroll
-    for (int d = 0; d < DP; ++d) g_ls[d] = wsum(g_ls[d]);
-    if (tx == 0) {
-        s_red[ty][0] = g_osa;
-        s_red[ty][1] = g_osg;
-        s_red[ty][2] = g_tr;
-#pragma unroll
-        for (int d = 0; d < DP; ++d) s_red[ty][3 + d] = g_ls[d];
-    }
-    __syncthreads();
-    if (threadIdx.x < 3 + DP)
-        partial[(int64_t)blockIdx.x * (3 + DP) + threadIdx.x] =
-            (s_red[0][threadIdx.x] + s_red[1][threadIdx.x]) + (s_red[2][threadIdx.x] + s_red[3][threadIdx.x]);
-}
-
-// the relationship kernel's: out_dev[0] = os_a, [1] = os_g, [2] = noise trace, [3..3+DP) = ls (zero from the id's coordinate on)
-template <typename T>
-int mll_grad_rel_launch(algp_ctx* c, const T* Sinv, int64_t ld, int64_t N, const T* Xs, int DP, const int64_t* aidx, const T* alpha,
-                        int kernel_a, T os_a, const T* G, int64_t Q, T os_g, int da, double* out_dev, double* partial) {
-    if (N <= 0) return ALGP_OK;
-    const int rp = c->train_has_repeats ? 1 : 0;
-    const unsigned nb = (unsigned)((N + 63) / 64);
-    ProfScope ps(c, ALGP_PROF_KMAT, 0.5 * (double)N * N * (3.0 * DP + 10.0), sizeof(T) * (double)N * N);
-    dim3 grid(nb * (nb + 1) / 2), blk(256);
-    with_dp(DP, [&](auto dp) {
-        hipLaunchKernelGGL((mll_grad_rel_kernel<T, decltype(dp)::value>), grid, blk, 0, c->cur, Sinv, ld, N, Xs, aidx, alpha, kernel_a, os_a,
-                           G, Q, os_g, da, rp, partial);
-    });
-    ALGP_HIP(hipGetLastError());
-    hipLaunchKernelGGL(mll_grad_reduce_kernel, dim3(1), dim3(256), 0, c->cur, partial, (int64_t)grid.x, 3 + DP, out_dev);
-    ALGP_HIP(hipGetLastError());
-    return ALGP_OK;
-}
-ALGP_INSTANTIATE(mll_grad_rel_launch);
-
 // ---------------------------------------------------------------------------------------------
-// The relationship form's gathers from its table (algp_genotype_posterior's B, the per-site prior of the candidates).
+// The relationship form's gathers from its table (algp_genotype_posterior's B, the per-site prior of the candidates).  Every
+// product os_g G is rel_entry's (common.h).
 // ---------------------------------------------------------------------------------------------
 // B[q][i] = os_g G[q, g_i] for q < Q and train row i < N (g_i: the id in coordinate da of the row's pool site), zero in the
-// padding up to Qpad x Npad: the right-hand sides of the genotype posterior.  The product rounds as kval_rel's does.
+// padding up to Qpad x Npad: the right-hand sides of the genotype posterior.
 template <typename T>
 __global__ __launch_bounds__(256) void rel_gather_b_kernel(const T* G, int64_t Q, T os_g, const T* Xs, int DP, int da, const int64_t* aidx,
                                                            int64_t N, int64_t Qpad, int64_t Npad, T* B) {
@@ -383,10 +281,7 @@ __global__ __launch_bounds__(256) void rel_gather_b_kernel(const T* G, int64_t Q
     const int64_t q = blockIdx.y;
     if (i >= Npad) return;
     T v = (T)0;
-    if (q < Q && i < N) {
-        const int64_t gi = (int64_t)Xs[aidx[i] * DP + da];
-        v = os_g * (G ? G[q * Q + gi] : (q == gi ? (T)1 : (T)0));
-    }
+    if (q < Q && i < N) v = rel_entry<T>(G, Q, os_g, q, (int64_t)Xs[aidx[i] * DP + da]);
     B[q * Npad + i] = v;
 }
 template <typename T>
@@ -411,7 +306,7 @@ __global__ __launch_bounds__(256) void rel_prior_kernel(const T* G, int64_t Q, T
     const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (j >= n) return;
     const int64_t g = (int64_t)Xs[j * DP + da];
-    const T vg = os_g * (G ? G[g * Q + g] : (T)1);
+    const T vg = rel_entry<T>(G, Q, os_g, g, g);
     prior[j] = os_a + vg;
 }
 template <typename T>
@@ -425,14 +320,13 @@ ALGP_INSTANTIATE(rel_prior_launch);
 
 // cov[p][q] = cov[q][p] = os_g G[p, q] - WW[p][q] for q <= p < Q (WW: the lower tiles of W W^T, leading dimension ldw; null: no
 // train rows, nothing is subtracted): the genotype posterior's covariance, both triangles from the one value -- identical bits.
-// The product os_g G rounds as kval_rel's does.
 template <typename T>
 __global__ __launch_bounds__(256) void rel_cov_finish_kernel(const T* G, int64_t Q, T os_g, const T* WW, int64_t ldw, T* cov) {
 #pragma clang fp contract(off)
     const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t p = blockIdx.y;
     if (q > p || p >= Q) return;
-    const T pr = os_g * (G ? G[p * Q + q] : (p == q ? (T)1 : (T)0));
+    const T pr = rel_entry<T>(G, Q, os_g, p, q);
     const T v = WW ? pr - WW[p * ldw + q] : pr;
     cov[p * Q + q] = v;
     cov[q * Q + p] = v;
@@ -453,7 +347,7 @@ __global__ __launch_bounds__(256) void rel_var_finish_kernel(const T* G, int64_t
 #pragma clang fp contract(off)
     const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (q >= Q) return;
-    const T pr = os_g * (G ? G[q * Q + q] : (T)1);
+    const T pr = rel_entry<T>(G, Q, os_g, q, q);
     var[q] = ss ? pr - ss[q] : pr;
 }
 template <typename T>

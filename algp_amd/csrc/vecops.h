@@ -182,17 +182,11 @@ int to_double_launch(algp_ctx* c, double* dst, const T* src, int64_t n);
 // inverse of the NB x NB lower-triangular diagonal block at A (no factorisation)
 template <typename T>
 int trinv_diag_launch(algp_ctx* c, const T* A, int64_t lda, T* inv_out);
+// the MLL gradient's sums (fit.hip), nos = 2 under the additive and the relationship form, else 1: out_dev[0, nos) += the
+// outputscale sums, [nos] the noise trace, [nos + 1, nos + 1 + DP) the lengthscale sums
 template <typename T>
-int mll_grad_launch(algp_ctx* c, const T* Sinv, int64_t ld, int64_t N, const T* Xs, int DP, const int64_t* aidx,
-                    const T* alpha, int kernel, T os, double* out_dev, double* partial);
-// under the additive kernel: out_dev[0] = os_a, [1] = os_b, [2] = noise trace, [3..3+DP) = ls (fit.hip)
-template <typename T>
-int mll_grad_add_launch(algp_ctx* c, const T* Sinv, int64_t ld, int64_t N, const T* Xs, int DP, const int64_t* aidx, const T* alpha,
-                        int kernel_a, T os_a, int kernel_b, T os_b, int da, double* out_dev, double* partial);
-// under the relationship kernel: out_dev[0] = os_a, [1] = os_g, [2] = noise trace, [3..3+DP) = ls (fit.hip)
-template <typename T>
-int mll_grad_rel_launch(algp_ctx* c, const T* Sinv, int64_t ld, int64_t N, const T* Xs, int DP, const int64_t* aidx, const T* alpha,
-                        int kernel_a, T os_a, const T* G, int64_t Q, T os_g, int da, double* out_dev, double* partial);
+int mll_grad_launch(algp_ctx* c, const T* Sinv, int64_t ld, int64_t N, const int64_t* aidx, const T* alpha, const KmatSrc& s,
+                    double* out_dev, double* partial);
 // the relationship form's gathers from its table (fit.hip): B[q][i] = os_g G[q, g_i] (Qpad x Npad, zero padded), the prior
 // variance os_a + os_g G[g_j, g_j] of every pool site, and the two last steps of algp_genotype_posterior
 template <typename T>
