@@ -62,6 +62,7 @@ SIGNATURES = {
     'algp_get_factor': (C.c_int, [_c_ctx, C.c_void_p]),
     'algp_get_mll': (C.c_int, [_c_ctx, _dblp]),
     'algp_get_mll_grad': (C.c_int, [_c_ctx, _dblp]),
+    'algp_get_mll_ai': (C.c_int, [_c_ctx, _dblp]),
     'algp_fit_step': (C.c_int, [_c_ctx, _dblp, _dblp]),
     'algp_set_candidates': (C.c_int, [_c_ctx, _i64p, C.c_int64, C.c_int, C.c_void_p]),
     'algp_solve_candidates': (C.c_int, [_c_ctx]),
@@ -370,6 +371,14 @@ class Context(object):
         g = np.empty(self._n_grad(), dtype=np.float64)
         self._check(self.lib.algp_get_mll_grad(self.h, g.ctypes.data_as(_dblp)))
         return g
+
+    def mll_ai(self):
+        """The (P, P) average-information matrix of the MLL in mll_grad's parameter order (algp_get_mll_ai):
+        AI_ab = 1/2 alpha' dS/dtheta_a S^-1 dS/dtheta_b alpha; not divided by N.  Needs a current factorisation."""
+        n = self._n_grad()
+        ai = np.empty((n, n), dtype=np.float64)
+        self._check(self.lib.algp_get_mll_ai(self.h, ai.ctypes.data_as(_dblp)))
+        return ai
 
     def fit_step(self, want_mll=True, want_grad=True):
         """(mll, grad): factorisation, marginal log likelihood and its gradient for the current hyper-parameters in one

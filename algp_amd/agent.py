@@ -95,7 +95,8 @@ class Agent(object):
                              'n_genotypes': None if G is not None else int(getattr(self.env, 'num_genotypes', 0))}
         self.gp = GPR(latent=args.latent, lr=args.lr, max_iterations=args.max_iterations,
                       kernel_params=kernel_params, learn_likelihood_noise=self.learn_likelihood_noise,
-                      dtype=getattr(args, 'dtype', np.float64), device=getattr(args, 'device', 0))
+                      dtype=getattr(args, 'dtype', np.float64), device=getattr(args, 'device', 0),
+                      fit_method=getattr(args, 'fit_method', 'adam'))
 
     def load_model(self, parent_agent):
         self.gp.reset(parent_agent.gp.train_x, parent_agent.gp.train_y, parent_agent.gp.train_var)

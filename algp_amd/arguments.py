@@ -3,7 +3,8 @@ Differences: `--kernel` accepts {rbf, matern, additive, genotype} only, and `--m
 (the reference fixes nu in its source, models.py:219-222); `--kernel additive` is the sum of `--kernel_a` over the first
 `--kernel_split` coordinates and `--kernel_b` over the others (`--matern_nu` applies to its Matern parts); `--kernel genotype` is
 `--kernel_a` (with `--matern_nu`) over the position plus a genotype effect per id in the last coordinate, with the relationship
-matrix of `--relationship PATH` (a .npy file) or independent genotypes without it; `--dtype`/`--device` select the GPU precision
+matrix of `--relationship PATH` (a .npy file) or independent genotypes without it; `--fit_method ai` fits by average-information
+Newton steps instead of Adam; `--dtype`/`--device` select the GPU precision
 and card; no results directory is created and nothing prompts (the reference's interactive
 `input()` at arguments.py:41-49 blocks unattended runs)."""
 import argparse
@@ -15,6 +16,9 @@ def get_parser():
     p = argparse.ArgumentParser(description='Adaptive Sampling and Informative Planning (MI355X GP path)')
     p.add_argument('--lr', default=.1, type=float)
     p.add_argument('--max_iterations', default=200, type=int)
+    p.add_argument('--fit_method', default='adam', choices=['adam', 'ai'],
+                   help="GPR.fit: the reference's Adam loop, or damped Newton steps on the average-information matrix "
+                        '(--max_iterations then caps the MLL evaluations)')
     p.add_argument('--data_file', default=None)
     p.add_argument('--phenotype', default='plant_height')
     p.add_argument('--kernel', default='matern', choices=['rbf', 'matern', 'additive', 'genotype'])

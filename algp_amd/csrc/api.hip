@@ -606,7 +606,7 @@ void algp_destroy(algp_ctx* c) {
     DevBuf* bufs[] = {&c->Xs, &c->Xraw, &c->Cp, &c->Aidx, &c->yA, &c->varA, &c->y0, &c->L, &c->invD, &c->z, &c->alpha,
                       &c->scal, &c->Cidx, &c->ckind, &c->cextra, &c->Vt, &c->dstat, &c->mu, &c->alive, &c->scores,
                       &c->lrow, &c->remote, &c->commbuf, &c->tvec, &c->amax, &c->prevrows, &c->fresh, &c->lazypicks, &c->yraw, &c->uvec, &c->wvec, &c->acc3, &c->rowstat, &c->inv512, &c->inv512_scr, &c->trsm_tmp, &c->gemm_part, &c->rhs_rx, &c->rhs_cx, &c->rhs_rk, &c->splitk, &c->dag_state, &c->dag_stats, &c->trsv_ctrl, &c->auxA, &c->auxInv, &c->auxW, &c->auxIdx,
-                      &c->auxVar, &c->auxD, &c->hostStage, &c->rowx, &c->tailE, &c->tailPart, &c->ldpart, &c->tw, &c->smp, &c->grp, &c->Gtab, &c->Gprior, &c->gen};
+                      &c->auxVar, &c->auxD, &c->hostStage, &c->rowx, &c->tailE, &c->tailPart, &c->ldpart, &c->tw, &c->smp, &c->grp, &c->Gtab, &c->Gprior, &c->gen, &c->ai};
     for (DevBuf* b : bufs) release(c, *b);
     release(c, c->mi);
     release(c, c->vr);

@@ -1,4 +1,5 @@
-// api_fit.hip -- one iteration of GPR.fit (models.py:145-158): MLL and its gradient w.r.t. the log hyper-parameters.
+// api_fit.hip -- one iteration of GPR.fit (models.py:145-158): MLL and its gradient w.r.t. the log hyper-parameters; the
+// average-information matrix of the MLL in the same parameters (algp_get_mll_ai).
 #include "api_impl.h"
 
 using namespace algp;
@@ -47,6 +48,51 @@ int Impl<T>::mll_grad(algp_ctx* c, double* grad_out, bool have_X, bool inv_enque
     for (int q = 0; q < nos; ++q) grad_out[nl + q] = 0.5 * h[q];
     grad_out[nl + nos] = 0.5 * c->hyp.noise * h[nos];
     return ALGP_OK;
+}
+
+
+// The average-information matrix AI_ab = 1/2 alpha' dS/dtheta_a S^-1 dS/dtheta_b alpha in the gradient's parameter order (fit_ai.hip):
+//   U (128 x Npad, P live rows)    u_a = dS/dtheta_a alpha, one pass over the N^2 pairs              mll_ai_u_launch
+//   V = U L^-T, in place           the blocked triangular solve through its plan                    trsm_blocked
+//   AI = 1/2 V V^T (P x P)         a fixed-order reduction in double, both triangles from one value  mll_ai_gram_launch
+// Beyond bringing alpha up to date nothing of the resident state is written, and nothing is expected in auxA / auxW; the scratch
+// is one buffer of the context (algp_ctx::ai), counted by algp_device_bytes and freed by algp_destroy.  One synchronisation.
+template <typename T>
+int Impl<T>::mll_ai(algp_ctx* c, double* ai_out) {
+    if (!c->factored || c->train_dirty) return fail(c, ALGP_ERR_STATE, "get_mll_ai: call algp_factorize first");
+    if (c->pool_is_cov) return fail(c, ALGP_ERR_BAD_ARG, "get_mll_ai needs a coordinate pool");
+    const int64_t N = c->N, Npad = c->Npad;
+    // [log ls | the log outputscales | log sigma_n^2]; under the relationship form the id has no lengthscale
+    const int nos = (c->hyp.additive || c->hyp.rel) ? 2 : 1, nl = c->hyp.rel ? c->hyp.D - 1 : c->hyp.D, P = nl + nos + 1;
+    if (N <= 0) {
+        for (int e = 0; e < P * P; ++e) ai_out[e] = 0.0;
+        return ALGP_OK;
+    }
+    size_t total = 0;
+    auto take = [&](size_t bytes) { const size_t o = total; total += (bytes + 255) / 256 * 256; return o; };
+    const size_t o_U = take(sizeof(T) * (size_t)NB * (size_t)Npad);
+    const size_t o_out = take(sizeof(double) * (size_t)P * (size_t)P);
+    if (total > c->ai.cap) {
+        size_t free_b = 0, total_b = 0;
+        ALGP_HIP(hipMemGetInfo(&free_b, &total_b));
+        if (total > c->ai.cap + free_b)
+            return fail(c, ALGP_ERR_OOM, "get_mll_ai: the scratch of " + std::to_string(N) + " train rows takes " + std::to_string(total) +
+                                             " bytes, " + std::to_string(c->ai.cap + free_b) + " available");
+    }
+    ALGP_TRY(ensure(c, c->ai, total));
+    ALGP_TRY(need_alpha(c));
+    T* U = (T*)((char*)c->ai.p + o_U);
+    double* out = (double*)((char*)c->ai.p + o_out);
+    // the rows behind the P live ones ride through the solve as zeros (the panel is one 128-row tile)
+    ALGP_HIP(hipMemsetAsync(U + (int64_t)P * Npad, 0, sizeof(T) * (size_t)(NB - P) * (size_t)Npad, c->stream));
+    ALGP_TRY(mll_ai_u_launch<T>(c, N, Npad, (const int64_t*)c->Aidx.p, (const T*)c->alpha.p, make_src(c), nl, U));
+    ALGP_TRY(trsm_blocked<T>(c, {.klass = ALGP_PROF_GEMM_TRSM, .X = U, .mpad = NB, .ldx = Npad, .L = p(c->L), .npad = Npad, .ldl = c->Lld,
+                                 .invD = p(c->invD)}));
+    ALGP_TRY(mll_ai_gram_launch<T>(c, U, Npad, N, P, out));
+    ALGP_HIP(hipMemcpyAsync(ai_out, out, sizeof(double) * (size_t)P * (size_t)P, hipMemcpyDeviceToHost, c->stream));
+    const int rc = sync_checked(c, "get_mll_ai");
+    if (rc != ALGP_OK) c->alpha_valid = false;
+    return rc;
 }
 
 
@@ -103,6 +149,12 @@ int algp_get_mll_grad(algp_ctx* c, double* grad) {
     CHECK_CTX(c);
     if (!grad) return fail(c, ALGP_ERR_BAD_ARG, "get_mll_grad: bad arguments");
     FINISH(c, DISPATCH(c, mll_grad(c, grad)));
+}
+
+int algp_get_mll_ai(algp_ctx* c, double* ai) {
+    CHECK_CTX(c);
+    if (!ai) return fail(c, ALGP_ERR_BAD_ARG, "get_mll_ai: bad arguments");
+    FINISH(c, DISPATCH(c, mll_ai(c, ai)));
 }
 
 int algp_fit_step(algp_ctx* c, double* mll, double* grad) {

@@ -3,7 +3,7 @@
 // factor of the train set and its updates), api_candidates.hip (candidate solve and posterior), api_greedy.hip (scoring,
 // picks, the sharded exchange), api_mi.hip (the MI criterion's state, on one GPU and over the ranks), api_vr.hip (the
 // variance-reduction criterion), api_paths.hip (best_path block scoring), api_paths_vr.hip (the variance-reduction utility of
-// whole paths), api_fit.hip (MLL gradient, one fit iteration), api_sample.hip (joint posterior draws),
+// whole paths), api_fit.hip (MLL gradient, one fit iteration, the average-information matrix), api_sample.hip (joint posterior draws),
 // api_group.hip (the joint posterior of group aggregates), api_genotype.hip (the genotype effects under the relationship form).
 // Every file defines its members of Impl<T> and instantiates Impl<float> / Impl<double> for them.
 #pragma once
@@ -208,6 +208,7 @@ struct Impl {
                               double* dMI, double* terms);
     static int score_paths_vr(algp_ctx* c, const int64_t* sites, int npaths, int maxlen, double mobile_std, int64_t max_union, double* dV);
     static int mll_grad(algp_ctx* c, double* grad_out, bool have_X = false, bool inv_enqueued = false);
+    static int mll_ai(algp_ctx* c, double* ai_out);
     static int fit_step(algp_ctx* c, double* mll_out, double* grad_out);
     static int get_alpha(algp_ctx* c, void* out);
     static int get_factor(algp_ctx* c, void* out);

@@ -598,7 +598,8 @@ struct algp_ctx {
     // os_a + os_g G[g_j, g_j] of every pool site (the per-site prior of cand_finalize_launch, rebuilt with the scaled pool), and
     // algp_genotype_posterior's scratch, one allocation carved up per call (api_genotype.hip)
     algp::DevBuf Gtab, Gprior, gen;
-    uint64_t gprior_stamp = 0;           // Gprior holds the priors for this hyp_stamp and gprior_noise (prior_includes_noise)
+    algp::DevBuf ai;                     // algp_get_mll_ai's scratch: the 128 x Npad panel U -> V and the P x P result (api_fit.hip)
+    uint64_t gprior_stamp = 0;          // Gprior holds the priors for this hyp_stamp and gprior_noise (prior_includes_noise)
     int gprior_noise = -1;
 
     // profiling

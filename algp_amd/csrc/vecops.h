@@ -187,6 +187,13 @@ int trinv_diag_launch(algp_ctx* c, const T* A, int64_t lda, T* inv_out);
 template <typename T>
 int mll_grad_launch(algp_ctx* c, const T* Sinv, int64_t ld, int64_t N, const int64_t* aidx, const T* alpha, const KmatSrc& s,
                     double* out_dev, double* partial);
+// the average-information matrix's two kernels (fit_ai.hip): U[a][i] = (dS/dtheta_a alpha)_i as a P x Npad panel in the gradient's
+// parameter order (nl lengthscale rows, the outputscales, the noise; rows >= N zero), and out[a P + b] = out[b P + a] =
+// 1/2 sum_{i < N} V[a][i] V[b][i] in double, both in fixed order
+template <typename T>
+int mll_ai_u_launch(algp_ctx* c, int64_t N, int64_t Npad, const int64_t* aidx, const T* alpha, const KmatSrc& s, int nl, T* U);
+template <typename T>
+int mll_ai_gram_launch(algp_ctx* c, const T* V, int64_t ld, int64_t N, int P, double* out);
 // the relationship form's gathers from its table (fit.hip): B[q][i] = os_g G[q, g_i] (Qpad x Npad, zero padded), the prior
 // variance os_a + os_g G[g_j, g_j] of every pool site, and the two last steps of algp_genotype_posterior
 template <typename T>

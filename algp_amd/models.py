@@ -28,7 +28,11 @@ What differs, deliberately:
     kernel_covar_module.kernels.0.log_outputscale, kernel_covar_module.kernels.1.log_outputscale (the table is data, not a
     parameter); GPR.genotype_effects gives the BLUPs with their variances or joint covariance;
   * `fit` uses the analytic MLL gradient computed on the device with the reference's own optimiser
-    objects (torch.optim.Adam + ReduceLROnPlateau(patience=50), models.py:121-124).
+    objects (torch.optim.Adam + ReduceLROnPlateau(patience=50), models.py:121-124);
+  * GPR(..., fit_method='ai') fits by damped Newton steps on the average-information matrix of the MLL instead (utils.ai_newton,
+    algp_get_mll_ai: tens of device steps, not hundreds); after either method hyper_covariance / hyper_standard_errors give the
+    covariance and standard errors of the log hyper-parameters and, under the genotype kernel, heritability gives h2 with its
+    standard error.
 """
 import numpy as np
 import torch
@@ -167,7 +171,11 @@ class ExactGPModel(nn.Module):
 
 class GPR(object):
     def __init__(self, latent=None, lr=.01, max_iterations=200, kernel_params=None, latent_params=None,
-                 learn_likelihood_noise=True, dtype=np.float64, device=0):
+                 learn_likelihood_noise=True, dtype=np.float64, device=0, fit_method='adam'):
+        if fit_method not in ('adam', 'ai'):
+            raise ValueError("fit_method is 'adam' or 'ai', got %r" % (fit_method,))
+        self.fit_method = fit_method
+        self.fit_info = None
         self._train_x = None
         self._train_y = None
         self._train_y_mean = None
@@ -283,30 +291,118 @@ class GPR(object):
         n = max(1, len(self._train_y))
         return -mll / n, -grad / n
 
+    def _gradient_route(self):
+        """[(name, parameter, a, b)]: the parameter that entries [a, b) of the device's gradient (and of the average-information
+        matrix's rows and columns) belong to, in the device's order."""
+        named = dict(self.model.named_parameters())
+        noise = 'likelihood.log_noise'
+        if self.model.relationship is not None:
+            # the D + 2 gradient: [log ls of the D - 1 spatial coordinates | log os_a, log os_g | log noise]
+            names = ['kernel_covar_module.kernels.0.base_kernel.log_lengthscale', 'kernel_covar_module.kernels.0.log_outputscale',
+                     'kernel_covar_module.kernels.1.log_outputscale', noise]
+        elif self.model.split is not None:
+            # the D + 3 gradient: [log ls in coordinate order | log os_a, log os_b | log noise]
+            names = ['kernel_covar_module.kernels.%d.base_kernel.log_lengthscale' % k for k in (0, 1)] + \
+                    ['kernel_covar_module.kernels.%d.log_outputscale' % k for k in (0, 1)] + [noise]
+        else:
+            names = ['kernel_covar_module.base_kernel.log_lengthscale', 'kernel_covar_module.log_outputscale', noise]
+        route, at = [], 0
+        for name in names:
+            p = named[name]
+            route.append((name, p, at, at + p.numel()))
+            at += p.numel()
+        return route
+
+    def _scalar_names(self, route):
+        """One name per scalar of the gradient: the parameter's, with [d] behind it where it has more than one entry."""
+        return [name if b - a == 1 else '%s[%d]' % (name, d) for name, _, a, b in route for d in range(b - a)]
+
+    def _learned(self, route):
+        """The gradient's entries that fit optimises: all, or all but the noise (the last one)."""
+        P = route[-1][3]
+        return np.arange(P if self.learn_likelihood_noise else P - 1)
+
+    def _fit_ai(self, disp=False):
+        """fit by utils.ai_newton: damped Newton steps on the average-information matrix from the model's current parameters,
+        one algp_fit_step per evaluation and one algp_get_mll_ai per accepted point; max_iterations caps the evaluations."""
+        from .utils import ai_newton
+        route = self._gradient_route()
+        c = self.ctx
+        n = max(1, len(self._train_y))
+        self.fit_info = None
+        if self.max_iter <= 0:
+            return []
+
+        def push(theta):
+            with torch.no_grad():
+                for _, p, a, b in route:
+                    p.copy_(torch.from_numpy(np.array(theta[a:b], dtype=np.float64)).reshape(p.shape))
+            self.sync_hypers()
+
+        def value_and_grad(theta):
+            push(theta)
+            mll, g = c.fit_step()            # raises LinAlgError (ALGP_ERR_NOT_PD) where S has no factor: a rejected trial
+            if disp:
+                print(-mll / n)
+            return mll, g
+
+        theta0 = np.concatenate([p.detach().double().reshape(-1).numpy() for _, p, _, _ in route])
+        theta, info = ai_newton(theta0, value_and_grad, lambda theta: c.mll_ai(), free=self._learned(route),
+                                max_evaluations=self.max_iter, n=n)
+        push(theta)                          # (the last trial may have been a rejected one)
+        self.fit_info = info
+        losses = [-m / n for m in info['trace']]
+        print('Initial LogLikelihood {:.3f} Final LogLikelihood {:.3f}'.format(-losses[0], -losses[-1]))
+        return losses
+
+    def hyper_covariance(self):
+        """(names, cov): the inverse of the average-information matrix of the MLL (algp_get_mll_ai) restricted to the learned
+        parameters, at the current hyper-parameters and train data -- one fit step and one AI matrix on the device, after
+        either fit method.  names: the named_parameters names in the gradient's order, one per scalar ('...[d]' for entry d of
+        a lengthscale vector).  The parameters are the LOG lengthscales, outputscales and noise.  This is the asymptotic
+        covariance of the estimates only at a stationary point of the MLL (a converged fit: fit_info['reason'] == 'gradient');
+        anywhere else it is just the inverse curvature there."""
+        if self.model is None:
+            raise ValueError('hyper_covariance: fit or reset the model first')
+        route = self._gradient_route()
+        self._load_train_on_device()
+        self.ctx.fit_step(want_grad=False)
+        ai = self.ctx.mll_ai()
+        keep = self._learned(route)
+        names = self._scalar_names(route)
+        return [names[k] for k in keep], np.linalg.inv(ai[np.ix_(keep, keep)])
+
+    def hyper_standard_errors(self):
+        """{name: standard error} of the learned log hyper-parameters: the square roots of hyper_covariance()'s diagonal (and
+        with its caveat: at a stationary point only)."""
+        names, cov = self.hyper_covariance()
+        return dict(zip(names, np.sqrt(np.diag(cov))))
+
+    def heritability(self):
+        """(h2, se) under the genotype kernel: h2 = gbar os_g / (gbar os_g + os_a + sigma_n^2) with gbar the mean diagonal of
+        the relationship matrix, and its delta-method standard error from hyper_covariance() (utils.heritability)."""
+        if self.model is None or self.model.relationship is None:
+            raise ValueError("heritability needs kernel_params['type'] = 'genotype'")
+        from .utils import heritability
+        G, _ = self.model.relationship
+        names, cov = self.hyper_covariance()
+        _, los, ln, _ = self.hypers()
+        at = [names.index('kernel_covar_module.kernels.0.log_outputscale'), names.index('kernel_covar_module.kernels.1.log_outputscale')]
+        if self.learn_likelihood_noise:
+            at.append(names.index('likelihood.log_noise'))
+        return heritability(los[0], los[1], ln, 1.0 if G is None else float(np.mean(np.diag(G))), cov[np.ix_(at, at)])
+
     def fit(self, x, y, var=None, disp=False):
         if var is None:
             var = np.full(len(y), 1e-5)                                           # models.py:138-139
         self.reset(x, y, var)
         self._load_train_on_device()
+        if self.fit_method == 'ai':
+            return self._fit_ai(disp)
         named = dict(self.model.named_parameters())
         p_n = named['likelihood.log_noise']
-        if self.model.relationship is not None:
-            # the D + 2 gradient: [log ls of the D - 1 spatial coordinates | log os_a, log os_g | log noise]
-            p = named['kernel_covar_module.kernels.0.base_kernel.log_lengthscale']
-            at = p.numel()
-            route = [(p, 0, at), (named['kernel_covar_module.kernels.0.log_outputscale'], at, at + 1),
-                     (named['kernel_covar_module.kernels.1.log_outputscale'], at + 1, at + 2), (p_n, at + 2, at + 3)]
-        elif self.model.split is not None:
-            # the D + 3 gradient: [log ls in coordinate order | log os_a, log os_b | log noise]
-            route = []
-            at = 0
-            for k in (0, 1):
-                p = named['kernel_covar_module.kernels.%d.base_kernel.log_lengthscale' % k]
-                route.append((p, at, at + p.numel()))
-                at += p.numel()
-            for k in (0, 1):
-                route.append((named['kernel_covar_module.kernels.%d.log_outputscale' % k], at + k, at + k + 1))
-            route.append((p_n, at + 2, at + 3))
+        if self.model.relationship is not None or self.model.split is not None:
+            route = [(p, a, b) for _, p, a, b in self._gradient_route()]
         else:
             p_ls = named['kernel_covar_module.base_kernel.log_lengthscale']
             p_os = named['kernel_covar_module.log_outputscale']

@@ -208,6 +208,92 @@ def group_posterior(gp, train_x, train_y, test_x, group, train_var=None, test_va
     return (mean, cov, cross) if return_cross else (mean, cov)
 
 
+def ai_newton(theta0, value_and_grad, information, free=None, max_evaluations=60, gtol=1e-6, n=1):
+    """Maximise a marginal log likelihood by damped Newton steps on its average-information matrix (AI-REML's iteration;
+    Gilmour, Thompson & Cullis 1995).  Pure NumPy: the caller supplies the numbers.
+
+    value_and_grad(theta) -> (MLL, gradient); it may raise numpy.linalg.LinAlgError or return a non-finite MLL where S is not
+    positive definite.  information(theta) -> the AI matrix; it is only ever called for the point value_and_grad was last
+    called for and accepted.  free: the entries of theta that are optimised (indices or a mask; default all) -- the others
+    stay fixed and their rows and columns of AI are dropped.
+
+    From lambda = 1e-2: the trial step is delta = solve(AI + lambda diag(diag AI), g), clipped elementwise to +-2 (log units).
+    A trial whose MLL is finite and larger is accepted: lambda <- max(lambda / 10, 1e-8), and the trial's own gradient and the
+    AI matrix at it are taken, so no point is evaluated twice.  Any other trial is rejected: lambda <- 10 lambda, again from the
+    same point.  AI is positive semi-definite, so every step is an ascent direction.  It ends with reason 'gradient' when
+    max|g_free| / n < gtol, 'stalled' when lambda passes 1e8, or 'max_evaluations' (calls of value_and_grad, the first included).
+
+    Returns (theta, info): info has evaluations, iterations (accepted steps), reason, mll, grad_max (max|g_free| / n), damping
+    (the last lambda) and trace (the MLL at the start and at every accepted point)."""
+    theta = np.array(theta0, dtype=np.float64).reshape(-1)
+    P = len(theta)
+    if free is None:
+        free = np.arange(P)
+    else:
+        free = np.asarray(free)
+        free = np.flatnonzero(free) if free.dtype == bool else free.astype(np.int64).reshape(-1)
+    f, g = value_and_grad(theta.copy())
+    if not np.isfinite(f):
+        raise np.linalg.LinAlgError('ai_newton: the MLL is not finite at the initial parameters')
+    g = np.asarray(g, dtype=np.float64)
+    A = np.asarray(information(theta.copy()), dtype=np.float64)
+    evaluations, iterations, lam, trace = 1, 0, 1e-2, [float(f)]
+    while True:
+        grad_max = float(np.max(np.abs(g[free]))) / n if len(free) else 0.0
+        if grad_max < gtol:
+            reason = 'gradient'
+            break
+        if lam > 1e8:
+            reason = 'stalled'
+            break
+        if evaluations >= max_evaluations:
+            reason = 'max_evaluations'
+            break
+        Af = A[np.ix_(free, free)]
+        try:
+            delta = np.linalg.solve(Af + lam * np.diag(np.diag(Af)), g[free])
+        except np.linalg.LinAlgError:
+            delta = None
+        if delta is None or not np.all(np.isfinite(delta)):
+            lam *= 10.0                                        # a singular damped matrix: more damping, nothing to evaluate
+            continue
+        trial = theta.copy()
+        trial[free] += np.clip(delta, -2.0, 2.0)
+        evaluations += 1
+        try:
+            ft, gt = value_and_grad(trial.copy())
+        except np.linalg.LinAlgError:                          # S is not positive definite there: a rejected trial
+            ft, gt = np.nan, None
+        if np.isfinite(ft) and ft > f:
+            theta, f, g = trial, ft, np.asarray(gt, dtype=np.float64)
+            A = np.asarray(information(theta.copy()), dtype=np.float64)
+            lam = max(lam / 10.0, 1e-8)
+            iterations += 1
+            trace.append(float(f))
+        else:
+            lam *= 10.0
+    return theta, dict(evaluations=evaluations, iterations=iterations, reason=reason, mll=float(f), grad_max=grad_max,
+                       damping=lam, trace=trace)
+
+
+def heritability(log_os_a, log_os_g, log_noise, gbar, cov3):
+    """(h2, se) under the relationship kernel: h2 = gbar os_g / (gbar os_g + os_a + sigma_n^2), gbar the mean of diag G (1 for
+    the identity table), with the delta-method standard error on the log parameters: d = dh2/d(log os_a, log os_g,
+    log sigma_n^2) = (-h2 os_a / tot, h2 (1 - h2), -h2 sigma_n^2 / tot), se = sqrt(d' C d).  cov3 = C is the block of those
+    three parameters of the INVERSE of the whole average-information matrix (the marginal covariance, not the inverse of the
+    block); 2 x 2 -- (log os_a, log os_g) -- where the noise was not learned."""
+    osa, osg, s2 = np.exp(log_os_a), np.exp(log_os_g), np.exp(log_noise)
+    tot = gbar * osg + osa + s2
+    h2 = gbar * osg / tot
+    d = np.array([-h2 * osa / tot, h2 * (1.0 - h2), -h2 * s2 / tot])
+    C = np.asarray(cov3, dtype=np.float64)
+    if C.shape == (2, 2):
+        d = d[:2]
+    elif C.shape != (3, 3):
+        raise ValueError('heritability: cov3 must be 3 x 3 (2 x 2 with the noise not learned), got %s' % (C.shape,))
+    return float(h2), float(np.sqrt(max(d @ C @ d, 0.0)))
+
+
 def compute_mae(true, pred):
     return np.mean(np.abs(true - pred))                        # utils.py:227-228
 

@@ -189,6 +189,19 @@ int algp_get_mll(algp_ctx* ctx, double* mll);                /* -1/2 y0'alpha - 
  * log_outputscale_b, log_noise); lengthscale entry d belongs to the part that owns coordinate d.  The same holds for
  * algp_fit_step.  Every sum is a fixed-order sum of per-workgroup partials: the same bits in every run.       */
 int algp_get_mll_grad(algp_ctx* ctx, double* grad_out);
+/* The average-information matrix of the MLL (Gilmour, Thompson & Cullis 1995; what AI-REML iterates on), in algp_get_mll_grad's
+ * parameters and order under the kernel in force (P = D+2 | D+3 additive | D+2 relationship):
+ *   ai_out[a * P + b] = 1/2 alpha' dS/dtheta_a S^-1 dS/dtheta_b alpha,   alpha = S^-1 (y - ybar),
+ * P x P host doubles, row-major.  dS/dtheta per pair as for the gradient: the noise entry is sigma_n^2 E alpha with E_ij = 1
+ * where rows i and j are the same pool site; the per-point var is no parameter; the relationship form's id coordinate has no
+ * entry.  Positive semi-definite by construction, so (AI + lambda diag AI)^-1 grad is an ascent direction: the curvature of a
+ * Newton fit and, inverted at a stationary point, the covariance of the estimates.  Costs one pass over the N^2 pairs, one
+ * triangular solve of P right-hand sides and a P x P Gram product beside the factorisation's N^3.
+ * Needs a coordinate pool (ALGP_ERR_BAD_ARG with an explicit covariance or ai_out == NULL) and a current factorisation
+ * (ALGP_ERR_STATE).  Brings alpha up to date and writes nothing else of the resident state (factor, z, log det, a candidate
+ * solve and its picks, the criteria's state).  Every sum has one order and both triangles come from one value: the same bits
+ * in every call, ai_out[a * P + b] == ai_out[b * P + a].  ALGP_ERR_OOM (with the byte count) when its scratch does not fit.   */
+int algp_get_mll_ai(algp_ctx* ctx, double* ai_out);
 /* The device work of ONE iteration of GPR.fit (models.py:145-158: output = model(train_x); loss = -mll(output, train_y);
  * loss.backward()) in one call, for the current hyper-parameters and train set: = algp_factorize + algp_get_mll +
  * algp_get_mll_grad with the same values, but L^-T comes out of the launch that factors S (the identity rides along as a

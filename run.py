@@ -43,6 +43,9 @@ def run_demo(args):
         print('genotype   fitted effect  (sd)     simulated')
         for q in range(len(mean)):
             print('{:8d}   {:+.4f}  ({:.4f})   {:+.4f}'.format(q, mean[q] - mean.mean(), np.sqrt(max(var[q], 0.0)), sim[q]))
+        if args.fit_method == 'ai':
+            h2, se = agent.gp.heritability()
+            print('heritability h2 = {:.3f} +- {:.3f}'.format(h2, se))
     return errors
 
 
