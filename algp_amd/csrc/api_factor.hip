@@ -127,6 +127,10 @@ bool Impl<T>::vt_rows_for_new_sites(algp_ctx* c, int64_t Nb, int64_t p0, std::ve
             lrow[(size_t)(i - p0)] = k;
             lscale[(size_t)(i - p0)] = (T)c->train_var_host[k];
             any_second = true;
+        } else if (c->pos_in_train[q] < Nb) {
+            // predictive semantics: V^T holds no unit rows, and the ordinary row of a site that already is a train row
+            // k < Nb lacks the sigma_n^2 the two rows of one site share at column k: solve instead
+            return false;
         }
         src_row[(size_t)(i - p0)] = j;
     }
@@ -190,6 +194,9 @@ int Impl<T>::exchange_new_rows(algp_ctx* c, int64_t Nb, int64_t p0, int* placed,
                 lrow[(size_t)slot[(size_t)i]] = k;
                 lscale[(size_t)slot[(size_t)i]] = (T)c->train_var_host[(size_t)k];
                 second = true;
+            } else if (c->pos_in_train[(size_t)q] < Nb) {
+                ok = false;                                              // (vt_rows_for_new_sites: no unit row to correct it with)
+                break;
             }
             src_row[(size_t)slot[(size_t)i]] = j;
         }
