@@ -63,6 +63,12 @@ SIGNATURES = {
     'algp_get_mll': (C.c_int, [_c_ctx, _dblp]),
     'algp_get_mll_grad': (C.c_int, [_c_ctx, _dblp]),
     'algp_get_mll_ai': (C.c_int, [_c_ctx, _dblp]),
+    'algp_set_fixed_effects': (C.c_int, [_c_ctx, _dblp, C.c_int64, C.c_int]),
+    'algp_get_gls': (C.c_int, [_c_ctx, _dblp, _dblp, _dblp]),
+    'algp_get_posterior_fixed': (C.c_int, [_c_ctx, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'algp_get_reml_grad': (C.c_int, [_c_ctx, _dblp]),
+    'algp_get_reml_ai': (C.c_int, [_c_ctx, _dblp]),
+    'algp_reml_step': (C.c_int, [_c_ctx, _dblp, _dblp]),
     'algp_fit_step': (C.c_int, [_c_ctx, _dblp, _dblp]),
     'algp_set_candidates': (C.c_int, [_c_ctx, _i64p, C.c_int64, C.c_int, C.c_void_p]),
     'algp_solve_candidates': (C.c_int, [_c_ctx]),
@@ -436,6 +442,64 @@ class Context(object):
         mi = C.c_double()
         self._check(self.lib.algp_get_posterior_cov(self.h, _ptr(cov), C.byref(mi) if want_mi else None))
         return cov, (mi.value if want_mi else None)
+
+    # -- fixed effects ---------------------------------------------------------
+    def set_fixed_effects(self, H):
+        """Attach the fixed effects' basis: H (n_pool, p), one row of basis values per pool site, 1 <= p <= 16; None detaches
+        (algp_set_fixed_effects).  A new pool drops it."""
+        if H is None:
+            self._check(self.lib.algp_set_fixed_effects(self.h, None, 0, 0))
+            self.fixed_p = 0
+            return
+        H = np.ascontiguousarray(H, dtype=np.float64)
+        if H.ndim != 2:
+            raise ValueError('H must be (n_pool, p)')
+        self._check(self.lib.algp_set_fixed_effects(self.h, H.ctypes.data_as(_dblp), H.shape[0], H.shape[1]))
+        self.fixed_p = H.shape[1]
+
+    def gls(self, want_cov=True, want_reml=True):
+        """(beta, cov, reml): the generalised-least-squares estimate of the fixed effects, its (p, p) covariance
+        (H_A' S^-1 H_A)^-1 and the restricted log-likelihood (algp_get_gls); None for what is not asked for.  Raises
+        LinAlgError (.pivot = the 1-based column) when the basis at the train sites is rank-deficient."""
+        p = getattr(self, 'fixed_p', 0) or 16
+        beta = np.empty(p, dtype=np.float64)
+        cov = np.empty((p, p), dtype=np.float64) if want_cov else None
+        v = C.c_double()
+        self._check(self.lib.algp_get_gls(self.h, beta.ctypes.data_as(_dblp), None if cov is None else cov.ctypes.data_as(_dblp),
+                                          C.byref(v) if want_reml else None))
+        return beta, cov, (v.value if want_reml else None)
+
+    def posterior_fixed(self, want_var=True, want_proj=False):
+        """(mu, var, proj) at the candidates with the estimated trend (algp_get_posterior_fixed): the universal-kriging mean
+        and variance, and the (M, p) rows R_j C with cov = posterior_cov + proj proj'; None for what is not asked for."""
+        p = getattr(self, 'fixed_p', 0) or 16
+        mu = np.empty(self.M, dtype=self.dtype)
+        var = np.empty(self.M, dtype=self.dtype) if want_var else None
+        proj = np.empty((self.M, p), dtype=self.dtype) if want_proj else None
+        self._check(self.lib.algp_get_posterior_fixed(self.h, _ptr(mu), _ptr(var), _ptr(proj)))
+        return mu, var, proj
+
+    def reml_grad(self):
+        """d l_R / d theta in mll_grad's parameters and order (algp_get_reml_grad); not divided by N."""
+        g = np.empty(self._n_grad(), dtype=np.float64)
+        self._check(self.lib.algp_get_reml_grad(self.h, g.ctypes.data_as(_dblp)))
+        return g
+
+    def reml_ai(self):
+        """The (P, P) average-information matrix of the restricted likelihood in mll_grad's parameter order
+        (algp_get_reml_ai): AI_R,ab = 1/2 alpha_R' dS/dtheta_a P dS/dtheta_b alpha_R."""
+        n = self._n_grad()
+        ai = np.empty((n, n), dtype=np.float64)
+        self._check(self.lib.algp_get_reml_ai(self.h, ai.ctypes.data_as(_dblp)))
+        return ai
+
+    def reml_step(self, want_reml=True, want_grad=True):
+        """(l_R, grad): fit_step for the restricted likelihood of the attached fixed effects (algp_reml_step)."""
+        g = np.empty(self._n_grad(), dtype=np.float64) if want_grad else None
+        v = C.c_double()
+        self._check(self.lib.algp_reml_step(self.h, C.byref(v) if want_reml else None,
+                                            g.ctypes.data_as(_dblp) if want_grad else None))
+        return (v.value if want_reml else None), g
 
     def last_jitter(self):
         """Diagonal jitter the last posterior_cov(want_mi=True) needed (0.0: none); see algp_last_jitter."""

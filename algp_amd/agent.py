@@ -96,7 +96,9 @@ class Agent(object):
         self.gp = GPR(latent=args.latent, lr=args.lr, max_iterations=args.max_iterations,
                       kernel_params=kernel_params, learn_likelihood_noise=self.learn_likelihood_noise,
                       dtype=getattr(args, 'dtype', np.float64), device=getattr(args, 'device', 0),
-                      fit_method=getattr(args, 'fit_method', 'adam'))
+                      fit_method=getattr(args, 'fit_method', 'adam'),
+                      fixed_effects={'none': None}.get(getattr(args, 'fixed_effects', None), getattr(args, 'fixed_effects', None)),
+                      fit_objective=getattr(args, 'fit_objective', 'mll'))
 
     def load_model(self, parent_agent):
         self.gp.reset(parent_agent.gp.train_x, parent_agent.gp.train_y, parent_agent.gp.train_var)

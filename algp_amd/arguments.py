@@ -19,6 +19,12 @@ def get_parser():
     p.add_argument('--fit_method', default='adam', choices=['adam', 'ai'],
                    help="GPR.fit: the reference's Adam loop, or damped Newton steps on the average-information matrix "
                         '(--max_iterations then caps the MLL evaluations)')
+    p.add_argument('--fixed_effects', default='none', choices=['none', 'intercept', 'linear'],
+                   help='fixed effects of the mean, estimated by generalised least squares: the constant, or the constant and '
+                        'a linear trend in every coordinate (predictions then carry the trend and its uncertainty)')
+    p.add_argument('--fit_objective', default='mll', choices=['mll', 'reml'],
+                   help="GPR.fit's objective: the marginal likelihood of y - mean(y), or the restricted likelihood of the fixed "
+                        "effects (with --fixed_effects none: of the intercept)")
     p.add_argument('--data_file', default=None)
     p.add_argument('--phenotype', default='plant_height')
     p.add_argument('--kernel', default='matern', choices=['rbf', 'matern', 'additive', 'genotype'])

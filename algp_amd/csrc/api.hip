@@ -606,7 +606,7 @@ void algp_destroy(algp_ctx* c) {
     DevBuf* bufs[] = {&c->Xs, &c->Xraw, &c->Cp, &c->Aidx, &c->yA, &c->varA, &c->y0, &c->L, &c->invD, &c->z, &c->alpha,
                       &c->scal, &c->Cidx, &c->ckind, &c->cextra, &c->Vt, &c->dstat, &c->mu, &c->alive, &c->scores,
                       &c->lrow, &c->remote, &c->commbuf, &c->tvec, &c->amax, &c->prevrows, &c->fresh, &c->lazypicks, &c->yraw, &c->uvec, &c->wvec, &c->acc3, &c->rowstat, &c->inv512, &c->inv512_scr, &c->trsm_tmp, &c->gemm_part, &c->rhs_rx, &c->rhs_cx, &c->rhs_rk, &c->splitk, &c->dag_state, &c->dag_stats, &c->trsv_ctrl, &c->auxA, &c->auxInv, &c->auxW, &c->auxIdx,
-                      &c->auxVar, &c->auxD, &c->hostStage, &c->rowx, &c->tailE, &c->tailPart, &c->ldpart, &c->tw, &c->smp, &c->grp, &c->Gtab, &c->Gprior, &c->gen, &c->ai};
+                      &c->auxVar, &c->auxD, &c->hostStage, &c->rowx, &c->tailE, &c->tailPart, &c->ldpart, &c->tw, &c->smp, &c->grp, &c->Gtab, &c->Gprior, &c->gen, &c->ai, &c->fxH, &c->fx};
     for (DevBuf* b : bufs) release(c, *b);
     release(c, c->mi);
     release(c, c->vr);
@@ -747,6 +747,7 @@ int algp_set_pool(algp_ctx* c, const void* x, int64_t n) {
     c->site_owner.clear();                                   // the owner map belongs to the pool it was given for (re-attach it: algp_comm_set_owners)
     c->site_owner_hash = 0;
     c->has_tw = false;                                       // and so do the target weights (algp_set_target_weights)
+    c->fx_p = 0;                                             // and the fixed effects' basis (algp_set_fixed_effects)
     c->vr.drop();
     FINISH(c, DISPATCH(c, set_pool(c, x, n)));
 }
@@ -762,6 +763,7 @@ int algp_set_pool_cov(algp_ctx* c, const void* cov, int64_t n) {
     c->site_owner.clear();                                   // the owner map belongs to the pool it was given for (re-attach it: algp_comm_set_owners)
     c->site_owner_hash = 0;
     c->has_tw = false;                                       // and so do the target weights (algp_set_target_weights)
+    c->fx_p = 0;                                             // and the fixed effects' basis (algp_set_fixed_effects)
     c->vr.drop();
     FINISH(c, DISPATCH(c, set_pool_cov(c, cov, n)));
 }

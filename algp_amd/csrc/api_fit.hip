@@ -102,8 +102,8 @@ int Impl<T>::mll_ai(algp_ctx* c, double* ai_out) {
 // triangular-aware launch, the pairwise gradient reduction.  Same values as algp_factorize + algp_get_mll +
 // algp_get_mll_grad (tested); N^3 flop in all (N^3/3 each for the factor, the inverse of the factor and the product).
 template <typename T>
-int Impl<T>::fit_step(algp_ctx* c, double* mll_out, double* grad_out) {
-    if (c->pool_is_cov) return fail(c, ALGP_ERR_BAD_ARG, "fit_step needs a coordinate pool");
+int Impl<T>::fit_step(algp_ctx* c, double* mll_out, double* grad_out, bool reml) {
+    if (c->pool_is_cov) return fail(c, ALGP_ERR_BAD_ARG, reml ? "reml_step needs a coordinate pool" : "fit_step needs a coordinate pool");
     const int64_t Npad = c->Npad;
     bool inv_enq = false;
     // Round 5: z rides along too (a dense tile row behind the identity that carries y - ybar), and alpha = X z is one pass
@@ -131,9 +131,14 @@ int Impl<T>::fit_step(algp_ctx* c, double* mll_out, double* grad_out) {
     } else {
         ALGP_TRY(factorize(c, 0));
     }
-    if (mll_out) *mll_out = -0.5 * c->yalpha - 0.5 * c->logdet - 0.5 * (double)c->N * 1.8378770664093453;
+    if (reml && !grad_out) {                                     // the value alone: the GLS read-out on the new factor
+        double beta[FX_P];
+        return mll_out ? get_gls(c, beta, nullptr, mll_out) : ALGP_OK;
+    }
+    if (mll_out && !reml) *mll_out = -0.5 * c->yalpha - 0.5 * c->logdet - 0.5 * (double)c->N * 1.8378770664093453;
     if (!grad_out) return ALGP_OK;
-    const int grc = mll_grad(c, grad_out, have_X, inv_enq);
+    // algp_reml_step: the same launch, then the restricted likelihood's tail (api_fixed.hip) on the X and S^-1 it leaves
+    const int grc = reml ? reml_grad(c, grad_out, mll_out, have_X, inv_enq) : mll_grad(c, grad_out, have_X, inv_enq);
     if (grc != ALGP_OK && inv_enq) hipStreamSynchronize(c->stream2);
     return grc;
 }

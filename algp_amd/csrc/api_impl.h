@@ -4,7 +4,8 @@
 // picks, the sharded exchange), api_mi.hip (the MI criterion's state, on one GPU and over the ranks), api_vr.hip (the
 // variance-reduction criterion), api_paths.hip (best_path block scoring), api_paths_vr.hip (the variance-reduction utility of
 // whole paths), api_fit.hip (MLL gradient, one fit iteration, the average-information matrix), api_sample.hip (joint posterior draws),
-// api_group.hip (the joint posterior of group aggregates), api_genotype.hip (the genotype effects under the relationship form).
+// api_group.hip (the joint posterior of group aggregates), api_genotype.hip (the genotype effects under the relationship form),
+// api_fixed.hip (fixed effects: the GLS estimates and the posterior with an estimated trend).
 // Every file defines its members of Impl<T> and instantiates Impl<float> / Impl<double> for them.
 #pragma once
 #include <limits.h>
@@ -209,7 +210,26 @@ struct Impl {
     static int score_paths_vr(algp_ctx* c, const int64_t* sites, int npaths, int maxlen, double mobile_std, int64_t max_union, double* dV);
     static int mll_grad(algp_ctx* c, double* grad_out, bool have_X = false, bool inv_enqueued = false);
     static int mll_ai(algp_ctx* c, double* ai_out);
-    static int fit_step(algp_ctx* c, double* mll_out, double* grad_out);
+    static int fit_step(algp_ctx* c, double* mll_out, double* grad_out, bool reml = false);   // reml: the restricted likelihood's (algp_reml_step)
+    // fixed effects (api_fixed.hip): the basis to the device; F^T, its Gram product and the p x p work (enqueued, no sync);
+    // the GLS estimates; the candidates' posterior with the estimated trend
+    static int set_fixed_effects(algp_ctx* c, const double* H, int p);
+    struct FixedPlan {
+        T* Ft; double* gram; double* gls; T* mu; T* var; T* proj;
+        T* aR;                       // fit: alpha_R (Npad)
+        T* panel;                    // fit: a second 128 x Npad panel ((F C)^T, then the AI's U -> V)
+        T* Gt;                       // fit, with the gradient: G^T (128 x Npad)
+        double* gram2;               // fit: the AI's products
+    };
+    // what a call needs of the scratch beyond F^T, the Gram product and the p x p work
+    struct FixedWants { int64_t post_rows = 0; bool proj = false, fit = false, grad = false; };
+    static int fixed_enqueue(algp_ctx* c, const char* who, const FixedWants& w, FixedPlan& pl);
+    static int fixed_alpha_r(algp_ctx* c, FixedPlan& pl);
+    static int get_gls(algp_ctx* c, double* beta_out, double* cov_out, double* reml_out);
+    static int get_posterior_fixed(algp_ctx* c, void* mu_out, void* var_out, void* proj_out);
+    // the restricted likelihood's gradient (have_X / inv_enqueued: mll_grad's), its value with it; its average information
+    static int reml_grad(algp_ctx* c, double* grad_out, double* reml_out, bool have_X = false, bool inv_enqueued = false);
+    static int reml_ai(algp_ctx* c, double* ai_out);
     static int get_alpha(algp_ctx* c, void* out);
     static int get_factor(algp_ctx* c, void* out);
     static int selftest(algp_ctx* c, int* mism);

@@ -33,6 +33,17 @@ constexpr int SC_STALL = 12;     // int, sticky: a one-launch kernel with inter-
 constexpr int SC_GRAD = 16;      // 16..27: partial sums of the MLL gradient
 constexpr int SC_COUNT = 32;
 
+// fixed effects (fixed.hip): the basis is held zero-padded to FX_P columns; the slots (doubles) of fixed_gls_small's output
+constexpr int FX_P = 16;
+constexpr int FX_BETA = 0;                 // beta, FX_P entries
+constexpr int FX_C = FX_P;                 // C (FX_P x FX_P, upper, zero-padded): A^-1 = C C^T
+constexpr int FX_COV = FX_C + FX_P * FX_P; // C C^T, p x p
+constexpr int FX_LOGDET_A = FX_COV + FX_P * FX_P;
+constexpr int FX_QUAD = FX_LOGDET_A + 1;   // b' beta
+constexpr int FX_ZZ = FX_QUAD + 1;         // z'z
+constexpr int FX_INFO = FX_ZZ + 1;         // 0, or the 1-based column of H_A that is in the span of the ones before it
+constexpr int FX_OUT = FX_INFO + 5;
+
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
@@ -485,6 +496,8 @@ struct algp_ctx {
     algp::DevBuf tw;        // target weight of every pool site in the context's dtype (algp_set_target_weights), while has_tw
     bool has_tw = false;    // the weights belong to their pool: a new pool drops them
     uint64_t tw_hash = 0;   // FNV-1a of the weights as attached (while has_tw): ranks scoring together must hold the same ones
+    algp::DevBuf fxH;       // the fixed effects' basis (algp_set_fixed_effects): n_pool x FX_P in the context's dtype, zero-padded, while fx_p > 0
+    int fx_p = 0;           // its columns; 0: none attached.  The basis belongs to its pool: a new pool drops it
     std::vector<int64_t> pos_in_train;   // host: pool index -> position in train set or -1
     std::vector<uint64_t> site_hash;     // host: fingerprint of every pool site's coordinates (algp_factorize_from)
 
@@ -599,6 +612,7 @@ struct algp_ctx {
     // algp_genotype_posterior's scratch, one allocation carved up per call (api_genotype.hip)
     algp::DevBuf Gtab, Gprior, gen;
     algp::DevBuf ai;                     // algp_get_mll_ai's scratch: the 128 x Npad panel U -> V and the P x P result (api_fit.hip)
+    algp::DevBuf fx;                     // the fixed effects' scratch, one allocation carved up per call (api_fixed.hip)
     uint64_t gprior_stamp = 0;          // Gprior holds the priors for this hyp_stamp and gprior_noise (prior_includes_noise)
     int gprior_noise = -1;
 

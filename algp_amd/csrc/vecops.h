@@ -194,6 +194,27 @@ template <typename T>
 int mll_ai_u_launch(algp_ctx* c, int64_t N, int64_t Npad, const int64_t* aidx, const T* alpha, const KmatSrc& s, int nl, T* U);
 template <typename T>
 int mll_ai_gram_launch(algp_ctx* c, const T* V, int64_t ld, int64_t N, int P, double* out);
+// fixed effects (fixed.hip): the 16 x Npad panel of F^T's right-hand sides (column a of H at the train sites); the (p + 1)^2 Gram
+// product of F^T's rows and z in double; the p x p work by one thread (out: the FX_* slots of common.h); the posterior pass over V^T
+template <typename T>
+int fixed_gather_launch(algp_ctx* c, const T* H, const int64_t* aidx, int64_t N, int64_t Npad, T* Pn);
+template <typename T>
+int fixed_gram_launch(algp_ctx* c, const T* Ft, int64_t ld, const T* z, int64_t N, int p, double* out);
+int fixed_gls_launch(algp_ctx* c, const double* g, int p, double tol, double* out);
+template <typename T>
+int fixed_post_launch(algp_ctx* c, const T* Vt, int64_t ldv, int64_t M, int64_t ncols, const T* Ft, int64_t ldf, const T* H,
+                      const int64_t* cidx, const double* gls, int p, const T* mu_in, const T* var_in, T* mu_out, T* var_out, T* proj_out);
+// the restricted likelihood's gradient and average information (fixed.hip): the rows of (F C)^T; w = z - F beta (alpha_R =
+// L^-T w); S^-1 -> P = S^-1 - G G^T on the entries j <= i < N mll_grad_launch reads (Gt = G^T, FX_P x ldg); out[r (P + p) + s] =
+// V's row r . (V's row s | Ft's row s - P)
+template <typename T>
+int fixed_fc_launch(algp_ctx* c, const T* Ft, int64_t npad, const double* gls, T* FCt);
+template <typename T>
+int fixed_resid_launch(algp_ctx* c, const T* Ft, int64_t npad, int64_t N, const T* z, const double* gls, T* w);
+template <typename T>
+int fixed_downdate_launch(algp_ctx* c, T* Sinv, int64_t ld, int64_t N, const T* Gt, int64_t ldg, int p);
+template <typename T>
+int fixed_gram2_launch(algp_ctx* c, const T* V, const T* Ft, int64_t ld, int64_t N, int P, int p, double* out);
 // the relationship form's gathers from its table (fit.hip): B[q][i] = os_g G[q, g_i] (Qpad x Npad, zero padded), the prior
 // variance os_a + os_g G[g_j, g_j] of every pool site, and the two last steps of algp_genotype_posterior
 template <typename T>

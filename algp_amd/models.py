@@ -32,7 +32,12 @@ What differs, deliberately:
   * GPR(..., fit_method='ai') fits by damped Newton steps on the average-information matrix of the MLL instead (utils.ai_newton,
     algp_get_mll_ai: tens of device steps, not hundreds); after either method hyper_covariance / hyper_standard_errors give the
     covariance and standard errors of the log hyper-parameters and, under the genotype kernel, heritability gives h2 with its
-    standard error.
+    standard error;
+  * GPR(..., fixed_effects='intercept' | 'linear' | callable) gives the mean a linear part h(x)' beta estimated by generalised
+    least squares (block, replicate and trend terms): predict returns the trend-aware mean and the variance with the
+    universal-kriging term, fixed_effect_estimates the estimates and their covariance; fit_objective='reml' fits either method
+    on the restricted likelihood (algp_reml_step, algp_get_reml_ai), and hyper_covariance, hyper_standard_errors and heritability
+    then use its average information.  Without the two arguments every path is the one it was.
 """
 import numpy as np
 import torch
@@ -171,10 +176,19 @@ class ExactGPModel(nn.Module):
 
 class GPR(object):
     def __init__(self, latent=None, lr=.01, max_iterations=200, kernel_params=None, latent_params=None,
-                 learn_likelihood_noise=True, dtype=np.float64, device=0, fit_method='adam'):
+                 learn_likelihood_noise=True, dtype=np.float64, device=0, fit_method='adam', fixed_effects=None,
+                 fit_objective='mll'):
         if fit_method not in ('adam', 'ai'):
             raise ValueError("fit_method is 'adam' or 'ai', got %r" % (fit_method,))
+        if fit_objective not in ('mll', 'reml'):
+            raise ValueError("fit_objective is 'mll' or 'reml', got %r" % (fit_objective,))
+        if not (fixed_effects is None or fixed_effects in ('intercept', 'linear') or callable(fixed_effects)):
+            raise ValueError("fixed_effects is None, 'intercept', 'linear' or a callable x -> (n, p), got %r" % (fixed_effects,))
+        if fit_objective == 'reml' and fixed_effects is None:
+            fixed_effects = 'intercept'                # REML of the constant mean: one degree of freedom
         self.fit_method = fit_method
+        self.fixed_effects = fixed_effects
+        self.fit_objective = fit_objective
         self.fit_info = None
         self._train_x = None
         self._train_y = None
@@ -275,19 +289,65 @@ class GPR(object):
         if var is not None:
             self._train_var = np.asarray(var, dtype=np.float64).reshape(-1)
 
+    # ---- fixed effects ------------------------------------------------------------------------
+    def fixed_basis(self, x, train_x=None):
+        """The (n, p) basis h(x) of the fixed effects, or None without any: 'intercept' is the constant; 'linear' the constant
+        and every coordinate centred on the train sites' mid-range and scaled by their range (train_x: the stored train
+        inputs by default; the genotype id column is no coordinate); a callable is evaluated on x."""
+        if self.fixed_effects is None:
+            return None
+        x = np.asarray(x, dtype=np.float64)
+        x = x.reshape(len(x), -1)
+        if callable(self.fixed_effects):
+            H = np.asarray(self.fixed_effects(x), dtype=np.float64).reshape(len(x), -1)
+        elif self.fixed_effects == 'intercept':
+            H = np.ones((len(x), 1))
+        else:
+            ref = self._train_x if train_x is None else np.asarray(train_x, dtype=np.float64).reshape(len(train_x), -1)
+            genotype = self.kernel_params is not None and self.kernel_params.get('type') == 'genotype'
+            nc = x.shape[1] - 1 if genotype else x.shape[1]
+            lo, hi = ref[:, :nc].min(0), ref[:, :nc].max(0)
+            H = np.c_[np.ones(len(x)), (x[:, :nc] - 0.5 * (lo + hi)) / np.where(hi > lo, hi - lo, 1.0)]
+        if not 1 <= H.shape[1] <= 16:
+            raise ValueError('fixed_effects: 1 <= p <= 16 basis columns, got %d' % H.shape[1])
+        return H
+
+    def fixed_effect_estimates(self):
+        """(beta, cov beta): the generalised-least-squares estimates of the fixed effects at the current hyper-parameters and
+        their covariance (H' S^-1 H)^-1, from the stored training data (algp_get_gls)."""
+        if self.fixed_effects is None:
+            raise ValueError('fixed_effect_estimates needs fixed_effects')
+        if self.model is None:
+            raise ValueError('fixed_effect_estimates: fit or reset the model first')
+        self._load_train_on_device()
+        self.ctx.factorize()
+        beta, cov, _ = self.ctx.gls(want_reml=False)
+        return beta, cov
+
     # ---- models.py:137-159 ------------------------------------------------------------------
     def _load_train_on_device(self):
         c = self.ctx
         self.sync_hypers()
         c.set_pool(self._train_x)
+        if self.fixed_effects is not None:
+            c.set_fixed_effects(self.fixed_basis(self._train_x))
         c.set_train(np.arange(len(self._train_x)), self._train_y, self._train_var)
 
+    def _objective_step(self, want_value=True, want_grad=True):
+        """One device step of the fit's objective: (MLL, gradient) or, with fit_objective='reml', (l_R, gradient)."""
+        if self.fit_objective == 'reml':
+            return self.ctx.reml_step(want_value, want_grad)
+        return self.ctx.fit_step(want_value, want_grad)
+
+    def _information(self):
+        return self.ctx.reml_ai() if self.fit_objective == 'reml' else self.ctx.mll_ai()
+
     def neg_mll_and_grad(self):
-        """loss = -MLL/N and its gradient w.r.t. the model parameters, from the device."""
+        """loss = -MLL/N (-l_R/N with fit_objective='reml') and its gradient w.r.t. the model parameters, from the device."""
         c = self.ctx
         if self.sync_hypers():
             pass
-        mll, grad = c.fit_step()             # factorisation + MLL + gradient: one ABI call per Adam iteration
+        mll, grad = self._objective_step()   # factorisation + objective + gradient: one ABI call per Adam iteration
         n = max(1, len(self._train_y))
         return -mll / n, -grad / n
 
@@ -341,15 +401,16 @@ class GPR(object):
 
         def value_and_grad(theta):
             push(theta)
-            mll, g = c.fit_step()            # raises LinAlgError (ALGP_ERR_NOT_PD) where S has no factor: a rejected trial
+            mll, g = self._objective_step()  # raises LinAlgError (ALGP_ERR_NOT_PD) where S has no factor: a rejected trial
             if disp:
                 print(-mll / n)
             return mll, g
 
         theta0 = np.concatenate([p.detach().double().reshape(-1).numpy() for _, p, _, _ in route])
-        theta, info = ai_newton(theta0, value_and_grad, lambda theta: c.mll_ai(), free=self._learned(route),
+        theta, info = ai_newton(theta0, value_and_grad, lambda theta: self._information(), free=self._learned(route),
                                 max_evaluations=self.max_iter, n=n)
         push(theta)                          # (the last trial may have been a rejected one)
+        info['objective'] = self.fit_objective
         self.fit_info = info
         losses = [-m / n for m in info['trace']]
         print('Initial LogLikelihood {:.3f} Final LogLikelihood {:.3f}'.format(-losses[0], -losses[-1]))
@@ -366,8 +427,8 @@ class GPR(object):
             raise ValueError('hyper_covariance: fit or reset the model first')
         route = self._gradient_route()
         self._load_train_on_device()
-        self.ctx.fit_step(want_grad=False)
-        ai = self.ctx.mll_ai()
+        self._objective_step(want_grad=False)
+        ai = self._information()             # the restricted likelihood's with fit_objective='reml'
         keep = self._learned(route)
         names = self._scalar_names(route)
         return [names[k] for k in keep], np.linalg.inv(ai[np.ix_(keep, keep)])
@@ -431,6 +492,8 @@ class GPR(object):
         if self.max_iter > 0:
             print('Initial LogLikelihood {:.3f} Final LogLikelihood {:.3f}'.format(initial_ll, final_ll))
         self.sync_hypers()
+        if self.fit_objective == 'reml':
+            self.fit_info = {'objective': 'reml', 'evaluations': len(losses)}
         return losses
 
     # ---- models.py:161-181 ------------------------------------------------------------------
@@ -462,8 +525,21 @@ class GPR(object):
         x = x.reshape(len(x), -1)
         N, M = len(self._train_x), len(x)
         c.set_pool(np.vstack([self._train_x, x]))
+        if self.fixed_effects is not None:
+            c.set_fixed_effects(self.fixed_basis(np.vstack([self._train_x, x])))
         c.set_train(np.arange(N), self._train_y, self._train_var)
         noise = float(np.exp(self.likelihood.log_noise.item()))
+        if self.fixed_effects is not None:
+            # the trend-aware mean, and the variance with the universal-kriging term (algp_get_posterior_fixed)
+            c.set_candidates(np.arange(N, N + M), prior_includes_noise=False)
+            c.fit_and_solve()
+            mu, var, proj = c.posterior_fixed(want_var=return_std, want_proj=return_cov and not return_std)
+            if return_std:
+                return mu, var + self.dtype.type(noise)
+            if not return_cov:
+                return mu
+            cov, _ = c.posterior_cov()
+            return mu, cov + proj @ proj.T + self.dtype.type(noise) * np.eye(M, dtype=self.dtype)
         if not (return_std or return_cov):
             c.factorize()
             return c.posterior_mean(np.arange(N, N + M))

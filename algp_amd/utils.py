@@ -50,8 +50,23 @@ def predictive_distribution(gp, train_x, train_y, test_x, train_var=None, test_v
     test_x = test_x.reshape(len(test_x), -1)
     N, M = len(train_x), len(test_x)
     c.set_pool(np.vstack([train_x, test_x]))
+    fixed = getattr(gp, 'fixed_effects', None) is not None     # a gp with fixed effects: the trend-aware mean, variance and covariance
+    if fixed:
+        c.set_fixed_effects(gp.fixed_basis(np.vstack([train_x, test_x]), train_x))
     c.set_train(np.arange(N), train_y, train_var)              # mean-centring inside (utils.py:294)
     test_idx = np.arange(N, N + M)
+    if fixed:                                                  # (mi stays the known-mean term)
+        c.set_candidates(test_idx, prior_includes_noise=False, extra_var=test_var)
+        c.fit_and_solve()
+        mu, var, proj = c.posterior_fixed(want_var=return_var, want_proj=return_cov)
+        cov = mi = None
+        if return_cov or return_mi:
+            cov, mi = c.posterior_cov(want_cov=return_cov, want_mi=return_mi)
+            if return_cov:
+                cov = cov + proj @ proj.T
+        if return_cov and return_mi:
+            return mu, cov, mi
+        return (mu, mi) if return_mi else (mu, cov) if return_cov else (mu, var) if return_var else mu
     if not (return_var or return_cov or return_mi):
         c.factorize()                                          # replaces inv(cov_aa), utils.py:300
         return c.posterior_mean(test_idx)                      # mu only: no triangular solve needed

@@ -202,6 +202,51 @@ int algp_get_mll_grad(algp_ctx* ctx, double* grad_out);
  * solve and its picks, the criteria's state).  Every sum has one order and both triangles come from one value: the same bits
  * in every call, ai_out[a * P + b] == ai_out[b * P + a].  ALGP_ERR_OOM (with the byte count) when its scratch does not fit.   */
 int algp_get_mll_ai(algp_ctx* ctx, double* ai_out);
+/* ---- fixed effects: the mean ybar + h(x)' beta, beta estimated by generalised least squares -------------------------------
+ * H[n_pool * p], row-major host doubles: one row of basis values per pool site, 1 <= p <= 16 (block, replicate, trend terms);
+ * kept on the device in the context's dtype, zero-padded to 16 columns.  H == NULL or p == 0 detaches.  The basis belongs to
+ * its pool (of either kind): a new pool drops it, n_pool must match (ALGP_ERR_BAD_ARG, as a non-finite entry; no pool:
+ * ALGP_ERR_STATE).  Nothing resident depends on it: the factor, a candidate solve and the criteria's state stay as they are,
+ * and every entry point but the two below ignores it (the criteria, paths, samples, group and genotype posteriors keep the
+ * known-mean variances).
+ * With H_A the rows of the train sites, S = L L', y0 = y - ybar, z = L^-1 y0:
+ *   F = L^-1 H_A    A = F'F = H_A' S^-1 H_A    b = F'z    beta = A^-1 b    cov beta = A^-1 = C C'  (C = R^-1, A = R'R, R upper)
+ *   l_R = -1/2 [ (N - p) log 2 pi + log|S| + log|A| + z'z - b' beta ]
+ * the restricted log-likelihood in Harville's convention (no + 1/2 log|H_A' H_A|: up to that constant the likelihood of N - p
+ * error contrasts).  With the constant in the span of H every quantity is invariant to ybar.
+ * algp_get_gls: beta_out[p]; cov_out[p * p] and reml_out may be NULL.  Needs a current factorisation and a basis
+ * (ALGP_ERR_STATE); N <= p: ALGP_ERR_BAD_ARG.  F' comes from one blocked triangular solve of a 128-row panel, A, b and z'z
+ * from a Gram product summed in double in one order, the p x p work runs in double on A scaled to a unit diagonal.  A column of
+ * H_A in the span of the columns before it (a scaled pivot <= 64 eps of the context's dtype): ALGP_ERR_NOT_PD,
+ * algp_last_pivot = its 1-based number.
+ * algp_get_posterior_fixed: the candidates of the resident solve (V' = B' L^-T) with the estimated trend,
+ *   R_j = h_j - V_j F    mu_j = mu_j(algp_get_posterior) + R_j beta    var_j = var_j(algp_get_posterior) + |C' R_j|^2
+ * mu_out[M], var_out[M], proj_out[M * p] (row j = R_j C: the covariance is algp_get_posterior_cov's + proj proj') in the
+ * context's dtype, each may be NULL.  One pass over V' on the matrix cores.  Refused with ALGP_ERR_STATE, as
+ * algp_get_posterior_cov refuses and for its reasons: a train site among the candidates under prior_includes_noise = 1 (a unit
+ * row: R_j is not the residual basis), picks committed since the solve; also a solve that is not the current factor's.
+ * Both write nothing resident, return the same bits in every call, synchronise once, and keep their scratch in one buffer of
+ * the context (counted by algp_device_bytes, freed by algp_destroy; ALGP_ERR_OOM with the byte count up front).  After
+ * ALGP_ERR_NOT_PD the outputs are unspecified.                                                                                  */
+int algp_set_fixed_effects(algp_ctx* ctx, const double* H, int64_t n_pool, int p);
+int algp_get_gls(algp_ctx* ctx, double* beta_out, double* cov_out, double* reml_out);
+int algp_get_posterior_fixed(algp_ctx* ctx, void* mu_out, void* var_out, void* proj_out);
+/* The restricted likelihood as a fit objective (REML: the variance components are not biased by the degrees of freedom the
+ * fixed effects consume).  With P = S^-1 - G G', G = S^-1 H_A C = L^-T F C, and alpha_R = P y0 = L^-T (z - F beta):
+ *   d l_R / d theta_a = 1/2 tr((alpha_R alpha_R' - P) dS/dtheta_a)
+ *   AI_R,ab = 1/2 alpha_R' dS_a P dS_b alpha_R = 1/2 [ v_a . v_b - (F'v_a)' A^-1 (F'v_b) ],  v_a = L^-1 dS_a alpha_R
+ * algp_get_reml_grad / algp_get_reml_ai: algp_get_mll_grad's / algp_get_mll_ai's parameters and order under every kernel form,
+ * with repeated sites, and their refusals (a current factorisation: ALGP_ERR_STATE; a coordinate pool: ALGP_ERR_BAD_ARG),
+ * besides those of algp_get_gls.  The gradient runs the MLL gradient's kernel unchanged on (P, alpha_R): S^-1 is turned into P
+ * on the lower triangle by a rank-p downdate (p fused multiply-adds per entry in a fixed order, no atomics).  The AI runs
+ * algp_get_mll_ai's pass with alpha_R and p more rows in its Gram product.  Both bring alpha up to date and write nothing else
+ * resident; the same bits in every call; ai_out is symmetric bit for bit; one synchronisation each.
+ * algp_reml_step: algp_fit_step for l_R -- the factorisation with L^-T and S^-1 out of its launch where algp_fit_step gets
+ * them there, then the tail above; = algp_factorize + algp_get_gls + algp_get_reml_grad with the same values.  reml / grad_out
+ * may each be NULL.                                                                                                              */
+int algp_get_reml_grad(algp_ctx* ctx, double* grad_out);
+int algp_get_reml_ai(algp_ctx* ctx, double* ai_out);
+int algp_reml_step(algp_ctx* ctx, double* reml, double* grad_out);
 /* The device work of ONE iteration of GPR.fit (models.py:145-158: output = model(train_x); loss = -mll(output, train_y);
  * loss.backward()) in one call, for the current hyper-parameters and train set: = algp_factorize + algp_get_mll +
  * algp_get_mll_grad with the same values, but L^-T comes out of the launch that factors S (the identity rides along as a

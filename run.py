@@ -36,6 +36,10 @@ def run_demo(args):
         errors.append(err)
         print('Run {}/{}: picks {} test ERROR {:.4f} predictive variance max {:.3f} min {:.3f} mean {:.3f} ({:.3f}s)'
               .format(i + 1, args.num_runs, picks, err, var.max(), var.min(), var.mean(), time.time() - t0))
+    if agent.gp.fixed_effects is not None:
+        beta, cov = agent.gp.fixed_effect_estimates()
+        print('fixed effects (' + agent.gp.fit_objective + '): ' +
+              '  '.join('{:+.4f} +- {:.4f}'.format(b, s) for b, s in zip(beta, np.sqrt(np.diag(cov)))))
     if args.kernel == 'genotype':
         # the genotype effects themselves, beside the simulated ones (both centred: the constant mean absorbs their average)
         mean, var = agent.gp.genotype_effects()
