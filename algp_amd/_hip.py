@@ -45,6 +45,8 @@ SIGNATURES = {
                                            C.c_double]),
     'algp_set_hypers_relationship': (C.c_int, [_c_ctx, C.c_int, C.c_int, C.c_double, _dblp, C.c_double, _dblp, C.c_int64,
                                                C.c_double]),
+    'algp_set_hypers_separable': (C.c_int, [_c_ctx, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _dblp, C.c_double, _dblp,
+                                            C.c_int64, C.c_double]),
     'algp_genotype_posterior': (C.c_int, [_c_ctx, C.c_void_p, C.c_void_p, C.c_void_p]),
     'algp_kernel_matrix': (C.c_int, [_c_ctx, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int,
                                      C.c_void_p]),
@@ -264,11 +266,45 @@ class Context(object):
         self.relationship = True
         self.Q = Q
 
+    def set_hypers_separable(self, log_lengthscale, split, log_outputscale, log_noise, kernel_a=KERNEL_RBF, kernel_b=KERNEL_RBF,
+                             log_outputscale_g=None, G=None, n_genotypes=None):
+        """The separable kernel os kappa_a(r_a) kappa_b(r_b) [+ os_g G[g, g']] (algp_set_hypers_separable): r_a over the first
+        `split` coordinates, r_b over the other spatial ones; log_lengthscale has one entry per SPATIAL coordinate.  With
+        log_outputscale_g the genotype term is on: the last coordinate of every site is its integer genotype id in [0, Q),
+        G a (Q, Q) symmetric matrix or None for the identity with Q = n_genotypes.  A refusal (ValueError) leaves the
+        hyper-parameters, the table and the pool in force untouched."""
+        ls = np.ascontiguousarray(np.atleast_1d(log_lengthscale), dtype=np.float64)
+        gp, Q, D, log_g = None, 0, len(ls), 0.0
+        if log_outputscale_g is None:
+            if G is not None or n_genotypes is not None:
+                raise ValueError('a relationship matrix or n_genotypes needs log_outputscale_g (the genotype term)')
+        else:
+            if G is not None:
+                G = np.ascontiguousarray(G, dtype=np.float64)
+                if G.ndim != 2 or G.shape[0] != G.shape[1]:
+                    raise ValueError('G must be a square matrix, got shape %s' % (G.shape,))
+                if n_genotypes is not None and int(n_genotypes) != G.shape[0]:
+                    raise ValueError('n_genotypes = %d does not match G of shape %s' % (int(n_genotypes), G.shape))
+                Q = G.shape[0]
+                gp = G.ctypes.data_as(_dblp)
+            elif n_genotypes is None:
+                raise ValueError('pass G or n_genotypes (the identity relationship of that many genotypes)')
+            else:
+                Q = int(n_genotypes)
+            D, log_g = len(ls) + 1, float(log_outputscale_g)
+        self._check(self.lib.algp_set_hypers_separable(self.h, D, int(kernel_a), int(split), int(kernel_b), float(log_outputscale),
+                                                       ls.ctypes.data_as(_dblp), log_g, gp, Q, float(log_noise)))
+        self.D = D
+        self.additive = False
+        self.relationship = Q > 0               # a genotype term is in force: genotype_posterior works
+        self.Q = Q
+
     def genotype_posterior(self, want_var=True, want_cov=False):
         """(mean, var or None, cov or None) of the Q genotype effects under the relationship kernel, in the context's dtype
         (algp_genotype_posterior): BLUPs, prediction-error variances, joint covariance.  Needs a current factorisation."""
         if not getattr(self, 'relationship', False):
-            raise ValueError('genotype_posterior: no relationship kernel is in force (set_hypers_relationship)')
+            raise ValueError('genotype_posterior: no kernel with a genotype term is in force (set_hypers_relationship, '
+                             'set_hypers_separable with log_outputscale_g)')
         mean = np.empty(self.Q, dtype=self.dtype)
         var = np.empty(self.Q, dtype=self.dtype) if want_var else None
         cov = np.empty((self.Q, self.Q), dtype=self.dtype) if want_cov else None
@@ -277,7 +313,7 @@ class Context(object):
 
     def _n_grad(self):
         # D + 2 for a single kernel, D + 3 under the additive one (two outputscales); the relationship kernel: D - 1
-        # lengthscales, two outputscales and the noise, D + 2
+        # lengthscales, two outputscales and the noise, D + 2; the separable kernel: D + 2 with and without its genotype term
         return self.D + (3 if getattr(self, 'additive', False) else 2)
 
     def _check_width(self, x, what):

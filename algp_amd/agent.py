@@ -86,6 +86,10 @@ class Agent(object):
             kernel_params = {'type': 'additive', 'split': getattr(args, 'kernel_split', 2),
                              'parts': ({'type': getattr(args, 'kernel_a', 'matern'), 'nu': nu},
                                        {'type': getattr(args, 'kernel_b', 'rbf'), 'nu': nu})}
+        if args.kernel == 'separable':
+            kernel_params = {'type': 'separable', 'split': getattr(args, 'kernel_split', 2),
+                             'parts': ({'type': getattr(args, 'kernel_a', 'matern'), 'nu': nu},
+                                       {'type': getattr(args, 'kernel_b', 'rbf'), 'nu': nu})}
         if args.kernel == 'genotype':
             # part a's form over the position, a table-valued genotype part over the ids in the last coordinate
             path = getattr(args, 'relationship', None)
@@ -93,6 +97,10 @@ class Agent(object):
             kernel_params = {'type': 'genotype', 'spatial': {'type': getattr(args, 'kernel_a', 'matern'), 'nu': nu},
                              'relationship': G,
                              'n_genotypes': None if G is not None else int(getattr(self.env, 'num_genotypes', 0))}
+            if getattr(args, 'spatial', 'single') == 'separable':
+                # AR1(row) x AR1(col) in the place of the single form over the position: the field-trial literature's spatial model
+                kernel_params['spatial'] = {'type': 'separable', 'split': 1,
+                                            'parts': ({'type': 'matern', 'nu': 0.5}, {'type': 'matern', 'nu': 0.5})}
         self.gp = GPR(latent=args.latent, lr=args.lr, max_iterations=args.max_iterations,
                       kernel_params=kernel_params, learn_likelihood_noise=self.learn_likelihood_noise,
                       dtype=getattr(args, 'dtype', np.float64), device=getattr(args, 'device', 0),

@@ -1,9 +1,13 @@
 """Command-line flags of the reference (reference arguments.py:7-52), same names and defaults.
-Differences: `--kernel` accepts {rbf, matern, additive, genotype} only, and `--matern_nu` {0.5, 1.5, 2.5} picks the Matern form
+Differences: `--kernel` accepts {rbf, matern, additive, separable, genotype} only, and `--matern_nu` {0.5, 1.5, 2.5} picks the Matern form
 (the reference fixes nu in its source, models.py:219-222); `--kernel additive` is the sum of `--kernel_a` over the first
 `--kernel_split` coordinates and `--kernel_b` over the others (`--matern_nu` applies to its Matern parts); `--kernel genotype` is
 `--kernel_a` (with `--matern_nu`) over the position plus a genotype effect per id in the last coordinate, with the relationship
-matrix of `--relationship PATH` (a .npy file) or independent genotypes without it; `--fit_method ai` fits by average-information
+matrix of `--relationship PATH` (a .npy file) or independent genotypes without it; `--kernel separable` is the product of
+`--kernel_a` over the first `--kernel_split` coordinates and `--kernel_b` over the others with one outputscale (`--matern_nu 0.5`
+with both parts matern and split 1: AR1 x AR1), and `--kernel genotype --spatial separable` puts AR1(row) x AR1(col) -- Matern-1/2
+over the row times Matern-1/2 over the column, whatever `--kernel_a` says -- in the place of the genotype kernel's spatial part;
+`--fit_method ai` fits by average-information
 Newton steps instead of Adam; `--dtype`/`--device` select the GPU precision
 and card; no results directory is created and nothing prompts (the reference's interactive
 `input()` at arguments.py:41-49 blocks unattended runs)."""
@@ -27,11 +31,14 @@ def get_parser():
                         "effects (with --fixed_effects none: of the intercept)")
     p.add_argument('--data_file', default=None)
     p.add_argument('--phenotype', default='plant_height')
-    p.add_argument('--kernel', default='matern', choices=['rbf', 'matern', 'additive', 'genotype'])
+    p.add_argument('--kernel', default='matern', choices=['rbf', 'matern', 'additive', 'separable', 'genotype'])
     p.add_argument('--matern_nu', default=1.5, type=float, choices=[0.5, 1.5, 2.5])
-    p.add_argument('--kernel_split', default=2, type=int, help='additive kernel: coordinates [0, split) belong to part a')
-    p.add_argument('--kernel_a', default='matern', choices=['rbf', 'matern'], help='additive kernel: form of part a')
-    p.add_argument('--kernel_b', default='rbf', choices=['rbf', 'matern'], help='additive kernel: form of part b')
+    p.add_argument('--kernel_split', default=2, type=int, help='additive and separable kernels: coordinates [0, split) belong to part a')
+    p.add_argument('--kernel_a', default='matern', choices=['rbf', 'matern'], help='additive and separable kernels: form of part a')
+    p.add_argument('--kernel_b', default='rbf', choices=['rbf', 'matern'], help='additive and separable kernels: form of part b')
+    p.add_argument('--spatial', default='single', choices=['single', 'separable'],
+                   help="genotype kernel: its spatial part is --kernel_a over the position, or the separable AR1(row) x AR1(col) "
+                        "(Matern-1/2 over the row times Matern-1/2 over the column)")
     p.add_argument('--relationship', default=None, help='genotype kernel: .npy file with the Q x Q relationship matrix (default: identity)')
     p.add_argument('--latent', default=None)
     p.add_argument('--num_sims', default=10, type=int)

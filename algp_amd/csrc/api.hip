@@ -179,6 +179,15 @@ KmatSrc make_src(algp_ctx* c) {
         s.Q = c->hyp.Q;
         s.outputscale_g = c->hyp.outputscale_g;
     }
+    if (c->hyp.sep) {
+        s.sep = true;
+        s.kernel_b = c->hyp.kernel_b;
+        s.da = c->hyp.Da;
+        s.dg = c->hyp.Q > 0 ? c->hyp.idc() : c->hyp.DP;
+        s.G = c->hyp.Q > 0 && c->hyp.has_table ? c->Gtab.p : nullptr;
+        s.Q = c->hyp.Q;
+        s.outputscale_g = c->hyp.outputscale_g;
+    }
     return s;
 }
 
@@ -262,11 +271,11 @@ int Impl<T>::rescale_pool(algp_ctx* c) {
 
 // the relationship form: the ids of the resident coordinate pool (read back from the raw coordinates) checked against Q
 template <typename T>
-int Impl<T>::rel_check_pool(algp_ctx* c, int D, int64_t Q) {
+int Impl<T>::rel_check_pool(algp_ctx* c, int D, int64_t Q, const char* what) {
     std::vector<T> x((size_t)c->n_pool * D);
     ALGP_HIP(hipMemcpyAsync(x.data(), c->Xraw.p, sizeof(T) * x.size(), hipMemcpyDeviceToHost, c->stream));
     ALGP_TRY(sync(c));
-    return rel_check_ids<T>(c, x.data(), c->n_pool, D, Q, "set_hypers_relationship: the resident pool");
+    return rel_check_ids<T>(c, x.data(), c->n_pool, D, Q, what);
 }
 
 // the table in the context's dtype into a buffer of its own (the caller swaps it in once nothing can fail any more)
@@ -663,34 +672,43 @@ int algp_set_hypers_additive(algp_ctx* c, int D, int kernel_a, int Da, double lo
     FINISH(c, install_hypers(c, next));
 }
 
+// What the two setters with a genotype term ask of (G, Q) before anything changes: Q >= 1 and within what the dtype and the table
+// index hold, G (if given) finite and bitwise symmetric.  *gmax = max_q G_qq (1 for the identity), *gh = the FNV-1a fingerprint
+// of the Q x Q doubles (0 for the identity).  who: the entry point, for the message.
+static int genotype_table_check(algp_ctx* c, const char* who, const double* G, int64_t Q, double* gmax, uint64_t* gh) {
+    const std::string w = std::string(who) + ": ";
+    if (Q < 1) return fail(c, ALGP_ERR_BAD_ARG, w + "Q >= 1 required");
+    if (c->dtype == ALGP_F32 && Q > ((int64_t)1 << 24)) return fail(c, ALGP_ERR_BAD_ARG, w + "an fp32 context holds the ids exactly up to Q = 2^24 only");
+    if (G && Q > 46340) return fail(c, ALGP_ERR_BAD_ARG, w + "a table of more than 46340 genotypes is not supported");
+    *gmax = 1.0;
+    *gh = 0;
+    if (!G) return ALGP_OK;
+    for (int64_t p = 0; p < Q; ++p)
+        for (int64_t q = 0; q <= p; ++q) {
+            const double a = G[p * Q + q], b = G[q * Q + p];
+            if (!std::isfinite(a) || !std::isfinite(b))
+                return fail(c, ALGP_ERR_BAD_ARG, w + "G[" + std::to_string(p) + ", " + std::to_string(q) + "] is not finite");
+            if (memcmp(&a, &b, sizeof(double)) != 0)
+                return fail(c, ALGP_ERR_BAD_ARG, w + "G[" + std::to_string(p) + ", " + std::to_string(q) +
+                                                     "] and its mirror entry differ (G must be bitwise symmetric)");
+        }
+    *gmax = G[0];
+    for (int64_t q = 1; q < Q; ++q) *gmax = std::max(*gmax, G[q * Q + q]);
+    uint64_t h = 1469598103934665603ull;
+    const unsigned char* bytes = (const unsigned char*)G;
+    for (size_t b = 0; b < sizeof(double) * (size_t)Q * (size_t)Q; ++b) h = (h ^ bytes[b]) * 1099511628211ull;
+    *gh = h == 0 ? 1 : h;
+    return ALGP_OK;
+}
+
 int algp_set_hypers_relationship(algp_ctx* c, int D, int kernel_a, double log_os_a, const double* log_ls, double log_os_g,
                                  const double* G, int64_t Q, double log_noise) {
     CHECK_CTX(c);
     if (D < 2 || D > MAXD || !log_ls) return fail(c, ALGP_ERR_BAD_ARG, "set_hypers_relationship: 2 <= D <= 8 required");
     if (kernel_a < ALGP_KERNEL_RBF || kernel_a > ALGP_KERNEL_MATERN25) return fail(c, ALGP_ERR_BAD_ARG, "set_hypers_relationship: unknown kernel");
-    if (Q < 1) return fail(c, ALGP_ERR_BAD_ARG, "set_hypers_relationship: Q >= 1 required");
-    if (c->dtype == ALGP_F32 && Q > ((int64_t)1 << 24))
-        return fail(c, ALGP_ERR_BAD_ARG, "set_hypers_relationship: an fp32 context holds the ids exactly up to Q = 2^24 only");
-    if (G && Q > 46340) return fail(c, ALGP_ERR_BAD_ARG, "set_hypers_relationship: a table of more than 46340 genotypes is not supported");
     double gmax = 1.0;
     uint64_t gh = 0;
-    if (G) {
-        for (int64_t p = 0; p < Q; ++p)
-            for (int64_t q = 0; q <= p; ++q) {
-                const double a = G[p * Q + q], b = G[q * Q + p];
-                if (!std::isfinite(a) || !std::isfinite(b))
-                    return fail(c, ALGP_ERR_BAD_ARG, "set_hypers_relationship: G[" + std::to_string(p) + ", " + std::to_string(q) + "] is not finite");
-                if (memcmp(&a, &b, sizeof(double)) != 0)
-                    return fail(c, ALGP_ERR_BAD_ARG, "set_hypers_relationship: G[" + std::to_string(p) + ", " + std::to_string(q) +
-                                                         "] and its mirror entry differ (G must be bitwise symmetric)");
-            }
-        gmax = G[0];
-        for (int64_t q = 1; q < Q; ++q) gmax = std::max(gmax, G[q * Q + q]);
-        gh = 1469598103934665603ull;
-        const unsigned char* bytes = (const unsigned char*)G;
-        for (size_t b = 0; b < sizeof(double) * (size_t)Q * (size_t)Q; ++b) gh = (gh ^ bytes[b]) * 1099511628211ull;
-        if (gh == 0) gh = 1;
-    }
+    ALGP_TRY(genotype_table_check(c, "set_hypers_relationship", G, Q, &gmax, &gh));
     // the resident coordinate pool stays only with the same width: its ids must fit the new Q.  A refusal changes nothing.
     const bool pool_stays = c->n_pool > 0 && !c->pool_is_cov && c->hyp.set && c->hyp.D == D;
     if (pool_stays) ALGP_TRY(DISPATCH(c, rel_check_pool(c, D, Q)));
@@ -716,12 +734,58 @@ int algp_set_hypers_relationship(algp_ctx* c, int D, int kernel_a, double log_os
     FINISH(c, install_hypers(c, next, tab));
 }
 
+int algp_set_hypers_separable(algp_ctx* c, int D, int kernel_a, int Da, int kernel_b, double log_os, const double* log_ls, double log_os_g,
+                              const double* G, int64_t Q, double log_noise) {
+    CHECK_CTX(c);
+    if (D < 2 || D > MAXD || !log_ls) return fail(c, ALGP_ERR_BAD_ARG, "set_hypers_separable: 2 <= D <= 8 required");
+    if (kernel_a < ALGP_KERNEL_RBF || kernel_a > ALGP_KERNEL_MATERN25 || kernel_b < ALGP_KERNEL_RBF || kernel_b > ALGP_KERNEL_MATERN25)
+        return fail(c, ALGP_ERR_BAD_ARG, "set_hypers_separable: unknown kernel");
+    if (Q < 0) return fail(c, ALGP_ERR_BAD_ARG, "set_hypers_separable: Q >= 0 required");
+    if (Q == 0 && G) return fail(c, ALGP_ERR_BAD_ARG, "set_hypers_separable: a table without a genotype term (Q == 0: G must be NULL)");
+    const int nsp = Q > 0 ? D - 1 : D;                       // the spatial coordinates: both factors take at least one
+    if (Da < 1 || Da > nsp - 1)
+        return fail(c, ALGP_ERR_BAD_ARG, Q > 0 ? "set_hypers_separable: 1 <= Da <= D - 2 required with a genotype term (coordinate D - 1 is the id)"
+                                               : "set_hypers_separable: 1 <= Da <= D - 1 required");
+    double gmax = 1.0;
+    uint64_t gh = 0;
+    algp::DevBuf tab;
+    if (Q > 0) {
+        ALGP_TRY(genotype_table_check(c, "set_hypers_separable", G, Q, &gmax, &gh));
+        // the resident coordinate pool stays only with the same width: its ids must fit the new Q.  A refusal changes nothing.
+        const bool pool_stays = c->n_pool > 0 && !c->pool_is_cov && c->hyp.set && c->hyp.D == D;
+        if (pool_stays) ALGP_TRY(DISPATCH(c, rel_check_pool(c, D, Q, "set_hypers_separable: the resident pool")));
+        if (G) {
+            const int rc = DISPATCH(c, rel_upload_table(c, G, Q, tab));
+            if (rc != ALGP_OK) { release(c, tab); return rc; }
+        }
+    }
+    Hypers next;
+    next.kernel = kernel_a;
+    next.sep = true;
+    next.kernel_b = kernel_b;
+    next.Da = Da;
+    next.Db = nsp - Da;
+    next.D = D;
+    for (int d = 0; d < nsp; ++d) next.inv_ls[d] = exp(-log_ls[d]);
+    next.outputscale = exp(log_os);
+    next.noise = exp(log_noise);
+    if (Q > 0) {
+        next.has_table = G != nullptr;
+        next.Q = Q;
+        next.Ghash = gh;
+        next.gdiag_max = gmax;
+        next.inv_ls[D - 1] = 1.0;                            // the id is never scaled: the scaled pool holds it exactly
+        next.outputscale_g = exp(log_os_g);
+    }
+    FINISH(c, install_hypers(c, next, tab));
+}
+
 int algp_kernel_matrix(algp_ctx* c, const void* x1, int64_t n1, const void* x2, int64_t n2, const void* diag_add,
                        int add_lik, void* out) {
     CHECK_CTX(c);
     NEED_HYPERS(c);
     if (!x1 || n1 < 0 || n2 < 0 || !out) return fail(c, ALGP_ERR_BAD_ARG, "kernel_matrix: bad arguments");
-    if (c->hyp.rel) {
+    if (c->hyp.has_ids()) {
         if (c->dtype == ALGP_F64) {
             ALGP_TRY(rel_check_ids<double>(c, (const double*)x1, n1, c->hyp.D, c->hyp.Q, "kernel_matrix: x1"));
             if (x2) ALGP_TRY(rel_check_ids<double>(c, (const double*)x2, n2, c->hyp.D, c->hyp.Q, "kernel_matrix: x2"));
@@ -737,7 +801,7 @@ int algp_set_pool(algp_ctx* c, const void* x, int64_t n) {
     CHECK_CTX(c);
     NEED_HYPERS(c);
     if (!x || n <= 0) return fail(c, ALGP_ERR_BAD_ARG, "set_pool: bad arguments");
-    if (c->hyp.rel)                                          // before anything changes: a refused pool leaves the one there was
+    if (c->hyp.has_ids())                                    // before anything changes: a refused pool leaves the one there was
         ALGP_TRY(c->dtype == ALGP_F64 ? rel_check_ids<double>(c, (const double*)x, n, c->hyp.D, c->hyp.Q, "set_pool")
                                       : rel_check_ids<float>(c, (const float*)x, n, c->hyp.D, c->hyp.Q, "set_pool"));
     c->factored = c->solved = false;

@@ -162,7 +162,7 @@ void Impl<T>::plan_route(algp_ctx* c, int incremental, bool allow_fold, typename
     // read back -- the update products generate their C tiles.  Two scaled coordinates per site only (rhs_gen_supported): wider
     // coordinates and an explicit pool covariance keep the kernel-matrix launch.
     pl.rhs_fused = pl.route == SolveRoute::Sweep && keep == 0 && M > 0 && env_switch("ALGP_RHS_FUSED", true) &&
-                   trsm_plan(c, pl.sweep_rows, pl.sweep_end, keep, {.gen = true}).gen && rhs_gen_supported(c->hyp.DP, c->pool_is_cov, c->hyp.additive || c->hyp.rel);
+                   trsm_plan(c, pl.sweep_rows, pl.sweep_end, keep, {.gen = true}).gen && rhs_gen_supported(c->hyp.DP, c->pool_is_cov, c->hyp.additive || c->hyp.rel || c->hyp.sep);
 }
 
 template <typename T>
@@ -325,11 +325,11 @@ template <typename T>
 int Impl<T>::site_prior(algp_ctx* c, SitePrior& pr) {
     const double noise = c->prior_noise ? c->hyp.noise : 0.0;
     pr = {c->pool_is_cov ? (const T*)c->Cp.p : nullptr, c->n_pool, (T)(c->hyp.prior_var() + noise)};
-    if (c->pool_is_cov || !c->hyp.rel) return ALGP_OK;
+    if (c->pool_is_cov || !c->hyp.has_ids()) return ALGP_OK;
     if (c->gprior_stamp != c->hyp_stamp || c->gprior_noise != c->prior_noise || !c->Gprior.p) {
         ALGP_TRY(ensure(c, c->Gprior, sizeof(T) * c->n_pool));
         ALGP_TRY(rel_prior_launch<T>(c, c->hyp.has_table ? (const T*)c->Gtab.p : nullptr, c->hyp.Q, (T)(c->hyp.outputscale + noise),
-                                     (T)c->hyp.outputscale_g, (const T*)c->Xs.p, c->hyp.DP, c->hyp.Da, c->n_pool, p(c->Gprior)));
+                                     (T)c->hyp.outputscale_g, (const T*)c->Xs.p, c->hyp.DP, c->hyp.idc(), c->n_pool, p(c->Gprior)));
         c->gprior_stamp = c->hyp_stamp;
         c->gprior_noise = c->prior_noise;
     }
@@ -632,8 +632,9 @@ int algp_posterior_mean_component(algp_ctx* c, int component, const int64_t* idx
     if (component < 0 || component > 1) return fail(c, ALGP_ERR_BAD_ARG, "posterior_mean_component: component must be 0 or 1");
     if (M < 0 || (M > 0 && (!idx || !mu))) return fail(c, ALGP_ERR_BAD_ARG, "posterior_mean_component: bad arguments");
     if (c->pool_is_cov) return fail(c, ALGP_ERR_BAD_ARG, "posterior_mean_component needs a coordinate pool");
-    if (!c->hyp.set || !(c->hyp.additive || c->hyp.rel))
-        return fail(c, ALGP_ERR_STATE, "posterior_mean_component: a single kernel is in force (algp_set_hypers_additive)");
+    if (!c->hyp.set || !(c->hyp.additive || c->hyp.has_ids()))
+        return fail(c, ALGP_ERR_STATE, c->hyp.sep ? "posterior_mean_component: a product has no additive shares (the separable kernel without a genotype term)"
+                                                  : "posterior_mean_component: a single kernel is in force (algp_set_hypers_additive)");
     for (int64_t i = 0; i < M; ++i)
         if (idx[i] < 0 || idx[i] >= c->n_pool) return fail(c, ALGP_ERR_BAD_ARG, "posterior_mean_component: index outside the pool");
     FINISH(c, DISPATCH(c, posterior_mean(c, idx, M, mu, 1 << component)));

@@ -43,7 +43,7 @@ int Impl<T>::mll_grad(algp_ctx* c, double* grad_out, bool have_X, bool inv_enque
         if (rc != ALGP_OK) { c->alpha_valid = false; return rc; }
     }
     // [log ls | the log outputscales | log sigma_n^2]; under the relationship form the id has no lengthscale
-    const int nos = (c->hyp.additive || c->hyp.rel) ? 2 : 1, nl = c->hyp.rel ? c->hyp.D - 1 : c->hyp.D;
+    const int nos = c->hyp.n_os(), nl = c->hyp.n_ls();
     for (int d = 0; d < nl; ++d) grad_out[d] = 0.5 * h[nos + 1 + d];
     for (int q = 0; q < nos; ++q) grad_out[nl + q] = 0.5 * h[q];
     grad_out[nl + nos] = 0.5 * c->hyp.noise * h[nos];
@@ -63,7 +63,7 @@ int Impl<T>::mll_ai(algp_ctx* c, double* ai_out) {
     if (c->pool_is_cov) return fail(c, ALGP_ERR_BAD_ARG, "get_mll_ai needs a coordinate pool");
     const int64_t N = c->N, Npad = c->Npad;
     // [log ls | the log outputscales | log sigma_n^2]; under the relationship form the id has no lengthscale
-    const int nos = (c->hyp.additive || c->hyp.rel) ? 2 : 1, nl = c->hyp.rel ? c->hyp.D - 1 : c->hyp.D, P = nl + nos + 1;
+    const int nos = c->hyp.n_os(), nl = c->hyp.n_ls(), P = nl + nos + 1;
     if (N <= 0) {
         for (int e = 0; e < P * P; ++e) ai_out[e] = 0.0;
         return ALGP_OK;

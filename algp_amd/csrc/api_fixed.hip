@@ -202,7 +202,7 @@ int Impl<T>::reml_grad(algp_ctx* c, double* grad_out, double* reml_out, bool hav
     }
     if (g[FX_INFO] != 0.0) return fixed_rank_error(c, "get_reml_grad", g[FX_INFO]);
     // [log ls | the log outputscales | log sigma_n^2], algp_get_mll_grad's order
-    const int nos = (c->hyp.additive || c->hyp.rel) ? 2 : 1, nl = c->hyp.rel ? c->hyp.D - 1 : c->hyp.D;
+    const int nos = c->hyp.n_os(), nl = c->hyp.n_ls();
     if (grad_out) {
         for (int d = 0; d < nl; ++d) grad_out[d] = 0.5 * h[nos + 1 + d];
         for (int q = 0; q < nos; ++q) grad_out[nl + q] = 0.5 * h[q];
@@ -221,7 +221,7 @@ int Impl<T>::reml_ai(algp_ctx* c, double* ai_out) {
     if (!c->factored || c->train_dirty) return fail(c, ALGP_ERR_STATE, "get_reml_ai: call algp_factorize first");
     if (c->pool_is_cov) return fail(c, ALGP_ERR_BAD_ARG, "get_reml_ai needs a coordinate pool");
     const int64_t N = c->N, Npad = c->Npad;
-    const int nos = (c->hyp.additive || c->hyp.rel) ? 2 : 1, nl = c->hyp.rel ? c->hyp.D - 1 : c->hyp.D, P = nl + nos + 1;
+    const int nos = c->hyp.n_os(), nl = c->hyp.n_ls(), P = nl + nos + 1;
     const int fp = c->fx_p, W = P + fp;
     FixedPlan pl;
     ALGP_TRY(fixed_enqueue(c, "get_reml_ai", {.fit = true}, pl));

@@ -1,5 +1,5 @@
 // api_genotype.hip -- algp_genotype_posterior: the posterior of the genotype effects u (Q of them, prior N(0, os_g G)) under the
-// relationship form k = os_a kappa_a + os_g G[g, g'], from the resident factor of S = K_AA + diag(var) + sigma_n^2 I.
+// relationship form k = os_a kappa_a + os_g G[g, g'] (or the separable form with its genotype term), from the resident factor of S = K_AA + diag(var) + sigma_n^2 I.
 // cov(u, y_A) = B with B[q][i] = os_g G[q, g_i] (g_i: the id of train row i), so with W = B L^-T and z = L^-1 (y - ybar):
 //   B (Qpad x Npad)                a gather from the table (or from the identity)                  rel_gather_b_launch
 //   W = B L^-T, in place           the blocked triangular solve through its plan                    trsm_blocked
@@ -18,8 +18,9 @@ namespace algp {
 
 template <typename T>
 int Impl<T>::genotype_posterior(algp_ctx* c, void* mean_out, void* var_out, void* cov_out) {
-    if (!c->hyp.set || !c->hyp.rel)
-        return fail(c, ALGP_ERR_STATE, "genotype_posterior: no relationship kernel is in force (algp_set_hypers_relationship)");
+    if (!c->hyp.set || !c->hyp.has_ids())
+        return fail(c, ALGP_ERR_STATE, "genotype_posterior: no kernel with a genotype term is in force (algp_set_hypers_relationship, "
+                                       "algp_set_hypers_separable with Q >= 1)");
     if (c->pool_is_cov || c->n_pool <= 0) return fail(c, ALGP_ERR_STATE, "genotype_posterior needs a coordinate pool");
     if (!c->factored || c->train_dirty) return fail(c, ALGP_ERR_STATE, "genotype_posterior: call algp_factorize first");
     if (c->solved && !c->picks.empty())                 // (a new factorisation invalidates the candidate solve and its picks with it)
@@ -51,7 +52,7 @@ int Impl<T>::genotype_posterior(algp_ctx* c, void* mean_out, void* var_out, void
     T *WW = (T*)(base + o_WW), *covD = (T*)(base + o_cov);
 
     if (N > 0) {
-        ALGP_TRY(rel_gather_b_launch<T>(c, G, Q, osg, (const T*)c->Xs.p, c->hyp.DP, c->hyp.Da, (const int64_t*)c->Aidx.p, N, Qpad, Npad, B));
+        ALGP_TRY(rel_gather_b_launch<T>(c, G, Q, osg, (const T*)c->Xs.p, c->hyp.DP, c->hyp.idc(), (const int64_t*)c->Aidx.p, N, Qpad, Npad, B));
         ALGP_TRY(trsm_blocked<T>(c, {.klass = ALGP_PROF_GEMM_TRSM, .X = B, .mpad = Qpad, .ldx = Npad, .L = p(c->L), .npad = Npad, .ldl = c->Lld,
                                      .invD = p(c->invD)}));
         ALGP_TRY(rows_reduce_launch<T>(c, B, Qpad, Npad, Npad, p(c->z), ss, meanD));

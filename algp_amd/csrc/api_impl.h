@@ -45,7 +45,7 @@ struct Impl {
     static int set_pool(algp_ctx* c, const void* x, int64_t n);
     // the relationship form (api.hip): the resident pool's ids against Q; the table to the device; (api_candidates.hip) the prior
     // variance of the candidates as cand_finalize_launch takes it; (api_genotype.hip) the genotype effects' posterior
-    static int rel_check_pool(algp_ctx* c, int D, int64_t Q);
+    static int rel_check_pool(algp_ctx* c, int D, int64_t Q, const char* what = "set_hypers_relationship: the resident pool");
     static int rel_upload_table(algp_ctx* c, const double* G, int64_t Q, DevBuf& dst);
     struct SitePrior { const T* tab; int64_t stride; T scalar; };
     static int site_prior(algp_ctx* c, SitePrior& pr);

@@ -36,7 +36,7 @@ int Impl<T>::sample_posterior(algp_ctx* c, int S, int F, const double* omega, co
     if (c->train_has_repeats)
         return fail(c, ALGP_ERR_STATE, "sample_posterior: the train set lists a pool site in more than one row");
     if (F > 0 && c->pool_is_cov) return fail(c, ALGP_ERR_BAD_ARG, "sample_posterior: random features need a coordinate pool (pass prior values)");
-    if (F > 0 && c->hyp.rel && !c->pool_is_cov)
+    if (F > 0 && c->hyp.has_ids() && !c->pool_is_cov)
         return fail(c, ALGP_ERR_BAD_ARG, "sample_posterior: under the relationship kernel the genotype part has no spectral density, so "
                                          "random features cannot draw it (pass prior values, F == 0)");
     if (N > 0 && !eps) return fail(c, ALGP_ERR_BAD_ARG, "sample_posterior: eps is NULL");

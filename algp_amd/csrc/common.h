@@ -80,15 +80,30 @@ struct Hypers {
     int64_t Q = 0;
     double outputscale_g = 0.0, gdiag_max = 1.0;
     uint64_t Ghash = 0;
+    // the separable form (algp_set_hypers_separable): k = os kappa_kernel(r_a) kappa_kernel_b(r_b) [+ os_g G[g, g']], r_a over the
+    // first Da coordinates, r_b over the next Db; with the genotype term (Q >= 1; the table's fields above are then this form's,
+    // rel stays false) the id sits in coordinate Da + Db = D - 1
+    bool sep = false;
+    int Db = 0;
+    // a genotype id rides in coordinate idc() of every site (validated on the host wherever coordinates arrive)
+    bool has_ids() const { return rel || (sep && Q > 0); }
+    int idc() const { return sep ? Da + Db : Da; }
     // K_jj where it is one scalar (the single and additive forms); under the relationship form the LARGEST prior variance (the
     // jitter's scale) -- the per-site prior goes through algp_ctx::Gprior
-    double prior_var() const { return rel ? outputscale + outputscale_g * gdiag_max : additive ? outputscale + outputscale_b : outputscale; }
+    double prior_var() const {
+        return has_ids() ? outputscale + outputscale_g * gdiag_max : additive ? outputscale + outputscale_b : outputscale;
+    }
+    // the gradient's layout [log ls (nl) | log outputscales (nos) | log sigma_n^2]: the id has no lengthscale
+    int n_ls() const { return has_ids() ? D - 1 : D; }
+    int n_os() const { return (additive || has_ids()) ? 2 : 1; }
     // the same covariance function of the sites' coordinates (algp_factorize_from): the form, and of each form the fields that
     // count under it, the table by its fingerprint
     bool same_model(const Hypers& b) const {
         bool same = D == b.D && kernel == b.kernel && outputscale == b.outputscale && noise == b.noise && additive == b.additive &&
                     (!additive || (kernel_b == b.kernel_b && Da == b.Da && outputscale_b == b.outputscale_b));
         same = same && rel == b.rel && (!rel || (Q == b.Q && outputscale_g == b.outputscale_g && Ghash == b.Ghash));
+        same = same && sep == b.sep && (!sep || (kernel_b == b.kernel_b && Da == b.Da && Db == b.Db && Q == b.Q &&
+                                                 (Q == 0 || (outputscale_g == b.outputscale_g && Ghash == b.Ghash))));
         for (int d = 0; same && d < D; ++d) same = inv_ls[d] == b.inv_ls[d];
         return same;
     }
@@ -370,6 +385,60 @@ __device__ __forceinline__ T kmat_value_rel(int ka, T osa, const T* G, int64_t Q
     rel_r2<DP>(&xr[0], &xc[0], da, ra, ia, ib);
     return kval_rel<T, T>(ka, osa, ra, G, Q, osg, ia, ib);
 }
+// The separable form, a fifth family (4): k = os kappa_a(r_a) kappa_b(r_b) [+ os_g G[ia Q + ib]], r_a over the scaled coordinates
+// [0, da), r_b over [da, dg), and -- with the genotype term (hasg, uniform over the launch) -- the two sites' integer ids held
+// exactly in coordinate dg, as under the relationship form.  Without the term dg is the padded width: no coordinate is read as
+// an id.  Compiled as instantiations of its own like the two forms above.  ONE definition for every site: r_a^2 and r_b^2 as
+// split_r2 sums them (each square rounded on its own, coordinate order, contraction off), the two factor values at outputscale
+// 1, one rounded product kappa_a kappa_b, one rounded product with os, then (hasg) one rounded sum with rel_entry's value.
+template <int DP, typename C, typename XA, typename XB>
+__device__ __forceinline__ void sep_r2(const XA* xa, const XB* xb, int da, int dg, C& ra, C& rb, int64_t& ia, int64_t& ib) {
+#pragma clang fp contract(off)
+    ra = (C)0;
+    rb = (C)0;
+    C ga = (C)0, gb = (C)0;
+#pragma unroll
+    for (int d = 0; d < DP; ++d) {
+        const C va = (C)xa[d], vb = (C)xb[d];
+        const C df = va - vb;
+        const C q = df * df;
+        const bool isid = d == dg;                                // (behind the id there is only zero padding: it adds nothing)
+        ra += d < da ? q : (C)0;
+        rb += (d < da || isid) ? (C)0 : q;
+        ga = isid ? va : ga;
+        gb = isid ? vb : gb;
+    }
+    ia = (int64_t)ga;
+    ib = (int64_t)gb;
+}
+// the product of the two factor values and the outputscale, in that order: kval_sep's, and the gradient's dS/dlog os
+template <typename C>
+__device__ __forceinline__ C sep_prod(C os, C fa, C fb) {
+#pragma clang fp contract(off)
+    const C p = fa * fb;
+    return os * p;
+}
+// parts: bit 0 = the spatial product, bit 1 = the genotype term (as kval_rel)
+template <typename C, typename T>
+__device__ __forceinline__ C kval_sep(int ka, int kb, C os, C ra, C rb, bool hasg, const T* G, int64_t Q, C osg, int64_t ia, int64_t ib,
+                                      int parts = 3) {
+#pragma clang fp contract(off)
+    C v = (C)0;
+    if (parts & 1) v = sep_prod<C>(os, kval<C>(ka, (C)1, ra), kval<C>(kb, (C)1, rb));
+    if (hasg && (parts & 2)) {
+        const C vg = rel_entry<C>(G, Q, osg, ia, ib);
+        v = v + vg;
+    }
+    return v;
+}
+template <typename T, int DP>
+__device__ __forceinline__ T kmat_value_sep(int ka, int kb, T os, int da, int dg, bool hasg, const T* G, int64_t Q, T osg, const T (&xr)[DP],
+                                            const T (&xc)[DP]) {
+    T ra, rb;
+    int64_t ia, ib;
+    sep_r2<DP>(&xr[0], &xc[0], da, dg, ra, rb, ia, ib);
+    return kval_sep<T, T>(ka, kb, os, ra, rb, hasg, G, Q, osg, ia, ib);
+}
 // Entry (row, global column gcol) of the candidates' right-hand side B^T = K(candidates, train) as the matrix build writes it:
 // kind -1: an ordinary row, k(x_row, x_col) in the columns of the train set (gcol < ncols), 0 in the padding behind them;
 // kind >= 0: the unit row e_kind (a candidate that is a train site under prior_includes_noise); kind -2: a padding row, 0.
@@ -430,10 +499,33 @@ struct is_rel : std::false_type {};
 template <typename S>
 struct is_rel<S, std::void_t<decltype(std::declval<S>().os_g)>> : std::true_type {};
 
+// The separable form's source: CovSrc (kernel: factor a, os: the product's outputscale), factor b, the split [0, sep_da) |
+// [sep_da, sep_dg), and the genotype term's table, order and outputscale while sep_hasg (then sep_dg is the id's coordinate).  A
+// source type of its own for the reason CovSrcAdd is one; its field names are its own so that neither trait above takes it.
+template <typename T, typename C = T>
+struct CovSrcSep : CovSrc<T, C> {
+    const T* sep_G;
+    int64_t sep_Q;
+    int sep_kb, sep_da, sep_dg, sep_hasg, sep_parts;
+    C sep_osg;
+};
+// S carries the separable fields (CovSrcSep, or the GEMM's argument structs with the same fields appended)
+template <typename S, typename = void>
+struct is_sep : std::false_type {};
+template <typename S>
+struct is_sep<S, std::void_t<decltype(std::declval<S>().sep_dg)>> : std::true_type {};
+
 template <int DP, bool NOISE = true, typename S, typename XA, typename XB>
 __device__ __forceinline__ auto pool_cov(const S& s, int64_t pa, int64_t pb, const XA* xa, const XB* xb) {
     using C = std::remove_cv_t<decltype(s.os)>;
-    if constexpr (is_rel<S>::value) {
+    if constexpr (is_sep<S>::value) {
+        C ra, rb;
+        int64_t ia, ib;
+        sep_r2<DP>(xa, xb, s.sep_da, s.sep_dg, ra, rb, ia, ib);
+        C v = kval_sep<C>(s.kernel, s.sep_kb, s.os, ra, rb, s.sep_hasg != 0, s.sep_G, s.sep_Q, s.sep_osg, ia, ib, s.sep_parts);
+        if (NOISE && pa == pb) v += s.noise;
+        return v;
+    } else if constexpr (is_rel<S>::value) {
         C ra;
         int64_t ia, ib;
         rel_r2<DP>(xa, xb, s.da, ra, ia, ib);
@@ -697,13 +789,19 @@ struct KmatSrc {
     // parts: bit 0 = a, bit 1 = b counts (3 everywhere but in algp_posterior_mean_component)
     int kernel_b = -1, da = 0, parts = 3;
     double outputscale_b = 0;
-    bool additive() const { return kernel_b >= 0 && !Cp; }
+    bool additive() const { return kernel_b >= 0 && !Cp && !sep; }
     // the relationship form (Q > 0; kernel / outputscale are then the spatial part's, da = D - 1 the id's coordinate, kernel_b
     // stays -1): the table in the context's dtype or null for the identity, its order, the genotype part's outputscale
     const void* G = nullptr;
     int64_t Q = 0;
     double outputscale_g = 0;
-    bool rel() const { return Q > 0 && !Cp; }
+    bool rel() const { return Q > 0 && !Cp && !sep; }
+    // the separable form (sep; kernel / kernel_b are then the two factors', outputscale the product's, da the split, dg the end
+    // of factor b's coordinates -- the id's coordinate while Q > 0, the padded width DP else; the table's fields above are then
+    // this form's): additive() and rel() are false under it
+    bool sep = false;
+    int dg = 0;
+    bool sepf() const { return sep && !Cp; }
 };
 // the device-side view of a source (CovSrc above).  The one place that says what `noise` means per pool kind: an explicit
 // covariance carries sigma_n^2 on its diagonal already, so nothing is added to it anywhere
@@ -711,11 +809,17 @@ template <typename T, typename C = T>
 inline CovSrc<T, C> cov_src(const KmatSrc& s) {
     return {(const T*)s.Xs, (const T*)s.Cp, s.n_pool, s.kernel, (C)s.outputscale, (C)(s.Cp ? 0.0 : s.noise)};
 }
-// f(the typed source): a CovSrc, a CovSrcAdd under the additive form or a CovSrcRel under the relationship form -- the kernel's
-// source type is a template argument, so those two forms run instantiations of their own
+// f(the typed source): a CovSrc, a CovSrcAdd under the additive form, a CovSrcRel under the relationship form or a CovSrcSep under
+// the separable form -- the kernel's source type is a template argument, so those three forms run instantiations of their own
 template <typename T, typename C = T, typename F>
 inline void with_src(const KmatSrc& s, F&& f) {
-    if (s.rel()) {
+    if (s.sepf()) {
+        CovSrcSep<T, C> a;
+        static_cast<CovSrc<T, C>&>(a) = cov_src<T, C>(s);
+        a.sep_G = (const T*)s.G; a.sep_Q = s.Q; a.sep_kb = s.kernel_b; a.sep_da = s.da; a.sep_dg = s.dg; a.sep_hasg = s.Q > 0 ? 1 : 0;
+        a.sep_parts = s.parts; a.sep_osg = (C)s.outputscale_g;
+        f(a);
+    } else if (s.rel()) {
         CovSrcRel<T, C> a;
         static_cast<CovSrc<T, C>&>(a) = cov_src<T, C>(s);
         a.G = (const T*)s.G; a.Q = s.Q; a.da = s.da; a.parts = s.parts; a.os_g = (C)s.outputscale_g;

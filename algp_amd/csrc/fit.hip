@@ -124,6 +124,47 @@ struct GradRel {
     }
 };
 
+// The separable kernel (common.h: family 4): S = os kappa_a(r_a) kappa_b(r_b) [+ os_g G[g_i, g_j]] + ..., so dS/dlog os = os kappa_a
+// kappa_b (sep_prod: the value the matrix build holds), dS/dlog os_g = os_g G (rel_entry; NOS_ = 2: the genotype term is there),
+// and by kdk's factors at outputscale 1 dS/dlog ls_d = (os kappa_b dk_a) u_d^2 for d in part a, (os kappa_a dk_b) u_d^2 in part
+// b; the id's coordinate and the padding get the factor 0.
+template <typename T, int NOS_>
+struct GradSep {
+    static constexpr int NOS = NOS_;
+    static constexpr bool SINV_UP_FRONT = false;
+    static constexpr double PAIR_FLOPS = 20.0, SINV_ELEMS = NOS_ == 2 ? 1.0 : 0.5;
+    int kernel_a, kernel_b;
+    T os;
+    const T* G;
+    int64_t Q;
+    T os_g;
+    int da, dg;
+    template <int DP>
+    __device__ __forceinline__ T pair(const T (&xi)[DP], const T (&xj)[DP], const T& ai, T aj, T s, T (&kv)[NOS], T (&dk)[DP], T (&u2)[DP]) const {
+#pragma clang fp contract(off)
+        T ra, rb, dka, dkb;
+        int64_t ia = 0, ib = 0;
+        const int sa = da, sg = dg;
+        if constexpr (NOS == 2) sep_r2<DP>(&xi[0], &xj[0], sa, sg, ra, rb, ia, ib);
+        else split_r2<DP>(&xi[0], &xj[0], sa, ra, rb);            // no id: sep_r2's sums with dg behind the last coordinate
+#pragma unroll
+        for (int d = 0; d < DP; ++d) {
+            const T df = xi[d] - xj[d];
+            u2[d] = df * df;                                     // the squares sep_r2 has just summed
+        }
+        const T aa = ai * aj;                                    // a rounded product, then the difference
+        const T w = aa - s;
+        const T fa = kdk<T>(kernel_a, (T)1, ra, dka);
+        const T fb = kdk<T>(kernel_b, (T)1, rb, dkb);
+        kv[0] = sep_prod<T>(os, fa, fb);
+        if constexpr (NOS == 2) kv[1] = rel_entry<T>(G, Q, os_g, ia, ib);
+        const T ga = sep_prod<T>(os, dka, fb), gb = sep_prod<T>(os, fa, dkb);
+#pragma unroll
+        for (int d = 0; d < DP; ++d) dk[d] = d < sa ? ga : ((NOS == 2 && d == sg) ? (T)0 : gb);   // (the padding's u2 is 0)
+        return w;
+    }
+};
+
 // Per workgroup, and after the reduction: [0, NOS) = the outputscale sums, [NOS] = the noise trace, [NOS+1, NOS+1+DP) = the
 // lengthscale sums -- 11 at most.
 template <typename T, int DP, typename Form>
@@ -261,6 +302,10 @@ int mll_grad_launch(algp_ctx* c, const T* Sinv, int64_t ld, int64_t N, const int
         return ALGP_OK;
     };
     const T os = (T)s.outputscale;
+    if (s.sepf()) {
+        if (s.Q > 0) return launch(GradSep<T, 2>{s.kernel, s.kernel_b, os, (const T*)s.G, s.Q, (T)s.outputscale_g, s.da, s.dg});
+        return launch(GradSep<T, 1>{s.kernel, s.kernel_b, os, nullptr, 0, (T)0, s.da, s.dg});
+    }
     if (s.rel()) return launch(GradRel<T>{s.kernel, os, (const T*)s.G, s.Q, (T)s.outputscale_g, s.da});
     if (s.additive()) return launch(GradAdd<T>{s.kernel, os, s.kernel_b, (T)s.outputscale_b, s.da});
     if (kernel_family(s.kernel)) return launch(GradSingle<T, 1>{s.kernel, os});

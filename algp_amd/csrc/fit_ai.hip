@@ -99,6 +99,47 @@ struct AiRel {
     }
 };
 
+// The separable kernel: GradSep's terms (fit.hip) without the weight -- dS/dlog os = os kappa_a kappa_b, dS/dlog os_g = os_g G where
+// the genotype term is there (NOS_ = 2), the lengthscale factors os kappa_b dk_a | os kappa_a dk_b by the part that owns the
+// coordinate, 0 for the id and the padding
+template <typename T, int NOS_>
+struct AiSep {
+    static constexpr int NOS = NOS_;
+    static constexpr double PAIR_FLOPS = 20.0;
+    int kernel_a, kernel_b;
+    T os;
+    const T* G;
+    int64_t Q;
+    T os_g;
+    int da, dg;
+    template <int DP>
+    __device__ __forceinline__ void pair(const T (&xi)[DP], const T (&xj)[DP], T (&kv)[NOS], T (&dk)[DP], T (&u2)[DP]) const {
+#pragma clang fp contract(off)
+        T ra, rb, dka, dkb;
+        int64_t ia = 0, ib = 0;
+        int sa = da, sg = dg;
+        // The 2 DP tests of a coordinate against the split are uniform and invariant in the kernel's loop over columns: hoisted
+        // out of it each holds an SGPR pair across it, and with the genotype term at DP = 8 the fp32 kernel spilled SGPRs to
+        // scratch.  There they are formed where they are used instead, on the otherwise idle scalar unit (the column loop of
+        // those two instantiations then stays rolled: the compiler says so).
+        if constexpr (DP == 8 && NOS == 2) asm volatile("" : "+s"(sa), "+s"(sg));
+        if constexpr (NOS == 2) sep_r2<DP>(&xi[0], &xj[0], sa, sg, ra, rb, ia, ib);
+        else split_r2<DP>(&xi[0], &xj[0], sa, ra, rb);            // no id: sep_r2's sums with dg behind the last coordinate
+#pragma unroll
+        for (int d = 0; d < DP; ++d) {
+            const T df = xi[d] - xj[d];
+            u2[d] = df * df;                                     // the squares sep_r2 has just summed
+        }
+        const T fa = kdk<T>(kernel_a, (T)1, ra, dka);
+        const T fb = kdk<T>(kernel_b, (T)1, rb, dkb);
+        kv[0] = sep_prod<T>(os, fa, fb);
+        if constexpr (NOS == 2) kv[1] = rel_entry<T>(G, Q, os_g, ia, ib);
+        const T ga = sep_prod<T>(os, dka, fb), gb = sep_prod<T>(os, fa, dkb);
+#pragma unroll
+        for (int d = 0; d < DP; ++d) dk[d] = d < sa ? ga : ((NOS == 2 && d == sg) ? (T)0 : gb);   // (the padding's u2 is 0)
+    }
+};
+
 // U[a][i] = sum_j (dS/dtheta_a)_ij alpha_j for the rows i of one 64-row group, a in the gradient's order: [0, nl) the
 // lengthscales, [nl, nl + NOS) the outputscales, [nl + NOS] the noise (sigma_n^2 times the alpha of every row of i's pool site).
 // One workgroup owns 64 rows: thread (lane, wave) holds row 64 b + lane's coordinates in registers and walks the columns in tiles
@@ -197,6 +238,10 @@ int mll_ai_u_launch(algp_ctx* c, int64_t N, int64_t Npad, const int64_t* aidx, c
         return ALGP_OK;
     };
     const T os = (T)s.outputscale;
+    if (s.sepf()) {
+        if (s.Q > 0) return launch(AiSep<T, 2>{s.kernel, s.kernel_b, os, (const T*)s.G, s.Q, (T)s.outputscale_g, s.da, s.dg});
+        return launch(AiSep<T, 1>{s.kernel, s.kernel_b, os, nullptr, 0, (T)0, s.da, s.dg});
+    }
     if (s.rel()) return launch(AiRel<T>{s.kernel, os, (const T*)s.G, s.Q, (T)s.outputscale_g, s.da});
     if (s.additive()) return launch(AiAdd<T>{s.kernel, os, s.kernel_b, (T)s.outputscale_b, s.da});
     if (kernel_family(s.kernel)) return launch(AiSingle<T, 1>{s.kernel, os});

@@ -172,6 +172,15 @@ struct RelGemmArgs : Base {
     T os_g;
 };
 
+// The separable form of the same structs: its fields appended (is_sep, common.h), kernels of their own likewise
+template <typename T, typename Base>
+struct SepGemmArgs : Base {
+    const T* sep_G;
+    int64_t sep_Q;
+    int sep_kb, sep_da, sep_dg, sep_hasg, sep_parts;
+    T sep_osg;
+};
+
 // C(prow, pcol) for the two epilogues below: pool_cov (common.h) over the launch's own source fields, the coordinates of the
 // row in registers and of the column staged in LDS, both at width MAXD
 template <typename T, typename G>
@@ -342,7 +351,7 @@ __device__ __forceinline__ void pvr_epilogue(const G& g, char* smem, const ACC (
                 Er[col] = (rowon && sw != (T)0) ? sw * (cv - acc[i][j][r]) : (T)0;
                 // the additive form evaluates two kernels per entry: one column after the other, or the scheduler overlaps the
                 // four and the fp64 kernel no longer fits its registers beside the accumulators (the single forms: as before)
-                if constexpr (is_additive<G>::value || is_rel<G>::value) __builtin_amdgcn_sched_barrier(0);
+                if constexpr (is_additive<G>::value || is_rel<G>::value || is_sep<G>::value) __builtin_amdgcn_sched_barrier(0);
             }
         }
 }
@@ -1022,6 +1031,13 @@ static void vr_fill(VrGemmArgs<T>& g, const KmatSrc& s, const int64_t* cidx, con
 // its additive form (AddGemmArgs) -- instantiations of their own
 template <typename T, typename G>
 static int vr_dispatch(algp_ctx* c, int klass, const Booking& bk, dim3 grid, const G& g, const KmatSrc& s) {
+    if (s.sepf()) {
+        SepGemmArgs<T, G> a;
+        static_cast<G&>(a) = g;
+        a.sep_G = (const T*)s.G; a.sep_Q = s.Q; a.sep_kb = s.kernel_b; a.sep_da = s.da; a.sep_dg = s.dg; a.sep_hasg = s.Q > 0 ? 1 : 0;
+        a.sep_parts = 3; a.sep_osg = (T)s.outputscale_g;
+        return dispatch(c, klass, bk.flops, bk.bytes, gemm_nt_kernel_dma4<T, false, SepGemmArgs<T, G>>, grid, a);
+    }
     if (s.rel()) {
         RelGemmArgs<T, G> a;
         static_cast<G&>(a) = g;

@@ -57,6 +57,20 @@ struct GroupCovSrc<T, -2> {
     int da, parts;
     T os_g;
 };
+// KERNEL = -3: the separable form -- the two factors' forms, the split, and the genotype term's table and outputscale while
+// sep_hasg, at run time (pool_cov's separable branch)
+template <typename T>
+struct GroupCovSrc<T, -3> {
+    static constexpr const T* Cp = nullptr;
+    const T* Xs;
+    int64_t n_pool;
+    T os, noise;
+    int kernel;
+    const T* sep_G;
+    int64_t sep_Q;
+    int sep_kb, sep_da, sep_dg, sep_hasg, sep_parts;
+    T sep_osg;
+};
 template <typename F>
 inline void with_kernel(int kernel, F&& f) {
     if (kernel == ALGP_KERNEL_RBF) f(std::integral_constant<int, ALGP_KERNEL_RBF>{});
@@ -178,7 +192,13 @@ int group_ksum_launch(algp_ctx* c, const KmatSrc& s, const int64_t* cidx, int64_
         ProfScope ps(c, ALGP_PROF_KMAT, evals * (3.0 * s.DP + 2.0), sizeof(T) * (double)Mpad * (double)(g.Q + 2 * nspan));
         const CovSrc<T> cs = cov_src<T>(s);
         const dim3 grid((unsigned)((Mpad + GROUP_KROWS - 1) / GROUP_KROWS), (unsigned)nch);
-        if (s.rel()) {
+        if (s.sepf()) {
+            GroupKsumArgs<T, -3> a = {{cs.Xs, cs.n_pool, cs.os, cs.noise, s.kernel, (const T*)s.G, s.Q, s.kernel_b, s.da, s.dg, s.Q > 0 ? 1 : 0, 3,
+                                       (T)s.outputscale_g}, cidx, M, Mpad, g, U, part};
+            with_dp(s.DP, [&](auto dp) {
+                hipLaunchKernelGGL((group_ksum_kernel<T, decltype(dp)::value, -3>), grid, dim3(256), 0, c->cur, a);
+            });
+        } else if (s.rel()) {
             GroupKsumArgs<T, -2> a = {{cs.Xs, cs.n_pool, cs.os, cs.noise, s.kernel, (const T*)s.G, s.Q, s.da, 3, (T)s.outputscale_g}, cidx, M, Mpad, g, U, part};
             with_dp(s.DP, [&](auto dp) {
                 hipLaunchKernelGGL((group_ksum_kernel<T, decltype(dp)::value, -2>), grid, dim3(256), 0, c->cur, a);

@@ -60,6 +60,10 @@ struct KmatArgs {
     const T* G;
     int64_t Q;
     T outputscale_g;
+    // the separable form (FAM = 4; sep = 0: another form): kernel / kernel_b are the two factors', outputscale the product's, da
+    // the split and dg the end of factor b's coordinates -- the id's coordinate while Q > 0 (the genotype term, the table's fields
+    // above), the padded width else
+    int sep, dg;
 };
 
 // (the kernel value itself: kval / kmat_value in common.h, shared with the product epilogue that generates B^T, gemm.hip)
@@ -69,7 +73,8 @@ struct KmatArgs {
 // bookkeeping were half of the kernel's VALU instructions, and the kernel is VALU-issue bound (profiles/r04_valu_by_kernel.json).
 // FAM: the family of a.kernel (kernel_family, common.h): one copy of the kernel per family, the form selected inside it; 2: the
 // additive form (kmat_value_add), any two of the four forms; 3: the relationship form (kmat_value_rel) -- the ids ride along as the
-// last coordinate of the row (LDS) and the column (registers), the table entry is one gather per output element
+// last coordinate of the row (LDS) and the column (registers), the table entry is one gather per output element; 4: the separable
+// form (kmat_value_sep), with the genotype term while a.Q > 0 (uniform over the launch)
 template <typename T, int DP, bool EQ, int FAM>
 __global__ __launch_bounds__(256) void kmat_kernel(KmatArgs<T> a) {
     constexpr int VEC = Vec16<T>::N;
@@ -141,7 +146,8 @@ __global__ __launch_bounds__(256) void kmat_kernel(KmatArgs<T> a) {
 #pragma unroll
                 for (int v = 0; v < VEC; ++v) {
                     T val;
-                    if constexpr (FAM == 3) val = kmat_value_rel<T, DP>(a.kernel, a.outputscale, a.G, a.Q, a.outputscale_g, a.da, xr, xc[v]);
+                    if constexpr (FAM == 4) val = kmat_value_sep<T, DP>(a.kernel, a.kernel_b, a.outputscale, a.da, a.dg, a.Q > 0, a.G, a.Q, a.outputscale_g, xr, xc[v]);
+                    else if constexpr (FAM == 3) val = kmat_value_rel<T, DP>(a.kernel, a.outputscale, a.G, a.Q, a.outputscale_g, a.da, xr, xc[v]);
                     else if constexpr (FAM == 2) val = kmat_value_add<T, DP>(a.kernel, a.outputscale, a.kernel_b, a.outputscale_b, a.da, xr, xc[v]);
                     else val = kmat_value<T, DP, FAM>(a.kernel, a.outputscale, xr, xc[v]);
                     o[v] = live[v] ? val : (T)0;
@@ -199,7 +205,8 @@ static int kmat_dispatch(algp_ctx* c, const KmatArgs<T>& a, int DP) {
                 else hipLaunchKernelGGL((kmat_kernel<T, decltype(dp)::value, false, FAM>), grid, dim3(256), 0, c->cur, b);
             });
         };
-        if (a.Q > 0 && !a.Cp) launch(std::integral_constant<int, 3>{});
+        if (a.sep && !a.Cp) launch(std::integral_constant<int, 4>{});
+        else if (a.Q > 0 && !a.Cp) launch(std::integral_constant<int, 3>{});
         else if (a.kernel_b >= 0 && !a.Cp) launch(std::integral_constant<int, 2>{});
         else if (kernel_family(a.kernel)) launch(std::integral_constant<int, 1>{});
         else launch(std::integral_constant<int, 0>{});
@@ -231,6 +238,7 @@ int kmat_launch(algp_ctx* c, const KmatSrc& s, const int64_t* ridx, int64_t rows
     a.outputscale = (T)s.outputscale;
     a.kernel_b = s.kernel_b; a.da = s.da; a.outputscale_b = (T)s.outputscale_b;
     a.G = (const T*)s.G; a.Q = s.Q; a.outputscale_g = (T)s.outputscale_g;
+    a.sep = s.sep ? 1 : 0; a.dg = s.dg;
     a.out = out;
     a.ldo = ldo;
     return kmat_dispatch<T>(c, a, s.DP);
@@ -257,8 +265,9 @@ int kmat_xy_launch(algp_ctx* c, const T* xs1, int64_t n1, const T* xs2, int64_t 
     a.col_shift = 0;
     a.kernel = c->hyp.kernel;
     a.outputscale = (T)c->hyp.outputscale;
-    a.kernel_b = c->hyp.additive ? c->hyp.kernel_b : -1; a.da = c->hyp.Da; a.outputscale_b = (T)c->hyp.outputscale_b;
-    a.G = c->hyp.rel && c->hyp.has_table ? (const T*)c->Gtab.p : nullptr; a.Q = c->hyp.rel ? c->hyp.Q : 0;
+    a.kernel_b = (c->hyp.additive || c->hyp.sep) ? c->hyp.kernel_b : -1; a.da = c->hyp.Da; a.outputscale_b = (T)c->hyp.outputscale_b;
+    a.G = c->hyp.has_ids() && c->hyp.has_table ? (const T*)c->Gtab.p : nullptr; a.Q = c->hyp.has_ids() ? c->hyp.Q : 0;
+    a.sep = c->hyp.sep ? 1 : 0; a.dg = c->hyp.sep && c->hyp.Q > 0 ? c->hyp.idc() : c->hyp.DP;
     a.outputscale_g = (T)c->hyp.outputscale_g;
     a.out = out;
     a.ldo = ldo;

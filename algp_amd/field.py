@@ -9,13 +9,19 @@ from .utils import generate_gaussian_data
 
 
 class SyntheticField(object):
-    def __init__(self, num_rows=20, num_cols=20, num_test=40, k=5, num_genotypes=0):
+    def __init__(self, num_rows=20, num_cols=20, num_test=40, k=5, num_genotypes=0, ar1=None):
         """num_genotypes > 0: a genotype-id column behind (row, col) -- every plot gets one of that many genotypes at
         random, as a field trial scatters its replicates -- and the genotype's effect is added to the smooth field: the data an
         additive kernel with split 2 (position | genotype) and the genotype kernel are meant for; genotype_effect keeps the simulated
-        effects."""
+        effects.  ar1 = (rho_row, rho_col): the smooth field is a draw of the separable process AR1(row) x AR1(col) with unit
+        variance instead of the mixture of Gaussians -- cov = rho_row^|drow| rho_col^|dcol|, drawn as L_row Z L_col' on the
+        complete grid -- so that the separable kernel fits what generated the data."""
         self.num_rows, self.num_cols = num_rows, num_cols
         x, y = generate_gaussian_data(num_rows, num_cols, k=k)          # utils.py:90-108
+        if ar1 is not None:
+            chol = [np.linalg.cholesky(float(rho) ** np.abs(np.subtract.outer(np.arange(n), np.arange(n))))
+                    for rho, n in zip(ar1, (num_rows, num_cols))]
+            y = (chol[0] @ np.random.standard_normal((num_rows, num_cols)) @ chol[1].T).reshape(-1)    # site (r, c) at r cols + c
         x = x.astype(np.float64)
         self.num_genotypes, self.genotype_effect = int(num_genotypes), None
         if num_genotypes > 0:

@@ -27,6 +27,14 @@ What differs, deliberately:
     follow the additive layout: kernel_covar_module.kernels.0.base_kernel.log_lengthscale (1, 1, D - 1),
     kernel_covar_module.kernels.0.log_outputscale, kernel_covar_module.kernels.1.log_outputscale (the table is data, not a
     parameter); GPR.genotype_effects gives the BLUPs with their variances or joint covariance;
+  * kernel_params = {'type': 'separable', 'split': Da, 'parts': (desc_a, desc_b)} is the PRODUCT os kappa_a(r_a) kappa_b(r_b) of two
+    such kernels over the coordinates [0, Da) and the others, with one outputscale -- two Matern-1/2 parts over one coordinate
+    each are AR1(row) x AR1(col) -- under gpytorch's ScaleKernel(ProductKernel(...)) names:
+    kernel_covar_module.base_kernel.kernels.{0,1}.log_lengthscale and kernel_covar_module.log_outputscale.  It may also be the
+    'spatial' entry of the genotype kernel, whose first part is then that ScaleKernel:
+    kernel_covar_module.kernels.0.base_kernel.kernels.{0,1}.log_lengthscale, kernel_covar_module.kernels.0.log_outputscale,
+    kernel_covar_module.kernels.1.log_outputscale.  GPR.ar1_correlations gives rho = exp(-spacing / ls) of its AR1 parts with
+    standard errors;
   * `fit` uses the analytic MLL gradient computed on the device with the reference's own optimiser
     objects (torch.optim.Adam + ReduceLROnPlateau(patience=50), models.py:121-124);
   * GPR(..., fit_method='ai') fits by damped Newton steps on the average-information matrix of the MLL instead (utils.ai_newton,
@@ -81,6 +89,23 @@ class _AdditiveKernel(nn.Module):
         self.kernels = nn.ModuleList([_ScaleKernel(split), _ScaleKernel(ard_num_dims - split)])
 
 
+class _ProductKernel(nn.Module):
+    """Two base kernels, the first on the leading `split` coordinates, the second on the others (gpytorch's ProductKernel)."""
+
+    def __init__(self, split, ard_num_dims):
+        super(_ProductKernel, self).__init__()
+        self.kernels = nn.ModuleList([_BaseKernel(split), _BaseKernel(ard_num_dims - split)])
+
+
+class _ScaleProductKernel(nn.Module):
+    """ScaleKernel(ProductKernel(a, b)): one outputscale for the product."""
+
+    def __init__(self, split, ard_num_dims):
+        super(_ScaleProductKernel, self).__init__()
+        self.base_kernel = _ProductKernel(split, ard_num_dims)
+        self.log_outputscale = nn.Parameter(torch.zeros(1, dtype=torch.float64))
+
+
 class _TableKernel(nn.Module):
     """The genotype part os_g G[g, g']: its outputscale is the only parameter."""
 
@@ -92,9 +117,20 @@ class _TableKernel(nn.Module):
 class _GenotypeKernel(nn.Module):
     """ScaleKernel over the D - 1 spatial coordinates plus the table-valued genotype part."""
 
-    def __init__(self, ard_num_dims):
+    def __init__(self, ard_num_dims, split=None):
         super(_GenotypeKernel, self).__init__()
-        self.kernels = nn.ModuleList([_ScaleKernel(ard_num_dims - 1), _TableKernel()])
+        spatial = _ScaleKernel(ard_num_dims - 1) if split is None else _ScaleProductKernel(split, ard_num_dims - 1)
+        self.kernels = nn.ModuleList([spatial, _TableKernel()])
+
+
+def _separable_ids(params, n_spatial):
+    """(split, id_a, id_b) of {'type': 'separable', 'split': Da, 'parts': (desc_a, desc_b)} over n_spatial coordinates."""
+    parts, split = params.get('parts'), params.get('split')
+    if parts is None or len(parts) != 2:
+        raise ValueError("separable kernel: 'parts' must hold two kernel descriptions")
+    if split is None or not 1 <= int(split) <= n_spatial - 1:
+        raise ValueError("separable kernel: 'split' must be in [1, %d] (%d spatial coordinates)" % (n_spatial - 1, n_spatial))
+    return int(split), _kernel_id(parts[0]), _kernel_id(parts[1])
 
 
 def _kernel_id(params):
@@ -129,6 +165,7 @@ class ExactGPModel(nn.Module):
         kernel = kernel_params['type'] if kernel_params is not None else 'rbf'
         self.split = None
         self.relationship = None               # (G or None, Q) under the genotype kernel
+        self.sep = None                        # (split, id_a, id_b) where the (spatial) kernel is the separable product
         if kernel == 'genotype':
             D = int(np.shape(train_x)[-1])
             if D < 2:
@@ -145,8 +182,23 @@ class ExactGPModel(nn.Module):
             elif Q is None:
                 raise ValueError("genotype kernel: pass 'relationship' or 'n_genotypes'")
             self.relationship = (G, int(Q))
-            self.kernel_type = ('genotype', _kernel_id(kernel_params.get('spatial')))
-            self.kernel_covar_module = _GenotypeKernel(D)
+            spatial = kernel_params.get('spatial')
+            if spatial is not None and spatial.get('type') == 'separable':
+                if D < 3:
+                    raise ValueError('genotype kernel over a separable spatial part: two spatial coordinates and the id column (D >= 3)')
+                self.sep = _separable_ids(spatial, D - 1)
+                self.kernel_type = ('genotype', ('separable',) + self.sep)
+                self.kernel_covar_module = _GenotypeKernel(D, self.sep[0])
+            else:
+                self.kernel_type = ('genotype', _kernel_id(spatial))
+                self.kernel_covar_module = _GenotypeKernel(D)
+            self.likelihood = likelihood
+            return
+        if kernel == 'separable':
+            D = int(np.shape(train_x)[-1])
+            self.sep = _separable_ids(kernel_params, D)
+            self.kernel_type = ('separable',) + self.sep
+            self.kernel_covar_module = _ScaleProductKernel(self.sep[0], D)
             self.likelihood = likelihood
             return
         if kernel == 'additive':
@@ -220,6 +272,15 @@ class GPR(object):
         """(log_lengthscale[D], log_outputscale, log_noise, kernel id) as plain floats.  Under the additive kernel the
         lengthscales of the two parts in coordinate order, log_outputscale a pair and the id ('additive', split, id_a, id_b)."""
         m = self.model
+        if m.sep is not None:
+            # the separable product: the lengthscales of the two parts in coordinate order, id ('separable', split, id_a, id_b);
+            # with the genotype term (log os, log os_g) and ('genotype', ('separable', split, id_a, id_b))
+            sk = m.kernel_covar_module if m.relationship is None else m.kernel_covar_module.kernels[0]
+            ls = np.concatenate([k.log_lengthscale.detach().double().reshape(-1).numpy() for k in sk.base_kernel.kernels])
+            los = float(sk.log_outputscale.item())
+            if m.relationship is not None:
+                los = (los, float(m.kernel_covar_module.kernels[1].log_outputscale.item()))
+            return ls, los, float(self.likelihood.log_noise.item()), m.kernel_type
         if m.relationship is not None:         # D - 1 spatial lengthscales, (log os_a, log os_g), ('genotype', id_a)
             ks = m.kernel_covar_module.kernels
             return (ks[0].base_kernel.log_lengthscale.detach().double().reshape(-1).numpy().copy(),
@@ -247,7 +308,13 @@ class GPR(object):
     def push_hypers(self, ctx):
         """Set the current hyper-parameters on `ctx` (this model's own context, or another one that is to compute with them)."""
         ls, los, ln, kt = self.hypers()
-        if isinstance(kt, tuple) and kt[0] == 'genotype':
+        if isinstance(kt, tuple) and kt[0] == 'separable':
+            ctx.set_hypers_separable(ls, kt[1], los, ln, kernel_a=kt[2], kernel_b=kt[3])
+        elif isinstance(kt, tuple) and kt[0] == 'genotype' and isinstance(kt[1], tuple):
+            G, Q = self.model.relationship
+            ctx.set_hypers_separable(ls, kt[1][1], los[0], ln, kernel_a=kt[1][2], kernel_b=kt[1][3], log_outputscale_g=los[1], G=G,
+                                     n_genotypes=Q)
+        elif isinstance(kt, tuple) and kt[0] == 'genotype':
             G, Q = self.model.relationship
             ctx.set_hypers_relationship(ls, los[0], los[1], ln, kernel_a=kt[1], G=G, n_genotypes=Q)
         elif isinstance(kt, tuple):
@@ -356,7 +423,15 @@ class GPR(object):
         matrix's rows and columns) belong to, in the device's order."""
         named = dict(self.model.named_parameters())
         noise = 'likelihood.log_noise'
-        if self.model.relationship is not None:
+        if self.model.sep is not None and self.model.relationship is not None:
+            # the D + 2 gradient: [log ls of part a, of part b | log os, log os_g | log noise]
+            names = ['kernel_covar_module.kernels.0.base_kernel.kernels.%d.log_lengthscale' % k for k in (0, 1)] + \
+                    ['kernel_covar_module.kernels.0.log_outputscale', 'kernel_covar_module.kernels.1.log_outputscale', noise]
+        elif self.model.sep is not None:
+            # the D + 2 gradient: [log ls of part a, of part b | log os | log noise]
+            names = ['kernel_covar_module.base_kernel.kernels.%d.log_lengthscale' % k for k in (0, 1)] + \
+                    ['kernel_covar_module.log_outputscale', noise]
+        elif self.model.relationship is not None:
             # the D + 2 gradient: [log ls of the D - 1 spatial coordinates | log os_a, log os_g | log noise]
             names = ['kernel_covar_module.kernels.0.base_kernel.log_lengthscale', 'kernel_covar_module.kernels.0.log_outputscale',
                      'kernel_covar_module.kernels.1.log_outputscale', noise]
@@ -453,6 +528,30 @@ class GPR(object):
             at.append(names.index('likelihood.log_noise'))
         return heritability(los[0], los[1], ln, 1.0 if G is None else float(np.mean(np.diag(G))), cov[np.ix_(at, at)])
 
+    def ar1_correlations(self, spacing=1.0):
+        """[(rho, se), (rho, se)] of the two parts of the separable kernel where each is Matern-1/2 over a single coordinate -- an
+        AR1 process along that coordinate: rho = exp(-spacing / ls) is the correlation of two sites `spacing` apart (one plot
+        for coordinates counted in plots), and se = rho (spacing / ls) se(log ls) its delta-method standard error from
+        hyper_covariance() (with that method's caveat: at a stationary point only).  ValueError for any other kernel or part."""
+        if self.model is None or self.model.sep is None:
+            raise ValueError("ar1_correlations needs the separable kernel (kernel_params['type'] = 'separable', or the genotype "
+                             "kernel's 'spatial' entry)")
+        split, ids = self.model.sep[0], self.model.sep[1:]
+        ls = np.exp(self.hypers()[0])
+        widths = (split, len(ls) - split)
+        for k in (0, 1):
+            if ids[k] != _hip.KERNEL_MATERN05 or widths[k] != 1:
+                raise ValueError('ar1_correlations: part %d is not Matern-1/2 over a single coordinate (kernel id %d over %d '
+                                 'coordinate(s))' % (k, ids[k], widths[k]))
+        names, cov = self.hyper_covariance()
+        head = 'kernel_covar_module.' if self.model.relationship is None else 'kernel_covar_module.kernels.0.'
+        out = []
+        for k in (0, 1):
+            at = names.index(head + 'base_kernel.kernels.%d.log_lengthscale' % k)
+            rho = float(np.exp(-spacing / ls[k]))
+            out.append((rho, float(rho * (spacing / ls[k]) * np.sqrt(max(cov[at, at], 0.0)))))
+        return out
+
     def fit(self, x, y, var=None, disp=False):
         if var is None:
             var = np.full(len(y), 1e-5)                                           # models.py:138-139
@@ -462,7 +561,7 @@ class GPR(object):
             return self._fit_ai(disp)
         named = dict(self.model.named_parameters())
         p_n = named['likelihood.log_noise']
-        if self.model.relationship is not None or self.model.split is not None:
+        if self.model.relationship is not None or self.model.split is not None or self.model.sep is not None:
             route = [(p, a, b) for _, p, a, b in self._gradient_route()]
         else:
             p_ls = named['kernel_covar_module.base_kernel.log_lengthscale']

@@ -106,9 +106,26 @@ def spectral_draws(kernel_id, D, n_features, rng):
     of kernels is the mixture of the parts' densities with weights os_c / (os_a + os_b), so every feature belongs to one
     part, chosen with that probability: its frequencies are that part's draw in the part's own coordinates and ZERO in the
     other's, and the amplitude is sqrt(2 (os_a + os_b) / F) (algp_sample_posterior).  Order: the parts' uniform draws (F),
-    part a's z and c, part b's z and c, phase."""
+    part a's z and c, part b's z and c, phase.
+    The separable kernel: kernel_id = ('separable', split, id_a, id_b).  A product over disjoint coordinate groups has the
+    product of the parts' spectral measures, so EVERY feature takes omega_a from part a's law in part a's coordinates and
+    omega_b from part b's in the others, concatenated; the amplitude is sqrt(2 os / F) as for a single form.  Order: part a's
+    z and c, part b's z and c, phase."""
     rng = _rng(rng)
     D, F = int(D), int(n_features)
+    if isinstance(kernel_id, tuple) and kernel_id[0] == 'separable':
+        _, split, id_a, id_b = kernel_id
+        split = int(split)
+        omega = np.empty((F, D))
+        for ident, lo, hi in ((id_a, 0, split), (id_b, split, D)):
+            w = rng.standard_normal((F, hi - lo))
+            if ident != _hip.KERNEL_RBF:
+                if ident not in _MATERN_NU:
+                    raise NotImplementedError('spectral_draws: kernel id %r' % (ident,))
+                w = w * np.sqrt(2.0 * _MATERN_NU[ident] / rng.chisquare(2.0 * _MATERN_NU[ident], size=F))[:, None]
+            omega[:, lo:hi] = w
+        phase = rng.uniform(0.0, 2.0 * np.pi, size=F)
+        return np.ascontiguousarray(omega, dtype=np.float64), np.ascontiguousarray(phase, dtype=np.float64)
     if isinstance(kernel_id, tuple):
         _, split, id_a, id_b, os_a, os_b = kernel_id
         split = int(split)
@@ -135,7 +152,7 @@ def spectral_draws(kernel_id, D, n_features, rng):
 
 def relationship_prior_draws(kernel_a, log_lengthscale, os_a, os_g, G, n_genotypes, x, n_samples, n_features, rng, chunk=4096):
     """(n_samples, len(x)) float64 draws of the PRIOR of the relationship kernel os_a kappa_a(r_a) + os_g G[g, g'] at the sites
-    `x` (last column: the genotype ids), built on the host in NumPy -- the genotype part has no spectral density, so the device's
+    `x` (last column: the genotype ids; kernel_a = ('separable', split, id_a, id_b): the separable product as the spatial part), built on the host in NumPy -- the genotype part has no spectral density, so the device's
     features mode cannot draw it, and the result goes to algp_sample_posterior in values mode.
     Spatial part: n_features random Fourier features of kappa_a over the D - 1 spatial coordinates scaled by 1 / lengthscale,
     amplitude sqrt(2 os_a / F), evaluated in chunks of `chunk` sites.  Genotype part: u = sqrt(os_g) chol(G + jitter I) xi with
@@ -194,7 +211,10 @@ def posterior_samples(gp, train_x, train_y, test_x, train_var=None, n_samples=1,
                                          n_samples, n_features, rng)
         eps = rng.standard_normal((int(n_samples), N))
         return c.sample_posterior(eps, prior=prior)
-    kid = hyp[3] + tuple(np.exp(hyp[1])) if isinstance(hyp[3], tuple) else hyp[3]      # additive: with the two outputscales
+    if isinstance(hyp[3], tuple) and hyp[3][0] == 'separable':
+        kid = hyp[3]
+    else:
+        kid = hyp[3] + tuple(np.exp(hyp[1])) if isinstance(hyp[3], tuple) else hyp[3]  # additive: with the two outputscales
     omega, phase = spectral_draws(kid, train_x.shape[1], n_features, rng)
     weights = rng.standard_normal((int(n_samples), int(n_features)))
     eps = rng.standard_normal((int(n_samples), N))

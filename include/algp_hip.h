@@ -128,6 +128,35 @@ int algp_set_hypers_additive(algp_ctx* ctx, int D, int kernel_a, int Da, double 
  * ALGP_ERR_BAD_ARG -- the genotype part has no spectral density.  The fused right-hand-side generation stays off.                */
 int algp_set_hypers_relationship(algp_ctx* ctx, int D, int kernel_a, double log_outputscale_a, const double* log_lengthscale,
                                  double log_outputscale_g, const double* G, int64_t Q, double log_noise);
+/* The separable kernel: a PRODUCT of two forms over disjoint coordinate groups, with or without the relationship kernel's genotype
+ * term,
+ *   k((x, g), (x', g')) = os kappa_a(r_a) kappa_b(r_b)  [ + os_g G[g, g'] ].
+ * r_a over the first Da coordinates, r_b over the next Db >= 1, each factor any of the four ids above at outputscale 1 with the
+ * ARD lengthscales of its coordinates; ONE outputscale os for the product.  kernel_a = kernel_b = ALGP_KERNEL_MATERN05 with
+ * Da = Db = 1 is AR1(row) x AR1(col), rho_d = exp(-1 / ls_d) per unit of distance -- not Matern-1/2 over (row, col), and not the
+ * additive form, which has no row x column interaction.
+ * Q == 0: no genotype term.  G must be NULL, log_outputscale_g is ignored, all D coordinates are spatial (log_lengthscale: D
+ * entries) and 1 <= Da <= D - 1.  Q >= 1: coordinate D - 1 is the genotype id, exactly as under algp_set_hypers_relationship (an
+ * integer in [0, Q), never scaled, validated on the host at algp_set_pool, algp_kernel_matrix and in this call against a resident
+ * pool of width D; G a Q x Q table or NULL for the identity; fp32: Q <= 2^24); log_lengthscale has D - 1 entries and
+ * 1 <= Da <= D - 2.  The prior variance of site j is os (+ os_g G[g_j, g_j]).  2 <= D <= 8.
+ * Every refusal (D, the split, a kernel id, Q < 0, a table with Q == 0, a table that is not finite or not bitwise symmetric, a bad
+ * id in the resident pool, Q > 2^24 in fp32) is ALGP_ERR_BAD_ARG, and the context keeps the hyper-parameters, the table and the
+ * pool it had.  Replaces the hyper-parameters as the sibling setters do; a later algp_set_hypers* call of another form returns
+ * the context to that form and frees the table.
+ * Under this kernel: the gradient and the average information have D + 2 parameters either way, in the order
+ * (log_lengthscale[...], log_outputscale, [log_outputscale_g,] log_noise), with
+ *   dk/dlog ls_d = os kappa_b dk_a u_d^2 for d in part a (dk_a: factor a's lengthscale factor at outputscale 1; symmetric for b),
+ *   dk/dlog os = os kappa_a kappa_b,  dk/dlog os_g = os_g G[g_i, g_j];
+ * algp_get_mll_grad, algp_fit_step, algp_get_mll_ai, algp_get_reml_grad, algp_get_reml_ai and algp_reml_step all work on it.
+ * With the genotype term algp_posterior_mean_component splits the mean (0: spatial, 1: genotype) and algp_genotype_posterior
+ * gives the genotype effects; without it both return ALGP_ERR_STATE (a product has no additive shares).
+ * algp_sample_posterior works in values mode; features mode works for Q == 0 -- the product's spectral measure is the product of
+ * the factors', so the caller draws omega_a from factor a's law and omega_b from factor b's and concatenates them -- and is
+ * refused for Q >= 1 as under the relationship kernel.  The fused right-hand-side generation stays off.                        */
+int algp_set_hypers_separable(algp_ctx* ctx, int D, int kernel_a, int Da, int kernel_b, double log_outputscale,
+                              const double* log_lengthscale, double log_outputscale_g, const double* G, int64_t Q,
+                              double log_noise);
 
 /* ---- a1: GPR.cov_mat (models.py:161-181) -------------------------------------------------
  * out[n1*n2] (host) = K(x1,x2) ; x2 == NULL -> symmetric K(x1,x1) (models.py:169-170);

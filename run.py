@@ -19,7 +19,9 @@ def run_demo(args):
     # an additive kernel whose first part is the whole position (row, col) needs a coordinate for its second: genotype ids
     # (the genotype kernel reads the ids from the same column)
     genotypes = 12 if (args.kernel == 'additive' and args.kernel_split == 2) or args.kernel == 'genotype' else 0
-    env = SyntheticField(args.rows, args.cols, num_test=args.num_test, num_genotypes=genotypes)
+    # the separable kernel over (row | col) gets a field drawn from AR1(row) x AR1(col): the demo fits what generated it
+    separable = (args.kernel == 'separable' and args.kernel_split == 1) or (args.kernel == 'genotype' and args.spatial == 'separable')
+    env = SyntheticField(args.rows, args.cols, num_test=args.num_test, num_genotypes=genotypes, ar1=(0.8, 0.6) if separable else None)
     agent = Agent(env, args, static_std=args.static_std, mobile_std=10 * args.static_std)
     agent.reset()
     agent._setup_ipp(args.criterion, args.update)
@@ -40,6 +42,12 @@ def run_demo(args):
         beta, cov = agent.gp.fixed_effect_estimates()
         print('fixed effects (' + agent.gp.fit_objective + '): ' +
               '  '.join('{:+.4f} +- {:.4f}'.format(b, s) for b, s in zip(beta, np.sqrt(np.diag(cov)))))
+    if separable and args.fit_method == 'ai':
+        try:
+            (rr, sr), (rc, sc) = agent.gp.ar1_correlations()
+            print('AR1 correlations: rho_row = {:.3f} +- {:.3f}  rho_col = {:.3f} +- {:.3f}'.format(rr, sr, rc, sc))
+        except ValueError:
+            pass                               # a part that is no Matern-1/2 over one coordinate has no AR1 correlation
     if args.kernel == 'genotype':
         # the genotype effects themselves, beside the simulated ones (both centred: the constant mean absorbs their average)
         mean, var = agent.gp.genotype_effects()
