@@ -68,6 +68,9 @@ SIGNATURES = {
     'algp_set_fixed_effects': (C.c_int, [_c_ctx, _dblp, C.c_int64, C.c_int]),
     'algp_get_gls': (C.c_int, [_c_ctx, _dblp, _dblp, _dblp]),
     'algp_get_posterior_fixed': (C.c_int, [_c_ctx, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'algp_genotype_posterior_fixed': (C.c_int, [_c_ctx, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'algp_posterior_mean_fixed': (C.c_int, [_c_ctx, C.c_int, _i64p, C.c_int64, C.c_void_p]),
+    'algp_group_posterior_fixed': (C.c_int, [_c_ctx, C.POINTER(C.c_int32), _dblp, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     'algp_get_reml_grad': (C.c_int, [_c_ctx, _dblp]),
     'algp_get_reml_ai': (C.c_int, [_c_ctx, _dblp]),
     'algp_reml_step': (C.c_int, [_c_ctx, _dblp, _dblp]),
@@ -81,6 +84,7 @@ SIGNATURES = {
     'algp_posterior_mean': (C.c_int, [_c_ctx, _i64p, C.c_int64, C.c_void_p]),
     'algp_posterior_mean_component': (C.c_int, [_c_ctx, C.c_int, _i64p, C.c_int64, C.c_void_p]),
     'algp_sample_posterior': (C.c_int, [_c_ctx, C.c_int, C.c_int, _dblp, _dblp, _dblp, _dblp, _dblp, C.c_void_p]),
+    'algp_sample_posterior_fixed': (C.c_int, [_c_ctx, C.c_int, C.c_int, _dblp, _dblp, _dblp, _dblp, _dblp, C.c_void_p]),
     'algp_group_posterior': (C.c_int, [_c_ctx, C.POINTER(C.c_int32), _dblp, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     'algp_scores': (C.c_int, [_c_ctx, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_int]),
     'algp_argmax': (C.c_int, [_c_ctx, _i64p, _i64p, _dblp]),
@@ -97,6 +101,8 @@ SIGNATURES = {
     'algp_selftest_mfma': (C.c_int, [_c_ctx, C.POINTER(C.c_int)]),
     'algp_bench_gemm': (C.c_int, [_c_ctx, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, _dblp]),
     'algp_bench_gemm_generated': (C.c_int, [_c_ctx, C.c_int64, C.c_int64, C.c_int64, C.c_int, _dblp]),
+    'algp_bench_fixed_fold': (C.c_int, [_c_ctx, C.c_int64, C.c_int64, C.c_int, C.c_int, _dblp, _dblp]),
+    'algp_bench_fixed_panel': (C.c_int, [_c_ctx, C.c_int64, C.c_int64, C.c_int, C.c_int, _dblp]),
     'algp_sync': (C.c_int, [_c_ctx]),
     'algp_device_bytes': (C.c_int64, [_c_ctx]),
     'algp_prof_enable': (C.c_int, [_c_ctx, C.c_int]),
@@ -299,16 +305,19 @@ class Context(object):
         self.relationship = Q > 0               # a genotype term is in force: genotype_posterior works
         self.Q = Q
 
-    def genotype_posterior(self, want_var=True, want_cov=False):
+    def genotype_posterior(self, want_var=True, want_cov=False, fixed=False):
         """(mean, var or None, cov or None) of the Q genotype effects under the relationship kernel, in the context's dtype
-        (algp_genotype_posterior): BLUPs, prediction-error variances, joint covariance.  Needs a current factorisation."""
+        (algp_genotype_posterior): BLUPs, prediction-error variances, joint covariance.  Needs a current factorisation.
+        fixed: with the attached fixed effects estimated (algp_genotype_posterior_fixed) -- the BLUPs B alpha_R adjusted for
+        them and the mixed-model equations' prediction-error variances os_g G - B P B'."""
         if not getattr(self, 'relationship', False):
             raise ValueError('genotype_posterior: no kernel with a genotype term is in force (set_hypers_relationship, '
                              'set_hypers_separable with log_outputscale_g)')
         mean = np.empty(self.Q, dtype=self.dtype)
         var = np.empty(self.Q, dtype=self.dtype) if want_var else None
         cov = np.empty((self.Q, self.Q), dtype=self.dtype) if want_cov else None
-        self._check(self.lib.algp_genotype_posterior(self.h, _ptr(mean), _ptr(var), _ptr(cov)))
+        call = self.lib.algp_genotype_posterior_fixed if fixed else self.lib.algp_genotype_posterior
+        self._check(call(self.h, _ptr(mean), _ptr(var), _ptr(cov)))
         return mean, var, cov
 
     def _n_grad(self):
@@ -555,12 +564,23 @@ class Context(object):
         self._check(self.lib.algp_posterior_mean_component(self.h, int(component), _i64(idx), len(idx), _ptr(mu)))
         return mu
 
-    def sample_posterior(self, eps, weights=None, omega=None, phase=None, prior=None):
+    def posterior_mean_fixed(self, component, idx):
+        """The posterior mean at the pool sites idx with the attached fixed effects estimated, without a candidate solve
+        (algp_posterior_mean_fixed).  component -1: all of it, mean + h' beta + k' alpha_R; 0, 1: that kernel part's share
+        (posterior_mean_component's rules); 2: the trend's share h' beta.  -1 = mean + 0 + 1 + 2 under a two-part kernel."""
+        idx = self._idx(idx)
+        mu = np.empty(len(idx), dtype=self.dtype)
+        self._check(self.lib.algp_posterior_mean_fixed(self.h, int(component), _i64(idx), len(idx), _ptr(mu)))
+        return mu
+
+    def sample_posterior(self, eps, weights=None, omega=None, phase=None, prior=None, fixed=False):
         """(S, M) joint draws of the latent field at the candidates, in the context's dtype (algp_sample_posterior).  The
         library draws nothing: eps (S, N) are the standard-normal draws of the train noise, and the prior draw is either
         random Fourier features -- weights (S, F) standard normal, omega (F, D) unit-lengthscale frequencies, phase (F,);
         see utils.spectral_draws -- or prior (S, n_pool) values at every pool site.  Raises ValueError for a bad combination
-        of arguments and for the states the ABI refuses (no solve, picks committed, a unit row, a repeated train site)."""
+        of arguments and for the states the ABI refuses (no solve, picks committed, a unit row, a repeated train site).
+        fixed: draws of mean + h' beta + f with the attached fixed effects' uncertainty in them (algp_sample_posterior_fixed):
+        their mean is posterior_fixed()'s mu, their covariance posterior_cov + proj proj'."""
         def dbl(a, shape, what):
             a = np.ascontiguousarray(a, dtype=np.float64)
             if a.shape != tuple(shape):
@@ -584,17 +604,21 @@ class Context(object):
             prior = dbl(prior, (S, self.n_pool), 'prior')
         out = np.empty((S, self.M), dtype=self.dtype)
         dp = lambda a: None if a is None else a.ctypes.data_as(_dblp)
-        self._check(self.lib.algp_sample_posterior(self.h, S, F, dp(omega), dp(phase), dp(weights), dp(prior), dp(eps), _ptr(out)))
+        call = self.lib.algp_sample_posterior_fixed if fixed else self.lib.algp_sample_posterior
+        self._check(call(self.h, S, F, dp(omega), dp(phase), dp(weights), dp(prior), dp(eps), _ptr(out)))
         return out
 
-    def group_posterior(self, group, weight=None, n_groups=None, want_cov=True, want_cross=False):
+    def group_posterior(self, group, weight=None, n_groups=None, want_cov=True, want_cross=False, fixed=False):
         """(mean, cov or None, cross or None): the joint posterior of the aggregates g_q = sum_{j in q} a_j f(x_j) of the latent
         field over groups of candidate rows (algp_group_posterior), in the context's dtype.  group (M,): a label in
         [0, n_groups) per candidate row, -1 for a row in no group; n_groups defaults to max(group) + 1.  weight (M,): the
         coefficients a_j as given, or None for the plain group means (a_j = 1 / n_q; every group then needs a member).
         mean (Q,) = A mu, cov (Q, Q) = A Sigma A^T with Sigma the matrix posterior_cov() returns, cross (Q, M) = A Sigma.
         Raises ValueError for bad shapes, labels or weights and for the states the ABI refuses (no solve, picks committed,
-        a unit row, an explicit-covariance pool)."""
+        a unit row, an explicit-covariance pool).
+        fixed: the aggregates of the total signal mean + h' beta + f with the attached fixed effects estimated
+        (algp_group_posterior_fixed): mean = A mu_fixed, cov = A (Sigma + proj proj') A^T, cross = A (Sigma + proj proj') for
+        the mu and proj posterior_fixed() returns."""
         group = np.asarray(group)
         if group.shape != (self.M,):
             raise ValueError('group: expected shape (%d,), got %s' % (self.M, group.shape))
@@ -615,9 +639,9 @@ class Context(object):
         mean = np.empty(Q, dtype=self.dtype)
         cov = np.empty((Q, Q), dtype=self.dtype) if want_cov else None
         cross = np.empty((Q, self.M), dtype=self.dtype) if want_cross else None
-        self._check(self.lib.algp_group_posterior(self.h, group.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                  None if weight is None else weight.ctypes.data_as(_dblp), Q, _ptr(mean),
-                                                  _ptr(cov), _ptr(cross)))
+        call = self.lib.algp_group_posterior_fixed if fixed else self.lib.algp_group_posterior
+        self._check(call(self.h, group.ctypes.data_as(C.POINTER(C.c_int32)), None if weight is None else weight.ctypes.data_as(_dblp), Q,
+                         _ptr(mean), _ptr(cov), _ptr(cross)))
         return mean, cov, cross
 
     # -- greedy ----------------------------------------------------------------
@@ -912,6 +936,20 @@ class Context(object):
             return ms.value
         self._check(self.lib.algp_bench_gemm(self.h, m, n, k, int(bool(lower_only)), int(bool(beta_one)),
                                              int(reps), C.byref(ms)))
+        return ms.value
+
+    def bench_fixed_fold(self, rows, cols, p=16, reps=5):
+        """(fold_ms, copy_ms): the fixed effects' rank-p fold on a device-resident rows x cols matrix and a device-to-device
+        copy of that matrix, average ms per launch (algp_bench_fixed_fold)."""
+        a, b = C.c_double(), C.c_double()
+        self._check(self.lib.algp_bench_fixed_fold(self.h, int(rows), int(cols), int(p), int(reps), C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def bench_fixed_panel(self, rows, ncols, p=16, reps=5):
+        """Average ms per launch of the fixed effects' posterior pass over a device-resident rows x ncols panel with a zero
+        basis row (algp_bench_fixed_panel); ncols a multiple of 128."""
+        ms = C.c_double()
+        self._check(self.lib.algp_bench_fixed_panel(self.h, int(rows), int(ncols), int(p), int(reps), C.byref(ms)))
         return ms.value
 
     # -- misc ----------------------------------------------------------------------

@@ -2,8 +2,12 @@
 //   algp_set_fixed_effects     the basis H (one row per pool site) to the device, zero-padded to FX_P columns
 //   algp_get_gls               beta, its covariance A^-1 and the restricted log-likelihood
 //   algp_get_posterior_fixed   the candidates' mean and variance with the estimated trend (universal kriging), the rows R_j C
-// Both read the resident factor (and candidate solve) and write none of it; their scratch is one buffer of the context
-// (algp_ctx::fx).  The kernels and the algebra: fixed.hip.
+//   algp_genotype_posterior_fixed   the genotype effects adjusted for the estimated effects, with beta's share of their variance
+//   algp_posterior_mean_fixed       the mean at pool sites with the estimated trend, whole or by share, without a candidate solve
+// (algp_group_posterior_fixed and algp_sample_posterior_fixed are branches of their siblings: api_group.hip, api_sample.hip)
+// All read the resident factor (and candidate solve) and write none of it; their scratch is one buffer of the context
+// (algp_ctx::fx), beside the sibling's own where a call has one (the genotype effects: algp_ctx::gen).  The kernels and the
+// algebra: fixed.hip.
 #include "api_impl.h"
 
 using namespace algp;
@@ -49,7 +53,7 @@ int Impl<T>::fixed_enqueue(algp_ctx* c, const char* who, const typename Impl<T>:
     const size_t o_mu = take(sizeof(T) * (size_t)post_rows);
     const size_t o_var = take(sizeof(T) * (size_t)post_rows);
     const size_t o_proj = take(want_proj ? sizeof(T) * (size_t)post_rows * FX_P : 0);
-    const size_t o_aR = take(wants.fit ? sizeof(T) * (size_t)Npad : 0);
+    const size_t o_aR = take(wants.fit || wants.resid ? sizeof(T) * (size_t)Npad : 0);
     const size_t o_panel = take(wants.fit ? sizeof(T) * (size_t)NB * (size_t)Npad : 0);
     const size_t o_Gt = take(wants.grad ? sizeof(T) * (size_t)NB * (size_t)Npad : 0);
     const size_t o_gram2 = take(wants.fit ? sizeof(double) * 12 * (12 + FX_P) : 0);
@@ -81,12 +85,6 @@ int Impl<T>::fixed_enqueue(algp_ctx* c, const char* who, const typename Impl<T>:
     // a scaled pivot at or below 64 eps: the column is in the span of the ones before it at the precision of F
     const double eps = sizeof(T) == 8 ? 2.220446049250313e-16 : 1.1920928955078125e-07;
     return fixed_gls_launch(c, pl.gram, p, 64.0 * eps, pl.gls);
-}
-
-static int fixed_rank_error(algp_ctx* c, const char* who, double info) {
-    c->pivot = (int64_t)info;
-    return fail(c, ALGP_ERR_NOT_PD, std::string(who) + ": column " + std::to_string((int64_t)info) +
-                                        " of the basis at the train sites is in the span of the columns before it (H_A' S^-1 H_A is singular)");
 }
 
 // Harville's restricted likelihood from the p x p work's read-back h, without the constant 1/2 log|H'H|
@@ -153,6 +151,115 @@ template <typename T>
 int Impl<T>::fixed_alpha_r(algp_ctx* c, typename Impl<T>::FixedPlan& pl) {
     ALGP_TRY(fixed_resid_launch<T>(c, pl.Ft, c->Npad, c->N, (const T*)c->z.p, pl.gls, pl.aR));
     return trsv_backward<T>(c, (const T*)c->L.p, c->Npad, c->Lld, (const T*)c->invD.p, pl.aR);
+}
+
+// The genotype effects with the estimated fixed effects: algp_genotype_posterior's W = B L^-T and then, with the effects' residual
+// basis R_u = -W F (u has no trend share of its own),
+//   mean = W z + R_u beta = B alpha_R       var_q = os_g G_qq - |W_q|^2 + |C' R_u,q|^2       cov = os_g G - W W^T + (R_u C)(R_u C)^T
+// the prediction-error variances of the mixed-model equations, os_g G - B P B^T.  The sibling's launches in the sibling's order
+// (its scratch, algp_ctx::gen), then the posterior pass over W in place of V^T with a zero basis row (fixed_post_launch: every row
+// reads row 0 of a zeroed h) and the fold of (R_u C)(R_u C)^T onto the covariance.  Nothing resident is written; one
+// synchronisation.
+template <typename T>
+int Impl<T>::genotype_posterior_fixed(algp_ctx* c, void* mean_out, void* var_out, void* cov_out) {
+    const char* who = "genotype_posterior_fixed";
+    if (!c->hyp.set || !c->hyp.has_ids())
+        return fail(c, ALGP_ERR_STATE, "genotype_posterior_fixed: no kernel with a genotype term is in force (algp_set_hypers_relationship, "
+                                       "algp_set_hypers_separable with Q >= 1)");
+    if (c->pool_is_cov || c->n_pool <= 0) return fail(c, ALGP_ERR_STATE, "genotype_posterior_fixed needs a coordinate pool");
+    if (c->fx_p <= 0) return fail(c, ALGP_ERR_STATE, "genotype_posterior_fixed: no fixed effects are attached (algp_set_fixed_effects)");
+    if (!c->factored || c->train_dirty) return fail(c, ALGP_ERR_STATE, "genotype_posterior_fixed: call algp_factorize first");
+    if (c->solved && !c->picks.empty())
+        return fail(c, ALGP_ERR_STATE, "genotype_posterior_fixed: " + std::to_string(c->picks.size()) +
+                                           " pick(s) were committed since the factorisation, which the effects would not "
+                                           "include: factorize again");
+    const int64_t Q = c->hyp.Q, N = c->N, Npad = c->Npad, Qpad = round_up(Q, NB);
+    const int p = c->fx_p;
+    if (N <= p)
+        return fail(c, ALGP_ERR_BAD_ARG, std::string(who) + ": " + std::to_string(N) + " train rows do not determine " + std::to_string(p) +
+                                             " fixed effects");
+    const T* G = c->hyp.has_table ? (const T*)c->Gtab.p : nullptr;
+    const T osg = (T)c->hyp.outputscale_g;
+
+    size_t total = 0;
+    auto take = [&](size_t bytes) { const size_t o = total; total += (bytes + 255) / 256 * 256; return o; };
+    const size_t o_B = take(sizeof(T) * (size_t)Qpad * (size_t)Npad);
+    const size_t o_ss = take(sizeof(T) * (size_t)Qpad);
+    const size_t o_mean = take(sizeof(T) * (size_t)Qpad);
+    const size_t o_var = take(sizeof(T) * (size_t)Qpad);
+    const size_t o_h0 = take(sizeof(T) * FX_P + sizeof(int64_t) * (size_t)Qpad);   // the zero basis row, and row 0 as every row's index
+    const size_t o_WW = take(cov_out ? sizeof(T) * (size_t)Qpad * (size_t)Qpad : 0);
+    const size_t o_cov = take(cov_out ? sizeof(T) * (size_t)Q * (size_t)Q : 0);
+    if (total > c->gen.cap) {
+        size_t free_b = 0, total_b = 0;
+        ALGP_HIP(hipMemGetInfo(&free_b, &total_b));
+        if (total > c->gen.cap + free_b)
+            return fail(c, ALGP_ERR_OOM, std::string(who) + ": the scratch of " + std::to_string(Q) + " genotypes takes " + std::to_string(total) +
+                                             " bytes, " + std::to_string(c->gen.cap + free_b) + " available");
+    }
+    ALGP_TRY(ensure(c, c->gen, total));
+    char* base = (char*)c->gen.p;
+    T *B = (T*)(base + o_B), *ss = (T*)(base + o_ss), *meanD = (T*)(base + o_mean), *varD = (T*)(base + o_var);
+    T *WW = (T*)(base + o_WW), *covD = (T*)(base + o_cov);
+    const int64_t* idx0 = (const int64_t*)(base + o_h0);
+    const T* h0 = (const T*)(base + o_h0 + sizeof(int64_t) * (size_t)Qpad);
+    FixedPlan pl;
+    ALGP_TRY(fixed_enqueue(c, who, {.post_rows = Qpad, .proj = cov_out != nullptr}, pl));
+
+    ALGP_TRY(rel_gather_b_launch<T>(c, G, Q, osg, (const T*)c->Xs.p, c->hyp.DP, c->hyp.idc(), (const int64_t*)c->Aidx.p, N, Qpad, Npad, B));
+    ALGP_TRY(trsm_blocked<T>(c, {.klass = ALGP_PROF_GEMM_TRSM, .X = B, .mpad = Qpad, .ldx = Npad, .L = (T*)c->L.p, .npad = Npad, .ldl = c->Lld,
+                                 .invD = (T*)c->invD.p}));
+    ALGP_TRY(rows_reduce_launch<T>(c, B, Qpad, Npad, Npad, (T*)c->z.p, ss, meanD));
+    ALGP_TRY(rel_var_finish_launch<T>(c, G, Q, osg, ss, varD));
+    ALGP_HIP(hipMemsetAsync(base + o_h0, 0, sizeof(T) * FX_P + sizeof(int64_t) * (size_t)Qpad, c->stream));
+    ALGP_TRY(fixed_post_launch<T>(c, B, Npad, Q, Npad, pl.Ft, Npad, h0, idx0, pl.gls, p, meanD, varD, pl.mu, var_out ? pl.var : (T*)nullptr,
+                                  pl.proj));
+    double info = 0.0;
+    ALGP_HIP(hipMemcpyAsync(&info, pl.gls + FX_INFO, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    ALGP_HIP(hipMemcpyAsync(mean_out, pl.mu, sizeof(T) * (size_t)Q, hipMemcpyDeviceToHost, c->stream));
+    if (var_out) ALGP_HIP(hipMemcpyAsync(var_out, pl.var, sizeof(T) * (size_t)Q, hipMemcpyDeviceToHost, c->stream));
+    if (cov_out) {
+        ALGP_TRY(gemm_nt_launch<T>(c, ALGP_PROF_GEMM_OTHER, Qpad, Qpad, Npad, (T)1, B, Npad, B, Npad, (T)0, (const T*)nullptr, Qpad, WW, Qpad, 1));
+        ALGP_TRY(rel_cov_finish_launch<T>(c, G, Q, osg, WW, Qpad, covD));
+        ALGP_TRY(fixed_fold_launch<T>(c, covD, Q, Q, Q, pl.proj, p, pl.proj, p, p, 1));
+        ALGP_HIP(hipMemcpyAsync(cov_out, covD, sizeof(T) * (size_t)Q * (size_t)Q, hipMemcpyDeviceToHost, c->stream));
+    }
+    ALGP_TRY(sync_checked(c, who));
+    if (info != 0.0) return fixed_rank_error(c, who, info);
+    return ALGP_OK;
+}
+
+// The mean at pool sites with the estimated trend and no candidate solve: the kernel-GEMV of algp_posterior_mean on alpha_R =
+// P (y - ybar) in alpha's place, and the trend's share h_j' beta.  component -1: ybar + h_j' beta + k_j' alpha_R; 0, 1: that
+// part's share k_c,j' alpha_R (algp_posterior_mean_component's rules); 2: h_j' beta.  Nothing resident is written (alpha is
+// not needed); one synchronisation.
+template <typename T>
+int Impl<T>::posterior_mean_fixed(algp_ctx* c, int component, const int64_t* idx, int64_t M, void* mu_out) {
+    const char* who = "posterior_mean_fixed";
+    if (c->fx_p <= 0) return fail(c, ALGP_ERR_STATE, "posterior_mean_fixed: no fixed effects are attached (algp_set_fixed_effects)");
+    if (!c->factored || c->train_dirty) return fail(c, ALGP_ERR_STATE, "posterior_mean_fixed: call algp_factorize first");
+    if (c->N <= c->fx_p)
+        return fail(c, ALGP_ERR_BAD_ARG, std::string(who) + ": " + std::to_string(c->N) + " train rows do not determine " +
+                                             std::to_string(c->fx_p) + " fixed effects");
+    if (M == 0) return ALGP_OK;
+    ALGP_TRY(ensure(c, c->auxIdx, sizeof(int64_t) * M));
+    FixedPlan pl;
+    ALGP_TRY(fixed_enqueue(c, who, {.post_rows = M, .resid = true}, pl));
+    ALGP_HIP(hipMemcpyAsync(c->auxIdx.p, idx, sizeof(int64_t) * M, hipMemcpyHostToDevice, c->stream));
+    const int64_t* didx = (const int64_t*)c->auxIdx.p;
+    if (component != 2) {
+        ALGP_TRY(fixed_alpha_r(c, pl));
+        KmatSrc s = make_src(c);
+        s.parts = component < 0 ? 3 : 1 << component;
+        ALGP_TRY(kgemv_launch<T>(c, M, didx, s, c->N, (const int64_t*)c->Aidx.p, pl.aR, component < 0 ? (T)c->ybar : (T)0, pl.mu));
+    }
+    if (component < 0 || component == 2) ALGP_TRY(fixed_trend_launch<T>(c, (const T*)c->fxH.p, didx, M, pl.gls, c->fx_p, component < 0, pl.mu));
+    double info = 0.0;
+    ALGP_HIP(hipMemcpyAsync(&info, pl.gls + FX_INFO, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    ALGP_HIP(hipMemcpyAsync(mu_out, pl.mu, sizeof(T) * M, hipMemcpyDeviceToHost, c->stream));
+    ALGP_TRY(sync_checked(c, who));
+    if (info != 0.0) return fixed_rank_error(c, who, info);
+    return ALGP_OK;
 }
 
 // d l_R / d theta = 1/2 tr((alpha_R alpha_R' - P) dS/dtheta): the MLL gradient's kernel, unchanged, on the projected pair.
@@ -302,6 +409,48 @@ int algp_reml_step(algp_ctx* c, double* reml, double* grad) {
 int algp_get_posterior_fixed(algp_ctx* c, void* mu, void* var, void* proj) {
     CHECK_CTX(c);
     FINISH(c, DISPATCH(c, get_posterior_fixed(c, mu, var, proj)));
+}
+
+int algp_genotype_posterior_fixed(algp_ctx* c, void* mean_out, void* var_out, void* cov_out) {
+    CHECK_CTX(c);
+    if (!mean_out) return fail(c, ALGP_ERR_BAD_ARG, "genotype_posterior_fixed: mean_out is NULL");
+    FINISH(c, DISPATCH(c, genotype_posterior_fixed(c, mean_out, var_out, cov_out)));
+}
+
+int algp_bench_fixed_fold(algp_ctx* c, int64_t rows, int64_t cols, int p, int reps, double* fold_ms, double* copy_ms) {
+    CHECK_CTX(c);
+    if (!fold_ms || !copy_ms || rows <= 0 || cols <= 0 || p < 1 || p > FX_P || reps <= 0) return fail(c, ALGP_ERR_BAD_ARG, "bench_fixed_fold: bad arguments");
+    const bool was = c->prof_on;
+    c->prof_on = false;
+    const int rc = c->dtype == ALGP_F64 ? bench_fixed<double>(c, rows, cols, p, reps, fold_ms, copy_ms, nullptr)
+                                        : bench_fixed<float>(c, rows, cols, p, reps, fold_ms, copy_ms, nullptr);
+    c->prof_on = was;
+    return rc;
+}
+
+int algp_bench_fixed_panel(algp_ctx* c, int64_t rows, int64_t ncols, int p, int reps, double* ms) {
+    CHECK_CTX(c);
+    if (!ms || rows <= 0 || ncols <= 0 || ncols % NB != 0 || p < 1 || p > FX_P || reps <= 0)
+        return fail(c, ALGP_ERR_BAD_ARG, "bench_fixed_panel: bad arguments (ncols a multiple of 128)");
+    const bool was = c->prof_on;
+    c->prof_on = false;
+    const int rc = c->dtype == ALGP_F64 ? bench_fixed<double>(c, rows, ncols, p, reps, nullptr, nullptr, ms)
+                                        : bench_fixed<float>(c, rows, ncols, p, reps, nullptr, nullptr, ms);
+    c->prof_on = was;
+    return rc;
+}
+
+int algp_posterior_mean_fixed(algp_ctx* c, int component, const int64_t* idx, int64_t M, void* mu) {
+    CHECK_CTX(c);
+    if (component < -1 || component > 2) return fail(c, ALGP_ERR_BAD_ARG, "posterior_mean_fixed: component must be -1, 0, 1 or 2");
+    if (M < 0 || (M > 0 && (!idx || !mu))) return fail(c, ALGP_ERR_BAD_ARG, "posterior_mean_fixed: bad arguments");
+    if (c->pool_is_cov) return fail(c, ALGP_ERR_BAD_ARG, "posterior_mean_fixed needs a coordinate pool");
+    if ((component == 0 || component == 1) && (!c->hyp.set || !(c->hyp.additive || c->hyp.has_ids())))
+        return fail(c, ALGP_ERR_STATE, c->hyp.sep ? "posterior_mean_fixed: a product has no additive shares (the separable kernel without a genotype term)"
+                                                  : "posterior_mean_fixed: a single kernel is in force (algp_set_hypers_additive)");
+    for (int64_t i = 0; i < M; ++i)
+        if (idx[i] < 0 || idx[i] >= c->n_pool) return fail(c, ALGP_ERR_BAD_ARG, "posterior_mean_fixed: index outside the pool");
+    FINISH(c, DISPATCH(c, posterior_mean_fixed(c, component, idx, M, mu)));
 }
 
 }  // extern "C"

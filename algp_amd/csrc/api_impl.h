@@ -31,6 +31,12 @@ int sync_checked(algp_ctx* c, const char* what);
 // the variance-reduction criterion is scored over the ranks of the communicator: a layout is attached (algp_comm_set_vr_exchange)
 // and there is more than one rank (a world of one keeps the one-GPU state, as under the MI criterion)
 inline bool vr_over_ranks(const algp_ctx* c) { return c->vr.xrows != 0 && c->comm_nranks > 1; }
+// the fixed effects' rank failure, from the p x p work's flag (FX_INFO: the 1-based column): ALGP_ERR_NOT_PD with that pivot
+inline int fixed_rank_error(algp_ctx* c, const char* who, double info) {
+    c->pivot = (int64_t)info;
+    return fail(c, ALGP_ERR_NOT_PD, std::string(who) + ": column " + std::to_string((int64_t)info) +
+                                        " of the basis at the train sites is in the span of the columns before it (H_A' S^-1 H_A is singular)");
+}
 
 // how the candidate solve runs (Impl::SolvePlan): the new columns only (tail.hip), one task-list launch (chol_dag.hip),
 // the sweep (trsm_blocked, potrf.hip), or folded into the factorisation's own launch (fit_and_solve)
@@ -127,11 +133,13 @@ struct Impl {
     // parts: KmatSrc::parts -- 3: the posterior mean; 1, 2: one part's share of it under the additive kernel, without ybar
     static int posterior_mean(algp_ctx* c, const int64_t* idx, int64_t M, void* mu_out, int parts = 3);
     // joint draws of the latent field at the candidates by pathwise conditioning (api_sample.hip)
+    // fixed: of ybar + h' beta + f with the attached fixed effects' uncertainty in the draws (algp_sample_posterior_fixed)
     static int sample_posterior(algp_ctx* c, int S, int F, const double* omega, const double* phase, const double* weights,
-                                const double* prior, const double* eps, void* out);
+                                const double* prior, const double* eps, void* out, bool fixed = false);
     // the joint posterior of sums over groups of candidate rows (api_group.hip)
+    // fixed: of the total signal ybar + h' beta + f with the attached fixed effects estimated (algp_group_posterior_fixed)
     static int group_posterior(algp_ctx* c, const int32_t* group, const double* weight, int64_t Q, void* mean_out, void* cov_out,
-                               void* cross_out);
+                               void* cross_out, bool fixed = false);
     static int build_set_matrix(algp_ctx* c, const int64_t* idx, int64_t m, const void* var, int64_t* mpad_out, T* dst = nullptr);
     static int set_entropy(algp_ctx* c, const int64_t* idx, int64_t m, const void* var, double* H);
     static int inverse_diag_resident(algp_ctx* c, int64_t m, int64_t mpad, void* diag_out);
@@ -222,11 +230,16 @@ struct Impl {
         double* gram2;               // fit: the AI's products
     };
     // what a call needs of the scratch beyond F^T, the Gram product and the p x p work
-    struct FixedWants { int64_t post_rows = 0; bool proj = false, fit = false, grad = false; };
+    // (resid: alpha_R alone of the fit's vectors)
+    struct FixedWants { int64_t post_rows = 0; bool proj = false, fit = false, grad = false, resid = false; };
     static int fixed_enqueue(algp_ctx* c, const char* who, const FixedWants& w, FixedPlan& pl);
     static int fixed_alpha_r(algp_ctx* c, FixedPlan& pl);
     static int get_gls(algp_ctx* c, double* beta_out, double* cov_out, double* reml_out);
     static int get_posterior_fixed(algp_ctx* c, void* mu_out, void* var_out, void* proj_out);
+    // the read-outs that carry the estimated effects: the genotype effects (mean B alpha_R, covariance os_g G - B P B^T); the
+    // mean at pool sites without a candidate solve (component -1: all of it; 0, 1: a kernel part's share; 2: the trend's)
+    static int genotype_posterior_fixed(algp_ctx* c, void* mean_out, void* var_out, void* cov_out);
+    static int posterior_mean_fixed(algp_ctx* c, int component, const int64_t* idx, int64_t M, void* mu_out);
     // the restricted likelihood's gradient (have_X / inv_enqueued: mll_grad's), its value with it; its average information
     static int reml_grad(algp_ctx* c, double* grad_out, double* reml_out, bool have_X = false, bool inv_enqueued = false);
     static int reml_ai(algp_ctx* c, double* ai_out);

@@ -7,6 +7,11 @@
 //   R^T (128 x Npad)  = the train rows' epilogue of the prior draw                 sample_features_launch / sample_values_launch
 //   Z^T               = R^T L^-T, in place                                          trsm_blocked
 //   out (128 x Mpad)  = ybar + G_X + Z^T (V^T)^T                                    gemm_nt_launch, beta = 1 on the prior draw
+// algp_sample_posterior_fixed: draws of ybar + h' beta + f with beta's uncertainty in them, the same rule on the universal-kriging
+// predictor: beta_s = C C^T F^T z_s per sample and f_s(j) += R_j beta_s = (R_j C) . (C^T F^T z_s).  The pass over the tile Z^T in
+// place of V^T with a zero basis row gives -(Z^T F) C (fixed.hip), so per tile
+//   out -= (Z^T F C) proj^T                          the rank-p fold, proj the candidates' rows R_j C   fixed_post_launch, fixed_fold_launch
+// The mean over draws is algp_get_posterior_fixed's mu, their covariance posterior_cov + proj proj^T.
 // Nothing of the resident state is written; the scratch is one buffer of the context (algp_ctx::smp).
 #include "api_impl.h"
 
@@ -16,8 +21,10 @@ namespace algp {
 
 template <typename T>
 int Impl<T>::sample_posterior(algp_ctx* c, int S, int F, const double* omega, const double* phase, const double* weights,
-                              const double* prior, const double* eps, void* out) {
-    if (!c->solved) return fail(c, ALGP_ERR_STATE, "sample_posterior: call algp_solve_candidates first");
+                              const double* prior, const double* eps, void* out, bool fixed) {
+    const std::string who = fixed ? "sample_posterior_fixed" : "sample_posterior";
+    if (fixed && c->fx_p <= 0) return fail(c, ALGP_ERR_STATE, who + ": no fixed effects are attached (algp_set_fixed_effects)");
+    if (!c->solved) return fail(c, ALGP_ERR_STATE, who + ": call algp_solve_candidates first");
     const int64_t N = c->N, Npad = c->Npad, M = c->M, Mpad = c->Mpad, n_pool = c->n_pool;
     // the two states algp_get_posterior_cov refuses, for its reasons: V_j . z is the conditional update only for ordinary rows
     // solved against the train set alone
@@ -25,22 +32,27 @@ int Impl<T>::sample_posterior(algp_ctx* c, int S, int F, const double* omega, co
         for (int64_t j = 0; j < M; ++j)
             if (c->vt_kind[j] >= 0)
                 return fail(c, ALGP_ERR_STATE,
-                            "sample_posterior: candidate " + std::to_string(j) + " (pool index " + std::to_string(c->cand_idx[j]) +
+                            who + ": candidate " + std::to_string(j) + " (pool index " + std::to_string(c->cand_idx[j]) +
                                 ") is a train site and was solved as a unit row (prior_includes_noise = 1): set the "
                                 "candidates with prior_includes_noise = 0");
     if (!c->picks.empty())
-        return fail(c, ALGP_ERR_STATE, "sample_posterior: " + std::to_string(c->picks.size()) +
+        return fail(c, ALGP_ERR_STATE, who + ": " + std::to_string(c->picks.size()) +
                                            " pick(s) were committed since the candidate solve, which the draws would not "
                                            "include: solve the candidates again");
     // rows of one site share its sigma_n^2 term (algp_set_train): independent eps cannot describe their noise
     if (c->train_has_repeats)
-        return fail(c, ALGP_ERR_STATE, "sample_posterior: the train set lists a pool site in more than one row");
-    if (F > 0 && c->pool_is_cov) return fail(c, ALGP_ERR_BAD_ARG, "sample_posterior: random features need a coordinate pool (pass prior values)");
+        return fail(c, ALGP_ERR_STATE, who + ": the train set lists a pool site in more than one row");
+    if (fixed) {                                                  // algp_get_posterior_fixed's
+        if (c->train_dirty || c->vt_hyp_stamp != c->hyp_stamp || c->vt_fact_idx != c->fact_idx || c->vt_fact_var != c->fact_var)
+            return fail(c, ALGP_ERR_STATE, who + ": the candidate solve is not the current factor's: solve the candidates again");
+        if (c->ldv % 4 != 0) return fail(c, ALGP_ERR_STATE, who + ": the row stride of V^T is not a multiple of 4");
+    }
+    if (F > 0 && c->pool_is_cov) return fail(c, ALGP_ERR_BAD_ARG, who + ": random features need a coordinate pool (pass prior values)");
     if (F > 0 && c->hyp.has_ids() && !c->pool_is_cov)
-        return fail(c, ALGP_ERR_BAD_ARG, "sample_posterior: under the relationship kernel the genotype part has no spectral density, so "
+        return fail(c, ALGP_ERR_BAD_ARG, who + ": under the relationship kernel the genotype part has no spectral density, so "
                                          "random features cannot draw it (pass prior values, F == 0)");
-    if (N > 0 && !eps) return fail(c, ALGP_ERR_BAD_ARG, "sample_posterior: eps is NULL");
-    if (M > 0 && !out) return fail(c, ALGP_ERR_BAD_ARG, "sample_posterior: out is NULL");
+    if (N > 0 && !eps) return fail(c, ALGP_ERR_BAD_ARG, who + ": eps is NULL");
+    if (M > 0 && !out) return fail(c, ALGP_ERR_BAD_ARG, who + ": out is NULL");
     if (M == 0) return ALGP_OK;
 
     // (An explicit covariance takes prior_includes_noise = 1 only, so a train site among its candidates is a unit row and was
@@ -59,11 +71,14 @@ int Impl<T>::sample_posterior(algp_ctx* c, int S, int F, const double* omega, co
     const size_t o_E = take(sizeof(T) * (size_t)SAMPLE_TILE * (size_t)Npad);
     const size_t o_R = take(sizeof(T) * (size_t)SAMPLE_TILE * (size_t)Npad);
     const size_t o_O = take(sizeof(T) * (size_t)SAMPLE_TILE * (size_t)Mpad);
+    // fixed: the tile's rows -(Z^T F) C; one zero basis row and row 0 as every row's index
+    const size_t o_pZ = take(fixed ? sizeof(T) * (size_t)SAMPLE_TILE * FX_P : 0);
+    const size_t o_h0 = take(fixed ? sizeof(int64_t) * (size_t)SAMPLE_TILE + sizeof(T) * FX_P : 0);
     if (total > c->smp.cap) {
         size_t free_b = 0, total_b = 0;
         ALGP_HIP(hipMemGetInfo(&free_b, &total_b));
         if (total > c->smp.cap + free_b)
-            return fail(c, ALGP_ERR_OOM, "sample_posterior: the scratch of one tile of 128 samples takes " + std::to_string(total) +
+            return fail(c, ALGP_ERR_OOM, who + ": the scratch of one tile of 128 samples takes " + std::to_string(total) +
                                              " bytes, " + std::to_string(c->smp.cap + free_b) + " available");
     }
     ALGP_TRY(ensure(c, c->smp, total));
@@ -71,6 +86,21 @@ int Impl<T>::sample_posterior(algp_ctx* c, int S, int F, const double* omega, co
     double *stA = (double*)(base + o_stA), *stB = (double*)(base + o_stB), *stC = (double*)(base + o_stC);
     T *G = (T*)(base + o_G), *om = (T*)(base + o_om), *ph = (T*)(base + o_ph), *E = (T*)(base + o_E), *R = (T*)(base + o_R);
     T* O = (T*)(base + o_O);
+    T* pZ = (T*)(base + o_pZ);
+    FixedPlan pl;
+    double info = 0.0;
+    const int fp = c->fx_p;
+    if (fixed) {
+        // F^T, the p x p work and the candidates' rows R_j C, once for every tile
+        ALGP_TRY(fixed_enqueue(c, who.c_str(), {.post_rows = M, .proj = true}, pl));
+        ALGP_TRY(fixed_post_launch<T>(c, p(c->Vt), c->ldv, M, Npad, pl.Ft, Npad, (const T*)c->fxH.p, (const int64_t*)c->Cidx.p, pl.gls, fp,
+                                      (const T*)nullptr, (const T*)nullptr, (T*)nullptr, (T*)nullptr, pl.proj));
+        ALGP_HIP(hipMemsetAsync(base + o_h0, 0, sizeof(int64_t) * (size_t)SAMPLE_TILE + sizeof(T) * FX_P, c->stream));
+        // the rank flag before the first tile: on a dependent column proj is not written, and no tile is to be folded with it
+        ALGP_HIP(hipMemcpyAsync(&info, pl.gls + FX_INFO, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        ALGP_TRY(sync_checked(c, who.c_str()));
+        if (info != 0.0) return fixed_rank_error(c, who.c_str(), info);
+    }
 
     if (F > 0) {
         ALGP_HIP(hipMemcpyAsync(stC, omega, sizeof(double) * (size_t)F * D, hipMemcpyHostToDevice, c->stream));
@@ -103,6 +133,12 @@ int Impl<T>::sample_posterior(algp_ctx* c, int S, int F, const double* omega, co
             ALGP_TRY(gemm_nt_launch<T>(c, ALGP_PROF_GEMM_OTHER, SAMPLE_TILE, Mpad, Npad, (T)1, R, Npad, p(c->Vt), c->ldv, (T)1, O, Mpad,
                                        O, Mpad, 0));
         }
+        if (fixed) {
+            ALGP_TRY(fixed_post_launch<T>(c, R, Npad, sl, Npad, pl.Ft, Npad, (const T*)(base + o_h0 + sizeof(int64_t) * (size_t)SAMPLE_TILE),
+                                          (const int64_t*)(base + o_h0), pl.gls, fp, (const T*)nullptr, (const T*)nullptr, (T*)nullptr,
+                                          (T*)nullptr, pZ));
+            ALGP_TRY(fixed_fold_launch<T>(c, O, Mpad, sl, M, pZ, fp, pl.proj, fp, fp, -1));
+        }
         ALGP_HIP(hipMemcpy2DAsync((T*)out + s0 * M, sizeof(T) * M, O, sizeof(T) * Mpad, sizeof(T) * M, (size_t)sl, hipMemcpyDeviceToHost,
                                   c->stream));
         ALGP_TRY(sync(c));                                           // the staging is reused by the next tile
@@ -125,6 +161,16 @@ int algp_sample_posterior(algp_ctx* c, int S, int F, const double* omega, const 
         return fail(c, ALGP_ERR_BAD_ARG, F > 0 ? "sample_posterior: F > 0 takes omega, phase and weights, and no prior values"
                                                : "sample_posterior: F == 0 takes prior values, and no omega, phase or weights");
     FINISH(c, DISPATCH(c, sample_posterior(c, S, F, omega, phase, weights, prior, eps, out)));
+}
+
+int algp_sample_posterior_fixed(algp_ctx* c, int S, int F, const double* omega, const double* phase, const double* weights,
+                                const double* prior, const double* eps, void* out) {
+    CHECK_CTX(c);
+    if (S < 1 || F < 0) return fail(c, ALGP_ERR_BAD_ARG, "sample_posterior_fixed: S >= 1 and F >= 0 required");
+    if (F > 0 ? (!omega || !phase || !weights || prior) : (omega || phase || weights || !prior))
+        return fail(c, ALGP_ERR_BAD_ARG, F > 0 ? "sample_posterior_fixed: F > 0 takes omega, phase and weights, and no prior values"
+                                               : "sample_posterior_fixed: F == 0 takes prior values, and no omega, phase or weights");
+    FINISH(c, DISPATCH(c, sample_posterior(c, S, F, omega, phase, weights, prior, eps, out, true)));
 }
 
 }  // extern "C"

@@ -1131,5 +1131,9 @@ int test_mfma_launch(algp_ctx* c, int* mismatches_dev);
 template <typename T>
 int bench_gemm(algp_ctx* c, int64_t m, int64_t n, int64_t k, int lower_only, int beta_one, int reps,
                double* ms_out, bool gen_c = false);
+// the rank-p fold on a rows x cols matrix beside a device-to-device copy of it (fold_ms, copy_ms; both or neither), the posterior
+// pass over a rows x cols panel with a zero basis row (panel_ms, or null): average ms per launch (fixed.hip)
+template <typename T>
+int bench_fixed(algp_ctx* c, int64_t rows, int64_t cols, int p, int reps, double* fold_ms, double* copy_ms, double* panel_ms);
 
 }  // namespace algp

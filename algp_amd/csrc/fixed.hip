@@ -16,6 +16,10 @@
 // fixed_resid_kernel    z - F beta (alpha_R is its backward substitution)
 // fixed_downdate_kernel S^-1 -> P on the lower-triangle entries mll_grad_kernel reads: the gradient is that kernel on (P, alpha_R)
 // fixed_gram2_kernel    the average information's products v_a . v_b and F^T v_a (v_a: mll_ai_u_kernel's rows from alpha_R, solved)
+// and for the read-outs that carry the estimated effects (the genotype effects, the mean at pool sites):
+// fixed_fold_kernel     out (+)= P Qm^T for two panels of p columns: the covariance's term for beta's uncertainty, streamed
+// fixed_trend_kernel    h_j' beta at pool sites
+// (the pass over a row panel other than V^T -- W = B L^-T -- is fixed_post_kernel itself with a zero basis row: R = -W F)
 // No atomics; the sum along a row of V^T has one order whatever the grid, so two calls return the same bits.
 #include "common.h"
 #include "mfma.h"
@@ -335,5 +339,195 @@ int fixed_post_launch(algp_ctx* c, const T* Vt, int64_t ldv, int64_t M, int64_t 
     return ALGP_OK;
 }
 ALGP_INSTANTIATE(fixed_post_launch);
+
+// ---- the read-outs with the estimated effects (algp_genotype_posterior_fixed, algp_group_posterior_fixed,
+// algp_posterior_mean_fixed, algp_sample_posterior_fixed) ------------------------------------------------------------------------
+// The rank-p fold: out[i][j] += sign sum_{a < p} P[i][a] Qm[j][a] for i < rows, j < cols -- the term (R C)(R' C)^T that beta's
+// uncertainty adds to a covariance (the genotype effects', the groups' Q x Q and Q x M) and, with sign = -1, R_j beta_s in a tile of
+// draws.  A streaming pass over out: a workgroup owns FOLD_ROWS rows x 256 chunks of 16 bytes; the rows
+// of P are staged in LDS (zero behind p and behind the last row), a lane keeps Qm's rows of its chunk's columns in registers (zero
+// behind p) and walks down the rows with one 16-byte load and store per row where the leading dimension allows, element by element
+// where it does not (an odd packed Q x Q).  Every entry takes FX_P fused multiply-adds in ascending order of the basis column from
+// 0 (the padding adds exact zeros), then one addition onto (sign = 1) or subtraction from (sign = -1) what is there: one writer per
+// entry, no atomics, and with P = Qm the entries (i, j) and (j, i) get the same bits (a product commutes; out's own are equal).
+constexpr int FOLD_ROWS = 64;
+template <typename T>
+__global__ __launch_bounds__(256) void fixed_fold_kernel(T* out, int64_t ldo, int64_t rows, int64_t cols, const T* P, int64_t ldp, const T* Qm,
+                                                         int64_t ldq, int p, int sign) {
+    constexpr int E = 16 / (int)sizeof(T);
+    struct alignas(16) chunk_t { T v[E]; };
+    __shared__ T sP[FOLD_ROWS][FX_P];
+    const int64_t i0 = (int64_t)blockIdx.y * FOLD_ROWS;
+    for (int e = threadIdx.x; e < FOLD_ROWS * FX_P; e += 256) {
+        const int li = e / FX_P, a = e % FX_P;
+        sP[li][a] = (a < p && i0 + li < rows) ? P[(i0 + li) * ldp + a] : (T)0;
+    }
+    __syncthreads();
+    const int64_t j0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * E;
+    if (j0 >= cols) return;
+    T q[E][FX_P];
+#pragma unroll
+    for (int s = 0; s < E; ++s)
+#pragma unroll
+        for (int a = 0; a < FX_P; ++a) q[s][a] = (a < p && j0 + s < cols) ? Qm[(j0 + s) * ldq + a] : (T)0;
+    const bool whole = ldo % E == 0 && j0 + E <= cols;
+    const int nr = (int)(rows - i0 < FOLD_ROWS ? rows - i0 : FOLD_ROWS);
+    auto update = [&](int li, chunk_t& c) {
+#pragma unroll
+        for (int s = 0; s < E; ++s) {
+            T t = (T)0;
+#pragma unroll
+            for (int a = 0; a < FX_P; ++a) t = __builtin_fma(sP[li][a], q[s][a], t);
+            c.v[s] = sign > 0 ? c.v[s] + t : c.v[s] - t;
+        }
+    };
+    if (whole) {
+        // FOLD_AHEAD rows' loads are issued before the first of them is used: a lane keeps that many 16-byte reads in flight
+        constexpr int FOLD_AHEAD = 4;
+        for (int l0 = 0; l0 < nr; l0 += FOLD_AHEAD) {
+            chunk_t c[FOLD_AHEAD];
+#pragma unroll
+            for (int u = 0; u < FOLD_AHEAD; ++u)
+                if (l0 + u < nr) c[u] = *reinterpret_cast<const chunk_t*>(out + (i0 + l0 + u) * ldo + j0);
+#pragma unroll
+            for (int u = 0; u < FOLD_AHEAD; ++u)
+                if (l0 + u < nr) {
+                    update(l0 + u, c[u]);
+                    *reinterpret_cast<chunk_t*>(out + (i0 + l0 + u) * ldo + j0) = c[u];
+                }
+        }
+        return;
+    }
+    for (int li = 0; li < nr; ++li) {
+        T* o = out + (i0 + li) * ldo + j0;
+        chunk_t c;
+#pragma unroll
+        for (int s = 0; s < E; ++s) c.v[s] = j0 + s < cols ? o[s] : (T)0;
+        update(li, c);
+#pragma unroll
+        for (int s = 0; s < E; ++s)
+            if (j0 + s < cols) o[s] = c.v[s];
+    }
+}
+template <typename T>
+int fixed_fold_launch(algp_ctx* c, T* out, int64_t ldo, int64_t rows, int64_t cols, const T* P, int64_t ldp, const T* Qm, int64_t ldq, int p,
+                      int sign) {
+    if (rows <= 0 || cols <= 0) return ALGP_OK;
+    constexpr int E = 16 / (int)sizeof(T);
+    const int64_t gx = (cols + 256 * E - 1) / (256 * E), gy = (rows + FOLD_ROWS - 1) / FOLD_ROWS;
+    if (gy > 65535 || gx > INT32_MAX) return fail(c, ALGP_ERR_BAD_ARG, "fixed_fold: the matrix is too large for one launch");
+    if ((uintptr_t)out % 16 != 0) return fail(c, ALGP_ERR_BAD_ARG, "fixed_fold: the matrix is not aligned to 16 bytes");
+    if (sign != 1 && sign != -1) return fail(c, ALGP_ERR_BAD_ARG, "fixed_fold: sign is 1 or -1");
+    ProfScope ps(c, ALGP_PROF_ROWS, 2.0 * FX_P * (double)rows * (double)cols, sizeof(T) * 2.0 * (double)rows * (double)cols);
+    hipLaunchKernelGGL(fixed_fold_kernel<T>, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, c->cur, out, ldo, rows, cols, P, ldp, Qm, ldq, p,
+                       sign);
+    ALGP_HIP(hipGetLastError());
+    return ALGP_OK;
+}
+ALGP_INSTANTIATE(fixed_fold_launch);
+
+// out[j] (+)= sum_{a < p} H[idx[j]][a] beta[a] for j < M, in double in ascending order of the basis column: the trend's share
+// h_j' beta of the mean at pool sites (idx: pool indices on the device)
+template <typename T>
+__global__ __launch_bounds__(256) void fixed_trend_kernel(const T* H, const int64_t* idx, int64_t M, const double* gls, int p, int add, T* out) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= M) return;
+    const T* h = H + idx[j] * FX_P;
+    double m = 0.0;
+    for (int a = 0; a < p; ++a) m = __builtin_fma((double)h[a], gls[FX_BETA + a], m);
+    out[j] = (T)(add ? (double)out[j] + m : m);
+}
+template <typename T>
+int fixed_trend_launch(algp_ctx* c, const T* H, const int64_t* idx, int64_t M, const double* gls, int p, bool add, T* out) {
+    if (M <= 0) return ALGP_OK;
+    ProfScope ps(c, ALGP_PROF_ROWS, 2.0 * p * (double)M, sizeof(T) * (FX_P + 2.0) * (double)M);
+    hipLaunchKernelGGL(fixed_trend_kernel<T>, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, c->cur, H, idx, M, gls, p, add ? 1 : 0, out);
+    ALGP_HIP(hipGetLastError());
+    return ALGP_OK;
+}
+ALGP_INSTANTIATE(fixed_trend_launch);
+
+// out[j][a] = H[idx[j]][a] for j < M, a < FX_P: the basis rows of listed pool sites, packed (the operand of the sums by group)
+template <typename T>
+__global__ __launch_bounds__(256) void fixed_rows_kernel(const T* H, const int64_t* idx, int64_t M, T* out) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= M * FX_P) return;
+    out[e] = H[idx[e / FX_P] * FX_P + e % FX_P];
+}
+template <typename T>
+int fixed_rows_launch(algp_ctx* c, const T* H, const int64_t* idx, int64_t M, T* out) {
+    if (M <= 0) return ALGP_OK;
+    ProfScope ps(c, ALGP_PROF_ROWS, 0.0, sizeof(T) * 2.0 * FX_P * (double)M);
+    hipLaunchKernelGGL(fixed_rows_kernel<T>, dim3((unsigned)((M * FX_P + 255) / 256)), dim3(256), 0, c->cur, H, idx, M, out);
+    ALGP_HIP(hipGetLastError());
+    return ALGP_OK;
+}
+ALGP_INSTANTIATE(fixed_rows_launch);
+
+// Timing on device-resident zeroed operands, no host traffic (algp_bench_fixed_fold, algp_bench_fixed_panel): the average ms per
+// launch of the fold on a rows x cols matrix beside a device-to-device copy of that matrix, and of the posterior pass over a
+// rows x ncols panel with a zero basis row (how W, T and a sample tile Z^T go through it).
+template <typename T>
+int bench_fixed(algp_ctx* c, int64_t rows, int64_t cols, int p, int reps, double* fold_ms, double* copy_ms, double* panel_ms) {
+    constexpr int E = 16 / (int)sizeof(T);
+    const int64_t ld = (cols + E - 1) / E * E, rpad = (rows + 63) / 64 * 64;
+    DevBuf a, b, sm;
+    const size_t small = sizeof(T) * (size_t)(rows + cols + rpad + 2) * FX_P + sizeof(int64_t) * (size_t)rpad + sizeof(double) * FX_OUT +
+                         sizeof(T) * 2 * (size_t)rpad + 4096;
+    int rc = ensure(c, a, sizeof(T) * (size_t)rpad * (size_t)ld);
+    if (rc == ALGP_OK) rc = ensure(c, b, fold_ms ? sizeof(T) * (size_t)rows * (size_t)ld : 16);
+    if (rc == ALGP_OK) rc = ensure(c, sm, small);
+    auto done = [&](int r) {
+        hipFree(a.p); hipFree(b.p); hipFree(sm.p);
+        c->dev_bytes -= (int64_t)(a.cap + b.cap + sm.cap);
+        return r;
+    };
+    if (rc != ALGP_OK) return done(rc);
+    hipMemsetAsync(a.p, 0, sizeof(T) * (size_t)rpad * (size_t)ld, c->cur);
+    hipMemsetAsync(sm.p, 0, small, c->cur);
+    // carved from sm, 256 bytes apart at least: gls | idx | P | Qm | h0 | mu, var | proj | Ft
+    char* q = (char*)sm.p;
+    auto take = [&](size_t bytes) { char* o = q; q += (bytes + 255) / 256 * 256; return o; };
+    double* gls = (double*)take(sizeof(double) * FX_OUT);
+    int64_t* idx = (int64_t*)take(sizeof(int64_t) * (size_t)rpad);
+    T* P = (T*)take(sizeof(T) * (size_t)rows * FX_P);
+    T* Qm = (T*)take(sizeof(T) * (size_t)cols * FX_P);
+    T* h0 = (T*)take(sizeof(T) * FX_P);
+    T* mu = (T*)take(sizeof(T) * 2 * (size_t)rpad);
+    T* proj = (T*)take(sizeof(T) * (size_t)rpad * FX_P);
+    hipEvent_t e0, e1;
+    hipEventCreate(&e0);
+    hipEventCreate(&e1);
+    auto timed = [&](auto&& one, double* out) {
+        for (int w = 0; w < 2 && rc == ALGP_OK; ++w) rc = one();
+        hipEventRecord(e0, c->cur);
+        for (int r = 0; r < reps && rc == ALGP_OK; ++r) rc = one();
+        hipEventRecord(e1, c->cur);
+        hipEventSynchronize(e1);
+        float ms = 0;
+        hipEventElapsedTime(&ms, e0, e1);
+        *out = ms / reps;
+    };
+    if (fold_ms) {
+        timed([&] { return fixed_fold_launch<T>(c, (T*)a.p, ld, rows, cols, P, p, Qm, p, p, 1); }, fold_ms);
+        timed([&] { return hipMemcpyAsync(b.p, a.p, sizeof(T) * (size_t)rows * (size_t)ld, hipMemcpyDeviceToDevice, c->cur) == hipSuccess
+                               ? ALGP_OK : ALGP_ERR_HIP; }, copy_ms);
+    }
+    if (panel_ms) {
+        DevBuf ft;                                                // F^T: FX_P x cols
+        rc = ensure(c, ft, sizeof(T) * FX_P * (size_t)ld);
+        if (rc == ALGP_OK) {
+            hipMemsetAsync(ft.p, 0, sizeof(T) * FX_P * (size_t)ld, c->cur);
+            timed([&] { return fixed_post_launch<T>(c, (const T*)a.p, ld, rows, cols, (const T*)ft.p, ld, h0, idx, gls, p, mu, mu + rpad, mu,
+                                                    mu + rpad, proj); }, panel_ms);
+        }
+        hipFree(ft.p);
+        c->dev_bytes -= (int64_t)ft.cap;
+    }
+    hipEventDestroy(e0);
+    hipEventDestroy(e1);
+    return done(rc);
+}
+ALGP_INSTANTIATE(bench_fixed);
 
 }  // namespace algp

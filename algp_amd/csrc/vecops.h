@@ -215,6 +215,16 @@ template <typename T>
 int fixed_downdate_launch(algp_ctx* c, T* Sinv, int64_t ld, int64_t N, const T* Gt, int64_t ldg, int p);
 template <typename T>
 int fixed_gram2_launch(algp_ctx* c, const T* V, const T* Ft, int64_t ld, int64_t N, int P, int p, double* out);
+// the read-outs with the estimated effects (fixed.hip): out[i][j] += sign sum_{a < p} P[i][a] Qm[j][a] for i < rows, j < cols, sign = 1
+// or -1 (out aligned to 16 bytes; one writer per entry, with P = Qm symmetric bit for bit); out[j] (+)= H[idx[j]] . beta for j < M
+template <typename T>
+int fixed_fold_launch(algp_ctx* c, T* out, int64_t ldo, int64_t rows, int64_t cols, const T* P, int64_t ldp, const T* Qm, int64_t ldq, int p,
+                      int sign);
+template <typename T>
+int fixed_trend_launch(algp_ctx* c, const T* H, const int64_t* idx, int64_t M, const double* gls, int p, bool add, T* out);
+// out[j][a] = H[idx[j]][a], j < M, a < FX_P
+template <typename T>
+int fixed_rows_launch(algp_ctx* c, const T* H, const int64_t* idx, int64_t M, T* out);
 // the relationship form's gathers from its table (fit.hip): B[q][i] = os_g G[q, g_i] (Qpad x Npad, zero padded), the prior
 // variance os_a + os_g G[g_j, g_j] of every pool site, and the two last steps of algp_genotype_posterior
 template <typename T>

@@ -653,31 +653,58 @@ class GPR(object):
     def predict_components(self, x):
         """(mean_a, mean_b): the two parts' shares of the posterior mean of the latent field at `x` under the additive kernel
         -- with the genotype coordinates first, mean_a is the genotype effect adjusted for spatial trend.  The constant mean
-        belongs to neither: mean_a + mean_b + mean(train y) = predict(x)."""
+        belongs to neither: mean_a + mean_b + mean(train y) = predict(x).  With fixed effects the shares are taken with the
+        effects estimated (alpha_R in alpha's place) and the trend's share is predict_trend's: mean_a + mean_b + predict_trend(x)
+        + mean(train y) = predict(x)."""
         if self.model is None or (self.model.split is None and self.model.relationship is None):
             raise ValueError("predict_components needs kernel_params['type'] = 'additive' or 'genotype'")
+        c = self.ctx
+        idx = self._load_pool_with(x)
+        if self.fixed_effects is not None:
+            return c.posterior_mean_fixed(0, idx), c.posterior_mean_fixed(1, idx)
+        return c.posterior_mean_component(0, idx), c.posterior_mean_component(1, idx)
+
+    def predict_trend(self, x):
+        """The fixed effects' share h(x)' beta of the posterior mean at `x`, beta estimated by generalised least squares at the
+        current hyper-parameters (algp_posterior_mean_fixed, component 2)."""
+        if self.fixed_effects is None:
+            raise ValueError('predict_trend needs fixed_effects')
+        if self.model is None:
+            raise ValueError('predict_trend: fit or reset the model first')
+        return self.ctx.posterior_mean_fixed(2, self._load_pool_with(x))
+
+    def _load_pool_with(self, x):
+        """Pool = train sites then `x` (the basis over both with fixed effects), train set, factorisation; x's pool indices."""
         c = self.ctx
         self.sync_hypers()
         x = np.asarray(x, dtype=np.float64)
         x = x.reshape(len(x), -1)
         N, M = len(self._train_x), len(x)
         c.set_pool(np.vstack([self._train_x, x]))
+        if self.fixed_effects is not None:
+            c.set_fixed_effects(self.fixed_basis(np.vstack([self._train_x, x])))
         c.set_train(np.arange(N), self._train_y, self._train_var)
         c.factorize()
-        idx = np.arange(N, N + M)
-        return c.posterior_mean_component(0, idx), c.posterior_mean_component(1, idx)
+        return np.arange(N, N + M)
 
     def genotype_effects(self, return_cov=False):
         """(mean, var), or (mean, cov) with return_cov: the posterior of the Q genotype effects under the genotype kernel,
         conditioned on the stored training data -- BLUPs, prediction-error variances or the joint covariance for rankings and
-        contrasts, genotypes without a plot included (algp_genotype_posterior)."""
+        contrasts, genotypes without a plot included (algp_genotype_posterior).  With fixed effects the BLUPs are adjusted for
+        the estimated effects and the variances carry beta's uncertainty, as the mixed-model equations give them
+        (algp_genotype_posterior_fixed)."""
         if self.model is None or self.model.relationship is None:
             raise ValueError("genotype_effects needs kernel_params['type'] = 'genotype'")
         c = self.ctx
         self.sync_hypers()
         c.set_pool(self._train_x)
+        if self.fixed_effects is not None:
+            c.set_fixed_effects(self.fixed_basis(self._train_x))
         c.set_train(np.arange(len(self._train_x)), self._train_y, self._train_var)
         c.factorize()
+        if self.fixed_effects is not None:
+            mean, var, cov = c.genotype_posterior(want_var=not return_cov, want_cov=return_cov, fixed=True)
+            return (mean, cov) if return_cov else (mean, var)
         mean, var, cov = c.genotype_posterior(want_var=not return_cov, want_cov=return_cov)
         return (mean, cov) if return_cov else (mean, var)
 
@@ -690,7 +717,7 @@ class GPR(object):
 
     def group_posterior(self, x, group, test_var=None, weight=None, n_groups=None, return_cross=False):
         """(mean, cov) or (mean, cov, cross) of the aggregates of the latent field f over groups of the sites `x`, conditioned
-        on the stored training data: utils.group_posterior."""
+        on the stored training data: utils.group_posterior.  With fixed effects: of the total signal with the effects estimated."""
         from .utils import group_posterior
         return group_posterior(self, self._train_x, self._train_y, x, group, self._train_var, test_var=test_var, weight=weight,
                                n_groups=n_groups, return_cross=return_cross)

@@ -191,7 +191,9 @@ def posterior_samples(gp, train_x, train_y, test_x, train_var=None, n_samples=1,
     comes from `rng` (a RandomState or a seed), in this order: spectral_draws(kernel, D, n_features, rng), the weights
     standard_normal((n_samples, n_features)), the train-noise draws standard_normal((n_samples, N)).
     Under the genotype kernel the prior is drawn on the host at every pool site (relationship_prior_draws, whose draws come
-    first, in its own order) and passed in values mode; then the train-noise draws standard_normal((n_samples, N))."""
+    first, in its own order) and passed in values mode; then the train-noise draws standard_normal((n_samples, N)).
+    A model with fixed effects (GPR(fixed_effects=...)) gives draws of the total signal mean + h' beta + f with beta's
+    uncertainty in them (algp_sample_posterior_fixed), from the same draws in the same order."""
     c = gp.ctx
     gp.sync_hypers()
     rng = _rng(rng)
@@ -201,6 +203,9 @@ def posterior_samples(gp, train_x, train_y, test_x, train_var=None, n_samples=1,
     test_x = test_x.reshape(len(test_x), -1)
     N, M = len(train_x), len(test_x)
     c.set_pool(np.vstack([train_x, test_x]))
+    fixed = getattr(gp, 'fixed_effects', None) is not None
+    if fixed:
+        c.set_fixed_effects(gp.fixed_basis(np.vstack([train_x, test_x]), train_x))
     c.set_train(np.arange(N), train_y, train_var)
     c.set_candidates(np.arange(N, N + M), prior_includes_noise=False)
     c.fit_and_solve()
@@ -210,7 +215,7 @@ def posterior_samples(gp, train_x, train_y, test_x, train_var=None, n_samples=1,
         prior = relationship_prior_draws(hyp[3][1], hyp[0], np.exp(hyp[1][0]), np.exp(hyp[1][1]), G, Q, np.vstack([train_x, test_x]),
                                          n_samples, n_features, rng)
         eps = rng.standard_normal((int(n_samples), N))
-        return c.sample_posterior(eps, prior=prior)
+        return c.sample_posterior(eps, prior=prior, fixed=fixed)
     if isinstance(hyp[3], tuple) and hyp[3][0] == 'separable':
         kid = hyp[3]
     else:
@@ -218,7 +223,7 @@ def posterior_samples(gp, train_x, train_y, test_x, train_var=None, n_samples=1,
     omega, phase = spectral_draws(kid, train_x.shape[1], n_features, rng)
     weights = rng.standard_normal((int(n_samples), int(n_features)))
     eps = rng.standard_normal((int(n_samples), N))
-    return c.sample_posterior(eps, weights=weights, omega=omega, phase=phase)
+    return c.sample_posterior(eps, weights=weights, omega=omega, phase=phase, fixed=fixed)
 
 
 def group_posterior(gp, train_x, train_y, test_x, group, train_var=None, test_var=None, weight=None, n_groups=None,
@@ -227,7 +232,9 @@ def group_posterior(gp, train_x, train_y, test_x, group, train_var=None, test_va
     latent field over groups of test sites -- a genotype's plots, a field row -- on the device (algp_group_posterior): pool,
     train set and candidates exactly as predictive_distribution sets them (prior_includes_noise=False, extra_var=test_var).
     group, weight, n_groups: see Context.group_posterior; cov = A Sigma A^T for the Sigma predictive_distribution returns
-    with return_cov, without that matrix being formed; cross = A Sigma."""
+    with return_cov, without that matrix being formed; cross = A Sigma.
+    A model with fixed effects (GPR(fixed_effects=...)) gives the aggregates of the total signal mean + h' beta + f with the
+    effects estimated (algp_group_posterior_fixed): Sigma then carries the universal-kriging term."""
     c = gp.ctx
     gp.sync_hypers()
     train_x = np.asarray(train_x, dtype=np.float64)
@@ -236,9 +243,15 @@ def group_posterior(gp, train_x, train_y, test_x, group, train_var=None, test_va
     test_x = test_x.reshape(len(test_x), -1)
     N, M = len(train_x), len(test_x)
     c.set_pool(np.vstack([train_x, test_x]))
+    fixed = getattr(gp, 'fixed_effects', None) is not None
+    if fixed:
+        c.set_fixed_effects(gp.fixed_basis(np.vstack([train_x, test_x]), train_x))
     c.set_train(np.arange(N), train_y, train_var)
     c.set_candidates(np.arange(N, N + M), prior_includes_noise=False, extra_var=test_var)
     c.fit_and_solve()
+    if fixed:
+        mean, cov, cross = c.group_posterior(group, weight=weight, n_groups=n_groups, want_cov=True, want_cross=return_cross, fixed=True)
+        return (mean, cov, cross) if return_cross else (mean, cov)
     mean, cov, cross = c.group_posterior(group, weight=weight, n_groups=n_groups, want_cov=True, want_cross=return_cross)
     return (mean, cov, cross) if return_cross else (mean, cov)
 

@@ -236,8 +236,10 @@ int algp_get_mll_ai(algp_ctx* ctx, double* ai_out);
  * kept on the device in the context's dtype, zero-padded to 16 columns.  H == NULL or p == 0 detaches.  The basis belongs to
  * its pool (of either kind): a new pool drops it, n_pool must match (ALGP_ERR_BAD_ARG, as a non-finite entry; no pool:
  * ALGP_ERR_STATE).  Nothing resident depends on it: the factor, a candidate solve and the criteria's state stay as they are,
- * and every entry point but the two below ignores it (the criteria, paths, samples, group and genotype posteriors keep the
- * known-mean variances).
+ * and the entry points without `fixed`, `gls` or `reml` in their names ignore it: the read-outs algp_get_posterior,
+ * algp_posterior_mean(_component), algp_genotype_posterior, algp_group_posterior and algp_sample_posterior keep the known-mean
+ * values and bits and have the siblings below; the acquisition criteria and the path utilities keep the known-mean variances
+ * and have none yet.
  * With H_A the rows of the train sites, S = L L', y0 = y - ybar, z = L^-1 y0:
  *   F = L^-1 H_A    A = F'F = H_A' S^-1 H_A    b = F'z    beta = A^-1 b    cov beta = A^-1 = C C'  (C = R^-1, A = R'R, R upper)
  *   l_R = -1/2 [ (N - p) log 2 pi + log|S| + log|A| + z'z - b' beta ]
@@ -260,6 +262,40 @@ int algp_get_mll_ai(algp_ctx* ctx, double* ai_out);
 int algp_set_fixed_effects(algp_ctx* ctx, const double* H, int64_t n_pool, int p);
 int algp_get_gls(algp_ctx* ctx, double* beta_out, double* cov_out, double* reml_out);
 int algp_get_posterior_fixed(algp_ctx* ctx, void* mu_out, void* var_out, void* proj_out);
+/* The other read-outs with the estimated effects.  alpha_R = P y0 = L^-T (z - F beta), P = S^-1 - S^-1 H_A A^-1 H_A' S^-1; for a
+ * panel X of rows solved against the factor (V', or another) and their basis rows h: R = h - X F, R beta joins a mean,
+ * |C' R|^2 a variance and (R C)(R' C)' a covariance -- the pass of algp_get_posterior_fixed over that panel, and a rank-p fold
+ * out[i][j] += sum_a (R C)[i][a] (R' C)[j][a] streamed over the matrix with one writer per entry, ascending a, no atomics.
+ * Each keeps its known-mean sibling's arguments, shapes, NULL rules, preconditions and refusals, adds algp_get_gls's (no basis:
+ * ALGP_ERR_STATE; N <= p: ALGP_ERR_BAD_ARG; a dependent column: ALGP_ERR_NOT_PD with its pivot, outputs unspecified), writes
+ * nothing resident, returns the same bits in every call, and keeps its scratch in the sibling's buffer and the fixed effects'.
+ * algp_genotype_posterior_fixed: the genotype effects u (no trend share of their own: h = 0) from W = B L^-T, R_u = -W F:
+ *   mean = W z + R_u beta = B alpha_R    var_q = os_g G_qq - |W_q|^2 + |C' R_u,q|^2    cov = os_g G - W W' + (R_u C)(R_u C)'
+ * = os_g G - B P B', the prediction-error variances of the mixed-model equations; both triangles of cov carry identical bits.
+ * One synchronisation.
+ * algp_group_posterior_fixed: the functionals of the total signal ybar + h(x)' beta + f(x) over groups of candidate rows.  With
+ * A_g the Q x M coefficients, T = A_g V' and R_g = A_g H_C - T F (H_C: the candidates' basis rows):
+ *   mean = A_g mu + R_g beta    cov = A_g Sigma A_g' + (R_g C)(R_g C)'    cross = A_g Sigma + (R_g C) proj'   (proj: R_j C)
+ * i.e. A_g applied to algp_get_posterior_fixed's mu and to algp_get_posterior_cov's matrix + proj proj'.  Without cross_out
+ * neither the Q x M product nor the pass over V' is launched; mean_out alone forms T and no Q x M matrix.  Also refused
+ * (ALGP_ERR_STATE) when the candidate solve is not the current factor's.  One synchronisation.
+ * algp_posterior_mean_fixed: the mean at M pool sites without a candidate solve, the kernel-GEMV of algp_posterior_mean on
+ * alpha_R.  component -1: ybar + h_j' beta + k_j' alpha_R; 0, 1: that kernel part's share k_c,j' alpha_R under the rules of
+ * algp_posterior_mean_component; 2: the trend's share h_j' beta; another value: ALGP_ERR_BAD_ARG.  -1 = ybar + 0 + 1 + 2 to
+ * rounding under a two-part kernel; with a genotype term component 1 at a site equals algp_genotype_posterior_fixed's mean of
+ * its id to rounding.  Does not need alpha.  One synchronisation.
+ * algp_sample_posterior_fixed: draws of ybar + h' beta + f at the candidates with beta's uncertainty in them, Matheron's rule on
+ * the universal-kriging predictor from the same arguments as algp_sample_posterior (both prior modes, tiles of 128 samples,
+ * the library draws nothing):
+ *   z_s = L^-1 (y0 - g_s(A) - sqrt(v) o eps_s)    beta_s = C C' F' z_s    f_s(j) = ybar + g_s(j) + V_j . z_s + R_j beta_s
+ * The mean over draws is algp_get_posterior_fixed's mu, their covariance algp_get_posterior_cov's + proj proj'.  One
+ * synchronisation for the rank flag before the first tile (a dependent column returns there), then one per tile as the sibling.  */
+int algp_genotype_posterior_fixed(algp_ctx* ctx, void* mean_out, void* var_out, void* cov_out);
+int algp_group_posterior_fixed(algp_ctx* ctx, const int32_t* group, const double* weight, int64_t Q, void* mean_out, void* cov_out,
+                               void* cross_out);
+int algp_posterior_mean_fixed(algp_ctx* ctx, int component, const int64_t* idx, int64_t M, void* mu_out);
+int algp_sample_posterior_fixed(algp_ctx* ctx, int S, int F, const double* omega, const double* phase, const double* weights,
+                                const double* prior, const double* eps, void* out);
 /* The restricted likelihood as a fit objective (REML: the variance components are not biased by the degrees of freedom the
  * fixed effects consume).  With P = S^-1 - G G', G = S^-1 H_A C = L^-T F C, and alpha_R = P y0 = L^-T (z - F beta):
  *   d l_R / d theta_a = 1/2 tr((alpha_R alpha_R' - P) dS/dtheta_a)
@@ -728,6 +764,11 @@ int algp_bench_gemm(algp_ctx* ctx, int64_t m, int64_t n, int64_t k, int lower_on
  * as the candidate sweep's update products form the right-hand sides (the scheduled launcher only: an
  * error where it is switched off).                                                                    */
 int algp_bench_gemm_generated(algp_ctx* ctx, int64_t m, int64_t n, int64_t k, int reps, double* ms_per_launch);
+/* the fixed effects' rank-p fold on a zeroed rows x cols matrix and a device-to-device copy of that matrix, average ms per
+ * launch each (the fold reads and writes every entry once: the copy is its yardstick); and the posterior pass over a zeroed
+ * rows x ncols panel (ncols a multiple of 128) with a zero basis row, as W, T and a sample tile go through it.  1 <= p <= 16.   */
+int algp_bench_fixed_fold(algp_ctx* ctx, int64_t rows, int64_t cols, int p, int reps, double* fold_ms, double* copy_ms);
+int algp_bench_fixed_panel(algp_ctx* ctx, int64_t rows, int64_t ncols, int p, int reps, double* ms_per_launch);
 
 /* ---- resident-buffer access for benchmarks / multi-GPU plumbing --------------------------- */
 int algp_sync(algp_ctx* ctx);
